@@ -7,6 +7,12 @@ One "step" = one pass of the hot path over one batch of synthetic boards, reside
 are SURVEY.md section 8(f) rows, reported in the `pipeline_e2e` block, never inside `value`).
 
     python bench.py --gpus N --steps K --warmup W [--dtype f16x3|f32|f16] [--unet-variant convT|bilinear] [--boards B]
+                    [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps, writes the last step's outputs when --dump-outputs is given, and prints the
+headline line.  Everything else -- the rooflines (event-timed passes of their own), the CPU baseline and the oracle parity, the
+other precisions and the bilinear variant, the host-images-to-FEN pipeline legs and the multi-rank checks -- runs with --full
+(--no-cpu-baseline / --no-extras then trim it as before).
 
 N > 1 from a bare shell: the process re-launches itself under torch.distributed.run (one rank per GPU, RCCL) BEFORE anything
 touches the GPU, relays rank 0's JSON line and exits with the children's return code.  Under a launcher (WORLD_SIZE set) it
@@ -564,6 +570,31 @@ def measure(eng, x, sq, steps, warmup, device, cvd, streams=None):
     return elapsed, out
 
 
+DUMP_LIMIT_BYTES = 60_000_000                                      # under the 64 MB a dump may hold, .npy headers included
+
+
+def dump_outputs(dst, out):
+    """What a caller of the timed path receives from its last step, as float32 .npy files in `dst`:
+      resnet18_logits.npy  (squares, 13), every square (up to half the limit, else a seeded sample of squares)
+      unet_logits.npy      (boards, 1, 256, 256), every board when it fits the rest of the limit, else the boards of a fixed
+                           seeded sample (numpy default_rng(0), sorted indices; 225 of the default 256 boards)
+    The sample depends on the shapes only, so two builds run with the same arguments write the same rows."""
+    import numpy as np
+
+    dst = Path(dst)
+    dst.mkdir(parents=True, exist_ok=True)
+    room = DUMP_LIMIT_BYTES
+    for name, t, share in (("resnet18_logits", out[1], 0.5), ("unet_logits", out[0], 1.0)):
+        n, row = t.shape[0], t[0].numel() * 4
+        k = min(n, int(room * share) // row)
+        if k < n:
+            keep = np.sort(np.random.default_rng(0).choice(n, size=k, replace=False))
+            t = t[torch.from_numpy(keep).to(t.device)]
+        a = t.float().cpu().numpy()
+        np.save(dst / f"{name}.npy", a)
+        room -= a.nbytes
+
+
 def rooflines(eng, x, sq, dtype, B, quiet=False):
     """HIP-event timing of every launch of one step on the launch stream (cv_profile_convs): the MFMA roofline of the conv
     family and the HBM roofline of each memory-bound kernel (algorithmic bytes / event time / 8 TB/s)."""
@@ -770,6 +801,10 @@ def main():
     ap.add_argument("--e2e-precision", default=None,
                     help="precision of the sharded host-images-to-FEN leg at N > 1 (BASELINE configs[4] says fp16: default "
                          "'<dtype>+f16r' = the headline UNet with the classifier in its fp16 mode)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: rooflines, CPU baseline + oracle parity, other precisions / variant, pipeline legs, multi-rank checks")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (rank 0's boards) as float32 .npy files into DIR")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -798,7 +833,8 @@ def main():
     uspec, rspec = synthetic.unet_spec(bilinear), synthetic.resnet18_spec()
     usd = cvd.broadcast_state_dict(synthetic.unet_state_dict(1, bilinear) if rank == 0 else None, uspec, device)
     rsd = cvd.broadcast_state_dict(synthetic.resnet18_state_dict(2) if rank == 0 else None, rspec, device)
-    rccl_ranks = cvd.count_ranks(device)                         # an all-reduce of ones over RCCL: every rank really took part
+    if args.full:
+        rccl_ranks = cvd.count_ranks(device)                     # an all-reduce of ones over RCCL: every rank really took part
 
     def make_engine(dtype, unet_sd=usd):
         e = HipEngine(device, precision=dtype, unet_chunk=args.unet_chunk, resnet_chunk=args.resnet_chunk)
@@ -810,9 +846,10 @@ def main():
     calibration = cvd.sync_calibration(eng, device)              # every rank computes with rank 0's tensor exponents
     torch.cuda.synchronize(device)
     init_mine = time.perf_counter() - t_init
-    init_s = cvd.stats_over_ranks(init_mine, device)   # weights: generate (rank 0) + broadcast + pack + calibrate
-    init_per_rank = cvd.list_over_ranks(init_mine, device)
-    mem = _DeviceMemory(device)
+    if args.full:
+        init_s = cvd.stats_over_ranks(init_mine, device)   # weights: generate (rank 0) + broadcast + pack + calibrate
+        init_per_rank = cvd.list_over_ranks(init_mine, device)
+        mem = _DeviceMemory(device)
 
     # ---- synthetic inputs, resident in HBM before the timed region ----
     # ONE global batch of world * B boards, board i drawn from its own seed; rank r holds boards r::world of it (SURVEY.md
@@ -831,9 +868,36 @@ def main():
     streams = [torch.cuda.Stream(device), torch.cuda.Stream(device)] if args.overlap else None
 
     elapsed, out = measure(eng, x, sq, args.steps, args.warmup, device, cvd, streams)
-    mem.sample()                                          # every rank's workspace has grown to its chunk
+    if args.full:
+        mem.sample()                                      # every rank's workspace has grown to its chunk
     ms_per_step = elapsed / args.steps * 1e3
     value = world * B * args.steps / elapsed
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out)
+
+    headline = {
+        "metric": "boards/sec (UNet 256x256 seg + 64-sq classify)",
+        "value": round(value, 2), "unit": "boards/sec",
+        "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 3),
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": args.dtype, "data": "synthetic",
+    }
+    workload = (f"e2e-cnn b={B}/GPU: UNet(3->1,{'bilinear' if bilinear else 'convT'}) 256x256 x{B} boards + ResNet-18(1ch,13cls) x{B * 64} "
+                "squares/step; in HBM (configs[3])")
+    parallelism = f"replicas x{world}, boards sharded, weights RCCL-broadcast once"
+    if not args.full:
+        if rank == 0:
+            macs_board = eng.model_macs("unet") + 64 * eng.model_macs("resnet18")
+            result = {**headline,
+                      "config": {"workload": workload, "boards_per_gpu": B, "global_boards_per_step": world * B, "parallelism": parallelism,
+                                 "gflop_per_board": round(2 * macs_board / 1e9, 3)},
+                      "calibration_sync": calibration, "host_threads_per_rank": cvd.host_threads(),
+                      "e2e_tflops": round(2 * macs_board * value / 1e12, 2)}
+            log(f"  step: {ms_per_step:.2f} ms over {args.steps} timed steps")
+            print(json.dumps(result), file=json_out, flush=True)
+        cvd.barrier(device)
+        cvd.shutdown()
+        return
 
     # outputs stay rank-local in a throughput run; one small gather proves the shard map: per board its global index and a
     # checksum of its 64 x 13 logits travel rank-major and must re-interleave to 0 .. world*B-1
@@ -885,15 +949,10 @@ def main():
 
     variant_name = "bilinear up-sampling" if bilinear else "transposed-conv"
     result = {
-        "metric": "boards/sec (UNet 256x256 seg + 64-sq classify)",
-        "value": round(value, 2), "unit": "boards/sec",
-        "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 3),
-        "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-        "dtype": args.dtype, "data": "synthetic",
-        "config": {"workload": f"e2e-cnn b={B}/GPU: UNet(3->1,{'bilinear' if bilinear else 'convT'}) 256x256 x{B} boards + ResNet-18(1ch,13cls) x{B * 64} squares/step; "
-                               "in HBM (configs[3])",
+        **headline,
+        "config": {"workload": workload,
                    "boards_per_gpu": B, "global_boards_per_step": world * B, "unet_chunk": eff_unet,
-                   "resnet_chunk": eff_resnet, "parallelism": f"replicas x{world}, boards sharded, weights RCCL-broadcast once",
+                   "resnet_chunk": eff_resnet, "parallelism": parallelism,
                    "gflop_per_board": round(2 * macs_board / 1e9, 3)},
         "rccl_ranks_seen": rccl_ranks, "dist_backend": cvd.backend_name(),
         "init_s": {k: round(v, 3) for k, v in init_s.items()}, "init_s_per_rank": [round(v, 3) for v in init_per_rank],

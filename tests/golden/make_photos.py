@@ -9,7 +9,7 @@ placement the reference's evaluation script scores against, scripts/eval/evaluat
 two folders are decoded and stored in the channel order cv2.imread hands the reference (BGR), together with their file
 names and ground-truth placements:
 
-    photos8.npz   bgr (8,512,512,3) uint8 | names (8,) str | fen (8,) str
+    photos8_{i}.npz, i = 0..7   bgr (1,512,512,3) uint8 | names (1,) str | fen (1,) str   (one photo per file: each under 1 MiB)
 
 These are inputs (and labels), not outputs of anything: the parity tests push real image statistics -- instead of uniform
 noise and synthetic boards -- through the load-time range calibration of the f16-based engines, the two CNNs and
@@ -38,8 +38,9 @@ def main():
         bgr.append(rgb[:, :, ::-1].copy())
         names.append(f"{path.parent.parent.name}/{path.name}")
         fens.append((path.parent.parent / "ground_truth" / (path.stem + ".txt")).read_text().strip())
-    np.savez_compressed(HERE / "photos8.npz", bgr=np.stack(bgr), names=np.array(names), fen=np.array(fens))
-    print("wrote", HERE / "photos8.npz", (HERE / "photos8.npz").stat().st_size, "bytes;", names)
+    for i in range(len(bgr)):
+        np.savez_compressed(HERE / f"photos8_{i}.npz", bgr=bgr[i][None], names=np.array(names[i:i + 1]), fen=np.array(fens[i:i + 1]))
+    print("wrote", [(HERE / f"photos8_{i}.npz").stat().st_size for i in range(len(bgr))], "bytes;", names)
 
 
 if __name__ == "__main__":

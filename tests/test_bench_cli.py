@@ -2,7 +2,8 @@
 
 CPU: `python bench.py --gpus 2` from a bare shell must neither hang nor exec -- without two devices it exits with a clear
 message before any launcher starts.  GPU (one device): the RCCL code path (process-group init, the weight broadcast, an
-all-reduce, the barriers) runs with world size 1 under CV_FORCE_DIST=1, and the line carries every block the contract names."""
+all-reduce, the barriers) runs with world size 1 under CV_FORCE_DIST=1, and the `--full` line carries every block the contract
+names; a plain run prints the headline alone and `--dump-outputs` writes the last timed step's outputs."""
 from __future__ import annotations
 
 import json
@@ -73,6 +74,31 @@ def test_parent_counts_gpus_without_the_hip_runtime(monkeypatch):
     assert bench.visible_gpus() == 0
 
 
+def test_dump_outputs_fits_64_mb_with_a_fixed_sample(tmp_path):
+    """The default shape (256 boards): every square's logits, and a seeded sample of 225 boards' UNet logits -- the same rows on
+    every call, float32, under 64 MB on disk."""
+    import numpy as np
+
+    sys.path.insert(0, str(ROOT))
+    import bench
+
+    logits = torch.arange(256, dtype=torch.float32).reshape(256, 1, 1, 1).expand(256, 1, 256, 256).contiguous()
+    cls = torch.randn(256 * 64, 13)
+    for d in (tmp_path / "a", tmp_path / "b"):
+        bench.dump_outputs(d, (logits, cls))
+    u, r = np.load(tmp_path / "a" / "unet_logits.npy"), np.load(tmp_path / "a" / "resnet18_logits.npy")
+    assert u.dtype == np.float32 and r.dtype == np.float32
+    assert r.shape == (256 * 64, 13) and np.array_equal(r, cls.numpy())
+    assert u.shape == (225, 1, 256, 256)
+    boards = u[:, 0, 0, 0]
+    assert np.all(np.diff(boards) > 0) and np.array_equal(u, logits.numpy()[boards.astype(int)])
+    assert np.array_equal(u, np.load(tmp_path / "b" / "unet_logits.npy"))
+    assert sum(f.stat().st_size for f in (tmp_path / "a").iterdir()) <= 64_000_000
+    small = (logits[:8], cls[:8 * 64])                       # small enough: everything, in order
+    bench.dump_outputs(tmp_path / "c", small)
+    assert np.array_equal(np.load(tmp_path / "c" / "unet_logits.npy"), small[0].numpy())
+
+
 @pytest.mark.gpu
 def test_bench_line_contract_with_rccl_world_of_one():
     import socket
@@ -84,7 +110,7 @@ def test_bench_line_contract_with_rccl_world_of_one():
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         env.pop(k, None)
     out = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--boards", "64", "--steps", "1", "--warmup", "1",
-                          "--no-cpu-baseline", "--no-extras"], env=env, capture_output=True, text=True, timeout=900)
+                          "--no-cpu-baseline", "--no-extras", "--full"], env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-3000:]
     line = json.loads(out.stdout.strip().splitlines()[-1])
     assert line["n_gpus"] == 1 and line["rccl_ranks_seen"] == 1 and line["value"] > 0
@@ -104,6 +130,45 @@ def test_bench_line_contract_with_rccl_world_of_one():
 
 
 @pytest.mark.gpu
+def test_plain_run_prints_the_headline_and_dumps_the_last_step(tmp_path):
+    """Without --full: the headline line only (no roofline or oracle legs), `--steps` timed steps, and the outputs of the last one
+    as .npy files that match what the engine computes on the same seeded boards."""
+    import numpy as np
+
+    out = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "1", "--boards", "8", "--steps", "3", "--warmup", "1",
+                          "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=900)
+    assert out.returncode == 0, out.stderr[-3000:]
+    line = json.loads(out.stdout.strip().splitlines()[-1])
+    assert line["metric"] == "boards/sec (UNet 256x256 seg + 64-sq classify)" and line["unit"] == "boards/sec"
+    assert line["higher_is_better"] is True and line["dtype"] == "f16x3" and line["steps"] == 3 and line["warmup"] == 1
+    assert line["value"] > 0 and abs(line["value"] - 8 * 1e3 / line["ms_per_step"]) <= 1e-2 * line["value"]
+    assert not {"roofline", "roofline_hbm", "cpu_baseline", "parity_vs_oracle", "pipeline_e2e", "by_dtype"} & set(line)
+    u, r = np.load(tmp_path / "unet_logits.npy"), np.load(tmp_path / "resnet18_logits.npy")
+    assert u.shape == (8, 1, 256, 256) and r.shape == (8 * 64, 13) and u.dtype == r.dtype == np.float32
+    assert np.isfinite(u).all() and np.isfinite(r).all() and u.std() > 0 and r.std() > 0
+
+    from chessvision import synthetic
+    from chessvision.hip_backend import HipEngine
+
+    x = torch.empty((8, 3, 256, 256), device="cuda")
+    sq = torch.empty((8 * 64, 1, 64, 64), device="cuda")
+    gen = torch.Generator(device="cuda")
+    for k in range(8):                                       # bench.py's boards: board i from seed 1234 + i
+        gen.manual_seed(1234 + k)
+        x[k] = torch.randint(0, 256, (3, 256, 256), dtype=torch.uint8, device="cuda", generator=gen)
+        sq[k * 64:(k + 1) * 64] = torch.randint(0, 256, (64, 1, 64, 64), dtype=torch.uint8, device="cuda", generator=gen)
+    x /= 255.0
+    sq /= 255.0
+    eng = HipEngine(precision="f16x3", unet_chunk=64, resnet_chunk=16384)
+    eng.load_unet(synthetic.unet_state_dict(1))                # bench.py's weights
+    eng.load_resnet18(synthetic.resnet18_state_dict(2))
+    want_u, want_r = eng.unet_forward(x).cpu().numpy(), eng.resnet18_forward(sq).cpu().numpy()
+    eng.close()
+    assert np.abs(u - want_u).max() <= 1e-3 * max(1.0, np.abs(want_u).max())
+    assert np.abs(r - want_r).max() <= 1e-3 * max(1.0, np.abs(want_r).max())
+
+
+@pytest.mark.gpu
 def test_two_ranks_on_one_gpu_over_gloo_run_the_sharded_bench():
     """The N > 1 code path of bench.py on a one-GPU box: RCCL refuses two ranks per device, so CV_DIST_BACKEND=gloo carries the
     collectives (host buffers) while both ranks compute on the same MI355X.  `python bench.py --gpus 2` from a bare shell starts
@@ -114,7 +179,7 @@ def test_two_ranks_on_one_gpu_over_gloo_run_the_sharded_bench():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "LOCAL_WORLD_SIZE", "CV_FORCE_DIST")}
     env["CV_DIST_BACKEND"] = "gloo"
     out = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "2", "--boards", "256", "--steps", "1", "--warmup", "1",
-                          "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=2400)
+                          "--no-cpu-baseline", "--full"], env=env, capture_output=True, text=True, timeout=2400)
     assert out.returncode == 0, out.stderr[-4000:]
     lines = [ln for ln in out.stdout.strip().splitlines() if ln.startswith("{")]
     assert len(lines) == 1, out.stdout[-2000:]
@@ -142,7 +207,7 @@ def test_four_ranks_on_one_gpu_over_gloo():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "LOCAL_WORLD_SIZE", "CV_FORCE_DIST")}
     env["CV_DIST_BACKEND"] = "gloo"
     out = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "4", "--boards", "32", "--steps", "1", "--warmup", "1",
-                          "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=2400)
+                          "--no-cpu-baseline", "--full"], env=env, capture_output=True, text=True, timeout=2400)
     assert out.returncode == 0, out.stderr[-4000:]
     lines = [ln for ln in out.stdout.strip().splitlines() if ln.startswith("{")]
     assert len(lines) == 1, out.stdout[-2000:]
@@ -165,7 +230,7 @@ def test_eight_ranks_on_one_gpu_run_configs4_global_shape():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "LOCAL_WORLD_SIZE", "CV_FORCE_DIST")}
     env["CV_DIST_BACKEND"] = "gloo"
     out = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "8", "--boards", "256", "--steps", "1", "--warmup", "1",
-                          "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=3000)
+                          "--no-cpu-baseline", "--full"], env=env, capture_output=True, text=True, timeout=3000)
     assert out.returncode == 0, out.stderr[-4000:]
     lines = [ln for ln in out.stdout.strip().splitlines() if ln.startswith("{")]
     assert len(lines) == 1, out.stdout[-2000:]

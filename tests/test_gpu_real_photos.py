@@ -1,4 +1,4 @@
-"""GPU: eight of the reference's own test photos (data/test/*/raw, committed as tests/golden/photos8.npz by make_photos.py)
+"""GPU: eight of the reference's own test photos (data/test/*/raw, committed as tests/golden/photos8_{0..7}.npz by make_photos.py)
 through both CNNs and the batched pipeline, against the CPU oracle on the same arrays.
 
 Everything else in the suite feeds uniform noise or synthetic boards; these are real 512x512 camera images -- smooth regions,
@@ -19,14 +19,14 @@ from oracle.resnet_ref import ResNet18
 from oracle.unet_ref import UNet
 
 pytestmark = pytest.mark.gpu
-PHOTOS = Path(__file__).resolve().parent / "golden" / "photos8.npz"
+PHOTOS = [Path(__file__).resolve().parent / "golden" / f"photos8_{i}.npz" for i in range(8)]     # one photo per file (< 1 MiB each)
 
 
 @pytest.fixture(scope="module")
 def photos():
-    z = np.load(PHOTOS)
-    assert z["bgr"].shape == (8, 512, 512, 3) and z["bgr"].dtype == np.uint8
-    return [np.ascontiguousarray(im) for im in z["bgr"]]
+    bgr = np.concatenate([np.load(p)["bgr"] for p in PHOTOS])
+    assert bgr.shape == (8, 512, 512, 3) and bgr.dtype == np.uint8
+    return [np.ascontiguousarray(im) for im in bgr]
 
 
 @pytest.mark.parametrize("prec,tol", [("f16x3", 1e-3), ("f32", 1e-3)])

@@ -15,7 +15,7 @@ bash tools/pmc_sq2.sh "$OUT" f16x3 unet > "$OUT/pmc_sq2_unet.log" 2>&1
 for d in f16x3 f32 f16; do
   python3 tools/layer_profile.py --prec $d > "$OUT/layer_profile_$d.txt" 2>&1
 done
-python3 bench.py --unet-variant bilinear --no-cpu-baseline --no-extras > "$OUT/bench_bilinear.json" 2> "$OUT/bench_bilinear.err"
+python3 bench.py --unet-variant bilinear --no-cpu-baseline --no-extras --full > "$OUT/bench_bilinear.json" 2> "$OUT/bench_bilinear.err"
 python3 tools/latency.py > "$OUT/latency.txt" 2>&1
 python3 tools/e2e_profile.py > "$OUT/e2e_profile.txt" 2>&1
 # round 4: the single-board shape (what process_image runs) and the byte kernels

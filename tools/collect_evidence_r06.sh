@@ -6,7 +6,7 @@ OUT=${1:-gpurun_out/final6}
 mkdir -p "$OUT"
 export TMPDIR=/tmp
 # the default bench line (20 timed steps) -- the figures of profiles/README.md's first r06 row
-python3 bench.py --steps 20 --warmup 5 > "$OUT/bench_f16x3.json" 2> "$OUT/bench_f16x3_layers.txt"
+python3 bench.py --steps 20 --warmup 5 --full > "$OUT/bench_f16x3.json" 2> "$OUT/bench_f16x3_layers.txt"
 # position-major launches: same box, off / on, per launch (section 1 of r06_tuning.md)
 for prec in f16r f16x3 f32; do
   for pos in 0 1; do

@@ -7,7 +7,7 @@ OUT=${1:-gpurun_out/rocprof}; shift || true
 REPO=$(pwd); mkdir -p "$OUT"; export TMPDIR=/tmp
 STEPS=3; WARM=1
 rm -rf /tmp/rp_bench
-(cd /tmp && rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/rp_bench -o r -- python3 "$REPO/bench.py" --steps $STEPS --warmup $WARM --no-cpu-baseline --no-extras "$@" > "$REPO/$OUT/bench_under_rocprof.json" 2> "$REPO/$OUT/rocprof.err")
+(cd /tmp && rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/rp_bench -o r -- python3 "$REPO/bench.py" --steps $STEPS --warmup $WARM --no-cpu-baseline --no-extras --full "$@" > "$REPO/$OUT/bench_under_rocprof.json" 2> "$REPO/$OUT/rocprof.err")
 find /tmp/rp_bench -name '*kernel_stats.csv' -exec cp {} "$OUT/kernel_stats.csv" \;
 TRACE=$(find /tmp/rp_bench -name '*kernel_trace.csv' | head -1)
 python3 - "$TRACE" "$OUT/bench_under_rocprof.json" "$OUT/kernel_trace_reduced.json" $STEPS $WARM <<'PY'
@@ -28,7 +28,7 @@ by_kernel = {}
 for r in timed:
     k = r["Kernel_Name"].split("(")[0].replace("void cv::", "")
     a = by_kernel.setdefault(k, [0, 0.0]); a[0] += 1; a[1] += (int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e6
-res = {"command": "rocprofv3 --kernel-trace --stats -- python3 bench.py --steps %d --warmup %d --no-cpu-baseline --no-extras" % (steps, warm),
+res = {"command": "rocprofv3 --kernel-trace --stats -- python3 bench.py --steps %d --warmup %d --no-cpu-baseline --no-extras --full" % (steps, warm),
        "conv_launches_in_process": len(conv), "launches_per_step": per_step,
        "timed_region": {"conv_launches": len(timed), "conv_ms_total": dur(timed), "avg_launch_ms": dur(timed) / max(1, len(timed))},
        "event_timed_pass": {"conv_launches": len(prof), "avg_launch_ms": dur(prof) / max(1, len(prof))},
