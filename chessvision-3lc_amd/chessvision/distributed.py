@@ -353,7 +353,8 @@ def broadcast_state_dict(state: Mapping[str, np.ndarray] | None, spec: Sequence[
 
 def sync_calibration(engine, device: torch.device, models: Sequence[str] = ("unet", "resnet18"), src: int = 0) -> dict:
     """Make every rank compute with rank ``src``'s range calibration (the per-tensor power-of-two exponents the f16-based engines
-    choose at load time, ``HipEngine.export_calibration``): one small broadcast per model, imported on every rank.  The calibration
+    choose at load time, ``HipEngine.export_calibration``): one small broadcast per model, imported on every rank.  ``models`` names
+    "unet" and the loaded classifier's architecture (``("unet", "resnet34")`` for a ResNet-34 classifier).  The calibration
     pass is deterministic, so the vectors normally agree already; the broadcast makes divergence IMPOSSIBLE instead of unlikely
     (a rank with other exponents would still be correct to 1e-3 but no longer bit-identical to its peers).  Returns
     {"models": ..., "changed_here": bool, "identical_across_ranks": bool}; a world of one is a no-op."""

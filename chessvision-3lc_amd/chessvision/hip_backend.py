@@ -23,6 +23,7 @@ import torch
 _LIB_NAME = "libchessvision_hip.so"
 PREC_F32, PREC_F16, PREC_F16X3, PREC_F16R = 0, 1, 2, 3
 ABI_VERSION = 6
+RESNET_ARCHS = ("resnet18", "resnet34")     # piece classifiers with a HIP implementation (cv_load_resnet)
 _PRECISIONS = {"f32": PREC_F32, "fp32": PREC_F32, "float32": PREC_F32, "f16": PREC_F16, "fp16": PREC_F16,
                "float16": PREC_F16, "f16x3": PREC_F16X3, "split": PREC_F16X3, "f16r": PREC_F16R}
 _PREC_NAMES = {PREC_F32: "f32", PREC_F16: "f16", PREC_F16X3: "f16x3", PREC_F16R: "f16r"}
@@ -79,6 +80,7 @@ SYMBOLS = [
     ("cv_trim_memory", _i, [ctypes.POINTER(ctypes.c_size_t)]),
     ("cv_load_unet", _i, [_vp, ctypes.POINTER(_Param), _i]),
     ("cv_load_resnet18", _i, [_vp, ctypes.POINTER(_Param), _i]),
+    ("cv_load_resnet", _i, [_vp, ctypes.c_char_p, ctypes.POINTER(_Param), _i]),
     ("cv_engine_set_chunk", _i, [_vp, _i, _i]),
     ("cv_unet_forward", _i, [_vp, _vp, _i, _vp, _vp]),
     ("cv_resnet18_forward", _i, [_vp, _vp, _i, _vp, _vp]),
@@ -343,6 +345,7 @@ class HipEngine:
             _check(self._lib.cv_engine_set_chunk(self._h, unet_chunk, resnet_chunk))
         self.has_unet = False
         self.has_resnet = False
+        self.classifier_arch: str | None = None      # "resnet18" | "resnet34" once a ResNet is loaded
 
     # -- lifecycle ------------------------------------------------------------------------------
     def close(self) -> None:
@@ -363,11 +366,20 @@ class HipEngine:
         del keep
         self.has_unet = True
 
-    def load_resnet18(self, state_dict: Mapping[str, object]) -> None:
+    def load_resnet(self, state_dict: Mapping[str, object], arch: str = "resnet18") -> None:
+        """Pack a timm ResNet piece classifier (in_chans=1, 13 classes): ``arch`` is "resnet18" or "resnet34" and decides which keys
+        the state dict must hold -- exactly those, with their shapes.  The engine holds one ResNet; ``resnet18_forward`` and
+        ``resnet18_forward_u8`` run whichever is loaded."""
+        if arch not in RESNET_ARCHS:
+            raise HipBackendError(f"ResNet architecture must be one of {RESNET_ARCHS}, got {arch!r}")
         table, n, keep = _as_param_table(state_dict)
-        _check(self._lib.cv_load_resnet18(self._h, table, n))
+        _check(self._lib.cv_load_resnet(self._h, arch.encode(), table, n))
         del keep
         self.has_resnet = True
+        self.classifier_arch = arch
+
+    def load_resnet18(self, state_dict: Mapping[str, object]) -> None:
+        self.load_resnet(state_dict, "resnet18")
 
     # -- forward ----------------------------------------------------------------------------------
     def _dev_f32(self, x: torch.Tensor, shape_tail) -> torch.Tensor:
@@ -383,7 +395,8 @@ class HipEngine:
         _check(self._lib.cv_engine_numeric_status(self._h, _stream_ptr(self.device)))
 
     def export_calibration(self, model: str) -> np.ndarray:
-        """The load-time range calibration of ``model`` ("unet" | "resnet18") as an int32 vector (two exponents per tensor)."""
+        """The load-time range calibration of ``model`` ("unet" | the loaded ResNet's architecture) as an int32 vector (two exponents
+        per tensor)."""
         n = _i()
         _check(self._lib.cv_engine_export_calibration(self._h, model.encode(), None, 0, ctypes.byref(n)))
         out = np.zeros(n.value, dtype=np.int32)
@@ -417,7 +430,7 @@ class HipEngine:
         return out
 
     def resnet18_forward(self, x: torch.Tensor, check: bool = True) -> torch.Tensor:
-        """(N,1,64,64) float32 in [0,1] -> (N,13) float32 logits (device tensor)."""
+        """(N,1,64,64) float32 in [0,1] -> (N,13) float32 logits (device tensor) of the loaded ResNet (18 or 34)."""
         x = self._dev_f32(x, (1, 64, 64))
         out = torch.empty((x.shape[0], 13), dtype=torch.float32, device=self.device)
         _check(self._lib.cv_resnet18_forward(self._h, _ptr(x), x.shape[0], _ptr(out), _stream_ptr(self.device)))
@@ -438,7 +451,7 @@ class HipEngine:
         return logits, mask
 
     def resnet18_forward_u8(self, squares_u8: torch.Tensor) -> torch.Tensor:
-        """(N,64,64) uint8 -> (N,13) float32 softmax probabilities."""
+        """(N,64,64) uint8 -> (N,13) float32 softmax probabilities of the loaded ResNet (18 or 34)."""
         if squares_u8.dtype != torch.uint8 or tuple(squares_u8.shape[1:]) != (64, 64):
             raise HipBackendError("resnet18_forward_u8 expects (N,64,64) uint8")
         squares_u8 = squares_u8.to(self.device).contiguous()
@@ -628,9 +641,16 @@ class HipBoardExtractor(_HipModel):
 
 
 class HipPieceClassifier(_HipModel):
-    """ResNet-18 (1ch, 13 classes) forward on MI355X; drop-in for ``ChessVision.classifier`` (core.py:74-82,241)."""
+    """timm ResNet-18 or ResNet-34 (1ch, 13 classes) forward on MI355X; drop-in for ``ChessVision.classifier`` (core.py:74-82,241).
+    ``model_name`` is the architecture, which decides how a checkpoint is loaded (``utils.load_model_checkpoint``)."""
 
     model_name = "resnet18"
+
+    def __init__(self, engine: HipEngine, metadata: dict | None = None, arch: str = "resnet18"):
+        if arch not in RESNET_ARCHS:
+            raise HipBackendError(f"classifier architecture {arch!r} has no HIP implementation (supported: {', '.join(RESNET_ARCHS)})")
+        super().__init__(engine, metadata)
+        self.model_name = arch
 
     def __call__(self, batch: torch.Tensor) -> torch.Tensor:
         return self.engine.resnet18_forward(batch)

@@ -4,7 +4,7 @@
 Product-side and self-contained (does not import the test oracle).  The shape tables below ARE the
 checkpoint contract of the two models -- the same key names / shapes that
 ``scripts/train/train_unet.py:31-40`` and ``scripts/train/train_classifier.py:114-125`` write and that
-``cv_load_unet`` / ``cv_load_resnet18`` validate.  ``tests/test_synthetic.py`` checks them against the oracle's
+``cv_load_unet`` / ``cv_load_resnet`` validate.  ``tests/test_synthetic.py`` checks them against the oracle's
 module trees and checks that both generators agree bit for bit.
 
 Distribution: conv / linear weights He-normal (fan-in), BN gamma ~ U(0.5,1.5),
@@ -89,12 +89,24 @@ def unet_spec(bilinear: bool = False):
     return spec
 
 
+RESNET_DEPTHS = {"resnet18": (2, 2, 2, 2), "resnet34": (3, 4, 6, 3)}     # BasicBlocks per stage
+
+
 def resnet18_spec(num_classes: int = 13, in_chans: int = 1):
     """[(key, shape, kind)] of timm resnet18(num_classes, in_chans)."""
+    return _resnet_spec(RESNET_DEPTHS["resnet18"], num_classes, in_chans)
+
+
+def resnet34_spec(num_classes: int = 13, in_chans: int = 1):
+    """[(key, shape, kind)] of timm resnet34(num_classes, in_chans): ResNet(BasicBlock, layers=[3, 4, 6, 3]), otherwise resnet18's."""
+    return _resnet_spec(RESNET_DEPTHS["resnet34"], num_classes, in_chans)
+
+
+def _resnet_spec(depths, num_classes: int, in_chans: int):
     spec = [("conv1.weight", (64, in_chans, 7, 7), "conv")] + _bn("bn1", 64)
     cin = 64
-    for layer, width in enumerate([64, 128, 256, 512], start=1):
-        for block in range(2):
+    for layer, (width, depth) in enumerate(zip([64, 128, 256, 512], depths), start=1):
+        for block in range(depth):
             p = f"layer{layer}.{block}"
             stride = 2 if (block == 0 and layer > 1) else 1
             spec += [(f"{p}.conv1.weight", (width, cin, 3, 3), "conv")] + _bn(f"{p}.bn1", width)
@@ -198,8 +210,24 @@ def resnet18_state_dict(seed: int = 2):
     return _fill(resnet18_spec(), seed, residual_gamma=0.5)
 
 
-def save_checkpoints(directory, seed_unet: int = 1, seed_resnet: int = 2, bilinear: bool = False, segmenting: bool = False):
-    """Write random-init checkpoints in the reference's formats (train_unet.py:31-40, train_classifier.py:114-125)."""
+RESNET34_RESIDUAL_GAMMA = 0.35
+
+
+def resnet34_state_dict(seed: int = 2):
+    # bn2 gamma x 0.35 (ResNet-18: x 0.5) so that sixteen stacked residual adds keep activations O(1): on 256 test squares the RMS at
+    # the end of layer1..layer4 is 1.8 / 2.3 / 3.2 / 3.5 and the logits' standard deviation 1.6 (ResNet-18's state: 2.2).  At x 0.5
+    # the trunk doubles per stage (2.1 -> 9.6).
+    return _fill(resnet34_spec(), seed, residual_gamma=RESNET34_RESIDUAL_GAMMA)
+
+
+def resnet_state_dict(arch: str = "resnet18", seed: int = 2):
+    return {"resnet18": resnet18_state_dict, "resnet34": resnet34_state_dict}[arch](seed)
+
+
+def save_checkpoints(directory, seed_unet: int = 1, seed_resnet: int = 2, bilinear: bool = False, segmenting: bool = False,
+                     classifier_arch: str = "resnet18"):
+    """Write random-init checkpoints in the reference's formats (train_unet.py:31-40, train_classifier.py:114-125);
+    ``classifier_arch`` = "resnet18" | "resnet34" picks the piece classifier's architecture."""
     import torch
     from pathlib import Path
 
@@ -208,6 +236,6 @@ def save_checkpoints(directory, seed_unet: int = 1, seed_resnet: int = 2, biline
     meta = {"synthetic": True}
     torch.save({"model_state_dict": {k: torch.from_numpy(v) for k, v in unet_state_dict(seed_unet, bilinear, segmenting).items()},
                 "metadata": dict(meta, seed=seed_unet)}, d / "best_extractor.pth")
-    torch.save({"model_state_dict": {k: torch.from_numpy(v) for k, v in resnet18_state_dict(seed_resnet).items()},
+    torch.save({"model_state_dict": {k: torch.from_numpy(v) for k, v in resnet_state_dict(classifier_arch, seed_resnet).items()},
                 "optimizer_state_dict": {}, "metadata": dict(meta, seed=seed_resnet)}, d / "best_classifier.pth")
     return d / "best_extractor.pth", d / "best_classifier.pth"

@@ -2,7 +2,7 @@
 
 What differs from the reference: ``get_classifier_model`` / ``get_board_extractor_model`` do not build torch
 modules (timm / Pytorch-UNet) -- they return the HIP model objects of ``hip_backend`` -- and checkpoint loading
-yields a plain state dict that is packed by ``cv_load_unet`` / ``cv_load_resnet18`` instead of
+yields a plain state dict that is packed by ``cv_load_unet`` / ``cv_load_resnet`` instead of
 ``module.load_state_dict``.  The four checkpoint layouts accepted are those of ``utils.py:57-80``.
 """
 from __future__ import annotations
@@ -61,20 +61,44 @@ def load_model_checkpoint(model, checkpoint_path: str, device: torch.device | No
     if model.model_name == "unet":
         model.engine.load_unet(state)
     else:
-        model.engine.load_resnet18(state)
+        # the architecture comes from the model id, never from the checkpoint (reference core.py:139-146); a mismatch fails on the
+        # first key the other architecture lacks, and the message says which id the checkpoint needs
+        from .hip_backend import HipBackendError
+
+        try:
+            if model.model_name == "resnet18":
+                model.engine.load_resnet18(state)
+            else:
+                model.engine.load_resnet(state, model.model_name)
+        except HipBackendError as exc:
+            found = _resnet_arch_of(state)
+            if found and found != model.model_name:
+                raise HipBackendError(f"{exc} -- {checkpoint_path} holds a {found} state dict: load it with "
+                                      f"classifier_model_id={found!r}") from exc
+            raise
     if metadata:
         model.metadata = metadata
     return model
 
 
+def _resnet_arch_of(state: Mapping[str, Any]) -> str | None:
+    """Which plain BasicBlock ResNet a state dict looks like, by the depth of its stages (error messages only)."""
+    depth = []
+    for layer in range(1, 5):
+        blocks = {k.split(".")[1] for k in state if k.startswith(f"layer{layer}.") and k.split(".")[1].isdigit()}
+        depth.append(len(blocks))
+    return {(2, 2, 2, 2): "resnet18", (3, 4, 6, 3): "resnet34"}.get(tuple(depth))
+
+
 def get_classifier_model(model_id: str = "resnet18", engine=None):
     """The piece classifier architecture (reference utils.py:32-39: timm ``model_id``, 13 classes, 1 input channel).
-    Only ``resnet18`` has a HIP implementation."""
-    from .hip_backend import HipBackendError, HipPieceClassifier
+    ``resnet18`` and ``resnet34`` have a HIP implementation; ``""`` / None mean ``resnet18``."""
+    from .hip_backend import RESNET_ARCHS, HipBackendError, HipPieceClassifier
 
-    if model_id not in ("resnet18", "", None):
-        raise HipBackendError(f"classifier architecture {model_id!r} has no HIP implementation (resnet18 only)")
-    return HipPieceClassifier(engine)
+    arch = model_id or "resnet18"
+    if arch not in RESNET_ARCHS:
+        raise HipBackendError(f"classifier architecture {model_id!r} has no HIP implementation (supported: {', '.join(RESNET_ARCHS)})")
+    return HipPieceClassifier(engine, arch=arch)
 
 
 def get_board_extractor_model(engine=None):

@@ -45,17 +45,20 @@ namespace cv {
 #endif
 constexpr int halo_waves_per_eu(int ct, int th, bool dbh, int chain = 0) { return chain == 1 ? 1 : (CV_HALO_TH8_SINGLE && ct == 64 && th == 8 && !dbh) ? 3 : 2; }
 // CHAIN (single halo buffer, f16, 64 -> 64 channels, 16 x 16 maps = one patch per image): the "channel blocks" of the K loop are
-// FOUR CONVOLUTIONS in a row (ResNet-18 layer1 = two BasicBlocks).  At every block boundary the epilogue of convolution c -- BN,
+// 2 CNB CONVOLUTIONS in a row (CNB = 2: ResNet-18 layer1 = two BasicBlocks; CNB = 3: ResNet-34 layer1).  At every block boundary the
+// epilogue of convolution c -- BN,
 // (+ f32 residual), ReLU -- rounds to f16 and writes the result over the halo buffer IN PLACE (every wave has drained its reads of
 // it by then; the zero border stays), which is then the resident input of convolution c + 1; the weight stream simply continues.
-// The three intermediate tensors never travel to HBM as f16; the f32 trunk twin does (written after convolution 1, read back by
-// the same lanes after convolution 3): round 5, profiles/r05_tuning.md.  CHAIN = 2: that form, two workgroups per CU.  CHAIN = 1: ONE
-// workgroup per CU with 512 registers per lane -- the f32 residual of the whole tile (64 registers) is fetched at kernel start and stays in
-// registers through both blocks, so the first block's output never leaves the chip and no epilogue waits for a load.
-template <typename T, int CT, int TH, int WGC, int NW, int TPS, int NSW, int IMG, bool PERSIST, bool DBH = true, bool FUSE0 = false, int CHAIN = 0>
+// The intermediate tensors never travel to HBM as f16; the f32 trunk twin does (block k's output written after convolution 2 k + 1,
+// read back by the same lanes after convolution 2 k + 3): round 5, profiles/r05_tuning.md.  CHAIN = 2: that form, two workgroups per CU.
+// CHAIN = 1: ONE workgroup per CU with 512 registers per lane -- the f32 residual of the whole tile (64 registers) is fetched at kernel
+// start and stays in registers through every block, so the inner blocks' outputs never leave the chip and no epilogue waits for a load.
+template <typename T, int CT, int TH, int WGC, int NW, int TPS, int NSW, int IMG, bool PERSIST, bool DBH = true, bool FUSE0 = false, int CHAIN = 0,
+          int CNB = 2>
 __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(halo_waves_per_eu(CT, TH, DBH, CHAIN), halo_waves_per_eu(CT, TH, DBH, CHAIN)))) void conv3x3_halo_kernel(const ConvParams p) {
     static_assert(!FUSE0 || (!DBH && !PERSIST && IMG == 0 && CT == 64 && NW == 4 && __is_same(T, split_t)), "fused producer: split-f16 64-channel single-halo tile");
     static_assert(!CHAIN || (!DBH && !PERSIST && !FUSE0 && IMG == 0 && CT == 64 && TH == 16 && NW == 4 && __is_same(T, half_t)), "chained convolutions: f16 64-channel single-halo tile over whole 16 x 16 images");
+    static_assert(CNB == 2 || (CHAIN && CNB == 3), "two or three chained BasicBlocks");
     static_assert(TPS == 1 && (NSW == 3 || NSW == 4), "stage shape");
     constexpr int SPC = 9 / TPS;                        // stages per channel block
     constexpr int WGP = NW / WGC;                       // wave groups along the patch rows
@@ -432,8 +435,8 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(halo_wa
     // ---- CHAIN: epilogue of convolution c, straight from the accumulator layout -------------------------------------
     // lane (q, l15) holds channels 16 q .. 16 q + 15 of the pixels (patch row wrow0 + g, column l15), g = 0 .. FP-1: 64 contiguous
     // bytes of an f32 plane / 32 of an f16 plane / two 16-byte chunks of the pixel's halo row per g.
-    constexpr int kChainStores = CHAIN == 2 ? 4 * FP : 0;       // f32 stores of convolution 1's epilogue (vmcnt bookkeeping)
-    f4 rtrunk[CHAIN == 1 ? FP : 1][4];                          // CHAIN 1: the f32 trunk of this lane's outputs (input twin, then block 0's output)
+    constexpr int kChainStores = CHAIN == 2 ? 4 * FP : 0;       // f32 stores of an inner block's epilogue (vmcnt bookkeeping)
+    f4 rtrunk[CHAIN == 1 ? FP : 1][4];                          // CHAIN 1: the f32 trunk of this lane's outputs (input twin, then each block's output)
     auto chain_load_trunk = [&]() __attribute__((always_inline)) {
         if constexpr (CHAIN == 1) {
             const float* const rb = reinterpret_cast<const float*>(p.ch_res0) + q * 16;
@@ -466,7 +469,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(halo_wa
                 sh[i] = b[0]; sh[i + 1] = b[1]; sh[i + 2] = b[2]; sh[i + 3] = b[3];
             }
             const float* const rb = reinterpret_cast<const float*>(p.ch_res0);
-            float* const ob32 = reinterpret_cast<float*>(p.ch_y32_mid);
+            float* const ob32 = reinterpret_cast<float*>(p.ch_y32_mid[0]);
             const float rm = p.ch_res_mul[0];
             // padded-plane pixel of (patch row wrow0 + g, column px) of image n
             auto pixel = [&](int g, int px) __attribute__((always_inline)) { return (unsigned)((n * p.yHp + wrow0 + g + 1) * p.yWp + px + 1); };
@@ -549,7 +552,8 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(halo_wa
     auto chain_epilogue = [&](int c) __attribute__((always_inline)) {
         if constexpr (CHAIN) {
             if (CHAIN == 2 && CV_CHAIN_MIDSTAGE_BUILD && c == 1 && (p.chain & 16)) { chain_epilogue_res_mid(); return; }
-            const bool has_res = (c & 1) != 0, last = c == 3;   // wave-uniform
+            const bool has_res = (c & 1) != 0, last = c == 2 * CNB - 1;   // wave-uniform
+            const int blk = c >> 1;                             // the BasicBlock convolution c belongs to
             const float* const scp = p.ch_scale[c] + q * 16;
             const float* const shp = p.ch_shift[c] + q * 16;
             float sc[16], sh[16];
@@ -565,14 +569,14 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(halo_wa
             // residual: two patch rows in flight (the whole tile's 64 registers do not fit beside the accumulators and the next
             // stage's weight fragments)
             f4 r[2][4];
-            const float* const rb = reinterpret_cast<const float*>(last ? p.ch_y32_mid : p.ch_res0) + q * 16;
+            const float* const rb = reinterpret_cast<const float*>(blk == 0 ? p.ch_res0 : p.ch_y32_mid[blk - 1]) + q * 16;
             auto fetch_res = [&](int g) __attribute__((always_inline)) {
 #pragma unroll
                 for (int f = 0; f < 4; ++f) r[g & 1][f] = *reinterpret_cast<const f4*>(rb + (size_t)(pix0 + (unsigned)(g * p.yWp)) * 64 + f * 4);
             };
             if (CHAIN == 2 && has_res) fetch_res(0);
-            const float rm = p.ch_res_mul[c >> 1];
-            float* const o32 = reinterpret_cast<float*>(last ? p.y32 : p.ch_y32_mid) + q * 16;
+            const float rm = p.ch_res_mul[blk];
+            float* const o32 = reinterpret_cast<float*>(has_res && !last ? p.ch_y32_mid[blk] : p.y32) + q * 16;   // (blk <= CNB - 2 there)
             half_t* const o16 = reinterpret_cast<half_t*>(p.y) + q * 16;
             const int hx = l15 + 1;
             float bad = 0.f;
@@ -592,7 +596,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(halo_wa
                         }
                         v[f * 4 + k] = __builtin_fmaxf(t, 0.f);
                         if constexpr (CHAIN == 1) {
-                            if (has_res) rtrunk[g][f][k] = v[f * 4 + k];   // block 0's output (stored units of ITS exponent) is block 1's residual
+                            if (has_res) rtrunk[g][f][k] = v[f * 4 + k];   // block k's output (stored units of ITS exponent) is block k + 1's residual
                         }
                     }
                 half8 h0, h1;
@@ -670,9 +674,9 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(halo_wa
         // next block's pixel reads start in the head of tap 8).
         // the next halo is younger than W(s+1): double buffered, issued at tap 0; single buffer, issued at tap 7
         const bool halo_young = !kRoles && !FUSE0 && !CHAIN && more_cb && (DBH ? (J >= 1 && J <= NSW - 1) : J == 8);
-        // CHAIN: the sixteen f32 stores of convolution 1's epilogue are younger than the weight stage issued in its tap 8 and older than
-        // the one issued in tap 0 of convolution 2: the first two barriers of convolution 2 may leave them in flight as well
-        const bool chain_young = CHAIN == 2 && J <= 1 && cb == 2;
+        // CHAIN: the sixteen f32 stores of an inner block's epilogue (convolution 2 k + 1) are younger than the weight stage issued in its
+        // tap 8 and older than the one issued in tap 0 of convolution 2 k + 2: the first two barriers of that one may leave them in flight as well
+        const bool chain_young = CHAIN == 2 && J <= 1 && cb >= 2 && (cb & 1) == 0;
 #if CV_STAMP
         const unsigned long long st_a = __builtin_amdgcn_s_memtime();
 #endif
@@ -809,13 +813,14 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(halo_wa
         o[4] = st_head; o[5] = st_t0 - st_k0; o[6] = st_tail;
     }
 #endif
-    if constexpr (CHAIN == 1) {                          // convolution 3 from the trunk registers: + block 0's output, ReLU -> f32 twin and f16 copy
-        chain_epilogue(3);
+    if constexpr (CHAIN == 1) {                          // the last convolution from the trunk registers: + the previous block's output, ReLU -> f32 twin and f16 copy
+        chain_epilogue(2 * CNB - 1);
         return;
     }
-    // CHAIN == 2: convolution 3 leaves through the ordinary epilogue below -- the ring and the halo are dead now, so its LDS-staged
-    // full-line stores and its residual burst apply; the host points scale / shift / res / res_mul at convolution 3's constants and at
-    // block 0's f32 output (written by this workgroup's convolution-1 epilogue, complete long ago: 18 stages of counted waits lie between)
+    // CHAIN == 2: the last convolution leaves through the ordinary epilogue below -- the ring and the halo are dead now, so its LDS-staged
+    // full-line stores and its residual burst apply; the host points scale / shift / res / res_mul at that convolution's constants and at
+    // the previous block's f32 output (written by this workgroup's epilogue of convolution 2 CNB - 3, complete long ago: 18 stages of counted
+    // waits lie between)
     // the epilogue works on the tile just finished; the DMA side moves on to the next one
     const int eCt = ctTile, eTx = tx, eTy = ty, eN = n;
     const unsigned nxt_tile = tile + nwg;
@@ -1209,6 +1214,10 @@ hipError_t conv_halo_prepare() {
                                  hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)) != hipSuccess) return e;
     if ((e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv3x3_halo_kernel<half_t, 64, 16, 1, 4, 1, 3, 0, false, false, false, 2>),
                                  hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)) != hipSuccess) return e;
+    if ((e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv3x3_halo_kernel<half_t, 64, 16, 1, 4, 1, 3, 0, false, false, false, 1, 3>),
+                                 hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)) != hipSuccess) return e;
+    if ((e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv3x3_halo_kernel<half_t, 64, 16, 1, 4, 1, 3, 0, false, false, false, 2, 3>),
+                                 hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)) != hipSuccess) return e;
 #endif
     return hipSuccess;
 }
@@ -1228,17 +1237,22 @@ bool conv_halo_supported(int ct, int Ho, int Wo) {
 
 bool conv_halo_has_th8(int ct) { return ct == 64 && CV_HALO_TH64 == 16; }
 
-// four chained 64 -> 64 convolutions on whole 16 x 16 images (ConvParams::chain): one workgroup per image, 69.6 KB of LDS
+// four or six chained 64 -> 64 convolutions (two or three BasicBlocks) on whole 16 x 16 images (ConvParams::chain): one workgroup per
+// image, 69.6 KB of LDS
 bool conv_halo_has_chain() { return CV_HALO_TH64 == 16 && CV_HALO_NSW64 == 3; }
 hipError_t conv_halo_chain_launch(const ConvParams& p, int n_images, hipStream_t stream) {
 #if CV_HALO_TH64 == 16 && CV_HALO_NSW64 == 3
-    if (!p.chain || p.nStages != 36 || p.Ho != 16 || p.Wo != 16 || p.yCs != 64 || p.xCs != 64 || p.ksplit > 1 || n_images < 1) return hipErrorInvalidValue;
+    if (!p.chain || (p.nStages != 36 && p.nStages != 54) || p.Ho != 16 || p.Wo != 16 || p.yCs != 64 || p.xCs != 64 || p.ksplit > 1 || n_images < 1)
+        return hipErrorInvalidValue;
     const size_t lds = halo_lds<64, 16, 4, 1, 3, 0>();
+    const bool three = p.nStages == 54;
     if ((p.chain & 3) == 1) {                            // one workgroup per CU (its 512 registers per lane see to that)
-        auto kern = conv3x3_halo_kernel<half_t, 64, 16, 1, 4, 1, 3, 0, false, false, false, 1>;
+        auto kern = three ? conv3x3_halo_kernel<half_t, 64, 16, 1, 4, 1, 3, 0, false, false, false, 1, 3>
+                          : conv3x3_halo_kernel<half_t, 64, 16, 1, 4, 1, 3, 0, false, false, false, 1>;
         hipLaunchKernelGGL(kern, dim3((unsigned)n_images), dim3(256), lds, stream, p);
     } else {
-        auto kern = conv3x3_halo_kernel<half_t, 64, 16, 1, 4, 1, 3, 0, false, false, false, 2>;
+        auto kern = three ? conv3x3_halo_kernel<half_t, 64, 16, 1, 4, 1, 3, 0, false, false, false, 2, 3>
+                          : conv3x3_halo_kernel<half_t, 64, 16, 1, 4, 1, 3, 0, false, false, false, 2>;
         hipLaunchKernelGGL(kern, dim3((unsigned)n_images), dim3(256), lds, stream, p);
     }
     return hipGetLastError();

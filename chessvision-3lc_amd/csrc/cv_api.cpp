@@ -183,16 +183,31 @@ static int impl_cv_load_unet(cv_engine_t* eng, const cv_param_t* params, int n_p
     return finish(s);
 }
 
-static int impl_cv_load_resnet18(cv_engine_t* eng, const cv_param_t* params, int n_params) {
+static int impl_cv_load_resnet(cv_engine_t* eng, const char* arch, const cv_param_t* params, int n_params) {
     Status s = check_engine(eng);
     if (!s.ok()) return finish(s);
+    if (!arch || !resnet_arch(arch))
+        return finish(fail(CV_ERR_INVALID, "cv_load_resnet: arch must be 'resnet18' or 'resnet34', got " +
+                                               (arch ? "'" + std::string(arch) + "'" : std::string("NULL"))));
     std::lock_guard<std::mutex> load_lk(load_mutex());
     std::lock_guard<std::mutex> lk(eng->impl.mu);
     DeviceGuard g(eng->impl.device);
     ParamMap pm;
     s = to_map(params, n_params, pm);
-    if (s.ok()) s = resnet_load(eng->impl, pm);
+    if (s.ok()) s = resnet_load(eng->impl, pm, arch);
     return finish(s);
+}
+
+// by-name entry points: "unet" | the loaded ResNet's architecture name.  Sets *is_resnet; a known name of a model that is not the loaded
+// one fails with CV_ERR_STATE naming what is loaded, an unknown name with CV_ERR_INVALID.
+static Status model_by_name(const Engine& e, const char* model, bool* is_resnet) {
+    *is_resnet = false;
+    if (std::strcmp(model, "unet") == 0) return Status();
+    if (!resnet_arch(model)) return fail(CV_ERR_INVALID, "model must be 'unet', 'resnet18' or 'resnet34'");
+    *is_resnet = true;
+    if (e.resnet && std::strcmp(e.resnet->arch->name, model) != 0)
+        return fail(CV_ERR_STATE, "model '" + std::string(model) + "' is not loaded: this engine holds " + e.resnet->arch->name);
+    return Status();
 }
 
 static int impl_cv_unet_forward(cv_engine_t* eng, const float* x, int batch, float* logits, void* stream) {
@@ -248,9 +263,9 @@ static int impl_cv_get_activation(cv_engine_t* eng, const char* model, const cha
     std::lock_guard<std::mutex> lk(eng->impl.mu);
     DeviceGuard g(eng->impl.device);
     TensorRef t;
-    if (std::strcmp(model, "unet") == 0) s = unet_activation(eng->impl, name, &t);
-    else if (std::strcmp(model, "resnet18") == 0) s = resnet_activation(eng->impl, name, &t);
-    else s = fail(CV_ERR_INVALID, "model must be 'unet' or 'resnet18'");
+    bool is_resnet = false;
+    s = model_by_name(eng->impl, model, &is_resnet);
+    if (s.ok()) s = is_resnet ? resnet_activation(eng->impl, name, &t) : unet_activation(eng->impl, name, &t);
     if (!s.ok()) return finish(s);
     dims[0] = t.N; dims[1] = t.C; dims[2] = t.H; dims[3] = t.W;
     const size_t numel = (size_t)t.N * t.C * t.H * t.W;
@@ -270,9 +285,10 @@ static int impl_cv_model_macs(cv_engine_t* eng, const char* model, int64_t* macs
     Status s = check_engine(eng);
     if (!s.ok()) return finish(s);
     if (!model || !macs) return finish(fail(CV_ERR_INVALID, "null argument"));
-    if (std::strcmp(model, "unet") == 0) *macs = unet_macs(eng->impl);
-    else if (std::strcmp(model, "resnet18") == 0) *macs = resnet_macs(eng->impl);
-    else return finish(fail(CV_ERR_INVALID, "model must be 'unet' or 'resnet18'"));
+    bool is_resnet = false;
+    s = model_by_name(eng->impl, model, &is_resnet);
+    if (!s.ok()) return finish(s);
+    *macs = is_resnet ? resnet_macs(eng->impl) : unet_macs(eng->impl);
     if (*macs == 0) return finish(fail(CV_ERR_STATE, "model not loaded"));
     return CV_OK;
 }
@@ -285,9 +301,12 @@ static int impl_cv_profile_convs(cv_engine_t* eng, const char* model, const void
     std::lock_guard<std::mutex> lk(eng->impl.mu);
     DeviceGuard g(eng->impl.device);
     Engine& e = eng->impl;
+    bool is_resnet = false;
+    s = model_by_name(e, model, &is_resnet);
+    if (!s.ok()) return finish(s);
     e.prof_clear();
     e.profiling = true;
-    const bool is_unet = std::strcmp(model, "unet") == 0;
+    const bool is_unet = !is_resnet;
     for (int i = 0; i < iters && s.ok(); ++i) {
         if (is_unet) s = unet_forward(e, x, false, batch, (float*)out, nullptr, 0.5f, (hipStream_t)stream);
         else s = resnet_forward(e, x, false, batch, (float*)out, false, (hipStream_t)stream);
@@ -556,9 +575,12 @@ static int impl_cv_engine_calibration(cv_engine_t* eng, const char* model, int32
     DeviceGuard g(eng->impl.device);
     Engine& e = eng->impl;
     std::vector<Activation*>* acts = nullptr;
-    if (std::strcmp(model, "unet") == 0 && e.unet) acts = &e.unet->acts;
-    else if (std::strcmp(model, "resnet18") == 0 && e.resnet) acts = &e.resnet->acts;
-    else return finish(fail(CV_ERR_STATE, "model must be a loaded 'unet' or 'resnet18'"));
+    bool is_resnet = false;
+    s = model_by_name(e, model, &is_resnet);
+    if (!s.ok()) return finish(s.code == CV_ERR_INVALID ? fail(CV_ERR_STATE, "model must be a loaded 'unet', 'resnet18' or 'resnet34'") : s);
+    if (!is_resnet && e.unet) acts = &e.unet->acts;
+    else if (is_resnet && e.resnet) acts = &e.resnet->acts;
+    else return finish(fail(CV_ERR_STATE, "model must be a loaded 'unet', 'resnet18' or 'resnet34'"));
     const int n = 2 * (int)acts->size();
     if (!import) {
         *count = n;
@@ -804,9 +826,9 @@ static int impl_cv_get_activation_exponent(cv_engine_t* eng, const char* model, 
     if (!model || !name || !exponent) return finish(fail(CV_ERR_INVALID, "null argument"));
     std::lock_guard<std::mutex> lk(eng->impl.mu);
     TensorRef t;
-    if (std::strcmp(model, "unet") == 0) s = unet_activation(eng->impl, name, &t);
-    else if (std::strcmp(model, "resnet18") == 0) s = resnet_activation(eng->impl, name, &t);
-    else s = fail(CV_ERR_INVALID, "model must be 'unet' or 'resnet18'");
+    bool is_resnet = false;
+    s = model_by_name(eng->impl, model, &is_resnet);
+    if (s.ok()) s = is_resnet ? resnet_activation(eng->impl, name, &t) : unet_activation(eng->impl, name, &t);
     if (!s.ok()) return finish(s);
     *exponent = t.exp;
     return CV_OK;
@@ -905,8 +927,12 @@ int cv_load_unet(cv_engine_t* eng, const cv_param_t* params, int n_params) {
     return guarded("cv_load_unet", [&]() -> int { return impl_cv_load_unet(eng, params, n_params); });
 }
 
+int cv_load_resnet(cv_engine_t* eng, const char* arch, const cv_param_t* params, int n_params) {
+    return guarded("cv_load_resnet", [&]() -> int { return impl_cv_load_resnet(eng, arch, params, n_params); });
+}
+
 int cv_load_resnet18(cv_engine_t* eng, const cv_param_t* params, int n_params) {
-    return guarded("cv_load_resnet18", [&]() -> int { return impl_cv_load_resnet18(eng, params, n_params); });
+    return guarded("cv_load_resnet18", [&]() -> int { return impl_cv_load_resnet(eng, "resnet18", params, n_params); });
 }
 
 int cv_unet_forward(cv_engine_t* eng, const float* x, int batch, float* logits, void* stream) {

@@ -143,19 +143,20 @@ struct ConvParams {
     float* partial;
     int ksplit, kper;
     int prow;                 // channels per pixel row of `partial` (= padded GEMM rows)
-    // CHAIN launch of conv_halo.hip (f16r ResNet-18 layer1: four 3x3 convolutions 64 -> 64 on 16 x 16 maps = two BasicBlocks in ONE
-    // launch, the image resident in LDS between them): `w` holds the 36 weight stages of convolutions 0..3 back to back, `x` is the
-    // f16 copy of the trunk entering the stage.  Convolution c = 0, 2: relu(bn(conv)) stays in LDS as f16.  c = 1: + ch_res0
-    // (f32 twin of the input) * ch_res_mul[0], ReLU -> f32 to ch_y32_mid (the first block's output twin) and f16 into LDS.
-    // c = 3: + ch_y32_mid * ch_res_mul[1], ReLU -> y32 (f32 twin) and y (f16 copy).  All tensors 18 x 18 x 64 padded planes.
+    // CHAIN launch of conv_halo.hip (f16r ResNet layer1: 2 nb 3x3 convolutions 64 -> 64 on 16 x 16 maps = nb = 2 | 3 BasicBlocks in ONE
+    // launch, the image resident in LDS between them): `w` holds the 18 nb weight stages of convolutions 0 .. 2 nb - 1 back to back
+    // (nStages = 18 nb), `x` is the f16 copy of the trunk entering the stage.  Convolution c = 2 k: relu(bn(conv)) stays in LDS as f16.
+    // c = 2 k + 1 < 2 nb - 1: + the block's residual (ch_res0 = f32 twin of the input for k = 0, else ch_y32_mid[k - 1]) * ch_res_mul[k],
+    // ReLU -> f32 to ch_y32_mid[k] (block k's output twin) and f16 into LDS.  c = 2 nb - 1: + ch_y32_mid[nb - 2] * ch_res_mul[nb - 1],
+    // ReLU -> y32 (f32 twin) and y (f16 copy).  All tensors 18 x 18 x 64 padded planes.
     int chain;                // 0 = off | 2 = the form described above, two workgroups per CU | 1 = one workgroup per CU, 512 registers: the
-                              // f32 trunk stays in registers through both blocks (ch_y32_mid is not touched)
-    const float* ch_scale[4]; // per-convolution epilogue constants (range factors folded, as `scale` / `shift`)
-    const float* ch_shift[4];
+                              // f32 trunk stays in registers through every block (ch_y32_mid is not touched)
+    const float* ch_scale[6]; // per-convolution epilogue constants (range factors folded, as `scale` / `shift`)
+    const float* ch_shift[6];
     const char* ch_res0;
-    char* ch_y32_mid;
-    float ch_res_mul[2];
-    unsigned ch_layer_id[4];  // numeric-guard ids of the four convolutions
+    char* ch_y32_mid[2];
+    float ch_res_mul[3];
+    unsigned ch_layer_id[6];  // numeric-guard ids of the chained convolutions
     // POSITION-MAJOR launch (conv_igemm_kernel<..., POS = true>; round 6: 3x3 layers on the 2x2 / 4x4 / 8x8 maps of ResNet-18 at
     // throughput batch sizes).  GEMM rows are ordered [output position][image] instead of [image][position], so all rows of a pixel
     // tile share ONE output position (oy, ox) and therefore one set of taps that read a real pixel: the K loop walks only those

@@ -379,7 +379,7 @@ Status unet_forward(Engine& e, const void* x, bool x_u8, int batch, float* logit
 Status unet_activation(Engine& e, const std::string& name, TensorRef* out);
 int64_t unet_macs(Engine& e);
 
-Status resnet_load(Engine& e, const ParamMap& pm);
+Status resnet_load(Engine& e, const ParamMap& pm, const std::string& arch);   // arch: "resnet18" | "resnet34"
 Status resnet_forward(Engine& e, const void* x, bool x_u8, int n, float* out, bool softmax, hipStream_t s);
 Status resnet_activation(Engine& e, const std::string& name, TensorRef* out);
 int64_t resnet_macs(Engine& e);

@@ -38,7 +38,15 @@ struct Engine::UNet {
     int64_t macs = 0;
 };
 
+// timm's plain BasicBlock ResNets: the same stem, stage widths, shortcuts and head; only the number of blocks per stage differs
+struct ResNetArch {
+    const char* name;
+    int depth[4];                                   // BasicBlocks per stage (layer1..layer4)
+};
+const ResNetArch* resnet_arch(const std::string& name);   // "resnet18" {2,2,2,2} | "resnet34" {3,4,6,3}; null otherwise
+
 struct Engine::ResNet {
+    const ResNetArch* arch = nullptr;
     int cap = 0;
     int max_cap = 16384;
     int last_n = 0;
@@ -57,12 +65,17 @@ struct Engine::ResNet {
         std::vector<float> h_sc_scale, h_sc_shift;   // BN affine with the weight rows' exponents folded in
         int sc_in_exp = 1 << 20, sc_out_exp = 1 << 20;   // exponents the device copies are folded for
         unsigned sc_id = 0;
-    } blocks[8];
+    };
+    std::unique_ptr<Block[]> blocks;                // layer1.0 .. layer4.(depth[3]-1), stage by stage
+    int nblocks = 0;
+    int first[5] = {0, 0, 0, 0, 0};                 // index of stage l's first block (first[4] = nblocks)
     Activation stem_out, pool_out;
-    // f16r: layer1 (two BasicBlocks = four 3x3 convolutions 64 -> 64 on 16 x 16 maps) as ONE launch with the image resident in LDS
-    // (conv_halo.hip: CHAIN).  chain_w = the four layers' packed weight stages back to back.  CV_RESNET_CHAIN=0 switches it off.
+    // f16r: the first chain_nb BasicBlocks of layer1 (2 * chain_nb 3x3 convolutions 64 -> 64 on 16 x 16 maps, chain_nb = 2 | 3) as ONE
+    // launch with the image resident in LDS (conv_halo.hip: CHAIN).  chain_w = those layers' packed weight stages back to back.
+    // CV_RESNET_CHAIN=0 switches it off; CV_RESNET_CHAIN_BLOCKS=2 chains two blocks of a three-block layer1 (the third runs layer by layer).
     DeviceBuffer chain_w;
     bool chain_ok = false;
+    int chain_nb = 0;
     std::vector<Activation*> acts;
     std::map<std::string, TensorRef> taps;
     int64_t macs = 0;

@@ -1,8 +1,9 @@
-// resnet.cpp -- timm ResNet-18 (in_chans=1, num_classes=13) plan: packing + forward schedule.
+// resnet.cpp -- timm ResNet-18 / ResNet-34 (in_chans=1, num_classes=13) plan: packing + forward schedule.
 //
 // Module tree per notebooks/model-summary.ipynb (reference) / SURVEY.md Appendix B:
-//   conv1 7x7 s2 p3 -> bn1 -> ReLU -> maxpool 3x3 s2 p1 -> layer1..4 (2 BasicBlocks each; first block of
-//   layer2-4 has stride 2 and a [conv1x1 s2, BN] shortcut) -> global avg pool -> fc 512 -> 13.
+//   conv1 7x7 s2 p3 -> bn1 -> ReLU -> maxpool 3x3 s2 p1 -> layer1..4 (BasicBlocks: {2,2,2,2} for resnet18, {3,4,6,3} for
+//   resnet34; first block of layer2-4 has stride 2 and a [conv1x1 s2, BN] shortcut) -> global avg pool -> fc 512 -> 13.
+// Everything below that depends on the depth (keys, taps, MACs, calibration, the chained layer1) is derived from ResNetArch.
 // BasicBlock = conv1-bn1-ReLU-conv2-bn2-(+shortcut)-ReLU: both BNs, the residual add and both ReLUs are conv
 // epilogues here; the squares of many boards are batched so the 2x2 / 4x4 stages still form large GEMMs.
 #include <cmath>
@@ -21,6 +22,14 @@ Status build_conv_bn_public(Engine& e, ConvLayer& L, const ParamMap& pm, const s
 Status need_public(const ParamMap& pm, const std::string& key, std::vector<int64_t> shape, const float** out);
 Status bn_fold_public(const ParamMap& pm, const std::string& prefix, int c, std::vector<float>& scale, std::vector<float>& shift);
 Status reject_unknown_keys_public(const ParamMap& pm, const std::vector<std::string>& known, const char* model);
+
+static const ResNetArch kResNetArchs[] = {{"resnet18", {2, 2, 2, 2}}, {"resnet34", {3, 4, 6, 3}}};
+
+const ResNetArch* resnet_arch(const std::string& name) {
+    for (const ResNetArch& a : kResNetArchs)
+        if (name == a.name) return &a;
+    return nullptr;
+}
 
 static Status resnet_reserve(Engine& e, int n);
 static Status layer1_chain(Engine& e, int n, hipStream_t s);
@@ -59,9 +68,15 @@ static Status stem_set_exp(Engine::ResNet& R, int dt, int out_exp, hipStream_t s
     return Status();
 }
 
-Status resnet_load(Engine& e, const ParamMap& pm) {
+Status resnet_load(Engine& e, const ParamMap& pm, const std::string& arch) {
+    const ResNetArch* A = resnet_arch(arch);
+    if (!A) return fail(1, "unknown ResNet architecture '" + arch + "' (supported: 'resnet18', 'resnet34')");
     auto m = std::make_unique<Engine::ResNet>();
     Engine::ResNet& R = *m;
+    R.arch = A;
+    for (int l = 0; l < 4; ++l) R.first[l + 1] = R.first[l] + A->depth[l];
+    R.nblocks = R.first[4];
+    R.blocks.reset(new Engine::ResNet::Block[R.nblocks]);
     const int dt = e.dt;
     CV_TRY(e.guard_init());
     // the f32 engine materialises the 32x32x64 stem output (34 x 34 x 64 x 4 B per square with its border): keep that
@@ -127,8 +142,8 @@ Status resnet_load(Engine& e, const ParamMap& pm) {
     int cin = 64;
     int64_t macs = 49LL * 64 * 32 * 32;
     for (int l = 0; l < 4; ++l) {
-        for (int bi = 0; bi < 2; ++bi) {
-            Engine::ResNet::Block& B = R.blocks[l * 2 + bi];
+        for (int bi = 0; bi < A->depth[l]; ++bi) {
+            Engine::ResNet::Block& B = R.blocks[R.first[l] + bi];
             const std::string p = "layer" + std::to_string(l + 1) + "." + std::to_string(bi);
             const int w = widths[l];
             const int stride = (bi == 0 && l > 0) ? 2 : 1;
@@ -222,18 +237,23 @@ Status resnet_load(Engine& e, const ParamMap& pm) {
         R.head_id = e.register_layer("fc");
         macs += 13 * 512;
     }
-    CV_TRY(reject_unknown_keys_public(pm, known, "resnet18(in_chans=1, num_classes=13)"));
+    CV_TRY(reject_unknown_keys_public(pm, known, (std::string(A->name) + "(in_chans=1, num_classes=13)").c_str()));
     R.macs = macs;
-    {   // f16r: layer1 as one chained launch -- the four layers' weight stages (9 taps x 64 rows x 128 B each) back to back
+    {   // f16r: layer1 as one chained launch -- the chained layers' weight stages (9 taps x 64 rows x 128 B each) back to back.
+        // A three-block layer1 (resnet34) chains all three blocks by default; CV_RESNET_CHAIN_BLOCKS=2 chains the first two.
         static const bool on = [] { const char* v = std::getenv("CV_RESNET_CHAIN"); return !(v && v[0] == '0'); }();
-        ConvLayer* L[4] = {&R.blocks[0].conv1, &R.blocks[0].conv2, &R.blocks[1].conv1, &R.blocks[1].conv2};
-        bool fits = on && e.trunk32 && dt == kF16 && conv_halo_has_chain();
+        static const int max_nb = [] { const char* v = std::getenv("CV_RESNET_CHAIN_BLOCKS"); return v && *v ? std::atoi(v) : 3; }();
+        const int nb = std::min(A->depth[0], max_nb);
+        std::vector<ConvLayer*> L;
+        for (int b = 0; b < nb; ++b) { L.push_back(&R.blocks[b].conv1); L.push_back(&R.blocks[b].conv2); }
+        bool fits = on && (nb == 2 || nb == 3) && e.trunk32 && dt == kF16 && conv_halo_has_chain();
         const size_t one = (size_t)9 * 64 * 128;
         for (ConvLayer* l : L) fits = fits && l->dt == kF16 && l->ct == 64 && l->rows == 64 && l->nStages == 9 && l->nCt == 1 && l->w.bytes >= one && l->halo_ok;
         if (fits) {
-            CV_TRY(R.chain_w.alloc(4 * one, false));
-            for (int i = 0; i < 4; ++i) CV_HIP(sync_memcpy((char*)R.chain_w.ptr + i * one, L[i]->w.ptr, one, hipMemcpyDeviceToDevice));
+            CV_TRY(R.chain_w.alloc(L.size() * one, false));
+            for (size_t i = 0; i < L.size(); ++i) CV_HIP(sync_memcpy((char*)R.chain_w.ptr + i * one, L[i]->w.ptr, one, hipMemcpyDeviceToDevice));
             R.chain_ok = true;
+            R.chain_nb = nb;
         }
     }
     e.resnet = std::move(m);
@@ -284,10 +304,14 @@ Status resnet_load(Engine& e, const ParamMap& pm) {
                     CV_TRY(resnet_chunk(e, (const float*)xin.ptr + (size_t)off * 4096, false, c, (float*)lout.ptr + (size_t)off * 13, false, nullptr));
                 }
                 return Status();
-            }, nullptr, "ResNet-18");
+            }, nullptr, A->name);
         if (st.ok()) {                                                          // exponents are final: rounding-bias pass of the f16 layers
             std::vector<ConvLayer*> layers;
-            for (auto& B : e.resnet->blocks) { layers.push_back(&B.conv1); layers.push_back(&B.conv2); if (B.has_down) layers.push_back(&B.down); }
+            for (int b = 0; b < e.resnet->nblocks; ++b) {
+                Engine::ResNet::Block& B = e.resnet->blocks[b];
+                layers.push_back(&B.conv1); layers.push_back(&B.conv2);
+                if (B.has_down) layers.push_back(&B.down);
+            }
             st = e.calibrate_rounding_bias(layers, [&]() -> Status {
                 for (int off = 0; off < kBias; off += e.resnet->cap) {
                     const int c = std::min(e.resnet->cap, kBias - off);
@@ -298,7 +322,7 @@ Status resnet_load(Engine& e, const ParamMap& pm) {
         }
         if (st.ok()) {
             hipError_t he = device_synchronize();
-            if (he != hipSuccess) st = hip_fail(he, "ResNet-18 calibration");
+            if (he != hipSuccess) st = hip_fail(he, (std::string(A->name) + " calibration").c_str());
         }
     }
     if (!st.ok()) e.resnet.reset();
@@ -318,19 +342,19 @@ static Status resnet_reserve(Engine& e, int n) {
     if (e.dt == kF32) R.taps["act1"] = R.stem_out.ref(S);
     R.taps["maxpool"] = R.pool_out.ref(S);
     for (int l = 0; l < 4; ++l) {
-        for (int bi = 0; bi < 2; ++bi) {
-            Engine::ResNet::Block& B = R.blocks[l * 2 + bi];
+        for (int bi = 0; bi < R.arch->depth[l]; ++bi) {
+            Engine::ResNet::Block& B = R.blocks[R.first[l] + bi];
             const std::string p = "layer" + std::to_string(l + 1) + "." + std::to_string(bi);
-            // chained layer1 (f16r): conv1's output of both blocks and the f16 copy of the first block's output live in LDS only --
-            // no tap for the former, the latter is read from its f32 twin
-            const bool chained = R.chain_ok && l == 0;
+            // chained layer1 (f16r): conv1's output of every chained block and the f16 copies of the chained blocks' outputs but the last
+            // live in LDS only -- no tap for the former, the latter are read from their f32 twins
+            const bool chained = R.chain_ok && l == 0 && bi < R.chain_nb;
             if (!chained) R.taps[p + ".act1"] = B.mid.ref(S);
-            if (chained && bi == 0) {                        // block 0's output: its f32 twin (form 2) or nowhere outside the kernel (form 1)
+            if (chained && bi < R.chain_nb - 1) {            // an inner chained block's output: its f32 twin (form 2) or nowhere outside the kernel (form 1)
                 if (chain_form() == 2) R.taps[p] = B.out.ref32(S);
             } else R.taps[p] = B.out.ref(S);
             if (B.has_down) R.taps[p + ".downsample"] = B.sc.only32 ? B.sc.ref32(S) : B.sc.ref(S);
         }
-        R.taps["layer" + std::to_string(l + 1)] = R.blocks[l * 2 + 1].out.ref(S);
+        R.taps["layer" + std::to_string(l + 1)] = R.blocks[R.first[l + 1] - 1].out.ref(S);
     }
     return Status();
 }
@@ -338,14 +362,27 @@ static Status resnet_reserve(Engine& e, int n) {
 int64_t resnet_macs(Engine& e) { return e.resnet ? e.resnet->macs : 0; }
 
 Status resnet_activation(Engine& e, const std::string& name, TensorRef* out) {
-    if (!e.resnet) return fail(3, "ResNet-18 not loaded");
-    auto it = e.resnet->taps.find(name);
-    if (it == e.resnet->taps.end()) {
-        // the fp16 classifier runs layer1 as ONE launch: conv1's outputs (and, in the one-workgroup form, block 0's output) exist in LDS only
-        if (e.resnet->chain_ok && (name == "layer1.0.act1" || name == "layer1.1.act1" || name == "layer1.0"))
-            return fail(1, "ResNet activation '" + name + "' is not materialised by precision f16r: layer1 runs as one chained launch and "
-                           "keeps it in LDS -- set CV_RESNET_CHAIN=0 before creating the engine to run layer1 as four launches");
-        return fail(1, "unknown ResNet activation '" + name + "'");
+    if (!e.resnet) return fail(3, "ResNet not loaded");
+    const Engine::ResNet& R = *e.resnet;
+    auto it = R.taps.find(name);
+    if (it == R.taps.end()) {
+        // the fp16 classifier runs the first chain_nb blocks of layer1 as ONE launch: their conv1 outputs (and, in the one-workgroup form,
+        // the outputs of every chained block but the last) exist in LDS / registers only
+        if (R.chain_ok) {
+            std::string kept;
+            bool hit = false;
+            for (int b = 0; b < R.chain_nb; ++b) {
+                const std::string p = "layer1." + std::to_string(b);
+                kept += (b ? ", " : "") + p + ".act1";
+                hit = hit || name == p + ".act1";
+                if (b < R.chain_nb - 1 && chain_form() == 1) { kept += ", " + p; hit = hit || name == p; }
+            }
+            if (hit)
+                return fail(1, "ResNet activation '" + name + "' is not materialised by precision f16r: layer1 runs " +
+                               std::to_string(2 * R.chain_nb) + " convolutions as one chained launch and keeps " + kept +
+                               " on the chip -- set CV_RESNET_CHAIN=0 before creating the engine to run layer1 layer by layer");
+        }
+        return fail(1, "unknown " + std::string(R.arch->name) + " activation '" + name + "'");
     }
     *out = it->second;
     out->exp = static_cast<Activation*>(out->owner)->exp;
@@ -383,10 +420,10 @@ static Status resnet_chunk(Engine& e, const void* x, bool x_u8, int n, float* ou
     int first_block = 0;
     if (R.chain_ok && !e.calibrating) {                // the calibration passes run layer by layer (every tensor is measured)
         CV_TRY(layer1_chain(e, n, s));
-        cur = R.blocks[1].out.ref(n);
-        first_block = 2;
+        cur = R.blocks[R.chain_nb - 1].out.ref(n);
+        first_block = R.chain_nb;
     }
-    for (int i = first_block; i < 8; ++i) {
+    for (int i = first_block; i < R.nblocks; ++i) {
         Engine::ResNet::Block& B = R.blocks[i];
         TensorRef shortcut = cur;
         bool conv1_done = false;
@@ -479,53 +516,62 @@ static Status resnet_chunk(Engine& e, const void* x, bool x_u8, int n, float* ou
     return Status();
 }
 
-// layer1.0 and layer1.1 in one launch (f16r engine): pool_out (f16 copy + f32 twin) -> blocks[1].out (f16 copy + f32 twin), the first
-// block's f32 output twin as the only intermediate in memory.  Same arithmetic as the four run_conv launches: f16 products, f32
-// accumulation, BN affine and residual in f32, one rounding to f16 per tensor.
+// the first chain_nb blocks of layer1 in one launch (f16r engine): pool_out (f16 copy + f32 twin) -> blocks[nb-1].out (f16 copy + f32 twin),
+// the inner blocks' f32 output twins as the only intermediates in memory (two-workgroup form; in the one-workgroup form they stay in
+// registers).  Same arithmetic as the 2 nb run_conv launches: f16 products, f32 accumulation, BN affine and residual in f32, one rounding
+// to f16 per tensor.
 static Status layer1_chain(Engine& e, int n, hipStream_t s) {
     Engine::ResNet& R = *e.resnet;
-    Engine::ResNet::Block &B0 = R.blocks[0], &B1 = R.blocks[1];
-    const TensorRef x = R.pool_out.ref(n), y0 = B0.out.ref(n), y1 = B1.out.ref(n);
-    if (!x.base || !x.base32 || !y0.base32 || !y1.base || !y1.base32 || x.Cs != 64 || y1.Cs != 64 || x.H != 16 || x.W != 16)
+    const int nb = R.chain_nb;
+    Engine::ResNet::Block& BL = R.blocks[nb - 1];
+    const TensorRef x = R.pool_out.ref(n), yl = BL.out.ref(n);
+    if (!x.base || !x.base32 || !yl.base || !yl.base32 || x.Cs != 64 || yl.Cs != 64 || x.H != 16 || x.W != 16)
         return fail(3, "layer1 chain: trunk tensors are not in the f16r layout");
     // tensor exponents exactly as the layer-by-layer path folds them
-    CV_TRY(B0.conv1.set_exps(x.exp, B0.mid.exp, s));
-    CV_TRY(B0.conv2.set_exps(B0.mid.exp, B0.out.exp, s));
-    CV_TRY(B1.conv1.set_exps(B0.out.exp, B1.mid.exp, s));
-    CV_TRY(B1.conv2.set_exps(B1.mid.exp, B1.out.exp, s));
-    ConvLayer* L[4] = {&B0.conv1, &B0.conv2, &B1.conv1, &B1.conv2};
+    ConvLayer* L[6];
+    int in_exp = x.exp;
+    for (int b = 0; b < nb; ++b) {
+        Engine::ResNet::Block& B = R.blocks[b];
+        if (!B.out.ref(n).base32) return fail(3, "layer1 chain: trunk tensors are not in the f16r layout");
+        CV_TRY(B.conv1.set_exps(in_exp, B.mid.exp, s));
+        CV_TRY(B.conv2.set_exps(B.mid.exp, B.out.exp, s));
+        L[2 * b] = &B.conv1; L[2 * b + 1] = &B.conv2;
+        in_exp = B.out.exp;
+    }
     ConvParams p;
     std::memset(&p, 0, sizeof(p));
     p.x = reinterpret_cast<const char*>(x.base);
     p.w = reinterpret_cast<const char*>(R.chain_w.ptr);
-    p.y = reinterpret_cast<char*>(y1.base);
-    p.y32 = reinterpret_cast<char*>(y1.base32);
+    p.y = reinterpret_cast<char*>(yl.base);
+    p.y32 = reinterpret_cast<char*>(yl.base32);
     p.M = n * 256; p.Ho = 16; p.Wo = 16;
     p.xHp = 18; p.xWp = 18; p.stride = 1; p.xCs = 64; p.xCoffBytes = 0;
     p.yHp = 18; p.yWp = 18; p.yCs = 64; p.yCoff = 0;
-    p.Cout = 64; p.rows = 64; p.nStages = 36; p.nCt = 1; p.relu = 1;
+    p.Cout = 64; p.rows = 64; p.nStages = 18 * nb; p.nCt = 1; p.relu = 1;
     p.flag = e.guard_ptr();
-    p.layer_id = B1.conv2.layer_id;
+    p.layer_id = BL.conv2.layer_id;
     // bit 4: convolution 1's residual epilogue staged through the (dead) halo buffer in the unit layout (CV_CHAIN_MIDSTAGE; two-workgroup form)
     static const int mid_staged = [] { const char* v = std::getenv("CV_CHAIN_MIDSTAGE"); return v && v[0] == '1' ? 16 : 0; }();
     p.chain = chain_form() | (chain_form() == 2 ? mid_staged : 0);
-    for (int i = 0; i < 4; ++i) {
+    for (int i = 0; i < 2 * nb; ++i) {
         p.ch_scale[i] = reinterpret_cast<const float*>(L[i]->scale.ptr);
         p.ch_shift[i] = reinterpret_cast<const float*>(L[i]->shift.ptr);
         p.ch_layer_id[i] = L[i]->layer_id;
     }
     p.ch_res0 = reinterpret_cast<const char*>(x.base32);
-    p.ch_y32_mid = reinterpret_cast<char*>(y0.base32);
-    p.ch_res_mul[0] = std::ldexp(1.f, x.exp - B0.out.exp);
-    p.ch_res_mul[1] = std::ldexp(1.f, B0.out.exp - B1.out.exp);
-    // the last convolution's epilogue is the kernel's ordinary one (two-workgroup form): its constants in the ordinary fields
-    p.scale = p.ch_scale[3]; p.shift = p.ch_shift[3];
-    p.res = reinterpret_cast<const char*>(y0.base32); p.res_f32 = 1; p.res_mul = p.ch_res_mul[1]; p.rCs = 64; p.rCoff = 0;
+    for (int b = 0; b + 1 < nb; ++b) p.ch_y32_mid[b] = reinterpret_cast<char*>(R.blocks[b].out.ref(n).base32);
+    in_exp = x.exp;
+    for (int b = 0; b < nb; ++b) { p.ch_res_mul[b] = std::ldexp(1.f, in_exp - R.blocks[b].out.exp); in_exp = R.blocks[b].out.exp; }
+    // the last convolution's epilogue is the kernel's ordinary one (two-workgroup form): its constants in the ordinary fields, the residual
+    // is the previous block's f32 output
+    p.scale = p.ch_scale[2 * nb - 1]; p.shift = p.ch_shift[2 * nb - 1];
+    p.res = p.ch_y32_mid[nb - 2]; p.res_f32 = 1; p.res_mul = p.ch_res_mul[nb - 1]; p.rCs = 64; p.rCoff = 0;
     if (e.profiling) {
-        // compulsory bytes: f16 input + its f32 twin, the first block's f32 output written and read back, f32 + f16 output, weights
+        // compulsory bytes: f16 input + its f32 twin, each inner block's f32 output written and read back, f32 + f16 output, weights
         const double px = (double)n * 256 * 64;
-        e.prof_begin("layer1 (4 convs, chained)", true, 4.0 * 9 * 64 * 64 * 256 * (double)n, s, px * (2 + 4 + 4 + 4 + 4 + 2) + 4.0 * 9 * 64 * 64 * 2);
-        e.prof.back().kernel = "conv3x3_halo_kernel<half_t,64,16x16,CHAIN4>";
+        e.prof_begin(("layer1 (" + std::to_string(2 * nb) + " convs, chained)").c_str(), true, 2.0 * nb * 9 * 64 * 64 * 256 * (double)n, s,
+                     px * (2 + 4 + 8 * (nb - 1) + 4 + 2) + 2.0 * nb * 9 * 64 * 64 * 2);
+        e.prof.back().kernel = "conv3x3_halo_kernel<half_t,64,16x16,CHAIN" + std::to_string(2 * nb) + ">";
     }
     const hipError_t err = conv_halo_chain_launch(p, n, s);
     if (e.profiling) e.prof_end(s);
@@ -534,7 +580,7 @@ static Status layer1_chain(Engine& e, int n, hipStream_t s) {
 }
 
 Status resnet_forward(Engine& e, const void* x, bool x_u8, int n, float* out, bool softmax, hipStream_t s) {
-    if (!e.resnet) return fail(3, "ResNet-18 weights not loaded (call cv_load_resnet18 first)");
+    if (!e.resnet) return fail(3, "ResNet weights not loaded (call cv_load_resnet or cv_load_resnet18 first)");
     if (n < 0 || (n > 0 && (!x || !out))) return fail(1, "cv_resnet18_forward: null tensor or negative batch");
     if (n == 0) return Status();
     CV_TRY(e.order_forward(1, s));

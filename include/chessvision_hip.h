@@ -57,7 +57,9 @@ extern "C" {
                                  5: cv_image_result_t gains `squares` (appended; zero the struct before use, as before)
                                  6: cv_process_image_v2 (the caller states sizeof(cv_image_result_t) as IT was compiled); cv_process_image is
                                     the ABI 3 / 4 entry point again and never touches `squares` -- a binary built against the shorter struct
-                                    of those versions is safe once more */
+                                    of those versions is safe once more
+                                 6 (addition, no version change): cv_load_resnet (timm "resnet18" | "resnet34"); consumers that need it
+                                    detect it with dlsym(handle, "cv_load_resnet") -- a library without the symbol loads ResNet-18 only */
 
 enum cv_status {
     CV_OK = 0,
@@ -121,6 +123,14 @@ int cv_trim_memory(size_t* bytes_freed);
  * presence of "up1.up.weight" and validates every key/shape, failing with the offending key name.
  * Replaces model.load_state_dict(...) of utils.py:59-79. */
 int cv_load_unet(cv_engine_t* eng, const cv_param_t* params, int n_params);
+/* The piece classifier: timm's plain BasicBlock ResNet, arch = "resnet18" (blocks per stage {2,2,2,2}) or "resnet34" ({3,4,6,3}),
+ * in_chans=1, num_classes=13.  Any other arch fails with CV_ERR_INVALID.  Validation as for the UNet: one missing, extra, renamed or
+ * mis-shaped key fails and the message names it.  cv_load_resnet18(e, p, n) is cv_load_resnet(e, "resnet18", p, n).
+ * An engine holds one ResNet at a time; cv_resnet18_forward, cv_resnet18_forward_u8, cv_process_image and cv_process_image_v2 run
+ * whichever ResNet it holds, and the by-name entry points (cv_get_activation, cv_get_activation_exponent, cv_model_macs,
+ * cv_profile_convs, cv_engine_export/import_calibration) take the loaded architecture's name -- the other ResNet name fails with
+ * CV_ERR_STATE naming what is loaded. */
+int cv_load_resnet(cv_engine_t* eng, const char* arch, const cv_param_t* params, int n_params);
 int cv_load_resnet18(cv_engine_t* eng, const cv_param_t* params, int n_params);
 
 /* Largest number of images (UNet) / squares (ResNet) processed per internal pass; larger batches are
@@ -161,7 +171,7 @@ int cv_engine_import_calibration(cv_engine_t* eng, const char* model, const int3
 int cv_unet_forward(cv_engine_t* eng, const float* x, int batch, float* logits, void* stream);
 
 /* x: (n,1,64,64) float32 in [0,1]  ->  logits: (n,13) float32 (no softmax).
- * Same tensor contract as `self.classifier(batch)` (core.py:241). */
+ * Same tensor contract as `self.classifier(batch)` (core.py:241).  Runs the loaded ResNet (18 or 34, cv_load_resnet). */
 int cv_resnet18_forward(cv_engine_t* eng, const float* x, int n, float* logits, void* stream);
 
 /* Fused variants for the batched pipeline (u8 in, pre/post-processing of core.py on device):
@@ -170,7 +180,7 @@ int cv_resnet18_forward(cv_engine_t* eng, const float* x, int n, float* logits, 
  * sigmoid(logit) > threshold else 0 (core.py:273, utils.py:101-112). */
 int cv_unet_forward_u8(cv_engine_t* eng, const uint8_t* x_u8, int batch, float* logits, uint8_t* mask,
                        float threshold, void* stream);
-/* squares_u8: (n,64,64) uint8 -> probs: (n,13) float32 = softmax(logits, dim=1) (core.py:236-242). */
+/* squares_u8: (n,64,64) uint8 -> probs: (n,13) float32 = softmax(logits, dim=1) (core.py:236-242).  Runs the loaded ResNet. */
 int cv_resnet18_forward_u8(cv_engine_t* eng, const uint8_t* squares_u8, int n, float* probs, void* stream);
 
 /* (n,13) logits -> softmax probabilities, in place allowed (core.py:242). */
@@ -181,9 +191,10 @@ int cv_softmax13(cv_engine_t* eng, const float* logits, int n, float* probs, voi
  * (n,c,h,w written to dims[4]).  `name` is the producing module's state-dict prefix, e.g.
  * "inc.double_conv.3", "down4.maxpool_conv.1.double_conv.5" (= named_modules()[52],
  * train_unet.py:210), "up1.up", "layer1.0", "maxpool".  out_capacity in floats.  Synchronises.
- * Tensors a fused launch never writes have no tap: under CV_PREC_F16R ResNet-18's layer1 runs as ONE chained launch, so
- * "layer1.0.act1" / "layer1.1.act1" do not exist and "layer1.0" is read from the block's f32 twin (CV_ERR_INVALID naming
- * CV_RESNET_CHAIN=0, the switch that runs layer1 as four launches and materialises them); the UNet's fused first two convolutions
+ * Tensors a fused launch never writes have no tap: under CV_PREC_F16R the ResNet's layer1 runs as ONE chained launch, so
+ * "layer1.B.act1" of the chained blocks do not exist and the inner blocks' outputs ("layer1.0", and "layer1.1" for resnet34) are read
+ * from their f32 twins (CV_ERR_INVALID naming CV_RESNET_CHAIN=0, the switch that runs layer1 layer by layer and materialises them);
+ * `model` is "unet" or the loaded ResNet's architecture name ("resnet18" | "resnet34"); the UNet's fused first two convolutions
  * (CV_FUSE_INC=0 to split them) likewise leave "inc.double_conv.2" unwritten at the throughput sizes. */
 int cv_get_activation(cv_engine_t* eng, const char* model, const char* name, float* out_host,
                       size_t out_capacity, int64_t dims[4]);

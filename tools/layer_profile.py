@@ -1,6 +1,8 @@
 """Per-layer event timing of one forward (developer tool; writes a table to stdout / gpurun_out).
 
 usage: python tools/layer_profile.py [--prec f16|f32] [--unet-batch 32] [--squares 4096] [--chunk 16] [--sq-chunk 4096]
+                                    [--arch resnet18|resnet34]
+--arch picks the piece classifier (synthetic weights of that architecture); --unet-batch 0 skips the UNet.
 """
 from __future__ import annotations
 
@@ -27,14 +29,18 @@ def main():
     ap.add_argument("--chunk", type=int, default=64)
     ap.add_argument("--sq-chunk", type=int, default=16384)
     ap.add_argument("--iters", type=int, default=3)
+    ap.add_argument("--arch", default="resnet18", choices=["resnet18", "resnet34"])
     args = ap.parse_args()
     eng = HipEngine(precision=args.prec, unet_chunk=args.chunk, resnet_chunk=args.sq_chunk)
-    eng.load_unet(synthetic.unet_state_dict(1))
-    eng.load_resnet18(synthetic.resnet18_state_dict(2))
+    if args.unet_batch:
+        eng.load_unet(synthetic.unet_state_dict(1))
+    eng.load_resnet(synthetic.resnet_state_dict(args.arch, 2), args.arch)
     g = torch.Generator(device="cuda"); g.manual_seed(3)
     x = torch.randint(0, 256, (max(args.unet_batch, 1), 3, 256, 256), dtype=torch.uint8, device="cuda", generator=g).float().div_(255)[: args.unet_batch]
     sq = torch.randint(0, 256, (max(args.squares, 1), 1, 64, 64), dtype=torch.uint8, device="cuda", generator=g).float().div_(255)[: args.squares]
-    for model, inp, units in (("unet", x, args.unet_batch), ("resnet18", sq, args.squares)):
+    for model, inp, units in (("unet", x, args.unet_batch), (args.arch, sq, args.squares)):
+        if units == 0:
+            continue
         fwd = eng.unet_forward if model == "unet" else eng.resnet18_forward
         for _ in range(2):
             fwd(inp)
