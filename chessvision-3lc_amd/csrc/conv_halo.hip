@@ -24,15 +24,15 @@
 
 namespace cv {
 
-// TPS = taps per weight stage and NSW = weight ring depth (1 and 3 in every shipped configuration: the pipelined loop is
-// written for them; a filter-row variant was measured and dropped, r01_tuning.md).
+// One tap per weight stage and a weight ring of NSW = 3 slots: the pipelined loop is written for them (a filter-row variant
+// was measured and dropped, r01_tuning.md).
 // IMG = 0: one TH x 16 patch of one (large) image per workgroup.  IMG = 8: feature maps of 8 x 8 (ResNet layer2): the
 // 16 x 16 pixel tile is four whole images (2 x 2), whose zero-bordered 10 x 10 PHWC planes are contiguous in memory, so
 // the "halo" is simply 400 consecutive pixels and a fragment's 16 lanes read row y of two neighbouring images.
 // PERSIST: the grid is one workgroup per CU slot and every workgroup walks tiles lid, lid + grid, ...; the first DMAs of the
 // next tile (its halo and three weight stages) are issued before the current tile's epilogue, so their latency, the
 // store drain and the workgroup relaunch disappear behind it (r01_tuning.md step 22).
-// DBH: halo double buffered (the next channel block's halo lands while the current one is computed).  DBH = false keeps ONE
+// DBH (= the 8 x 16 patch, TH == 8): halo double buffered (the next channel block's halo lands while the current one is computed).  DBH = false keeps ONE
 // halo buffer: at every channel-block boundary the workgroup drains, DMAs the next halo and waits for it -- a bubble that the
 // second workgroup resident on the CU fills; what it buys is LDS: a 64-channel tile over a 16 x 16 patch (four patch rows per
 // wave = twice the MFMAs per weight byte and per fragment read of the 8 x 16 tile) then fits twice per CU.
@@ -40,10 +40,8 @@ namespace cv {
 // 27 -> one MFMA k-step) from a 20 x 20 x 3 patch of the caller's image -- UNet inc.double_conv.0 fused into inc.double_conv.3.
 // The 64-channel full-resolution tensor between the two convs (1.07 GB per 64 images, written once and read 1.27x) never
 // exists; the recompute is the 18^2/16^2 halo overlap of a layer that holds 0.2 % of the network's MACs.
-#ifndef CV_HALO_TH8_SINGLE
-#define CV_HALO_TH8_SINGLE 0      // experiment (with -DCV_HALO_TH64=8): 8 x 16 patch with ONE halo buffer = 47 KB -> THREE workgroups per CU
-#endif
-constexpr int halo_waves_per_eu(int ct, int th, bool dbh, int chain = 0) { return chain == 1 ? 1 : (CV_HALO_TH8_SINGLE && ct == 64 && th == 8 && !dbh) ? 3 : 2; }
+constexpr int kHaloCT = 64, kHaloNW = 4, kHaloNSW = 3;    // channel tile, waves and weight ring depth of every instantiation
+constexpr int halo_waves_per_eu(int chain) { return chain == 1 ? 1 : 2; }
 // CHAIN (single halo buffer, f16, 64 -> 64 channels, 16 x 16 maps = one patch per image): the "channel blocks" of the K loop are
 // 2 CNB CONVOLUTIONS in a row (CNB = 2: ResNet-18 layer1 = two BasicBlocks; CNB = 3: ResNet-34 layer1).  At every block boundary the
 // epilogue of convolution c -- BN,
@@ -53,35 +51,27 @@ constexpr int halo_waves_per_eu(int ct, int th, bool dbh, int chain = 0) { retur
 // read back by the same lanes after convolution 2 k + 3): round 5, profiles/r05_tuning.md.  CHAIN = 2: that form, two workgroups per CU.
 // CHAIN = 1: ONE workgroup per CU with 512 registers per lane -- the f32 residual of the whole tile (64 registers) is fetched at kernel
 // start and stays in registers through every block, so the inner blocks' outputs never leave the chip and no epilogue waits for a load.
-template <typename T, int CT, int TH, int WGC, int NW, int TPS, int NSW, int IMG, bool PERSIST, bool DBH = true, bool FUSE0 = false, int CHAIN = 0,
-          int CNB = 2>
-__global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(halo_waves_per_eu(CT, TH, DBH, CHAIN), halo_waves_per_eu(CT, TH, DBH, CHAIN)))) void conv3x3_halo_kernel(const ConvParams p) {
-    static_assert(!FUSE0 || (!DBH && !PERSIST && IMG == 0 && CT == 64 && NW == 4 && __is_same(T, split_t)), "fused producer: split-f16 64-channel single-halo tile");
-    static_assert(!CHAIN || (!DBH && !PERSIST && !FUSE0 && IMG == 0 && CT == 64 && TH == 16 && NW == 4 && __is_same(T, half_t)), "chained convolutions: f16 64-channel single-halo tile over whole 16 x 16 images");
+template <typename T, int TH, int IMG, bool PERSIST, bool FUSE0 = false, int CHAIN = 0, int CNB = 2>
+__global__ __launch_bounds__(64 * kHaloNW) __attribute__((amdgpu_waves_per_eu(halo_waves_per_eu(CHAIN), halo_waves_per_eu(CHAIN)))) void conv3x3_halo_kernel(const ConvParams p) {
+    constexpr int CT = kHaloCT, NW = kHaloNW, NSW = kHaloNSW;
+    constexpr bool DBH = TH == 8;
+    static_assert(CT == 64 && NSW == 3, "every wave owns a 64-channel slab; the ring slot of a stage is tap % 3");
+    static_assert(TH == 16 || (TH == 8 && IMG == 0 && !PERSIST), "16 x 16 patch with one halo buffer | 8 x 16 patch, double buffered");
+    static_assert(!FUSE0 || (!DBH && !PERSIST && IMG == 0 && __is_same(T, split_t)), "fused producer: split-f16 64-channel single-halo tile");
+    static_assert(!CHAIN || (!DBH && !PERSIST && !FUSE0 && IMG == 0 && __is_same(T, half_t)), "chained convolutions: f16 64-channel single-halo tile over whole 16 x 16 images");
     static_assert(CNB == 2 || (CHAIN && CNB == 3), "two or three chained BasicBlocks");
-    static_assert(TPS == 1 && (NSW == 3 || NSW == 4), "stage shape");
-    constexpr int SPC = 9 / TPS;                        // stages per channel block
-    constexpr int WGP = NW / WGC;                       // wave groups along the patch rows
-    static_assert(CT / WGC == 64, "every wave owns a 64-channel slab");
+    constexpr int SPC = 9;                              // stages per channel block
     constexpr int FC = 4;
-    constexpr int FP = TH / WGP;                        // patch rows (= 16-pixel fragments) per wave
-    static_assert(FP >= 1 && FP <= 4 && TH % WGP == 0, "wave tile");
-    constexpr int WTAP = CT * 128;                      // weight bytes of one tap
-    constexpr int WSTAGE = TPS * WTAP;
+    constexpr int FP = TH / NW;                         // patch rows (= 16-pixel fragments) per wave
+    static_assert(FP >= 1 && FP <= 4 && TH % NW == 0, "wave tile");
+    constexpr int WSTAGE = CT * 128;                    // weight bytes of one stage (= one tap)
     static_assert(IMG == 0 || (IMG == 8 && TH == 16), "packed-image mode: 2 x 2 images of 8 x 8");
     constexpr int HLW = IMG ? IMG + 2 : 18;             // pixels per halo line
     constexpr int HR = IMG ? 4 * HLW * HLW : 18 * (TH + 2);   // halo rows (one pixel = one 128-byte LDS row)
-    // DMA roles.  With 8 waves, waves w and w + 4 share a SIMD: if both issued their DMA pieces right after the barrier
-    // (each piece costs its wave ~60-100 issue cycles) the matrix pipe of that SIMD would sit idle meanwhile.  So waves
-    // 0..3 move the weight stages and waves 4..7 the halo (two pieces per stage over taps 0..5): on every SIMD one wave
-    // issues DMA while the other already feeds MFMAs.  4-wave workgroups (one wave per SIMD) keep symmetric duties.
-    constexpr bool kRoles = NW == 8;
-    constexpr int NWI = kRoles ? NW / 2 : NW;           // waves sharing one kind of DMA
-    constexpr int H = ((HR + 7) / 8 + NWI - 1) / NWI;   // halo DMA wave-instructions per issuing wave (8 rows each)
-    constexpr int HPS = kRoles ? (H + 5) / 6 : H;       // ... of which per stage (roles: spread over taps 0..5)
-    constexpr int HBYTES = H * NWI * 1024;
-    constexpr int LW = TPS * CT / (8 * NWI);
-    static_assert(LW >= 1 && LW + H <= 63 && (!kRoles || 6 * HPS >= H), "vmcnt range / halo spread");
+    constexpr int H = ((HR + 7) / 8 + NW - 1) / NW;     // halo DMA wave-instructions per wave (8 rows each)
+    constexpr int HBYTES = H * NW * 1024;
+    constexpr int LW = CT / (8 * NW);                   // weight DMA wave-instructions per wave and stage
+    static_assert(LW >= 1 && LW + H <= 63, "vmcnt range");
     constexpr bool kSplit16 = sizeof(T) == 4 && !__is_same(T, float);
     typedef typename FragT<T>::V V;
 
@@ -113,21 +103,16 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(halo_wa
     const char* wsrc;                                   // wave-uniform: this wave's first weight piece of the tile (stage 0)
     // 4-wave tiles have registers to spare: the byte offsets of this lane's halo rows are computed once per tile instead of
     // once per channel block (a divide by 18 and a swizzle per piece: ~14 vector instructions x 11 pieces in one stage)
-    constexpr bool kHoistHalo = NW == 4;
-    unsigned hoff[kHoistHalo ? H : 1];
+    unsigned hoff[H];
 
     // DMA sources of this lane's halo rows: row r of the halo <-> padded input pixel (ty*TH + r/18, tx*16 + r%18).
-    // Needed once per channel block only, so they are re-derived at each use (the lane id is made opaque to keep LICM
-    // from parking H more VGPRs across the whole K loop).
     const unsigned xpix = (unsigned)p.xCs * (unsigned)sizeof(T);
     const char* const xsrc = p.x + p.xCoffBytes;
-    const bool is_w = !kRoles || wave < NWI;            // this wave moves weight stages / halo pieces
-    const bool is_h = !kRoles || wave >= NWI;
-    const int wi = kRoles && wave >= NWI ? wave - NWI : wave;     // index among the waves of its role
+    const int wi = wave;                                // this wave's share of every DMA (a name of its own: see the note at wci)
     const unsigned lane16 = (unsigned)lane * 16u;
     // byte offset (from xsrc, channel block 0) of the halo row this lane moves in piece i
     auto halo_row_offset = [&](int i) __attribute__((always_inline)) -> unsigned {
-        const int r = (i * NWI + wi) * 8 + (lane >> 3);
+        const int r = (i * NW + wi) * 8 + (lane >> 3);
         const int rr = r < HR ? r : HR - 1;             // rows of the padded tail re-read the last real one
         if constexpr (IMG == 0) {
             const int hy = rr / 18, hx = rr - hy * 18;
@@ -159,48 +144,22 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(halo_wa
         ty = pt % tilesY;
         n = IMG ? 4 * (pt / tilesY) : pt / tilesY;      // (first) image of the tile
         hbase = (unsigned)((n * p.xHp + ty * TH) * p.xWp + tx * 16);
-        wsrc = p.w + ((size_t)ctTile * p.nStages + (size_t)cbBase * 9) * WTAP + wi * 1024;
-        if constexpr (kHoistHalo) {
+        wsrc = p.w + ((size_t)ctTile * p.nStages + (size_t)cbBase * 9) * WSTAGE + wi * 1024;
 #pragma unroll
-            for (int i = 0; i < H; ++i) hoff[i] = halo_row_offset(i);
-        }
+        for (int i = 0; i < H; ++i) hoff[i] = halo_row_offset(i);
     };
 
     const int q = lane >> 4, l15 = lane & 15;
     auto issue_w = [&](int s, int slot) __attribute__((always_inline)) {
         char* sW = smem + slot * WSTAGE;
 #pragma unroll
-        for (int i = 0; i < LW; ++i) glds16s(wsrc + (size_t)s * WSTAGE + i * (NWI * 1024), lane16, sW + (i * NWI + wi) * 1024);   // stage s = TPS consecutive taps
+        for (int i = 0; i < LW; ++i) glds16s(wsrc + (size_t)s * WSTAGE + i * (NW * 1024), lane16, sW + (i * NW + wi) * 1024);
     };
-    auto issue_halo = [&](int cb, int hb, auto i0_tag, auto n_tag) __attribute__((always_inline)) {          // pieces [I0, I0 + N) of this wave's H
-        constexpr int I0 = decltype(i0_tag)::value, N = decltype(n_tag)::value;
+    auto issue_halo = [&](int cb, int hb) __attribute__((always_inline)) {
         char* sH = halo + hb * HBYTES;
         const char* const src = xsrc + (cbBase + cb) * 128;   // wave-uniform base of this channel block
-        if constexpr (kHoistHalo) {
 #pragma unroll
-            for (int i = I0; i < I0 + N && i < H; ++i) glds16s(src, hoff[i], sH + (i * NWI + wi) * 1024);
-        } else {
-            // 8-wave tiles sit at the register limit: the offsets are re-derived at each use (needed once per channel block; the
-            // lane id is made opaque to keep LICM from parking H more VGPRs across the whole K loop)
-            int ln = lane;
-            asm volatile("" : "+v"(ln));
-#pragma unroll
-            for (int i = I0; i < I0 + N && i < H; ++i) {
-                const int r = (i * NWI + wi) * 8 + (ln >> 3);
-                const int rr = r < HR ? r : HR - 1;     // rows of the padded tail re-read the last real one
-                unsigned off;
-                if constexpr (IMG == 0) {
-                    const int hy = rr / 18, hx = rr - hy * 18;
-                    off = (hbase + (unsigned)(hy * p.xWp + hx)) * xpix + (unsigned)(((ln & 7) ^ (hx & 7)) * 16);
-                } else {                                 // 400 consecutive pixels; images past the batch re-read the last one
-                    const int lim = (nImg - n) * (HLW * HLW) - 1;
-                    const int rc = rr < lim ? rr : lim;
-                    const int hx = (rr % (HLW * HLW)) % HLW;
-                    off = (unsigned)(n * (HLW * HLW) + rc) * xpix + (unsigned)(((ln & 7) ^ (hx & 7)) * 16);
-                }
-                glds16s(src, off, sH + (i * NWI + wi) * 1024);
-            }
-        }
+        for (int i = 0; i < H; ++i) glds16s(src, hoff[i], sH + (i * NW + wi) * 1024);
     };
 
     // ---- fused producer (FUSE0) --------------------------------------------------------------------------------------
@@ -336,7 +295,11 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(halo_wa
         }
     };
 
-    const int wci = wave / WGP, wpi = wave % WGP;
+    // wci is 0 for each of the NW waves (one 64-channel slab) and wi above is simply `wave`.  Both stay spelled as they were when
+    // a 128-row, 8-wave tile shared this template: the compiler does not derive wci's range, folding either by hand changes
+    // instruction selection and register allocation of every kernel, and the emitted code is held instruction for instruction
+    // to that build (profiles/halo_prune.md)
+    const int wci = wave / NW, wpi = wave % NW;
     const int rowW = (wci * 64 + l15) * 128;
     const int wrow0 = wpi * FP;                          // first patch row of this wave
     const int l7 = lane & 7;
@@ -368,15 +331,10 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(halo_wa
         boff[0][kx] = NSW * WSTAGE + row * 128 + ((c0 ^ (col & 7)) << 4);
         boff[1][kx] = NSW * WSTAGE + row * 128 + ((c1 ^ (col & 7)) << 4);
     }
-    // Weight ring slot of a stage: NSW == 3 divides the nine taps of a channel block, so slot = tap % 3 is an immediate;
-    // NSW == 4 (one more stage of L2 -> LDS latency hidden) tracks the slot at run time: `wslot` = byte offset of the slot
-    // of the stage being computed, two VALU adds per stage.
-    int wslot = 0;
-    auto next_slot = [&](int off) __attribute__((always_inline)) { return off + WSTAGE == NSW * WSTAGE ? 0 : off + WSTAGE; };
-    auto load_a = [&](Frags& F, auto slot_tag, int roff) __attribute__((always_inline)) {        // weights: published by the barrier of the previous stage
+    // Weight ring slot of a stage: NSW == 3 divides the nine taps of a channel block, so slot = tap % 3 is an immediate.
+    auto load_a = [&](Frags& F, auto slot_tag) __attribute__((always_inline)) {        // weights: published by the barrier of the previous stage
         constexpr int SLOT = decltype(slot_tag)::value;
-        const int so = NSW == 3 ? SLOT * WSTAGE : roff;
-        const int a0 = aoff[0] + so, a1 = aoff[1] + so;
+        const int a0 = aoff[0] + SLOT * WSTAGE, a1 = aoff[1] + SLOT * WSTAGE;
 #pragma unroll
         for (int f = 0; f < FC; ++f) F.a[0][f] = *reinterpret_cast<const V*>(smem + a0 + f * 2048);
 #pragma unroll
@@ -447,111 +405,8 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(halo_wa
                 for (int f = 0; f < 4; ++f) rtrunk[g][f] = *reinterpret_cast<const f4*>(rb + (size_t)(pix0 + (unsigned)(g * p.yWp)) * 64 + f * 4);
         }
     };
-    // CHAIN 2, convolution 1 (block 0's output): the residual epilogue in the UNIT layout of the kernel's ordinary epilogue -- the
-    // accumulators are staged through LDS (the halo buffer is dead here and is the staging area; the weight ring stays live) and read
-    // back so that a lane holds 8 consecutive channels of a pixel and 8 consecutive lanes one pixel: the f32 residual arrives in one
-    // burst of full lines, the f32 output leaves in full lines, and a unit's f16 values are exactly one 16-byte chunk of the pixel's
-    // halo row, written once every wave has finished with the staging area.  (Straight from the accumulator layout the same traffic was
-    // 64 requests of 16 bytes per wave instruction: r05_tuning.md step 2.)
-#ifndef CV_CHAIN_MIDSTAGE_BUILD
-#define CV_CHAIN_MIDSTAGE_BUILD 0      // 1: also build the staged form of convolution 1's epilogue (CV_CHAIN_MIDSTAGE=1 selects it).  Measured (r05_tuning.md step 8): its mere presence costs the kernel 35 spilled loop invariants and 10 %; enabled it wins half of that back
-#endif
-    auto chain_epilogue_res_mid = [&]() __attribute__((always_inline)) {
-        if constexpr (CHAIN == 2 && CV_CHAIN_MIDSTAGE_BUILD) {
-            constexpr int UN = 8, UPP = 64 / UN, UPL = 16 * UPP / 64, SROW = 272, RG = 2;
-            static_assert(NW * RG * 16 * SROW <= HBYTES && FP % RG == 0, "staging fits in the halo buffer");
-            float sc[16], sh[16];
-#pragma unroll
-            for (int i = 0; i < 16; i += 4) {
-                const f4 a = *reinterpret_cast<const f4*>(p.ch_scale[1] + q * 16 + i);
-                const f4 b = *reinterpret_cast<const f4*>(p.ch_shift[1] + q * 16 + i);
-                sc[i] = a[0]; sc[i + 1] = a[1]; sc[i + 2] = a[2]; sc[i + 3] = a[3];
-                sh[i] = b[0]; sh[i + 1] = b[1]; sh[i + 2] = b[2]; sh[i + 3] = b[3];
-            }
-            const float* const rb = reinterpret_cast<const float*>(p.ch_res0);
-            float* const ob32 = reinterpret_cast<float*>(p.ch_y32_mid[0]);
-            const float rm = p.ch_res_mul[0];
-            // padded-plane pixel of (patch row wrow0 + g, column px) of image n
-            auto pixel = [&](int g, int px) __attribute__((always_inline)) { return (unsigned)((n * p.yHp + wrow0 + g + 1) * p.yWp + px + 1); };
-            // the residual of one row pair at a time (the whole tile's 64 registers spill here): the second pair's burst is issued before
-            // the first pair is worked on
-            f4 rraw[2][RG][UPL][2];
-            auto fetch_pair = [&](int g0, int slot) __attribute__((always_inline)) {
-#pragma unroll
-                for (int r = 0; r < RG; ++r)
-#pragma unroll
-                    for (int i = 0; i < UPL; ++i) {
-                        const int unit = lane + 64 * i, px = unit / UPP, co = (unit % UPP) * UN;
-                        trunk32_fetch(rb + ((size_t)pixel(g0 + r, px) * 64 + co), rraw[slot][r][i]);
-                    }
-            };
-            fetch_pair(0, 0);
-            char* const stg = halo + wave * (RG * 16 * SROW);
-            half8 hold[FP][UPL];
-            float bad = 0.f;
-#pragma unroll
-            for (int g0 = 0; g0 < FP; g0 += RG) {
-                if (g0 + RG < FP) fetch_pair(g0 + RG, ((g0 / RG) + 1) & 1);
-#pragma unroll
-                for (int r = 0; r < RG; ++r)
-#pragma unroll
-                    for (int f = 0; f < FC; ++f) {
-                        f4 t;
-#pragma unroll
-                        for (int k = 0; k < 4; ++k) t[k] = acc[f][g0 + r][k] * sc[f * 4 + k] + sh[f * 4 + k];
-                        *reinterpret_cast<f4*>(stg + r * (16 * SROW) + l15 * SROW + (q * 16 + f * 4) * 4) = t;
-                    }
-                wave_lds_sync();
-#pragma unroll
-                for (int i = 0; i < UPL; ++i) {
-                    const int unit = lane + 64 * i, px = unit / UPP, cu = unit % UPP;
-#pragma unroll
-                    for (int r = 0; r < RG; ++r) {
-                        float w[UN];
-#pragma unroll
-                        for (int j = 0; j < UN; j += 4) {
-                            const f4 t = *reinterpret_cast<const f4*>(stg + r * (16 * SROW) + px * SROW + (cu * UN + j) * 4);
-                            w[j] = t[0]; w[j + 1] = t[1]; w[j + 2] = t[2]; w[j + 3] = t[3];
-                        }
-                        trunk32_add_raw(rraw[(g0 / RG) & 1][r][i], w, rm);
-#pragma unroll
-                        for (int j = 0; j < UN; ++j) w[j] = __builtin_fmaxf(w[j], 0.f);
-                        trunk32_store(ob32 + ((size_t)pixel(g0 + r, px) * 64 + cu * UN), w);
-                        half8 h;
-#pragma unroll
-                        for (int j = 0; j < UN; ++j) { h[j] = (half_t)w[j]; bad = __builtin_fmaf((float)h[j], 0.f, bad); }
-                        hold[g0 + r][i] = h;
-                    }
-                }
-                wave_lds_sync();
-            }
-            asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");      // every wave has read its staged rows back: the buffer becomes the halo again
-#pragma unroll
-            for (int g = 0; g < FP; ++g)
-#pragma unroll
-                for (int i = 0; i < UPL; ++i) {
-                    const int unit = lane + 64 * i, px = unit / UPP, cu = unit % UPP, hx = px + 1;
-                    *reinterpret_cast<half8*>(halo + ((wrow0 + g + 1) * 18 + hx) * 128 + ((cu ^ (hx & 7)) << 4)) = hold[g][i];
-                }
-            // the staging area covered halo rows 0 .. 271, border pixels included: the zero border (= the next convolution's padding) is
-            // restored -- 68 border pixels x 8 chunks of 16 bytes
-            typedef unsigned u4z __attribute__((ext_vector_type(4)));
-#pragma unroll
-            for (int k = 0; k < 3; ++k) {
-                const int idx = tid + 256 * k, bp = idx >> 3, ch = idx & 7;
-                if (bp < 68) {
-                    const int j = bp - 36;
-                    const int hy = bp < 18 ? 0 : bp < 36 ? 17 : 1 + (j >> 1);
-                    const int hxz = bp < 18 ? bp : bp < 36 ? bp - 18 : ((j & 1) ? 17 : 0);
-                    *reinterpret_cast<u4z*>(halo + (hy * 18 + hxz) * 128 + ch * 16) = u4z{0u, 0u, 0u, 0u};
-                }
-            }
-            if (bad != bad && p.flag) atomicMin(p.flag, p.ch_layer_id[1]);
-        }
-    };
     auto chain_epilogue = [&](int c) __attribute__((always_inline)) {
         if constexpr (CHAIN) {
-            if (CHAIN == 2 && CV_CHAIN_MIDSTAGE_BUILD && c == 1 && (p.chain & 16)) { chain_epilogue_res_mid(); return; }
             const bool has_res = (c & 1) != 0, last = c == 2 * CNB - 1;   // wave-uniform
             const int blk = c >> 1;                             // the BasicBlock convolution c belongs to
             const float* const scp = p.ch_scale[c] + q * 16;
@@ -626,13 +481,10 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(halo_wa
     Frags F0, F1;
     int s = 0;
     auto issue_prologue_halo = [&]() __attribute__((always_inline)) {
-        if (is_h && !FUSE0) issue_halo(0, 0, std::integral_constant<int, 0>{}, std::integral_constant<int, H>{});
+        if (!FUSE0) issue_halo(0, 0);
     };
     auto issue_prologue_w = [&]() __attribute__((always_inline)) {
-        if (is_w) {
-            issue_w(0, 0); issue_w(1, 1); issue_w(2, 2);
-            if (NSW == 4) issue_w(3 < nS ? 3 : nS - 1, 3);
-        }
+        issue_w(0, 0); issue_w(1, 1); issue_w(2, 2);
     };
     auto issue_prologue = [&]() __attribute__((always_inline)) {                        // first DMAs of the tile `decode` was last called for
         issue_prologue_halo();
@@ -669,11 +521,10 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(halo_wa
         }
 #endif
         // vmcnt at the barrier of stage s: W(s+1) must have landed, W(s+2) (issued one stage ago; a weight stage is
-        // issued at every barrier, clamped at the end) may fly.  Symmetric duties: plus the next halo when it was issued
-        // one or two stages ago.  Roles: the halo waves drain theirs at tap 7 (its last pieces leave at tap 5; the
-        // next block's pixel reads start in the head of tap 8).
+        // issued at every barrier, clamped at the end) may fly.  Plus the next halo when it was issued
+        // one or two stages ago.
         // the next halo is younger than W(s+1): double buffered, issued at tap 0; single buffer, issued at tap 7
-        const bool halo_young = !kRoles && !FUSE0 && !CHAIN && more_cb && (DBH ? (J >= 1 && J <= NSW - 1) : J == 8);
+        const bool halo_young = !FUSE0 && !CHAIN && more_cb && (DBH ? (J >= 1 && J <= NSW - 1) : J == 8);
         // CHAIN: the sixteen f32 stores of an inner block's epilogue (convolution 2 k + 1) are younger than the weight stage issued in its
         // tap 8 and older than the one issued in tap 0 of convolution 2 k + 2: the first two barriers of that one may leave them in flight as well
         const bool chain_young = CHAIN == 2 && J <= 1 && cb >= 2 && (cb & 1) == 0;
@@ -683,10 +534,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(halo_wa
         __builtin_amdgcn_sched_barrier(0);              // the head MFMAs stay in front of the rendezvous, the tail behind it
         constexpr int FLY = (NSW - 2) * LW;             // weight pieces of the stages after W(s+1), still allowed in flight
         static_assert(FLY + H <= 63, "vmcnt range");
-        if (kRoles && !is_w) {
-            if (J == 7) wait_vm_barrier<0>();
-            else wait_vm_barrier<63>();
-        } else if (halo_young) wait_vm_barrier<FLY + H>();
+        if (halo_young) wait_vm_barrier<FLY + H>();
         else if (chain_young) wait_vm_barrier<FLY + kChainStores>();
         else wait_vm_barrier<FLY>();
         __builtin_amdgcn_sched_barrier(0);
@@ -698,33 +546,22 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(halo_wa
         // issues and LDS reads out between the tail MFMAs instead of leaving the matrix pipe idle while both waves
         // of a SIMD issue them back to back (measured r01: that phase alone was 29 % of the stage).
 #if CV_ABLATE != 1 && CV_ABLATE != 3
-        if constexpr (kRoles) {
-            // un-interleaved on purpose: the other wave of this SIMD covers the matrix pipe meanwhile
-            if (is_w) issue_w(s + NSW < nS ? s + NSW : nS - 1, NSW == 3 ? J % 3 : wslot / WSTAGE);
-            else if (DBH && J < 6 && more_cb) issue_halo(cb + 1, HB ^ 1, std::integral_constant<int, J * HPS>{}, std::integral_constant<int, HPS>{});
-        } else {
-            issue_w(s + NSW < nS ? s + NSW : nS - 1, NSW == 3 ? J % 3 : wslot / WSTAGE);
-            if (kRefillIssue && !FUSE0 && !CHAIN && more_cb) issue_halo(cb + 1, 0, std::integral_constant<int, 0>{}, std::integral_constant<int, H>{});
-            if (DBH && J == 0 && more_cb) issue_halo(cb + 1, HB ^ 1, std::integral_constant<int, 0>{}, std::integral_constant<int, H>{});
-        }
+        issue_w(s + NSW < nS ? s + NSW : nS - 1, J % 3);
+        if (kRefillIssue && !FUSE0 && !CHAIN && more_cb) issue_halo(cb + 1, 0);
+        if (DBH && J == 0 && more_cb) issue_halo(cb + 1, HB ^ 1);
 #endif
 #if CV_ABLATE != 3
-        wslot = next_slot(wslot);                         // now the slot of stage s + 1
-        // CHAIN 2, tap 8 of convolution 1: its epilogue needs these registers for the residual burst -- the weight fragments are read after it
-        const bool late_a = CHAIN == 2 && CV_CHAIN_MIDSTAGE_BUILD && J == 8 && cb == 1 && (p.chain & 16);
-        if (!late_a) load_a(nxt, std::integral_constant<int, (J + 1) % 3>{}, wslot);
+        load_a(nxt, std::integral_constant<int, (J + 1) % 3>{});
 #endif
 #if CV_STAMP
         const unsigned long long st_c = __builtin_amdgcn_s_memtime();
 #endif
         mma_tail(cur);
 #if CV_SCHED_HINTS
-        if constexpr (!kRoles) {
 #pragma unroll
-            for (int i = 0; i < LW + (kRefillIssue && !FUSE0 && !CHAIN ? H : 0); ++i) {
-                __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);           // one LDS-DMA (VMEM read)
-                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);           // one MFMA
-            }
+        for (int i = 0; i < LW + (kRefillIssue && !FUSE0 && !CHAIN ? H : 0); ++i) {
+            __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);               // one LDS-DMA (VMEM read)
+            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);               // one MFMA
         }
 #pragma unroll
         for (int i = 0; i < 2 * FC; ++i) {
@@ -748,7 +585,6 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(halo_wa
 #pragma unroll
                         for (int g = 0; g < FP; ++g) acc[f][g] = f4{0.f, 0.f, 0.f, 0.f};
                     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-                    if (late_a) load_a(nxt, std::integral_constant<int, (J + 1) % 3>{}, wslot);
                 } else {
                     // everybody's pieces of the next halo have landed (only the weight stage issued after them may still fly)
                     asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" ::"n"(LW) : "memory");
@@ -790,13 +626,11 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(halo_wa
 #pragma unroll
         for (int g = 0; g < FP; ++g) acc[f][g] = f4{0.f, 0.f, 0.f, 0.f};
     if (first) {
-        if (is_w) wait_vm_barrier<(NSW - 1) * LW>();    // halo(0) and W(0) landed; the later weight stages may still fly
-        else wait_vm_barrier<0>();
+        wait_vm_barrier<(NSW - 1) * LW>();              // halo(0) and W(0) landed; the later weight stages may still fly
     } else {
         wait_vm_barrier<0>();                            // issued a whole epilogue ago; also drains that epilogue's stores
     }
-    wslot = 0;
-    load_a(F0, std::integral_constant<int, 0>{}, 0);
+    load_a(F0, std::integral_constant<int, 0>{});
     load_b(F0, std::integral_constant<int, 0>{}, std::integral_constant<int, 0>{});
     s = 0;
     for (int cb = 0; cb < nCb; cb += 2) {
@@ -895,16 +729,15 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(halo_wa
 #endif
     if (more_tiles) {                                    // next tile: halo(0) -> buffer 0, W(0..2) -> ring; lands during this epilogue
         decode(nxt_tile);
-        if constexpr (DBH) issue_prologue();
-        else issue_prologue_halo();                      // single halo buffer: the ring is this epilogue's staging area, the weights follow it
+        issue_prologue_halo();                           // the ring is this epilogue's staging area, the weights follow it
     }
     // Patch rows are staged RG at a time in wave-private LDS and read back so that consecutive lanes hold consecutive
     // bytes; output addresses are derived from the pixel index.  A persistent workgroup stages where the next tile's DMAs in
-    // flight do not write, one row per wave: double-buffered halo -> halo buffer 1 (halo(0) and the first weight stages fly);
-    // single halo buffer -> the weight ring (only the next halo flies; the weight stages are issued behind the staging).
+    // flight do not write, one row per wave: the weight ring (only the next halo flies; the weight stages are issued behind the
+    // staging).
     constexpr int RG = PERSIST ? 1 : 2;
-    static_assert(FP % 2 == 0 && NW * RG * 16 * SROW <= (PERSIST ? (DBH ? HBYTES : NSW * WSTAGE) : NSW * WSTAGE + (DBH ? 2 : 1) * HBYTES), "staging must fit in LDS");
-    char* const stg = (PERSIST && DBH ? halo + HBYTES : smem) + wave * (RG * 16 * SROW);
+    static_assert(FP % 2 == 0 && NW * RG * 16 * SROW <= (PERSIST ? NSW * WSTAGE : NSW * WSTAGE + (DBH ? 2 : 1) * HBYTES), "staging must fit in LDS");
+    char* const stg = smem + wave * (RG * 16 * SROW);
     const int slab0 = eCt * CT + wci * 64;
     T* const pbase = reinterpret_cast<T*>(p.pool_y);
     const bool relu_early = p.relu && !rbase;
@@ -925,7 +758,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(halo_wa
     // epilogue of a residual layer took 26 k cycles against 11 k without one -- as long as the 18-stage K loop itself).
     constexpr bool kHalf = __is_same(T, half_t);         // f16 kernels can take the shortcut from the trunk's f32 twin (two chunks per unit)
     constexpr int RC = kHalf ? 2 : OutVec<T, UN>::kRawChunks;
-    constexpr bool kPrefetchRes = !PERSIST && NW == 4;   // the 4-wave tile has the registers (FP x UPL units x RC chunks)
+    constexpr bool kPrefetchRes = !PERSIST;              // the 4-wave tile has the registers (FP x UPL units x RC chunks)
     const bool res32 = kHalf && p.res_f32;               // wave-uniform
     const float* const rbase32 = reinterpret_cast<const float*>(p.res);
     float* const ybase32 = kHalf ? reinterpret_cast<float*>(p.y32) : nullptr;
@@ -1065,7 +898,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(halo_wa
 #endif
     report_bad(p, bad);
     if (!more_tiles) break;
-    if constexpr (PERSIST && !DBH) {                     // every wave has read its staged rows back: the ring is free for the next tile
+    if constexpr (PERSIST) {                             // every wave has read its staged rows back: the ring is free for the next tile
         asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
         issue_prologue_w();
     }
@@ -1074,92 +907,63 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(halo_wa
 }
 
 // ---- host-side launch -------------------------------------------------------------------------------------
-// the 64-channel tile over a 16 x 16 patch keeps a single halo buffer (see the kernel: DBH)
-template <int CT, int TH> static constexpr bool halo_double() { return !(CT == 64 && (TH == 16 || (TH == 8 && CV_HALO_TH8_SINGLE))); }
-
-template <int CT, int TH, int NW, int TPS, int NSW, int IMG>
+// the tile over a 16 x 16 patch keeps a single halo buffer (see the kernel: DBH)
+template <int TH, int IMG>
 static constexpr size_t halo_lds() {
     constexpr int HR = IMG ? 4 * (IMG + 2) * (IMG + 2) : 18 * (TH + 2);
-    constexpr int NWI = NW == 8 ? NW / 2 : NW;          // as in the kernel: waves per DMA role
-    constexpr int H = ((HR + 7) / 8 + NWI - 1) / NWI;
-    return (size_t)NSW * TPS * CT * 128 + (size_t)(halo_double<CT, TH>() ? 2 : 1) * H * NWI * 1024;
+    constexpr int H = ((HR + 7) / 8 + kHaloNW - 1) / kHaloNW;       // as in the kernel
+    return (size_t)kHaloNSW * kHaloCT * 128 + (size_t)(TH == 8 ? 2 : 1) * H * kHaloNW * 1024;
 }
 
 static int g_halo_cus = 256;                            // CUs of the device (set by conv_halo_prepare)
 
-// 8-wave tiles (one 136-152 KB workgroup per CU) run persistent; CV_HALO_PERSIST=0 launches one workgroup per tile
-template <int NW> static bool halo_persistent() {
-    static const bool on = [] { const char* v = std::getenv("CV_HALO_PERSIST"); return !(v && v[0] == '0'); }();
-    return NW == 8 && on;
-}
-
 constexpr size_t kFuse0Lds = 4864 + 4096 + 512;         // [3][20][20] f32 input patch + zero slot | block-1 weight fragments | BN constants
-template <typename T, int CT, int TH> static constexpr bool halo_can_fuse0() { return CT == 64 && TH == 16 && __is_same(T, split_t); }
+template <typename T, int TH, int IMG> static constexpr bool halo_can_fuse0() { return TH == 16 && IMG == 0 && __is_same(T, split_t); }
 
-template <typename T, int CT, int TH, int WGC, int NW, int TPS, int NSW, int IMG>
+template <typename T, int TH, int IMG>
 static hipError_t launch_halo(const ConvParams& p, int n_images, hipStream_t stream) {
     const bool split = p.ksplit > 1;
     if (split && (IMG != 0 || p.f0_x || !p.partial || p.kper < 1)) return hipErrorInvalidValue;
     const int tiles = (IMG ? (n_images + 3) / 4 : n_images * (p.Ho / TH) * (p.Wo / 16)) * p.nCt * (split ? p.ksplit : 1);
-    const size_t lds = halo_lds<CT, TH, NW, TPS, NSW, IMG>();
+    const size_t lds = halo_lds<TH, IMG>();
     if (p.f0_x) {
-        if constexpr (halo_can_fuse0<T, CT, TH>() && IMG == 0) {
-            auto kern = conv3x3_halo_kernel<T, CT, TH, WGC, NW, TPS, NSW, IMG, false, false, true>;
-            hipLaunchKernelGGL(kern, dim3((unsigned)tiles), dim3(64 * NW), lds + kFuse0Lds, stream, p);
+        if constexpr (halo_can_fuse0<T, TH, IMG>()) {
+            auto kern = conv3x3_halo_kernel<T, TH, IMG, false, true>;
+            hipLaunchKernelGGL(kern, dim3((unsigned)tiles), dim3(64 * kHaloNW), lds + kFuse0Lds, stream, p);
             return hipGetLastError();
         } else {
             return hipErrorInvalidValue;
         }
     }
-    static_assert(halo_lds<CT, TH, NW, TPS, NSW, IMG>() <= 160 * 1024, "LDS budget");
-    // persistent only where it pays (same-box A/B, r01_tuning.md step 22): several tiles per CU and a K loop short enough
-    // for the hidden prologue to matter; long loops lose ~1 % to the single-row staging
-    static const int max_k = [] { const char* v = std::getenv("CV_HALO_PERSIST_MAXK"); return v && *v ? std::atoi(v) : 72; }();
-    bool launched = false;
-    if constexpr (CT == 64 && NW == 4 && IMG == 0 && !halo_double<CT, TH>()) {
+    static_assert(halo_lds<TH, IMG>() <= 160 * 1024, "LDS budget");
+    if constexpr (TH == 16 && IMG == 0) {
         // the production tile, persistent (two resident workgroups per CU walk the tiles; the next tile's halo flies during the
         // epilogue): CV_HALO_PERSIST64=1, launches of short K with many tiles only
         static const int on64 = [] { const char* v = std::getenv("CV_HALO_PERSIST64"); return v && *v ? std::atoi(v) : 0; }();
         static const int max_k64 = [] { const char* v = std::getenv("CV_HALO_PERSIST64_MAXK"); return v && *v ? std::atoi(v) : 36; }();
         if (on64 && !split && !p.head_w && !p.res && tiles >= 8 * g_halo_cus && p.nStages <= max_k64) {
-            auto kern = conv3x3_halo_kernel<T, CT, TH, WGC, NW, TPS, NSW, IMG, true, false>;
-            hipLaunchKernelGGL(kern, dim3((unsigned)(2 * g_halo_cus)), dim3(64 * NW), lds, stream, p);
-            launched = true;
+            auto kern = conv3x3_halo_kernel<T, TH, IMG, true>;
+            hipLaunchKernelGGL(kern, dim3((unsigned)(2 * g_halo_cus)), dim3(64 * kHaloNW), lds, stream, p);
+            return hipGetLastError();
         }
     }
-    if constexpr (NW == 8) {
-        if (halo_persistent<NW>() && !split && tiles >= 4 * g_halo_cus && p.nStages <= max_k) {
-            auto kern = conv3x3_halo_kernel<T, CT, TH, WGC, NW, TPS, NSW, IMG, true, true>;
-            const int grid = tiles < g_halo_cus ? tiles : g_halo_cus;
-            hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(64 * NW), lds, stream, p);
-            launched = true;
-        }
-    }
-    if (!launched) {
-        auto kern = conv3x3_halo_kernel<T, CT, TH, WGC, NW, TPS, NSW, IMG, false, halo_double<CT, TH>()>;
-        hipLaunchKernelGGL(kern, dim3((unsigned)tiles), dim3(64 * NW), lds, stream, p);
-    }
+    auto kern = conv3x3_halo_kernel<T, TH, IMG, false>;
+    hipLaunchKernelGGL(kern, dim3((unsigned)tiles), dim3(64 * kHaloNW), lds, stream, p);
     return hipGetLastError();
 }
 
-template <typename T, int CT, int TH, int WGC, int NW, int TPS, int NSW, int IMG>
+static hipError_t halo_allow_lds(void (*kern)(const ConvParams)) {
+    return hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+}
+
+template <typename T, int TH, int IMG>
 static hipError_t prepare_halo() {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv3x3_halo_kernel<T, CT, TH, WGC, NW, TPS, NSW, IMG, false, halo_double<CT, TH>()>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if constexpr (halo_can_fuse0<T, CT, TH>() && IMG == 0) {
-        if (e == hipSuccess)
-            e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv3x3_halo_kernel<T, CT, TH, WGC, NW, TPS, NSW, IMG, false, false, true>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    hipError_t e = halo_allow_lds(conv3x3_halo_kernel<T, TH, IMG, false>);
+    if constexpr (halo_can_fuse0<T, TH, IMG>()) {
+        if (e == hipSuccess) e = halo_allow_lds(conv3x3_halo_kernel<T, TH, IMG, false, true>);
     }
-    if constexpr (CT == 64 && NW == 4 && IMG == 0 && !halo_double<CT, TH>()) {
-        if (e == hipSuccess)
-            e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv3x3_halo_kernel<T, CT, TH, WGC, NW, TPS, NSW, IMG, true, false>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    }
-    if constexpr (NW == 8) {                             // persistent variants of the 8-wave (double-buffered) tiles
-        if (e == hipSuccess)
-            e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv3x3_halo_kernel<T, CT, TH, WGC, NW, TPS, NSW, IMG, true, true>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    if constexpr (TH == 16 && IMG == 0) {
+        if (e == hipSuccess) e = halo_allow_lds(conv3x3_halo_kernel<T, TH, IMG, true>);
     }
     return e;
 }
@@ -1167,105 +971,67 @@ static hipError_t prepare_halo() {
 // configurations: 64 channels x 16x16 patch (4 waves, four patch rows each), one tap per stage, ring 3, ONE halo buffer: 68 KB,
 //                 so two workgroups share a CU; each fills the other's barrier stalls and its halo refill at the channel-block
 //                 boundaries (r02_tuning.md: +8-16 % over the double-buffered 8x16 patch of round 1, which did half the MFMAs per
-//                 weight byte and per fragment read; -DCV_HALO_TH64=8 builds that tile).  THE production tile: layers of any
+//                 weight byte and per fragment read).  THE production tile: layers of any
 //                 width run it as Cout/64 channel tiles (engine.cpp: choose_ct), with the fused first-layer producer for
 //                 UNet inc (FUSE0) and over four packed 8x8 images for ResNet-18 layer2;
-//                 128 channels x 16x16 patch (8 waves as 2 x 4, four patch rows each, halo double buffered, persistent for short
-//                 K) and its packed-image form: round 1's tile for Cout >= 128, now an A/B option (CV_CT64_MAXROWS=64,
-//                 CV_HALO_IMG8_64=0) -- one 136 KB workgroup per CU loses to two 68 KB ones at every width (r02_tuning.md step 14).
-// (Measured and dropped: an 8-wave 64 x 16x16 variant, -10 % (r01_tuning.md step 17); the 16x16 patch with a double-buffered halo
-//  and therefore one workgroup per CU, -8..-17 %; a 4-deep weight ring, +-1 % (r02_tuning.md).)
-#ifndef CV_HALO_NSW64
-#define CV_HALO_NSW64 3
-#endif
-#ifndef CV_HALO_NSW128
-#define CV_HALO_NSW128 3
-#endif
-#ifndef CV_HALO_TH64
-#define CV_HALO_TH64 16                       // patch rows of the 64-channel tile: 16 (single halo buffer, 68 KB) | 8 (double buffered, 72 KB)
-#endif
-#define CV_FOR_EACH_HALO_MAIN(X, T)           \
-    X(T, 64, CV_HALO_TH64, 1, 4, 1, CV_HALO_NSW64, 0)    \
-    X(T, 128, 16, 2, 8, 1, CV_HALO_NSW128, 0) \
-    X(T, 128, 16, 2, 8, 1, 3, 8)              \
-    X(T, 64, 16, 1, 4, 1, 3, 8)
 // round 4: the 64-channel tile over an 8 x 16 patch (double-buffered halo, 72 KB, two workgroups per CU -- round 1's tile) next to the
 // production 16 x 16 one, for launches whose 16 x 16 patches number fewer than the chip can hold (single boards: 128 tiles on 256
 // CUs): twice the workgroups for the same work
-#if CV_HALO_TH64 == 16
-#define CV_FOR_EACH_HALO(X, T) CV_FOR_EACH_HALO_MAIN(X, T) X(T, 64, 8, 1, 4, 1, 3, 0)
-#else
-#define CV_FOR_EACH_HALO(X, T) CV_FOR_EACH_HALO_MAIN(X, T)
-#endif
+// (Measured and dropped: an 8-wave 64 x 16x16 variant, -10 % (r01_tuning.md step 17); the 16x16 patch with a double-buffered halo
+//  and therefore one workgroup per CU, -8..-17 %; a 4-deep weight ring, +-1 % (r02_tuning.md); round 1's 128 channels x 16x16 patch
+//  (8 waves as 2 x 4 with split DMA roles, halo double buffered, persistent for short K) and its packed-image form: one 136 KB
+//  workgroup per CU loses to two 68 KB ones at every width (r02_tuning.md step 14); the chain's first residual epilogue staged
+//  through LDS in the unit layout: its mere presence cost the kernel 35 spilled loop invariants and 10 % (r05_tuning.md step 8).)
+#define CV_FOR_EACH_HALO(X, T) X(T, 16, 0) X(T, 16, 8) X(T, 8, 0)
+
+// four or six chained 64 -> 64 convolutions (two or three BasicBlocks) on whole 16 x 16 images (ConvParams::chain): one workgroup per
+// image, 69.6 KB of LDS
+static void (*const kChainKernels[2][2])(const ConvParams) = {      // [CHAIN - 1][CNB - 2]
+    {conv3x3_halo_kernel<half_t, 16, 0, false, false, 1, 2>, conv3x3_halo_kernel<half_t, 16, 0, false, false, 1, 3>},
+    {conv3x3_halo_kernel<half_t, 16, 0, false, false, 2, 2>, conv3x3_halo_kernel<half_t, 16, 0, false, false, 2, 3>}};
 
 hipError_t conv_halo_prepare() {
     hipError_t e;
     int dev = 0, cus = 0;
     if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && cus > 0)
         g_halo_cus = cus;
-#define X(T, CT, TH, WGC, NW, TPS, NSW, IMG) \
-    if ((e = prepare_halo<T, CT, TH, WGC, NW, TPS, NSW, IMG>()) != hipSuccess) return e;
+#define X(T, TH, IMG) \
+    if ((e = prepare_halo<T, TH, IMG>()) != hipSuccess) return e;
     CV_FOR_EACH_HALO(X, half_t)
     CV_FOR_EACH_HALO(X, float)
     CV_FOR_EACH_HALO(X, split_t)
 #undef X
-#if CV_HALO_TH64 == 16 && CV_HALO_NSW64 == 3
-    if ((e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv3x3_halo_kernel<half_t, 64, 16, 1, 4, 1, 3, 0, false, false, false, 1>),
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)) != hipSuccess) return e;
-    if ((e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv3x3_halo_kernel<half_t, 64, 16, 1, 4, 1, 3, 0, false, false, false, 2>),
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)) != hipSuccess) return e;
-    if ((e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv3x3_halo_kernel<half_t, 64, 16, 1, 4, 1, 3, 0, false, false, false, 1, 3>),
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)) != hipSuccess) return e;
-    if ((e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv3x3_halo_kernel<half_t, 64, 16, 1, 4, 1, 3, 0, false, false, false, 2, 3>),
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)) != hipSuccess) return e;
-#endif
+    for (const auto& form : kChainKernels)
+        for (const auto kern : form)
+            if ((e = halo_allow_lds(kern)) != hipSuccess) return e;
     return hipSuccess;
 }
 
 // The 64-row tile (4 waves, two workgroups per CU) beats conv_igemm's 64x256 tile on the 64-channel layers (r01_tuning.md step
-// 16, r02_tuning.md); CV_HALO64=0 switches it off for A/B runs, CV_HALO_IMG8=0 the packed-image mode.
-bool conv_halo_can_fuse_first_layer(int ct, int dt) { return ct == 64 && CV_HALO_TH64 == 16 && dt == kSplit; }
+// 16, r02_tuning.md); CV_HALO_IMG8=0 switches the packed-image mode off for A/B runs.
+bool conv_halo_can_fuse_first_layer(int dt) { return dt == kSplit; }
 
-bool conv_halo_supported(int ct, int Ho, int Wo) {
-    static const bool allow64 = [] { const char* v = std::getenv("CV_HALO64"); return !(v && v[0] == '0'); }();
+bool conv_halo_supported(int Ho, int Wo) {
     static const bool allow_img8 = [] { const char* v = std::getenv("CV_HALO_IMG8"); return !(v && v[0] == '0'); }();
-    static const bool img8_64 = [] { const char* v = std::getenv("CV_HALO_IMG8_64"); return !(v && v[0] == '0'); }();
-    if (ct == 128 && Ho == 8 && Wo == 8) return allow_img8;
-    if (ct == 64 && Ho == 8 && Wo == 8) return allow_img8 && img8_64 && CV_HALO_TH64 == 16;
-    return (ct == 128 || (ct == 64 && allow64)) && Ho % 16 == 0 && Wo % 16 == 0;
+    if (Ho == 8 && Wo == 8) return allow_img8;
+    return Ho % 16 == 0 && Wo % 16 == 0;
 }
 
-bool conv_halo_has_th8(int ct) { return ct == 64 && CV_HALO_TH64 == 16; }
-
-// four or six chained 64 -> 64 convolutions (two or three BasicBlocks) on whole 16 x 16 images (ConvParams::chain): one workgroup per
-// image, 69.6 KB of LDS
-bool conv_halo_has_chain() { return CV_HALO_TH64 == 16 && CV_HALO_NSW64 == 3; }
 hipError_t conv_halo_chain_launch(const ConvParams& p, int n_images, hipStream_t stream) {
-#if CV_HALO_TH64 == 16 && CV_HALO_NSW64 == 3
     if (!p.chain || (p.nStages != 36 && p.nStages != 54) || p.Ho != 16 || p.Wo != 16 || p.yCs != 64 || p.xCs != 64 || p.ksplit > 1 || n_images < 1)
         return hipErrorInvalidValue;
-    const size_t lds = halo_lds<64, 16, 4, 1, 3, 0>();
-    const bool three = p.nStages == 54;
-    if ((p.chain & 3) == 1) {                            // one workgroup per CU (its 512 registers per lane see to that)
-        auto kern = three ? conv3x3_halo_kernel<half_t, 64, 16, 1, 4, 1, 3, 0, false, false, false, 1, 3>
-                          : conv3x3_halo_kernel<half_t, 64, 16, 1, 4, 1, 3, 0, false, false, false, 1>;
-        hipLaunchKernelGGL(kern, dim3((unsigned)n_images), dim3(256), lds, stream, p);
-    } else {
-        auto kern = three ? conv3x3_halo_kernel<half_t, 64, 16, 1, 4, 1, 3, 0, false, false, false, 2, 3>
-                          : conv3x3_halo_kernel<half_t, 64, 16, 1, 4, 1, 3, 0, false, false, false, 2>;
-        hipLaunchKernelGGL(kern, dim3((unsigned)n_images), dim3(256), lds, stream, p);
-    }
+    // CHAIN 1: one workgroup per CU (its 512 registers per lane see to that)
+    const size_t lds = halo_lds<16, 0>();
+    auto kern = kChainKernels[p.chain == 1 ? 0 : 1][p.nStages == 54];
+    hipLaunchKernelGGL(kern, dim3((unsigned)n_images), dim3(64 * kHaloNW), lds, stream, p);
     return hipGetLastError();
-#else
-    return hipErrorInvalidValue;
-#endif
 }
 
-hipError_t conv_halo_launch(int ct, int dt, const ConvParams& p, int n_images, hipStream_t stream, int th) {
+hipError_t conv_halo_launch(int dt, const ConvParams& p, int n_images, hipStream_t stream, int th) {
     const int img = (p.Ho == 8 && p.Wo == 8) ? 8 : 0;
-    if (img || !(th == 8 && conv_halo_has_th8(ct))) th = ct == 64 ? CV_HALO_TH64 : 16;
-#define X(T, CT, TH, WGC, NW, TPS, NSW, IMG) \
-    if (ct == CT && img == IMG && (IMG != 0 || th == TH)) return launch_halo<T, CT, TH, WGC, NW, TPS, NSW, IMG>(p, n_images, stream);
+    if (img || th != 8) th = 16;
+#define X(T, TH, IMG) \
+    if (img == IMG && th == TH) return launch_halo<T, TH, IMG>(p, n_images, stream);
     if (dt == kF16) { CV_FOR_EACH_HALO(X, half_t) } else if (dt == kSplit) { CV_FOR_EACH_HALO(X, split_t) } else { CV_FOR_EACH_HALO(X, float) }
 #undef X
     return hipErrorInvalidValue;

@@ -32,14 +32,12 @@ int conv_cfg_ct(int cfg);
 
 // conv_halo.hip: 3x3 / stride-1 layers with the input patch (+halo) resident in LDS across the nine taps
 hipError_t conv_halo_prepare();
-bool conv_halo_supported(int ct, int Ho, int Wo);
-bool conv_halo_can_fuse_first_layer(int ct, int dt);     // ConvParams::f0_* (the 64-channel single-halo tile, split-f16)
-bool conv_halo_has_th8(int ct);                          // the 8 x 16 patch variant of the tile exists (64-channel tile)
+bool conv_halo_supported(int Ho, int Wo);                // the one channel tile is 64 rows: layers are packed with ct = 64 for it
+bool conv_halo_can_fuse_first_layer(int dt);             // ConvParams::f0_* (the 64-channel single-halo tile, split-f16)
 // th: patch rows of the tile, 16 (default) or 8 (twice the workgroups: launches with few patches)
-hipError_t conv_halo_launch(int ct, int dt, const ConvParams& p, int n_images, hipStream_t stream, int th = 16);
+hipError_t conv_halo_launch(int dt, const ConvParams& p, int n_images, hipStream_t stream, int th = 16);
 int conv_cfg_pt(int cfg);
 // ConvParams::chain: four chained 3x3 convolutions 64 -> 64 over whole 16 x 16 images in one launch (f16 kernels, f16r trunk)
-bool conv_halo_has_chain();
 hipError_t conv_halo_chain_launch(const ConvParams& p, int n_images, hipStream_t stream);
 
 }  // namespace cv

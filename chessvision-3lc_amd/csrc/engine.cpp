@@ -333,7 +333,7 @@ static Status finish_layer(ConvLayer& L, std::vector<float>& Wk, int K, const st
     // experiment knob: channel tile of the k2 s2 transposed convolutions (64 -> the 80 KB 64x256 tile, two workgroups per CU)
     static const int convt_ct = env_int("CV_CONVT_CT", 0);
     const int CT = L.ct = (L.shuffle && (convt_ct == 64 || convt_ct == 128) && L.rows % convt_ct == 0)
-                              ? convt_ct : choose_ct(L.rows, L.pixels_hint, L.halo_ok, L.halo_img8);
+                              ? convt_ct : choose_ct(L.rows, L.pixels_hint, L.halo_ok);
     L.nStages = (chunks_for(L.dt, K) + 7) / 8;
     L.nCt = (L.rows + CT - 1) / CT;
     L.rowsPad = L.nCt * CT;
@@ -467,7 +467,6 @@ Status ConvLayer::build_conv(const std::string& name_, int dt_, const float* w_o
     want_round_err = dt_ == kF16 && calibration_enabled() && bias_correction_enabled();
     halo_ok = k_ == 3 && stride_ == 1 && out_hw_ > 0 && (out_hw_ % 16 == 0 || (out_hw_ == 8 && cout_ % 128 == 0)) &&
               cinPad_ % (128 / dtype_size(dt_)) == 0;
-    halo_img8 = out_hw_ == 8;
     if (cinPad % 8 || cinPad < cin) return fail(1, name + ": input channel padding must be a multiple of 8");
     if (k != 1 && k != 3) return fail(1, name + ": implicit-GEMM path supports 1x1 and 3x3 kernels");
     if (cout % 16) return fail(1, name + ": output channels must be a multiple of 16");
@@ -639,15 +638,12 @@ static int env_cached(int idx) {                      // 0: CV_CONV_W8, 1: CV_CO
 // channel-tile height of a layer: fixed at pack time (weights are packed per channel tile).  256-row tiles (fewest
 // L2->LDS bytes per MFMA: the r01 ablation shows the DMA side alone costs 60-85 % of a layer's time) are used when
 // the layer still fills the chip with 256x256 workgroups at the engine's chunk size.
-int choose_ct(int rows, int64_t pixels_hint, bool halo_ok, bool img8) {
+int choose_ct(int rows, int64_t pixels_hint, bool halo_ok) {
     // The 64-row halo tile (4 waves, single halo buffer, two workgroups per CU) beats the 128-row 8-wave tile on every UNet layer it
     // was tried on, 64 to 1024 output channels (r02_tuning.md step 14: two resident workgroups cover each other's barrier, DMA-issue
-    // and epilogue phases; the halo of a patch is simply fetched once per 64-channel tile, from L2).  The 128-row tile remains for
-    // the packed 8x8-image mode (ResNet-18 layer2).  CV_CT64_MAXROWS=64 restores round 1's choice for A/B runs.
-    static const int ct64_max_rows = env_int("CV_CT64_MAXROWS", 1024);
-    static const int img8_64 = env_int("CV_HALO_IMG8_64", 1);        // the packed 8x8-image mode (ResNet-18 layer2) on the 64-row tile too: +3-7 %
-    if (halo_ok && knobs().halo && (!img8 || img8_64) && rows <= ct64_max_rows && rows % 64 == 0) return 64;
-    if (halo_ok && knobs().halo) return rows % 128 == 0 ? 128 : 64;   // the halo kernel has 64- and 128-row tiles
+    // and epilogue phases; the halo of a patch is simply fetched once per 64-channel tile, from L2), and on the packed 8x8-image
+    // mode (ResNet-18 layer2): +3-7 %.  It is the halo kernel's only channel tile.
+    if (halo_ok && knobs().halo) return 64;
     if (rows % 256 == 0 && knobs().ct256 && blocks_for(rows, pixels_hint, 256, 256) >= knobs().ct256_min_blocks)
         return 256;
     return rows % 128 == 0 ? 128 : 64;
@@ -824,7 +820,7 @@ size_t Engine::workspace_bytes() const {
 
 static bool halo_th8_for(const ConvLayer& L, const ConvParams& p, int ct, int Ho, bool fused) {
     const int64_t wgs = blocks_for(L.rows, p.M, ct, 256) * (p.ksplit > 1 ? p.ksplit : 1);
-    return !fused && Ho != 8 && conv_halo_has_th8(ct) && knobs().halo_th8 && wgs < knobs().halo_th8_max_tiles;
+    return !fused && Ho != 8 && knobs().halo_th8 && wgs < knobs().halo_th8_max_tiles;
 }
 
 Status Engine::run_conv(ConvLayer& L, const TensorRef& x, const TensorRef& y, const TensorRef* res, bool relu,
@@ -895,9 +891,9 @@ Status Engine::run_conv(ConvLayer& L, const TensorRef& x, const TensorRef& y, co
     p.nCt = (L.rows + conv_cfg_ct(cfg) - 1) / conv_cfg_ct(cfg);
     // 3x3 / stride-1 layers whose patch grid divides the image keep the input patch in LDS across the nine taps
     const bool halo_capable = L.k == 3 && L.stride == 1 && !L.shuffle && kbase != nullptr && L.nStages % 9 == 0 &&
-                              knobs().halo && conv_halo_supported(ct, Ho, Wo);
+                              knobs().halo && ct == 64 && conv_halo_supported(Ho, Wo);
     // few patches: the generic kernel's smaller tiles give more workgroups (with the 8 x 16 patch variant the halo kernel doubles its own)
-    bool halo = halo_capable && blocks_for(L.rows, p.M, ct, 256) >= ((conv_halo_has_th8(ct) && knobs().halo_th8 && Ho != 8) ? 64 : 128);
+    bool halo = halo_capable && blocks_for(L.rows, p.M, ct, 256) >= ((knobs().halo_th8 && Ho != 8) ? 64 : 128);
     // Split-K: a launch with fewer output tiles than CUs leaves most of the chip idle while every workgroup walks a long K loop
     // alone (UNet B=1 down4: 16 tiles x 288 stages; ResNet-18 layer4 at 64 squares: 8 tiles x 144 stages).  Such launches deal their
     // K loop to several workgroups per tile -- the halo kernel by input-channel blocks (3x3 layers on maps of 16 x 16 and up: the
@@ -908,7 +904,7 @@ Status Engine::run_conv(ConvLayer& L, const TensorRef& x, const TensorRef& y, co
         const int64_t tiles_igemm = blocks_for(L.rows, p.M, conv_cfg_ct(cfg), conv_cfg_pt(cfg));
         const int64_t tiles_halo = blocks_for(L.rows, p.M, ct, 256);
         const int64_t tiles_now = halo ? tiles_halo : tiles_igemm;
-        const bool halo_split_ok = halo_capable && ct == 64 && Ho != 8 && knobs().splitk_halo;   // the production tile only (the 128-row A/B tile is not split)
+        const bool halo_split_ok = halo_capable && Ho != 8 && knobs().splitk_halo;   // not the packed-image mode
         const int nCb = L.nStages / 9;
         const double bytes_igemm = 2.0 * (double)p.M * (double)p.nCt * conv_cfg_ct(cfg) * sizeof(float);   // one split's partials, written + read
         const double bytes_halo = 2.0 * (double)p.M * (double)((L.rows + ct - 1) / ct * ct) * sizeof(float);
@@ -936,7 +932,7 @@ Status Engine::run_conv(ConvLayer& L, const TensorRef& x, const TensorRef& y, co
                     const int kper = (nCb + k - 1) / k, ks = (nCb + kper - 1) / kper;
                     if (ks != k) continue;
                     // the 8 x 16 patch doubles the workgroups (and halves a stage) while the chip is not full
-                    const bool th8 = conv_halo_has_th8(ct) && knobs().halo_th8 && tiles_halo * ks < knobs().halo_th8_max_tiles;
+                    const bool th8 = knobs().halo_th8 && tiles_halo * ks < knobs().halo_th8_max_tiles;
                     const double wgs = (double)tiles_halo * ks * (th8 ? 2 : 1);
                     const double waves = std::max(1.0, wgs / (double)knobs().splitk_target);
                     const double t = 2.0 * t_launch + t_stage_halo * (th8 ? 0.6 : 1.0) * 9.0 * kper * waves + ks * bytes_halo / bw;
@@ -995,7 +991,7 @@ Status Engine::run_conv(ConvLayer& L, const TensorRef& x, const TensorRef& y, co
         pos_major = true;
     }
     if (fuse0) {
-        if (!halo || !conv_halo_can_fuse_first_layer(ct, dt)) { Status ns; ns.code = kNotFused; return ns; }   // caller runs the layers apart
+        if (!halo || !conv_halo_can_fuse_first_layer(dt)) { Status ns; ns.code = kNotFused; return ns; }   // caller runs the layers apart
         p.f0_x = fuse0->x; p.f0_u8 = fuse0->u8 ? 1 : 0; p.f0_w = fuse0->w; p.f0_scale = fuse0->scale; p.f0_shift = fuse0->shift;
         p.f0_in_mul = fuse0->in_mul;
     }
@@ -1048,7 +1044,7 @@ Status Engine::run_conv(ConvLayer& L, const TensorRef& x, const TensorRef& y, co
     }
     // launches with fewer 16 x 16 patches than the chip holds workgroups (2 per CU) take the 8 x 16 patch: twice the workgroups
     const int th = (halo && halo_th8_for(L, p, ct, Ho, fuse0 != nullptr)) ? 8 : 16;
-    hipError_t e = halo ? conv_halo_launch(ct, dt, p, x.N, s, th) : pos_major ? conv_igemm_pos_launch(cfg, ns, dt, p, s) : conv_igemm_launch(cfg, ns, dt, p, s);
+    hipError_t e = halo ? conv_halo_launch(dt, p, x.N, s, th) : pos_major ? conv_igemm_pos_launch(cfg, ns, dt, p, s) : conv_igemm_launch(cfg, ns, dt, p, s);
     if (e == hipSuccess && p.ksplit > 1) e = conv_splitk_reduce_launch(dt, p, s);
     if (profiling) prof_end(s);
     if (stamp_dev) {

@@ -246,7 +246,7 @@ Status resnet_load(Engine& e, const ParamMap& pm, const std::string& arch) {
         const int nb = std::min(A->depth[0], max_nb);
         std::vector<ConvLayer*> L;
         for (int b = 0; b < nb; ++b) { L.push_back(&R.blocks[b].conv1); L.push_back(&R.blocks[b].conv2); }
-        bool fits = on && (nb == 2 || nb == 3) && e.trunk32 && dt == kF16 && conv_halo_has_chain();
+        bool fits = on && (nb == 2 || nb == 3) && e.trunk32 && dt == kF16;
         const size_t one = (size_t)9 * 64 * 128;
         for (ConvLayer* l : L) fits = fits && l->dt == kF16 && l->ct == 64 && l->rows == 64 && l->nStages == 9 && l->nCt == 1 && l->w.bytes >= one && l->halo_ok;
         if (fits) {
@@ -550,9 +550,7 @@ static Status layer1_chain(Engine& e, int n, hipStream_t s) {
     p.Cout = 64; p.rows = 64; p.nStages = 18 * nb; p.nCt = 1; p.relu = 1;
     p.flag = e.guard_ptr();
     p.layer_id = BL.conv2.layer_id;
-    // bit 4: convolution 1's residual epilogue staged through the (dead) halo buffer in the unit layout (CV_CHAIN_MIDSTAGE; two-workgroup form)
-    static const int mid_staged = [] { const char* v = std::getenv("CV_CHAIN_MIDSTAGE"); return v && v[0] == '1' ? 16 : 0; }();
-    p.chain = chain_form() | (chain_form() == 2 ? mid_staged : 0);
+    p.chain = chain_form();
     for (int i = 0; i < 2 * nb; ++i) {
         p.ch_scale[i] = reinterpret_cast<const float*>(L[i]->scale.ptr);
         p.ch_shift[i] = reinterpret_cast<const float*>(L[i]->shift.ptr);

@@ -68,7 +68,8 @@ CONV_CASES = [
     ("cin128_c64_halo_4blocks", 8, 128, 64, 64, 64, 3, 1, True, False),
     ("layer2_like_8x8_packed_images_tail", 514, 128, 8, 8, 128, 3, 1, True, True),
     ("layer2_like_8x8_packed_c256", 516, 128, 8, 8, 256, 3, 1, False, False),
-    # >= 4 tiles per CU and K <= 72 stages: the persistent variants of the 8-wave halo tiles (with a ragged last image group)
+    # many tiles per CU and a short K loop, Cout = 128 (with a ragged last image group): the 64-row halo tile, two channel tiles
+    # per patch (the ids date from round 1, when these shapes ran the persistent 8-wave 128-row tile)
     ("persistent_halo128_residual", 64, 64, 64, 64, 128, 3, 1, True, True),
     ("persistent_packed_8x8_tail", 4098, 128, 8, 8, 128, 3, 1, True, True),
     # round 4, split-K launches (few output tiles, long K): the halo kernel dealt by channel blocks (maps of 16 x 16 and up) ...
@@ -79,6 +80,8 @@ CONV_CASES = [
     ("splitk_generic_resnet_layer4_like", 64, 512, 2, 2, 512, 3, 1, True, True),
     ("splitk_generic_stride2", 16, 256, 8, 8, 512, 3, 2, True, False),
     ("splitk_generic_4x4", 64, 256, 4, 4, 256, 3, 1, True, True),
+    # a non-square map is packed for the generic kernel (128-row channel tile) although both extents divide by 16: 256 tiles, no split-K
+    ("nonsquare_32x64_c128_residual", 32, 64, 32, 64, 128, 3, 1, True, True),
 ]
 
 

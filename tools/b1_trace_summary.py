@@ -5,9 +5,9 @@ import sys
 
 rows = sorted(csv.DictReader(open(sys.argv[1])), key=lambda r: int(r["Start_Timestamp"]))
 rows = [r for r in rows if "copyBuffer" not in r["Kernel_Name"] and "fillBuffer" not in r["Kernel_Name"]]
-# one iteration = from a fused first-layer launch (FUSE0 instantiation: ", true>" as the last template flag of the halo kernel) to the next
+# one iteration = from a fused first-layer launch (FUSE0 instantiation of the halo kernel: <T, TH, IMG, PERSIST, FUSE0, CHAIN, CNB>) to the next
 import re
-fuse0 = re.compile(r"true(, \d+)?>\(cv::ConvParams\)$")       # round 5: the template gained a trailing CHAIN parameter
+fuse0 = re.compile(r"conv3x3_halo_kernel<[^,]+, \d+, \d+, (true|false), true, \d+, \d+>\(cv::ConvParams\)$")
 starts = [i for i, r in enumerate(rows) if "conv3x3_halo_kernel" in r["Kernel_Name"] and fuse0.search(r["Kernel_Name"].rstrip())]
 if len(starts) < 3:
     print("no complete iteration found"); sys.exit(0)
