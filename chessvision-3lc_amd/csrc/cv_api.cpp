@@ -123,6 +123,7 @@ static int impl_cv_engine_create(int device, int precision, cv_engine_t** out) {
         if (device >= 64 || !prepared[device]) {
             if ((e = conv_igemm_prepare()) != hipSuccess) return finish(hip_fail(e, "conv_igemm_prepare"));
             if ((e = conv_halo_prepare()) != hipSuccess) return finish(hip_fail(e, "conv_halo_prepare"));
+            if ((e = conv1x1_lds_prepare()) != hipSuccess) return finish(hip_fail(e, "conv1x1_lds_prepare"));
             if (device < 64) prepared[device] = true;
         }
     }

@@ -36,7 +36,7 @@ typedef float f4 __attribute__((ext_vector_type(4)));
 // so the single rounding equals the convert-back / subtract / convert chain the compiler emits for the C expression, which costs
 // ~3 more instructions per value; r03_tuning.md steps 20-21).  hp / lp = the packed f16 pairs (element 0 in the low half).
 // NOT for code where the scheduler may place it between INDEPENDENT MFMAs (epilogues that consume the accumulators are fine): the
-// compiler does not look inside inline asm when it pads MFMA hazards, and pointwise.hip: shortcut1x1s2_kernel gave run-to-run
+// compiler does not look inside inline asm when it pads MFMA hazards, and conv1x1_lds.hip: shortcut1x1s2_kernel gave run-to-run
 // different results with it until the C form replaced it (round 5, r05_tuning.md).
 __device__ __forceinline__ void split_pair(float v0, float v1, unsigned& hp, unsigned& lp) {
     typedef _Float16 h2_t __attribute__((ext_vector_type(2)));

@@ -426,19 +426,25 @@ Status ConvLayer::fold_rounding_bias() {
     return Status();
 }
 
-// Re-fold the tensor exponents into the device copies of the epilogue constants (only when they change: calibration).
-Status ConvLayer::set_exps(int in_exp_, int out_exp_, hipStream_t s) {
-    if (in_exp_ == in_exp && out_exp_ == out_exp) return Status();
+Status fold_exps(const std::string& name, const std::vector<float>& h_scale, const std::vector<float>& h_shift, void* scale, void* shift,
+                 int in_exp, int out_exp, hipStream_t s) {
     if (capture_flag()) return fail(1, name + ": epilogue constants re-folded during graph capture");
     CV_HIP(hipStreamSynchronize(s));                     // launches that still read the old constants
     std::vector<float> sc(h_scale.size()), sh(h_shift.size());
     for (size_t i = 0; i < sc.size(); ++i) {
-        sc[i] = std::ldexp(h_scale[i], in_exp_ - out_exp_);
-        sh[i] = std::ldexp(h_shift[i], -out_exp_);
+        sc[i] = std::ldexp(h_scale[i], in_exp - out_exp);
+        sh[i] = std::ldexp(h_shift[i], -out_exp);
         if (!std::isfinite(sc[i]) || !std::isfinite(sh[i])) return fail(1, name + ": range factors leave the f32 range");
     }
-    CV_HIP(sync_memcpy(scale.ptr, sc.data(), sc.size() * sizeof(float), hipMemcpyHostToDevice));
-    CV_HIP(sync_memcpy(shift.ptr, sh.data(), sh.size() * sizeof(float), hipMemcpyHostToDevice));
+    CV_HIP(sync_memcpy(scale, sc.data(), sc.size() * sizeof(float), hipMemcpyHostToDevice));
+    CV_HIP(sync_memcpy(shift, sh.data(), sh.size() * sizeof(float), hipMemcpyHostToDevice));
+    return Status();
+}
+
+// Re-fold the tensor exponents into the device copies of the epilogue constants (only when they change: calibration).
+Status ConvLayer::set_exps(int in_exp_, int out_exp_, hipStream_t s) {
+    if (in_exp_ == in_exp && out_exp_ == out_exp) return Status();
+    CV_TRY(fold_exps(name, h_scale, h_shift, scale.ptr, shift.ptr, in_exp_, out_exp_, s));
     in_exp = in_exp_; out_exp = out_exp_;
     return Status();
 }

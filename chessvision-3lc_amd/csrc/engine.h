@@ -169,6 +169,11 @@ struct Activation {
     size_t bytes_per_image() const { return (size_t)(H + 2) * (W + 2) * C * dtype_size(dt); }
 };
 
+// Device copies of a layer's per-row epilogue constants for the tensor exponents it runs with: scale = h_scale * 2^(in_exp - out_exp),
+// shift = h_shift * 2^-out_exp.  Waits for `s` first (launches that still read the old constants); refused during graph capture.
+Status fold_exps(const std::string& name, const std::vector<float>& h_scale, const std::vector<float>& h_shift, void* scale, void* shift,
+                 int in_exp, int out_exp, hipStream_t s);
+
 // a packed implicit-GEMM layer (conv k x k, or k2 s2 transposed conv as 1-tap GEMM + pixel shuffle)
 struct ConvLayer {
     std::string name;

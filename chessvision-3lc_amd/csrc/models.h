@@ -1,5 +1,6 @@
 // models.h -- per-model state owned by an Engine (packed layers + activation workspace).
 #pragma once
+#include "conv1x1_lds.h"
 #include "engine.h"
 
 namespace cv {
@@ -18,14 +19,10 @@ struct Engine::UNet {
     ConvLayer inc0, inc1, d[4][2], upT[4], u[4][2];
     unsigned up_id[4] = {0, 0, 0, 0}, outc_id = 0;  // numeric-guard ids of the non-conv producers
     // split-f16 engine, throughput batches: up3.up / up4.up (K = 256 / 128: the whole weight block fits in LDS) on the persistent
-    // LDS-resident-weights kernel (pointwise.hip: convt2x2_lds) instead of the generic tile; upT[i] remains for calibration, small
-    // batches and CV_CONVT_FAST=0.  Same products in the same order: bit-identical.
-    struct FastUp {
-        bool on = false;
-        DeviceBuffer wpk, scale, shift;
-        std::vector<float> h_scale, h_shift;           // per GEMM row (dy, dx, co): 2^(row exponent) | bias
-        int in_exp = 1 << 20, out_exp = 1 << 20;       // exponents the device copies are folded for
-    } fast_up[4];
+    // LDS-resident-weights kernel (conv1x1_lds.h: kConvT) instead of the generic tile; upT[i] remains for calibration, small
+    // batches (CV_CONVT_FAST_MIN) and CV_CONVT_FAST=0; up3.up takes it with CV_CONVT_FAST_256=1 only.  Same products in the same order:
+    // bit-identical.  GEMM row (dy, dx, co): scale 1, shift = the bias.
+    Lds1x1 fast_up[4];
     DeviceBuffer outc_w, outc_b;
     DeviceBuffer inc0_wpk;                          // f16-based engines: MFMA image of inc.double_conv.0 for the fused first-layer kernel
     DeviceBuffer inc0_wpk2;                         // split-f16: the same layer for the in-kernel producer of inc.double_conv.3 (conv_halo.hip: FUSE0)
@@ -58,13 +55,11 @@ struct Engine::ResNet {
         ConvLayer conv1, conv2, down;
         bool has_down = false;
         Activation mid, out, sc;                     // conv1 output, block output, shortcut (if downsampled)
-        // f16r: the shortcut convolution as a dedicated split-f16 kernel between the f32 twins (pointwise.hip: shortcut1x1s2);
-        // `down` (the same layer on the f32-input MFMA through the generic kernel) remains for the calibration passes and CV_SHORTCUT_FAST=0
-        bool fast_sc = false;
-        DeviceBuffer sc_wpk, sc_scale, sc_shift;
-        std::vector<float> h_sc_scale, h_sc_shift;   // BN affine with the weight rows' exponents folded in
-        int sc_in_exp = 1 << 20, sc_out_exp = 1 << 20;   // exponents the device copies are folded for
-        unsigned sc_id = 0;
+        // f16r: the shortcut convolution as a dedicated split-f16 kernel between the f32 twins (conv1x1_lds.h: kShortcutF32; the f16x3
+        // engine takes its kShortcutSplit form from CV_SHORTCUT_SPLIT_MIN squares); `down` (the same layer through the generic kernel)
+        // remains for the calibration passes and CV_SHORTCUT_FAST=0.  CV_SHORTCUT_LDS=0 / CV_SHORTCUT_STAGE=0: the f32-twin kernel's
+        // first form / unstaged stores (same bits).  GEMM row = output channel: the folded BN affine.
+        Lds1x1 fast_sc;
     };
     std::unique_ptr<Block[]> blocks;                // layer1.0 .. layer4.(depth[3]-1), stage by stage
     int nblocks = 0;

@@ -35,7 +35,7 @@ hipError_t stem7x7(int dt, const void* x, bool x_is_u8, int n, const float* w, c
                    const float* shift, const TensorRef& dst, hipStream_t s);
 
 // Fused stem for the f16 / split-f16 engines: conv 7x7 s2 p3 + BN + ReLU + max_pool2d(3,2,1) on the MFMA.
-// wpk: packed filter bank [hi|lo][k-step 2][fragment 4][lane 64] x half8 (resnet.cpp: pack_stem_mfma).  dst: 64 ch @ 16x16.
+// wpk: packed filter bank [hi|lo][k-step 2][fragment 4][lane 64] x half8 (packed by resnet.cpp: resnet_load).  dst: 64 ch @ 16x16.
 // in_exp: the input plane is held as x * 2^-in_exp inside the kernel (x in [0,1] -> in_exp = -7 keeps the lo halves normal)
 hipError_t stem_pool_mfma(int dt, const void* x, bool x_is_u8, int n, const void* wpk, const float* scale,
                           const float* shift, int in_exp, const TensorRef& dst, unsigned* flag, unsigned layer_id,
@@ -43,7 +43,7 @@ hipError_t stem_pool_mfma(int dt, const void* x, bool x_is_u8, int n, const void
 
 // UNet first layer for the f16 / split-f16 engines, fused with the input packing: conv 3x3 p1 (3 -> 64) + BN + ReLU straight from
 // the caller's image (x: (n,3,256,256) f32 or (n,256,256,3) u8, scaled by /255).  wpk: [hi|lo][fragment 4][lane 64] x half8
-// (unet.cpp: pack_inc0_mfma), k = (ky*3 + kx)*3 + c.  dst: 64 ch @ 256x256, whole buffer (Cs == 64).
+// (packed by unet.cpp: unet_load), k = (ky*3 + kx)*3 + c.  dst: 64 ch @ 256x256, whole buffer (Cs == 64).
 hipError_t inc0_mfma(int dt, const void* x, bool x_is_u8, int n, const void* wpk, const float* scale, const float* shift,
                      int in_exp, const TensorRef& dst, unsigned* flag, unsigned layer_id, hipStream_t s);
 
@@ -51,18 +51,6 @@ hipError_t inc0_mfma(int dt, const void* x, bool x_is_u8, int n, const void* wpk
 hipError_t head_avgpool_fc(int dt, const TensorRef& src, const float* w, const float* b, float* out,
                            int softmax, unsigned* flag, unsigned layer_id, hipStream_t s);
 hipError_t softmax13(const float* logits, int n, float* probs, hipStream_t s);
-
-// f16r engine: ResNet shortcut conv 1x1 / stride 2 + BN between f32 twins (x32 -> y32, both f32_only PHWC tensors, y32.C == 2 x32.C,
-// C in {64, 128, 256}) at f32 grade: three split-f16 MFMA products per MAC.  wpk: [C_out/128][C_in/32][fragment 8][hi | lo][lane 64] x
-// half8, MFMA row i of fragment f = channel 32 (i/4) + 4 f + i%4 of the group (resnet.cpp: pack_shortcut); scale / shift [C_out].
-hipError_t shortcut1x1s2(const TensorRef& x32, const void* wpk, const float* scale, const float* shift, const TensorRef& y32,
-                         unsigned* flag, unsigned layer_id, hipStream_t s, bool split = false);
-
-// UNet up3.up / up4.up (split-f16 engine): conv_transpose2d k2 s2 + bias, x (C in {128, 256}, own buffer) -> channel slice y (C/2 channels,
-// 2H x 2W) of the concatenated tensor, on the LDS-resident-weights kernel (`CONVT` form).  wpk as for shortcut1x1s2 with GEMM row
-// r = (dy * 2 + dx) * C/2 + co; scale / shift [2 C] (shift = the bias per row).
-hipError_t convt2x2_lds(const TensorRef& x, const void* wpk, const float* scale, const float* shift, const TensorRef& y, unsigned* flag,
-                        unsigned layer_id, hipStream_t s);
 
 // MFMA lane-map probes used by cv_selftest_mfma (D = A*B^T with A:16xK, B:16xK row-major)
 hipError_t mfma_probe_f16(const half_t* a, const half_t* b, float* d, hipStream_t s);   // K = 32

@@ -18,7 +18,7 @@ import pytest
 ROOT = Path(__file__).resolve().parent.parent
 CSRC = ROOT / "chessvision-3lc_amd" / "csrc"
 CLANG = Path("/opt/rocm/lib/llvm/bin/clang++")
-UNITS = ["conv_igemm.hip", "conv_halo.hip", "pointwise.hip", "pipeline.hip", "engine.cpp", "unet.cpp", "resnet.cpp", "contour.cpp",
+UNITS = ["conv_igemm.hip", "conv_halo.hip", "pointwise.hip", "conv1x1_lds.hip", "pipeline.hip", "engine.cpp", "unet.cpp", "resnet.cpp", "contour.cpp",
          "position.cpp", "homography.cpp", "cv_api.cpp"]            # the Makefile's SRCS
 SAN = ["-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer"]
 
