@@ -37,7 +37,7 @@ import torch
 from numpy.typing import NDArray
 
 from . import classical, constants, utils
-from .cv_types import BoardExtractionResult, ChessVisionResult, PositionResult, ValidationFix
+from .cv_types import BoardExtractionResult, ChessVisionResult, ExtractionQuality, PositionResult, ValidationFix
 from .fen import board_fen
 
 logger = logging.getLogger(__name__)
@@ -492,16 +492,18 @@ class ChessVision:
     def process_images(self, images: Sequence[NDArray[np.uint8]], threshold: float = 0.5, flip: bool = False,
                        fallback_quad: bool = False, pipeline_chunk: int = 64, return_crops: bool = True,
                        timings: dict | None = None, first_job: int | None = None,
-                       last_job: int | None = None) -> list[ChessVisionResult]:
+                       last_job: int | None = None, quality: str | None = None) -> list[ChessVisionResult]:
         """Batched pipeline: see ``_process_images_native`` (this wrapper adds the numeric-guard recovery: a call whose f16-based
         engine reports a non-finite value is repeated as a whole on the exact-f32 instance, ``_recover``)."""
+        if quality not in (None, "logits", "sigmoid"):
+            raise ValueError(f"quality must be None, 'logits' or 'sigmoid', got {quality!r}")
         return self._recover(lambda cv: cv._process_images_native(images, threshold, flip, fallback_quad, pipeline_chunk, return_crops,
-                                                                  timings, first_job, last_job))
+                                                                  timings, first_job, last_job, quality))
 
     def _process_images_native(self, images: Sequence[NDArray[np.uint8]], threshold: float = 0.5, flip: bool = False,
                                fallback_quad: bool = False, pipeline_chunk: int = 64, return_crops: bool = True,
                                timings: dict | None = None, first_job: int | None = None,
-                               last_job: int | None = None) -> list[ChessVisionResult]:
+                               last_job: int | None = None, quality: str | None = None) -> list[ChessVisionResult]:
         """Batched pipeline (new; the reference processes one image per call, core.py:152-195).
 
         Images stay on the device between the two CNNs: INTER_AREA resize -> UNet (u8 in, logits + thresholded mask out);
@@ -518,7 +520,14 @@ class ChessVision:
         (64,64,64,1) crops as in the reference; throughput callers pass ``return_crops=False`` (None instead: the crops are
         ``ChessVision.extract_squares(board_image)`` and cost a 256 KB host copy per board); ``timings`` (a dict) receives
         host-side seconds per stage and event-timed GPU milliseconds.  Host worker threads (staging copies, contour stage) are
-        sized per rank: ``distributed.host_threads()`` = CPUs of this process / ranks on the host, capped."""
+        sized per rank: ``distributed.host_threads()`` = CPUs of this process / ranks on the host, capped.
+
+        ``quality`` ("logits" | "sigmoid"; None = off, nothing extra is launched, copied or returned) attaches an ``ExtractionQuality``
+        to every result: the four scores of the reference's enrichment job (``chessvision/quality.py``).  Per job one more kernel runs
+        right behind the UNet on the logits where they are (``HipEngine.extraction_scores_dev``); its 64-byte records and its
+        ``v > 0.5`` mask travel back behind the logits, and the host finishes the scores after the job's classifier has been queued.
+        "logits" scores the raw logits (the reference's letter), "sigmoid" their sigmoid (what the column names promise).
+        ``quad_score`` is that of the quadrangle found in the mask, in mask pixels; a fallback quadrangle scores 0 like none."""
         started = time.time()
         for image in images:
             assert isinstance(image, np.ndarray) and image.dtype == np.uint8 and image.ndim == 3
@@ -533,11 +542,12 @@ class ChessVision:
             # events when it ends, so nothing is left to order against the caller's stream.
             with torch.cuda.stream(self._pipeline_streams()[2]):
                 return self._process_images_native(images, threshold, flip, fallback_quad, pipeline_chunk, return_crops, timings,
-                                                   first_job, last_job)
+                                                   first_job, last_job, quality)
         from concurrent.futures import ThreadPoolExecutor
 
         from .distributed import host_threads
-        from .hip_backend import board_homographies, decode_positions, find_quadrangles
+        from .hip_backend import (SCORE_RECORD, board_homographies, decode_positions, find_quadrangles, mask_completenesses,
+                                  quadrangle_regularity, scores_finish)
 
         n_host = host_threads()
 
@@ -564,6 +574,8 @@ class ChessVision:
         tm = timings if timings is not None else {}
         for key in ("stage_s", "wait_masks_s", "contours_s", "homography_s", "wait_probs_s", "decode_s", "assemble_s"):
             tm.setdefault(key, 0.0)
+        if quality:
+            tm.setdefault("quality", 0.0)                    # host seconds of the score stage (its kernel: quality_ms)
         gpu_events: list[tuple[str, torch.cuda.Event, torch.cuda.Event]] = []
 
         def clock(key, t0):
@@ -627,15 +639,24 @@ class ChessVision:
             tm.setdefault("first_enqueue_s", time.time() - started)      # host time until the first kernel of the call is queued
             small = gpu_timed("resize_ms", lambda: eng.resize_area_u8(batch, (constants.INPUT_SIZE[1], constants.INPUT_SIZE[0])))
             lg, mk = gpu_timed("unet_ms", lambda: eng.unet_forward_u8(small, threshold=threshold, want_mask=True))
+            scored = None
+            if quality:                                      # the score reductions, on the logits where the UNet left them
+                scored = gpu_timed("quality_ms", lambda: eng.extraction_scores_dev(lg, "none" if quality == "logits" else "sigmoid",
+                                                                                   want_mask=True))
             done = torch.cuda.Event()
             done.record()
             st = {"ids": ids, "batch": batch, "logits": pinned((len(ids), 256, 256), torch.float32), "unet_done": done,
-                  "masks": pinned((len(ids), 256, 256), torch.uint8), "ev": torch.cuda.Event(), "keep": (lg, mk, u["staged"])}
+                  "masks": pinned((len(ids), 256, 256), torch.uint8), "ev": torch.cuda.Event(), "keep": (lg, mk, u["staged"], scored)}
             with torch.cuda.stream(down):
                 down.wait_event(done)
                 st["masks"].copy_(mk, non_blocking=True)     # masks first: the contour stage waits for them only
                 st["ev"].record()
                 st["logits"].copy_(lg[:, 0], non_blocking=True)
+                if scored is not None:
+                    st["records"] = pinned((len(ids), 64), torch.uint8)
+                    st["half"] = pinned((len(ids), 256, 256), torch.uint8)
+                    st["records"].copy_(scored[0], non_blocking=True)
+                    st["half"].copy_(scored[1].view(len(ids), 256, 256), non_blocking=True)
                 st["ev_logits"] = torch.cuda.Event()
                 st["ev_logits"].record()
             return st
@@ -682,6 +703,15 @@ class ChessVision:
             else:
                 clock("homography_s", t0)
             st["batch"] = None
+            if quality:                                      # the device has this job's classifier queued: finish its scores meanwhile
+                t0 = time.perf_counter()
+                st["ev_logits"].synchronize()
+                conf, dist = scores_finish(st["records"].numpy().view(SCORE_RECORD).reshape(-1))
+                comp = mask_completenesses(st["half"].numpy(), n_threads=n_host)
+                for k, i in enumerate(ids):
+                    quality_of[i] = ExtractionQuality(confidence=float(conf[k]), quad_score=quadrangle_regularity(found_quads[k]),
+                                                      completeness=float(comp[k]), distribution=float(dist[k]))
+                clock("quality", t0)
             return st
 
         logits_of: dict[int, NDArray[np.float32]] = {}
@@ -689,6 +719,7 @@ class ChessVision:
         quads_of: dict[int, NDArray[np.float32] | None] = {}
         boards: dict[int, NDArray[np.uint8]] = {}
         positions: dict[int, PositionResult] = {}
+        quality_of: dict[int, ExtractionQuality] = {}
 
         def finish(st):                                     # probabilities -> labels, FEN, pawn rule (one native call per job)
             ids = st["ids"]
@@ -753,7 +784,7 @@ class ChessVision:
             extraction = BoardExtractionResult(board_image=boards.get(i), binary_mask=masks_of[i], quadrangle=quads_of[i],
                                                probabilities=logits_of[i])
             results.append(ChessVisionResult(board_extraction=extraction, position=positions.get(i),
-                                             processing_time=per_image))
+                                             processing_time=per_image, quality=quality_of.get(i)))
         clock("assemble_s", t0)
         if timings is not None:
             for name, a, b in gpu_events:

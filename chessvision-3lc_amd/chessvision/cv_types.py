@@ -52,10 +52,21 @@ class PositionResult:
 
 
 @dataclass
+class ExtractionQuality:
+    """The four board-extraction scores the reference's enrichment job writes into its 3LC table per image
+    (``scripts/process_new_raw/process_pipeline.py:287-311``); the attribute names are that table's column names."""
+    confidence: float = _doc("2 * mean |v - 0.5| over the largest quarter of the scored values")
+    quad_score: float = _doc("quadrangle regularity, 1 = a square; 0 when the mask gave no quadrangle")
+    completeness: float = _doc("mask pixels / pixels of the filled outline of the largest mask component")
+    distribution: float = _doc("1 - normalised entropy of the ten-bin histogram of the scored values over [0, 1]")
+
+
+@dataclass
 class ChessVisionResult:
     board_extraction: BoardExtractionResult = _doc("always present")
     position: PositionResult | None = _doc("None when board extraction failed")
     processing_time: float = _doc("seconds spent in process_image (per image for process_images)")
+    quality: ExtractionQuality | None = field(default=None, metadata={"doc": "process_images(quality=...) only; NOT a reference field"})
 
 
 @dataclass

@@ -120,7 +120,18 @@ SYMBOLS = [
     ("cv_board_homographies", _i, [_fp, _i, _i, _i, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]),
     ("cv_decode_positions", _i, [_fp, _i, _i, ctypes.c_char_p, ctypes.c_char_p, ctypes.POINTER(ctypes.c_int8),
                                  ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32)]),
+    ("cv_extraction_scores", _i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
+    ("cv_extraction_scores_finish", _i, [_vp, _i, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]),
+    ("cv_mask_completeness", _i, [_vp, _i, _i, ctypes.POINTER(ctypes.c_double)]),
+    ("cv_mask_completenesses", _i, [_vp, _i, _i, _i, ctypes.POINTER(ctypes.c_double), _i]),
+    ("cv_quadrangle_regularity", _i, [_fp, ctypes.POINTER(ctypes.c_double)]),
 ]
+
+# cv_score_record_t (include/chessvision_hip.h): one 64-byte record per image
+SCORE_RECORD = np.dtype({"names": ["hist", "above_half", "n_nan", "top_sum", "top_count", "reserved"],
+                         "formats": [("<i4", (10,)), "<i4", "<i4", "<f8", "<i4", "<i4"],
+                         "offsets": [0, 40, 44, 48, 56, 60], "itemsize": 64})
+_TRANSFORMS = {"none": 0, "sigmoid": 1}
 
 
 def trim_memory() -> int:
@@ -246,6 +257,58 @@ def find_quadrangles(masks: np.ndarray, n_threads: int = 0) -> list:
                                        quads.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
                                        found.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), int(n_threads)))
     return [quads[i].reshape(4, 1, 2).copy() if found[i] else None for i in range(n)]
+
+
+def scores_finish(records: np.ndarray):
+    """(N,) ``SCORE_RECORD`` array -> (confidence, distribution), two (N,) float64 arrays (``cv_extraction_scores_finish``):
+    ``np.mean(np.abs(np.sort(v)[-k:] - 0.5)) * 2`` and ``1 - entropy(hist / hist.sum()) / log2(10)`` of the scored values."""
+    lib = load_library()
+    r = np.ascontiguousarray(records, dtype=SCORE_RECORD).reshape(-1)
+    conf, dist = np.zeros(r.size, dtype=np.float64), np.zeros(r.size, dtype=np.float64)
+    dp = ctypes.POINTER(ctypes.c_double)
+    if r.size:
+        _check(lib.cv_extraction_scores_finish(r.ctypes.data_as(_vp), int(r.size), conf.ctypes.data_as(dp), dist.ctypes.data_as(dp)))
+    return conf, dist
+
+
+def mask_completeness(mask: np.ndarray) -> float:
+    """Binary mask (H, W) uint8 (0 / non-0) -> foreground pixels of the whole mask / pixels of the filled outer border of its largest
+    8-connected component (``cv_mask_completeness``); 0.0 for an empty mask.  Host-side C++; needs neither a GPU nor an engine."""
+    lib = load_library()
+    m = np.ascontiguousarray(mask, dtype=np.uint8)
+    if m.ndim != 2:
+        raise HipBackendError("mask_completeness expects a 2-D uint8 mask")
+    score = ctypes.c_double(0.0)
+    _check(lib.cv_mask_completeness(m.ctypes.data_as(_vp), m.shape[0], m.shape[1], ctypes.byref(score)))
+    return float(score.value)
+
+
+def mask_completenesses(masks: np.ndarray, n_threads: int = 0) -> np.ndarray:
+    """(N,H,W) uint8 masks -> (N,) float64 completeness scores on native host threads (GIL released)."""
+    lib = load_library()
+    m = np.ascontiguousarray(masks, dtype=np.uint8)
+    if m.ndim != 3:
+        raise HipBackendError("mask_completenesses expects (N,H,W) uint8 masks")
+    scores = np.zeros(m.shape[0], dtype=np.float64)
+    if m.shape[0]:
+        _check(lib.cv_mask_completenesses(m.ctypes.data_as(_vp), m.shape[0], m.shape[1], m.shape[2],
+                                          scores.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), int(n_threads)))
+    return scores
+
+
+def quadrangle_regularity(quad) -> float:
+    """Four (x, y) vertices in the order given (any array of 8 numbers, e.g. (4,1,2)), or None -> 1 - 0.5 std(sides) / mean(sides)
+    - 0.5 std(interior angles) / (pi / 2); 0.0 for None (``cv_quadrangle_regularity``)."""
+    lib = load_library()
+    score = ctypes.c_double(0.0)
+    if quad is None:
+        _check(lib.cv_quadrangle_regularity(None, ctypes.byref(score)))
+    else:
+        q = np.ascontiguousarray(quad, dtype=np.float32).reshape(-1)
+        if q.size != 8:
+            raise HipBackendError("quadrangle_regularity expects four (x, y) vertices")
+        _check(lib.cv_quadrangle_regularity(q.ctypes.data_as(_fp), ctypes.byref(score)))
+    return float(score.value)
 
 
 def board_homographies(quads: np.ndarray, out_size=(512, 512), want_forward: bool = False):
@@ -459,6 +522,34 @@ class HipEngine:
         out = torch.empty((n, 13), dtype=torch.float32, device=self.device)
         _check(self._lib.cv_resnet18_forward_u8(self._h, _ptr(squares_u8), n, _ptr(out), _stream_ptr(self.device)))
         return out
+
+    def extraction_scores_dev(self, values: torch.Tensor, transform: str = "none", want_mask: bool = False):
+        """The device half of ``extraction_scores``: launches the score kernel on the current stream behind whatever produced
+        ``values`` ((N, ...) float32 on this device, each image contiguous) and returns (records (N,64) uint8 device tensor, half_mask
+        (N,count) uint8 device tensor | None).  Nothing is synchronised or copied."""
+        if transform not in _TRANSFORMS:
+            raise HipBackendError(f"transform must be one of {sorted(_TRANSFORMS)}, got {transform!r}")
+        if not isinstance(values, torch.Tensor) or values.dtype != torch.float32 or values.device != self.device or values.dim() < 1:
+            raise HipBackendError("extraction_scores expects an (N, ...) float32 tensor on the engine's device")
+        n = int(values.shape[0])
+        count = int(values.numel() // n) if n else 0
+        if n and not values.is_contiguous():
+            raise HipBackendError("extraction_scores expects contiguous images")
+        records = torch.empty((n, 64), dtype=torch.uint8, device=self.device)
+        mask = torch.empty((n, count), dtype=torch.uint8, device=self.device) if want_mask else None
+        _check(self._lib.cv_extraction_scores(self._h, _ptr(values), n, count, _TRANSFORMS[transform], _ptr(records),
+                                              _ptr(mask) if want_mask else None, _stream_ptr(self.device)))
+        return records, mask
+
+    def extraction_scores(self, values: torch.Tensor, transform: str = "none", want_mask: bool = False):
+        """(N, ...) float32 device tensor -> (records, confidence, distribution[, half_mask]): per image the ``SCORE_RECORD`` the
+        kernel wrote (numpy), the two scores computed from it (float64; the reference's ``probability_confidence`` and
+        ``probability_distribution`` of the values, or of their sigmoid with ``transform="sigmoid"``), and with ``want_mask`` the
+        (N, count) uint8 mask ``v > 0.5``.  Synchronises the current stream."""
+        records, mask = self.extraction_scores_dev(values, transform, want_mask)
+        rec = records.cpu().numpy().view(SCORE_RECORD).reshape(-1)
+        conf, dist = scores_finish(rec)
+        return (rec, conf, dist, mask.cpu().numpy()) if want_mask else (rec, conf, dist)
 
     def softmax13(self, logits: torch.Tensor) -> torch.Tensor:
         logits = logits.to(self.device, torch.float32).contiguous()

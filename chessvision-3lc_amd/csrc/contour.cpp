@@ -469,4 +469,81 @@ long find_contours_flat(const uint8_t* mask, int h, int w, bool tc89, int32_t* x
     return (long)contours.size();
 }
 
+// Mask completeness of the reference's enrichment job (scripts/process_new_raw/process_pipeline.py:380-414), restated from its published
+// behaviour: the outer borders of all 8-connected components (cv2.findContours RETR_EXTERNAL; CHAIN_APPROX_SIMPLE leaves the polygon
+// and so its contourArea unchanged), the one with the largest contourArea -- ties go to the first in OpenCV's order, i.e. the border
+// found LAST in raster order -- and score = foreground pixels of the WHOLE mask / pixels drawContours(thickness = -1) sets for that
+// border.  `filled` is taken as the component itself plus every pixel that 4-connected steps from the image frame cannot reach without
+// crossing the component (its holes and whatever lies inside them); that is a restatement, not a measured match with cv2.  The score
+// can exceed 1 (other components count above the line, not below) and is 0 for an empty mask.
+double mask_completeness(const uint8_t* mask, int h, int w) {
+    const Image f{mask, h, w};
+    RowBits rb;
+    rb.build(mask, h, w);
+    RunIndex fg;
+    const std::vector<Comp> outer = component_starts(rb, h, false, true, false, &fg);
+    if (outer.empty()) return 0.0;
+    int best = -1;
+    double best_area = -1.0;
+    for (int a = (int)outer.size() - 1; a >= 0; --a) {
+        const Comp& s = outer[a];
+        // the border polygon runs through pixel centres, so its area is at most (bw - 1) * (bh - 1): most specks of a noisy mask are
+        // never traced
+        if ((double)(s.bw - 1) * (s.bh - 1) <= best_area) continue;
+        const double area = contour_area(trace_border(f, s.y, s.x, s.y, s.x - 1));
+        if (area > best_area) { best_area = area; best = a; }
+    }
+    // pixels of the whole mask and of the chosen component; the component alone as a bit image
+    RowBits only;
+    only.w = rb.w; only.words = rb.words;
+    only.bits.assign(rb.bits.size(), 0);
+    long foreground = 0, filled = 0;
+    for (int y = 0; y < h; ++y) {
+        uint64_t* row = only.bits.data() + (size_t)y * only.words;
+        for (int r = fg.row_begin[y]; r < fg.row_begin[y + 1]; ++r) {
+            const int x0 = fg.runs[r].x0, x1 = fg.runs[r].x1;
+            foreground += x1 - x0;
+            if (fg.comp_of_root[find_root(fg.runs, r)] != best) continue;
+            filled += x1 - x0;
+            for (int x = x0; x < x1;) {                        // set bits [x, x1) word by word
+                const int k = x >> 6, end = std::min(x1, (k + 1) << 6), len = end - x;
+                row[k] |= (len == 64 ? ~0ULL : ((1ULL << len) - 1)) << (x & 63);
+                x = end;
+            }
+        }
+    }
+    // what the component encloses: the 4-connected regions of its complement that do not touch the frame
+    RunIndex bg;
+    component_starts(only, h, true, false, true, &bg);
+    for (int r = 0; r < (int)bg.runs.size(); ++r)
+        if (bg.comp_of_root[find_root(bg.runs, r)] >= 0) filled += bg.runs[r].x1 - bg.runs[r].x0;
+    return filled > 0 ? (double)foreground / (double)filled : 0.0;
+}
+
+// Quadrangle regularity (process_pipeline.py:417-457): 1 - 0.5 std(sides) / mean(sides) - 0.5 std(angles) / (pi / 2) over the four side
+// lengths and the four interior angles acos(v1 . v2 / (|v1| |v2|)) of the vertices in the order given; population standard deviations,
+// angle 0 where a neighbouring vertex coincides, side term 1 when all four vertices coincide.  Computed in double (the reference: in
+// the float32 of its input); the cosine is clamped to [-1, 1] so that rounding on a straight angle cannot produce a NaN.
+double quadrangle_regularity(const float quad[8]) {
+    double sides[4], angles[4];
+    for (int i = 0; i < 4; ++i) {
+        const int nx = (i + 1) & 3, pv = (i + 3) & 3;
+        const double ax = (double)quad[2 * pv] - quad[2 * i], ay = (double)quad[2 * pv + 1] - quad[2 * i + 1];
+        const double bx = (double)quad[2 * nx] - quad[2 * i], by = (double)quad[2 * nx + 1] - quad[2 * i + 1];
+        sides[i] = std::sqrt(bx * bx + by * by);
+        const double norm = std::sqrt(ax * ax + ay * ay) * sides[i];
+        angles[i] = norm > 0 ? std::acos(std::max(-1.0, std::min(1.0, (ax * bx + ay * by) / norm))) : 0.0;
+    }
+    auto mean_std = [](const double (&v)[4], double* mean) {
+        *mean = (v[0] + v[1] + v[2] + v[3]) / 4;
+        double ss = 0;
+        for (double x : v) ss += (x - *mean) * (x - *mean);
+        return std::sqrt(ss / 4);
+    };
+    double side_mean, angle_mean;
+    const double side_std = mean_std(sides, &side_mean), angle_std = mean_std(angles, &angle_mean);
+    const double side_term = side_mean > 0 ? side_std / side_mean : 1.0;
+    return 1.0 - (side_term * 0.5 + angle_std / (3.14159265358979323846 / 2) * 0.5);
+}
+
 }  // namespace cv

@@ -3,6 +3,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <cstddef>
 #include <cstring>
 #include <new>
 #include <stdexcept>
@@ -26,7 +27,12 @@ hipError_t extract_squares_u8(const uint8_t* images, int n, int h, int w, const 
                               uint8_t* boards, hipStream_t s);
 hipError_t extract_squares_u8_one(const uint8_t* image, int h, int w, const double* inv_host, uint8_t* squares, uint8_t* board, hipStream_t s);
 void board_homographies(const float* quads, int n, int out_w, int out_h, double* forward, double* inverse);
+double mask_completeness(const uint8_t* mask, int h, int w);
+double quadrangle_regularity(const float quad[8]);
 }  // namespace cv
+
+static_assert(sizeof(cv_score_record_t) == sizeof(cv::ScoreRecord) && offsetof(cv_score_record_t, top_sum) == offsetof(cv::ScoreRecord, top_sum) &&
+              offsetof(cv_score_record_t, top_count) == offsetof(cv::ScoreRecord, top_count), "cv_score_record_t is the kernel's record");
 
 using namespace cv;
 
@@ -497,6 +503,65 @@ static int impl_cv_find_quadrangles(const uint8_t* masks, int n, int h, int w, i
     std::vector<std::thread> pool;
     for (int t = 0; t < nt; ++t) pool.emplace_back(work, t);
     for (auto& th : pool) th.join();
+    return CV_OK;
+}
+
+// contiguous slices of [0, n) on up to `nt` host threads (the quality scores: every item costs about the same)
+template <class F> static void parallel_slices(int n, int nt, F&& work) {
+    if (nt <= 1) { work(0, n); return; }
+    std::vector<std::thread> pool;
+    for (int t = 0; t < nt; ++t) pool.emplace_back([&work, n, nt, t] { work((int)((long long)n * t / nt), (int)((long long)n * (t + 1) / nt)); });
+    for (auto& th : pool) th.join();
+}
+
+static int impl_cv_extraction_scores(cv_engine_t* eng, const float* values, int n, int count, int transform, cv_score_record_t* records,
+                                     uint8_t* half_mask, void* stream) {
+    Status s = check_engine(eng);
+    if (!s.ok()) return finish(s);
+    if (!values || !records) return finish(fail(CV_ERR_INVALID, "cv_extraction_scores: null tensor"));
+    if (((uintptr_t)values & 3u) || ((uintptr_t)records & 7u)) return finish(fail(CV_ERR_INVALID, "cv_extraction_scores: values must be 4-byte, records 8-byte aligned"));
+    if (n < 1) return finish(fail(CV_ERR_INVALID, "cv_extraction_scores: n must be at least 1"));
+    if (count < 4 || count > (1 << 24)) return finish(fail(CV_ERR_INVALID, "cv_extraction_scores: count must be in [4, 2^24]"));
+    if (transform != 0 && transform != 1) return finish(fail(CV_ERR_INVALID, "cv_extraction_scores: transform must be 0 (as given) or 1 (sigmoid)"));
+    DeviceGuard g(eng->impl.device);
+    hipError_t e = extraction_scores(values, n, count, transform, reinterpret_cast<ScoreRecord*>(records), half_mask, (hipStream_t)stream);
+    if (e != hipSuccess) return finish(hip_fail(e, "extraction_scores"));
+    return CV_OK;
+}
+
+static int impl_cv_extraction_scores_finish(const cv_score_record_t* records, int n, double* confidence, double* distribution) {
+    if (n < 0 || (n > 0 && (!records || !confidence || !distribution))) return finish(fail(CV_ERR_INVALID, "cv_extraction_scores_finish: bad argument"));
+    const double nan = std::nan("");
+    for (int i = 0; i < n; ++i) {
+        const cv_score_record_t& r = records[i];
+        // numpy's sort puts NaN last, so one NaN in the image reaches the top quarter and the mean
+        confidence[i] = r.n_nan > 0 || r.top_count <= 0 ? nan : 2.0 * r.top_sum / (double)r.top_count;
+        long long total = 0;
+        for (int b = 0; b < 10; ++b) total += r.hist[b];
+        if (total == 0) { distribution[i] = nan; continue; }           // 0 / 0 in the reference's hist / sum(hist)
+        double entropy = 0.0;
+        for (int b = 0; b < 10; ++b) {
+            const double p = (double)r.hist[b] / (double)total;
+            entropy -= p * std::log2(p + 1e-10);
+        }
+        distribution[i] = 1.0 - entropy / std::log2(10.0);
+    }
+    return CV_OK;
+}
+
+static int impl_cv_mask_completenesses(const uint8_t* masks, int n, int h, int w, double* scores, int n_threads) {
+    if (!masks || !scores || n < 0 || h <= 0 || w <= 0) return finish(fail(CV_ERR_INVALID, "cv_mask_completenesses: bad argument"));
+    int nt = n_threads > 0 ? n_threads : (int)std::thread::hardware_concurrency();
+    nt = std::max(1, std::min(nt, std::min((n + 7) / 8, 32)));          // as cv_find_quadrangles: at least eight masks per thread
+    parallel_slices(n, nt, [&](int lo, int hi) {
+        for (int i = lo; i < hi; ++i) scores[i] = mask_completeness(masks + (size_t)i * h * w, h, w);
+    });
+    return CV_OK;
+}
+
+static int impl_cv_quadrangle_regularity(const float* quad, double* score) {
+    if (!score) return finish(fail(CV_ERR_INVALID, "cv_quadrangle_regularity: null score"));
+    *score = quad ? quadrangle_regularity(quad) : 0.0;
     return CV_OK;
 }
 
@@ -1101,3 +1166,26 @@ int cv_extract_squares_u8_dev(cv_engine_t* eng, const uint8_t* images, int n, in
 }
 
 }  // extern "C"
+
+int cv_extraction_scores(cv_engine_t* eng, const float* values, int n, int count, int transform, cv_score_record_t* records,
+                         uint8_t* half_mask, void* stream) {
+    return guarded("cv_extraction_scores", [&]() -> int {
+        return impl_cv_extraction_scores(eng, values, n, count, transform, records, half_mask, stream);
+    });
+}
+
+int cv_extraction_scores_finish(const cv_score_record_t* records, int n, double* confidence, double* distribution) {
+    return guarded("cv_extraction_scores_finish", [&]() -> int { return impl_cv_extraction_scores_finish(records, n, confidence, distribution); });
+}
+
+int cv_mask_completeness(const uint8_t* mask, int h, int w, double* score) {
+    return guarded("cv_mask_completeness", [&]() -> int { return impl_cv_mask_completenesses(mask, 1, h, w, score, 1); });
+}
+
+int cv_mask_completenesses(const uint8_t* masks, int n, int h, int w, double* scores, int n_threads) {
+    return guarded("cv_mask_completenesses", [&]() -> int { return impl_cv_mask_completenesses(masks, n, h, w, scores, n_threads); });
+}
+
+int cv_quadrangle_regularity(const float* quad, double* score) {
+    return guarded("cv_quadrangle_regularity", [&]() -> int { return impl_cv_quadrangle_regularity(quad, score); });
+}

@@ -52,6 +52,25 @@ hipError_t head_avgpool_fc(int dt, const TensorRef& src, const float* w, const f
                            int softmax, unsigned* flag, unsigned layer_id, hipStream_t s);
 hipError_t softmax13(const float* logits, int n, float* probs, hipStream_t s);
 
+// Board-extraction quality scores (the per-image reductions behind the reference's `confidence` and `distribution` columns,
+// scripts/process_new_raw/process_pipeline.py:357-377, 460-467).  values: n images of `count` contiguous float32 (4 <= count <= 2^24);
+// transform 0 scores them as given, 1 scores v = 1 / (1 + __expf(-x)) (outc_1x1's mask expression).  One record per image:
+//   hist       np.histogram(v, bins=10, range=(0, 1)) of a float32 array: float32 edges 0.f, 0.1f, .. 1.f, e[i] <= v < e[i+1], v == 1 in
+//              the last bin, NaN / inf / anything outside [0, 1] dropped
+//   above_half number of v > 0.5f;  n_nan: number of NaNs
+//   top_sum    sum of fabsf(v - 0.5f) over the top_count = count / 4 largest values, selected exactly (ties at the smallest selected
+//              value t contribute (top_count - number of values > t) * |t - 0.5|), accumulated in float64 in a fixed order
+// half_mask (nullable, n x count uint8) = v > 0.5f ? 255 : 0.  Asynchronous on `s`; allocates nothing.
+struct ScoreRecord {
+    int32_t hist[10];
+    int32_t above_half, n_nan;
+    double  top_sum;
+    int32_t top_count, reserved;
+};
+static_assert(sizeof(ScoreRecord) == 64, "one 64-byte record per image");
+hipError_t extraction_scores(const float* values, int n, int count, int transform, ScoreRecord* records, uint8_t* half_mask,
+                             hipStream_t s);
+
 // MFMA lane-map probes used by cv_selftest_mfma (D = A*B^T with A:16xK, B:16xK row-major)
 hipError_t mfma_probe_f16(const half_t* a, const half_t* b, float* d, hipStream_t s);   // K = 32
 hipError_t mfma_probe_f32(const float* a, const float* b, float* d, hipStream_t s);     // K = 16

@@ -990,6 +990,193 @@ __global__ void softmax13_kernel(const float* __restrict__ logits, int n, float*
     for (int j = 0; j < 13; ++j) probs[(size_t)i * 13 + j] = v[j] * r;
 }
 
+// ---- board-extraction quality scores: per-image reductions over the UNet's logits ------------------------------------------------
+// One workgroup of 16 waves per image.  Sweep 0 reads the image once for the ten-bin histogram, the `> 0.5` count and mask, the NaN
+// count and the first radix histogram; three more sweeps narrow the k-th largest value (k = count / 4) eight key bits at a time, and
+// a last one sums |v - 0.5| above it.  The image (256 KB at 256x256) does not fit LDS: sweeps 1..4 re-read it through L2.  Every
+// count is an integer and the float64 sum runs in a fixed order (thread, wave shuffle, waves in order), so a record is bit-identical
+// run to run.
+constexpr int kScoreThreads = 1024, kScoreWaves = kScoreThreads / 64;
+
+template <int N> struct ScoreInt { static constexpr int value = N; };
+
+template <int TR> __device__ __forceinline__ float score_value(float x) {
+    return TR ? 1.f / (1.f + __expf(-x)) : x;                 // the expression of outc_1x1_kernel's mask
+}
+
+// order-preserving key of a float (larger value <=> larger key); -0.0 shares +0.0's key
+__device__ __forceinline__ unsigned score_key(float v) {
+    const unsigned u = __float_as_uint(v);
+    const unsigned k = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+    return k == 0x7fffffffu ? 0x80000000u : k;
+}
+__device__ __forceinline__ float score_unkey(unsigned k) {
+    return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
+}
+
+// f(values, ScoreInt<m>, index of values[0]): m = 4 for the 16-byte aligned body, 1 for the elements before and after it
+template <int TR, class F>
+__device__ __forceinline__ void score_sweep(const float* __restrict__ img, int count, int head, int nvec, F&& f) {
+    const float4* body = reinterpret_cast<const float4*>(img + head);
+    for (int i = threadIdx.x; i < nvec; i += kScoreThreads) {
+        const float4 q = body[i];
+        const float v[4] = {score_value<TR>(q.x), score_value<TR>(q.y), score_value<TR>(q.z), score_value<TR>(q.w)};
+        f(v, ScoreInt<4>(), head + 4 * i);
+    }
+    const int tail = head + 4 * nvec;
+    for (int i = threadIdx.x; i < count - 4 * nvec; i += kScoreThreads) {
+        const int at = i < head ? i : tail + (i - head);
+        const float v[1] = {score_value<TR>(img[at])};
+        f(v, ScoreInt<1>(), at);
+    }
+}
+
+// One radix step (every thread of the block calls it): merge the per-wave histograms, let wave 0 find the bin that holds the
+// `krem`-th largest of the candidates, clear the histograms for the next sweep.  Returns the bin; krem becomes the rank inside it.
+__device__ __forceinline__ int score_select(int (*whist)[256], int* tot, int* sel, int& krem) {
+    const int tid = threadIdx.x, lane = tid & 63;
+    __syncthreads();
+    if (tid < 256) {
+        int s = 0;
+#pragma unroll
+        for (int w = 0; w < kScoreWaves; ++w) s += whist[w][tid];
+        tot[tid] = s;
+    }
+    __syncthreads();
+    if (tid < 64) {                                           // lane l owns bins 255-4l .. 252-4l: a scan from the largest key down
+        const int hi = 255 - 4 * lane;
+        const int b0 = tot[hi], b1 = tot[hi - 1], b2 = tot[hi - 2], b3 = tot[hi - 3];
+        const int own = b0 + b1 + b2 + b3;
+        int incl = own;
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+            const int t = __shfl_up(incl, d);
+            if (lane >= d) incl += t;
+        }
+        int acc = incl - own;
+        if (acc < krem && krem <= incl) {                     // exactly one lane
+            int bin = hi;
+            if (acc + b0 < krem) { acc += b0; bin = hi - 1;
+                if (acc + b1 < krem) { acc += b1; bin = hi - 2;
+                    if (acc + b2 < krem) { acc += b2; bin = hi - 3; } } }
+            sel[0] = bin;
+            sel[1] = krem - acc;
+        }
+    }
+    for (int i = tid; i < kScoreWaves * 256; i += kScoreThreads) (&whist[0][0])[i] = 0;
+    __syncthreads();
+    krem = sel[1];
+    return sel[0];
+}
+
+template <int TR>
+__global__ __launch_bounds__(kScoreThreads) void extraction_scores_kernel(const float* __restrict__ values, int count,
+                                                                          ScoreRecord* __restrict__ records,
+                                                                          uint8_t* __restrict__ half_mask) {
+    __shared__ int whist[kScoreWaves][256];
+    __shared__ int tot[256];
+    __shared__ int wstat[kScoreWaves][12];
+    __shared__ int stat[12];
+    __shared__ double wsum[kScoreWaves];
+    __shared__ int sel[2];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const float* img = values + (size_t)blockIdx.x * count;
+    uint8_t* mk = half_mask ? half_mask + (size_t)blockIdx.x * count : nullptr;
+    const int head = min(count, (int)(((16u - (unsigned)((uintptr_t)img & 15u)) & 15u) >> 2));
+    const int nvec = (count - head) >> 2;
+    const bool mk4 = mk && (((uintptr_t)(mk + head)) & 3u) == 0;       // the body's mask bytes go out four at a time
+    int* myhist = whist[wave];
+    for (int i = tid; i < kScoreWaves * 256; i += kScoreThreads) (&whist[0][0])[i] = 0;
+    __syncthreads();
+
+    // sweep 0.  c[0] counts the values in [0, 1], c[j] those of them >= the float32 edge j/10 (numpy's float32 bin edges: a value is in
+    // bin i iff e[i] <= v < e[i+1], v == 1 joins the last bin), c[10] the values > 0.5, c[11] the NaNs
+    int c[12];
+#pragma unroll
+    for (int j = 0; j < 12; ++j) c[j] = 0;
+    score_sweep<TR>(img, count, head, nvec, [&](const float* v, auto M, int at) {
+        constexpr int m = decltype(M)::value;
+        constexpr float edge[10] = {0.f, 0.1f, 0.2f, 0.3f, 0.4f, 0.5f, 0.6f, 0.7f, 0.8f, 0.9f};
+        uint8_t bits[m];
+#pragma unroll
+        for (int j = 0; j < m; ++j) {
+            const float x = v[j];
+            const bool in = x >= 0.f && x <= 1.f;
+            c[0] += in;
+#pragma unroll
+            for (int e = 1; e < 10; ++e) c[e] += in && x >= edge[e];
+            c[10] += x > 0.5f;
+            c[11] += x != x;
+            bits[j] = x > 0.5f ? 255 : 0;
+            atomicAdd(&myhist[score_key(x) >> 24], 1);
+        }
+        if (mk) {
+            bool stored = false;
+            if constexpr (m == 4) {
+                if (mk4) { *reinterpret_cast<uchar4*>(mk + at) = make_uchar4(bits[0], bits[1], bits[2], bits[3]); stored = true; }
+            }
+            if (!stored) {
+#pragma unroll
+                for (int j = 0; j < m; ++j) mk[at + j] = bits[j];
+            }
+        }
+    });
+#pragma unroll
+    for (int j = 0; j < 12; ++j) {
+        int s = c[j];
+#pragma unroll
+        for (int d = 32; d > 0; d >>= 1) s += __shfl_down(s, d);
+        if (lane == 0) wstat[wave][j] = s;
+    }
+    int krem = count >> 2;                                    // k: how many of the largest values are averaged
+    const int k = krem;
+    unsigned prefix = (unsigned)score_select(whist, tot, sel, krem);      // (its first barrier publishes wstat too)
+    if (tid < 12) {
+        int s = 0;
+        for (int w = 0; w < kScoreWaves; ++w) s += wstat[w][tid];
+        stat[tid] = s;
+    }
+
+    // sweeps 1..3: among the values whose key starts with `prefix`, histogram the next eight key bits
+#pragma unroll 1
+    for (int shift = 16; shift >= 0; shift -= 8) {
+        score_sweep<TR>(img, count, head, nvec, [&](const float* v, auto M, int) {
+#pragma unroll
+            for (int j = 0; j < decltype(M)::value; ++j) {
+                const unsigned key = score_key(v[j]);
+                if ((key >> (shift + 8)) == prefix) atomicAdd(&myhist[(key >> shift) & 255u], 1);
+            }
+        });
+        prefix = (prefix << 8) | (unsigned)score_select(whist, tot, sel, krem);
+    }
+
+    // sweep 4: prefix is the key of the k-th largest value t; sum |v - 0.5| over the values above it.  The krem values equal to t
+    // that complete the k are added once at the end (ties at t contribute (k - number strictly greater) * |t - 0.5|).
+    double sum = 0.0;
+    score_sweep<TR>(img, count, head, nvec, [&](const float* v, auto M, int) {
+#pragma unroll
+        for (int j = 0; j < decltype(M)::value; ++j)
+            if (score_key(v[j]) > prefix) sum += (double)fabsf(v[j] - 0.5f);
+    });
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) sum += __shfl_down(sum, d);
+    if (lane == 0) wsum[wave] = sum;
+    __syncthreads();
+    if (tid == 0) {
+        ScoreRecord r;
+        for (int i = 0; i < 9; ++i) r.hist[i] = stat[i] - stat[i + 1];
+        r.hist[9] = stat[9];
+        r.above_half = stat[10];
+        r.n_nan = stat[11];
+        double total = 0.0;
+        for (int w = 0; w < kScoreWaves; ++w) total += wsum[w];
+        r.top_sum = total + (double)krem * (double)fabsf(score_unkey(prefix) - 0.5f);
+        r.top_count = k;
+        r.reserved = 0;
+        records[blockIdx.x] = r;
+    }
+}
+
 // ---- MFMA lane-map probes (same fragment addressing as conv_igemm.hip) ---------------------------
 __global__ void mfma_probe_f16_kernel(const half_t* a, const half_t* b, float* d) {
     const int lane = threadIdx.x, q = lane >> 4, r = lane & 15;
@@ -1138,6 +1325,14 @@ hipError_t head_avgpool_fc(int dt, const TensorRef& src, const float* w, const f
     if (dt == kF16) hipLaunchKernelGGL(head_kernel<half_t>, g, blk, 0, s, src, w, b, mul, out, softmax, flag, layer_id);
     else if (dt == kSplit) hipLaunchKernelGGL(head_kernel<split_t>, g, blk, 0, s, src, w, b, mul, out, softmax, flag, layer_id);
     else hipLaunchKernelGGL(head_kernel<float>, g, blk, 0, s, src, w, b, mul, out, softmax, flag, layer_id);
+    return hipGetLastError();
+}
+hipError_t extraction_scores(const float* values, int n, int count, int transform, ScoreRecord* records, uint8_t* half_mask,
+                             hipStream_t s) {
+    if (!values || !records || n < 1 || count < 4 || count > (1 << 24) || ((uintptr_t)values & 3u) || (transform != 0 && transform != 1))
+        return hipErrorInvalidValue;
+    if (transform) hipLaunchKernelGGL(extraction_scores_kernel<1>, dim3((unsigned)n), dim3(kScoreThreads), 0, s, values, count, records, half_mask);
+    else hipLaunchKernelGGL(extraction_scores_kernel<0>, dim3((unsigned)n), dim3(kScoreThreads), 0, s, values, count, records, half_mask);
     return hipGetLastError();
 }
 hipError_t softmax13(const float* logits, int n, float* probs, hipStream_t s) {

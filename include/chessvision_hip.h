@@ -298,6 +298,44 @@ int cv_extract_squares_u8_dev(cv_engine_t* eng, const uint8_t* images, int n, in
 int cv_decode_positions(const float* probs, int n_boards, int flip, char* fen, char* original_fen, int8_t* labels,
                         int32_t* fixes, int32_t* n_fixes);
 
+/* ---- board-extraction quality scores (additions under ABI 6; detect with dlsym(handle, "cv_extraction_scores")) ------------------- */
+/* The four floats the reference's enrichment job writes per image beside the FEN (scripts/process_new_raw/process_pipeline.py:287-311,
+ * functions at 357-467): `confidence`, `distribution`, `completeness`, `quad_score`.  The first two are reductions over the UNet's
+ * output and run on the device, where the logits already are; the other two are host geometry.
+ *
+ * cv_extraction_scores: values = n images of `count` contiguous float32 (DEVICE, 4-byte aligned; 4 <= count <= 2^24, n >= 1);
+ * transform 0 scores the values as given (the reference's letter: it passes BoardExtractionResult.probabilities, which holds raw
+ * logits), 1 scores v = 1 / (1 + exp(-x)) with the expression the UNet's mask uses, so `v > 0.5` agrees bit for bit with the mask of
+ * cv_unet_forward_u8 at threshold 0.5.  records: n records (DEVICE, 8-byte aligned); half_mask (nullable, DEVICE, n x count uint8) =
+ * 255 where v > 0.5 else 0.  Asynchronous on `stream`; allocates nothing and synchronises nothing.  A record is bit-identical run
+ * to run (integer counts; the float64 sum runs in a fixed order, no float atomics). */
+typedef struct cv_score_record {
+    int32_t hist[10];     /* np.histogram(v, bins=10, range=(0, 1)) for a float32 array: float32 edges 0.f, 0.1f, .., 0.9f, 1.f; v is in
+                             bin i iff e[i] <= v < e[i+1], v == 1 joins the last bin; NaN, +-inf and everything outside [0, 1] dropped */
+    int32_t above_half;   /* number of values with v > 0.5f */
+    int32_t n_nan;
+    double  top_sum;      /* sum of |v - 0.5| (float32 subtraction, float64 sum) over the top_count largest values, selected exactly:
+                             ties at the smallest selected value t contribute (top_count - number of values > t) * |t - 0.5| */
+    int32_t top_count;    /* count / 4 */
+    int32_t reserved;     /* 0; pads the record to 64 bytes */
+} cv_score_record_t;
+int cv_extraction_scores(cv_engine_t* eng, const float* values, int n, int count, int transform, cv_score_record_t* records,
+                         uint8_t* half_mask, void* stream);
+/* Records (HOST) -> the two scores, n doubles each: confidence = 2 * top_sum / top_count = np.mean(np.abs(np.sort(v)[-k:] - 0.5)) * 2
+ * (NaN when the image holds a NaN, as numpy's sort puts NaN last); distribution = 1 - H / log2(10) with p = hist / sum(hist) and
+ * H = -sum p log2(p + 1e-10) (NaN for an empty histogram, as numpy's 0 / 0).  Needs no GPU and no engine. */
+int cv_extraction_scores_finish(const cv_score_record_t* records, int n, double* confidence, double* distribution);
+/* Binary mask (h*w uint8, 0 / non-0) -> foreground pixels of the whole mask / pixels of the filled outer border of the 8-connected
+ * component with the largest contourArea (cv2.findContours RETR_EXTERNAL, max by contourArea, drawContours thickness -1; ties go to
+ * the first contour in OpenCV's order).  `Filled` = the component plus every pixel the image frame cannot reach by 4-connected steps
+ * around it -- a restatement of drawContours, not measured against cv2.  0 for an empty mask; can exceed 1.  Host only. */
+int cv_mask_completeness(const uint8_t* mask, int h, int w, double* score);
+/* The same for n masks (n,h,w) on n_threads host threads (0 = hardware concurrency, capped at 32); scores: n doubles. */
+int cv_mask_completenesses(const uint8_t* masks, int n, int h, int w, double* scores, int n_threads);
+/* quad: 4 x (x, y) float32 in the order given, or NULL (no quadrangle: score 0).  score = 1 - 0.5 std(sides) / mean(sides)
+ * - 0.5 std(angles) / (pi / 2), population standard deviations, in double.  Host only. */
+int cv_quadrangle_regularity(const float* quad, double* score);
+
 /* ---- one image, host to host: the native form of ChessVision.process_image (core.py:152-195) ---------------------------------- */
 /* Everything a cgo / JNI / C++ host needs for the reference's per-image entry point in ONE call: INTER_AREA resize to 256x256
  * (core.py:212), UNet forward, sigmoid / threshold mask (core.py:273, utils.py:101-112), contours -> quadrangle (core.py:357-411),
