@@ -1,0 +1,351 @@
+"""The batched pipeline behind ``ChessVision.process_images`` (new; the reference processes one image per call, core.py:152-195).
+
+Images stay on the device between the two CNNs: INTER_AREA resize -> UNet (u8 in, logits + thresholded mask out); only the 64 KB
+masks come back for the C++ contour stage; the quadrangles go back as 3x3 maps and ONE fused warp+gray+flip+split kernel writes the
+classifier input; the classifier runs with softmax on device; labels, pawn rule and FEN of a whole job are decoded by one native
+call.  Work is cut into jobs of up to ``pipeline_chunk`` equally sized images (``plan_jobs``) and software-pipelined
+(``_Call.issue``): host->device copies run on their own stream out of a pinned staging buffer filled by a few copy threads,
+device->host copies on a third stream behind events, and while the GPU runs the UNet of job k+1 the host finds the quadrangles of
+job k and decodes job k-1.  Nothing on the host blocks the compute stream.
+
+The streams and the copy threads belong to the ``ChessVision`` instance and live across calls (the HIP runtime binds a stream to a
+hardware queue at its first use); everything else here lives for one call.
+"""
+from __future__ import annotations
+
+import contextlib
+import time
+from concurrent.futures import ThreadPoolExecutor
+from dataclasses import dataclass
+from typing import Sequence
+
+import numpy as np
+import torch
+
+from . import constants
+from .cv_types import BoardExtractionResult, ChessVisionResult, ExtractionQuality, PositionResult, pawn_rule_fix
+from .distributed import host_threads
+from .hip_backend import (SCORE_RECORD, board_homographies, decode_positions, find_quadrangles, mask_completenesses,
+                          quadrangle_regularity, scores_finish)
+
+_HOST_STAGES = ("stage_s", "wait_masks_s", "contours_s", "homography_s", "wait_probs_s", "decode_s", "assemble_s")
+
+
+def plan_jobs(shapes: Sequence[tuple], pipeline_chunk: int, first: int, last: int) -> list[list[int]]:
+    """Image indices per job: images of one shape together, at most ``pipeline_chunk`` per job, in order of first appearance.
+
+    Pipeline fill and drain are the only parts of a call the GPU does not overlap: nothing hides the staging + upload of the FIRST
+    job, and after the last UNet the host still finds the LAST job's quadrangles before its classifier can start.  Both ends can
+    therefore be cut short: the first job to ``first`` images, the last one to ``last`` (measured on MI355X, r03: 3578 -> 3658
+    boards/s for a 16-board first job at 256 boards, although the UNet runs ~5 % slower on part-chunks); 0 switches a split off,
+    and a call of one job is never split."""
+    groups: dict[tuple, list[int]] = {}
+    for i, shape in enumerate(shapes):
+        groups.setdefault(shape, []).append(i)
+    step = max(1, int(pipeline_chunk))
+    jobs = [ids[k:k + step] for ids in groups.values() for k in range(0, len(ids), step)]
+    if len(jobs) > 1 and 0 < first < len(jobs[0]):
+        jobs = [jobs[0][:first], jobs[0][first:]] + jobs[1:]
+    if len(jobs) > 2 and 0 < last and len(jobs[-1]) >= 2 * last:
+        jobs = jobs[:-1] + [jobs[-1][:-last], jobs[-1][-last:]]
+    return jobs
+
+
+@dataclass(slots=True)
+class Job:
+    """One job on its way through upload -> compute -> classify -> finish.
+
+    Lifetime invariant: a device tensor written on one stream and read by a copy on ANOTHER stream stays referenced from the job
+    until the event recorded behind that copy has been synchronised -- otherwise the caching allocator, which orders reuse against
+    the allocating stream only, may hand its memory to a later job while the copy still reads it.  ``unet_out`` (read by the
+    download stream up to ``logits_ready``) and ``cls_out`` (up to ``probs_ready``) exist for nothing else; ``release`` drops them
+    once ``finish`` has synchronised both events.  ``batch`` is written by the upload stream and read by the compute stream: it is
+    handed over with ``record_stream`` and dropped as soon as its last kernel (the warp) is queued."""
+    ids: list[int]
+    # upload
+    staged: torch.Tensor | None = None          # pinned source of the upload
+    batch: torch.Tensor | None = None           # the photos on the device
+    arrived: torch.cuda.Event | None = None     # upload stream: the batch is there
+    # compute
+    unet_done: torch.cuda.Event | None = None   # compute stream: UNet (and scores) queued up to here; gates the upload two jobs on
+    unet_out: tuple | None = None               # device: logits, masks, score records -- held for the download stream
+    masks: torch.Tensor | None = None           # pinned (n,256,256) u8
+    logits: torch.Tensor | None = None          # pinned (n,256,256) f32
+    records: torch.Tensor | None = None         # pinned (n,64) u8 score records, ``quality`` only
+    half: torch.Tensor | None = None            # pinned (n,256,256) u8 ``v > 0.5`` masks, ``quality`` only
+    masks_ready: torch.cuda.Event | None = None     # download stream: masks have landed
+    logits_ready: torch.cuda.Event | None = None    # download stream: logits (and records, half) have landed
+    # classify
+    quads: list | None = None                   # per image: quadrangle in photo pixels or None
+    found: list[int] | None = None              # positions within the job that have one
+    quality: list[ExtractionQuality] | None = None
+    cls_out: tuple | None = None                # device: probabilities, boards, squares -- held for the download stream
+    boards: torch.Tensor | None = None          # pinned (found,512,512) u8
+    probs: torch.Tensor | None = None           # pinned (found*64,13) f32
+    probs_ready: torch.cuda.Event | None = None     # download stream: boards and probabilities have landed
+
+    def release(self) -> None:
+        self.batch = self.unet_out = self.cls_out = None
+
+
+@dataclass(slots=True)
+class _ImageSlot:
+    """What the jobs leave behind for image i; ``assemble`` wraps it into the result records."""
+    logits: np.ndarray
+    mask: np.ndarray
+    quad: np.ndarray | None
+    quality: ExtractionQuality | None
+    board: np.ndarray | None = None
+    position: PositionResult | None = None
+
+
+def _pinned(shape, dtype):
+    return torch.empty(shape, dtype=dtype, pin_memory=True)
+
+
+class _Call:
+    """The state one ``process_images`` call shares between its stages.  The compute stream is the CURRENT stream."""
+
+    def __init__(self, cv, images, threshold, flip, fallback_quad, return_crops, timings, quality, started):
+        self.cv, self.images, self.started = cv, images, started
+        self.threshold, self.flip, self.fallback_quad, self.return_crops, self.quality = threshold, flip, fallback_quad, return_crops, quality
+        self.eng, self.eng_cls, self.dev = cv._get_engine("unet"), cv._get_engine("resnet18"), cv.device
+        self.names = constants.SQUARE_NAMES_FLIPPED if flip else constants.SQUARE_NAMES_NORMAL
+        self.n_host = host_threads()
+        self.main = torch.cuda.current_stream(self.dev)
+        self.up, self.down = cv._pipeline_streams()[:2]
+        if cv._copy_pool is None:
+            cv._copy_pool = ThreadPoolExecutor(max_workers=min(16, self.n_host), thread_name_prefix="cv-stage")
+        self.pool = cv._copy_pool
+        self.timed = timings is not None                 # no events are created for a caller that does not ask
+        self.tm = timings if self.timed else {}
+        for key in _HOST_STAGES:
+            self.tm.setdefault(key, 0.0)
+        if quality:
+            self.tm.setdefault("quality", 0.0)           # host seconds of the score stage (its kernel: quality_ms)
+        self.gpu_events: list[tuple[str, torch.cuda.Event, torch.cuda.Event]] = []
+        self.slots: list[_ImageSlot | None] = [None] * len(images)
+
+    def clock(self, key, t0):
+        self.tm[key] += time.perf_counter() - t0
+
+    def gpu_timed(self, name, fn, *args, **kw):
+        if not self.timed:
+            return fn(*args, **kw)
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        out = fn(*args, **kw)
+        b.record()
+        self.gpu_events.append((name, a, b))
+        return out
+
+    # ---- the four stages, each once per job -------------------------------------------------------------------------------------
+    def upload(self, ids, sliced=False, gate=None) -> Job:
+        """host -> pinned staging -> device, on the upload stream.  ``gate``: an event of the compute stream the copy must not start
+        before.  Jobs are uploaded TWO ahead, gated on the end of the previous job's UNet, so that the 50 MB copy runs beside the
+        (short, HBM-light) warp + classifier phase instead of beside a UNet, whose launches it slows by 4-7 % (r03_tuning.md step 17;
+        the ungated one-ahead schedule lost its same-box A/B by 3.7 %, r04_tuning.md step 12)."""
+        t0 = time.perf_counter()
+        images, up = self.images, self.up
+        shape = images[ids[0]].shape
+        job = Job(ids, staged=_pinned((len(ids),) + shape, torch.uint8))
+        view = job.staged.numpy()
+        with torch.cuda.stream(up):
+            job.batch = torch.empty((len(ids),) + shape, dtype=torch.uint8, device=self.dev)
+            if gate is not None:
+                up.wait_event(gate)
+        # the first job of a call is staged and uploaded in slices of 16 images (the upload of a slice overlaps the host copies
+        # of the next one: nothing else hides that job's staging); later jobs are staged in one go behind the GPU's work
+        step = 16 if sliced else len(ids)
+
+        def copy_group(lo, hi):                          # one task per group of images: few Python-level dispatches, the
+            for k in range(lo, hi):                      # memcpys themselves run without the GIL
+                np.copyto(view[k], images[ids[k]])
+
+        for k0 in range(0, len(ids), step):
+            k1 = min(len(ids), k0 + step)
+            per = max(1, -(-(k1 - k0) // 16))
+            list(self.pool.map(lambda lo: copy_group(lo, min(k1, lo + per)), range(k0, k1, per)))
+            with torch.cuda.stream(up):
+                job.batch[k0:k1].copy_(job.staged[k0:k1], non_blocking=True)
+        self.clock("stage_s", t0)
+        with torch.cuda.stream(up):
+            job.arrived = torch.cuda.Event()
+            job.arrived.record()
+        return job
+
+    def compute(self, job: Job) -> None:
+        """resize + UNet (+ the score reductions, on the logits where the UNet left them) on the compute stream; masks start back."""
+        n, eng, down = len(job.ids), self.eng, self.down
+        self.main.wait_event(job.arrived)
+        job.batch.record_stream(self.main)
+        self.tm.setdefault("first_enqueue_s", time.time() - self.started)   # host time until the first kernel of the call is queued
+        small = self.gpu_timed("resize_ms", eng.resize_area_u8, job.batch, (constants.INPUT_SIZE[1], constants.INPUT_SIZE[0]))
+        lg, mk = self.gpu_timed("unet_ms", eng.unet_forward_u8, small, threshold=self.threshold, want_mask=True)
+        scored = None
+        if self.quality:
+            scored = self.gpu_timed("quality_ms", eng.extraction_scores_dev, lg, "none" if self.quality == "logits" else "sigmoid",
+                                    want_mask=True)
+        job.unet_done = torch.cuda.Event()
+        job.unet_done.record()
+        job.unet_out = (lg, mk, scored)
+        job.logits, job.masks = _pinned((n, 256, 256), torch.float32), _pinned((n, 256, 256), torch.uint8)
+        job.masks_ready, job.logits_ready = torch.cuda.Event(), torch.cuda.Event()
+        with torch.cuda.stream(down):
+            down.wait_event(job.unet_done)
+            job.masks.copy_(mk, non_blocking=True)       # masks first: the contour stage waits for them only
+            job.masks_ready.record()
+            job.logits.copy_(lg[:, 0], non_blocking=True)
+            if scored is not None:
+                job.records, job.half = _pinned((n, 64), torch.uint8), _pinned((n, 256, 256), torch.uint8)
+                job.records.copy_(scored[0], non_blocking=True)
+                job.half.copy_(scored[1].view(n, 256, 256), non_blocking=True)
+            job.logits_ready.record()
+
+    def classify(self, job: Job) -> None:
+        """masks -> quadrangles (host) -> warp + split + classifier (device); boards and probabilities start back."""
+        t0 = time.perf_counter()
+        job.masks_ready.synchronize()
+        self.clock("wait_masks_s", t0)
+        ids, down = job.ids, self.down
+        t0 = time.perf_counter()
+        found_quads = find_quadrangles(job.masks.numpy(), n_threads=self.n_host)
+        self.clock("contours_s", t0)
+        t0 = time.perf_counter()
+        job.quads = []
+        for k, q in enumerate(found_quads):
+            if q is None and self.fallback_quad:
+                q = constants.WHOLE_MASK_QUADRANGLE
+            shape = self.images[ids[k]].shape
+            job.quads.append(None if q is None else self.cv._scale_quadrangle(q, (shape[0], shape[1])))
+        found = job.found = [k for k in range(len(ids)) if job.quads[k] is not None]
+        if found:
+            inv = board_homographies(np.stack([job.quads[k].reshape(4, 2) for k in found]), constants.BOARD_SIZE)
+        self.clock("homography_s", t0)
+        if found:
+            src = job.batch if len(found) == len(ids) else job.batch[torch.as_tensor(found, device=self.dev)]
+            squares_dev, boards_dev = self.gpu_timed("warp_ms", self.eng.extract_squares_u8, src, inv)
+            warped = torch.cuda.Event()
+            warped.record()
+            job.boards = _pinned((len(found), constants.BOARD_SIZE[1], constants.BOARD_SIZE[0]), torch.uint8)
+            with torch.cuda.stream(down):                # the rectified boards travel back while the classifier runs
+                down.wait_event(warped)
+                job.boards.copy_(boards_dev, non_blocking=True)
+            probs_dev = self.gpu_timed("resnet_ms", self.eng_cls.resnet18_forward_u8, squares_dev)
+            done = torch.cuda.Event()
+            done.record()
+            job.probs = _pinned((len(found) * 64, constants.NUM_CLASSES), torch.float32)
+            job.cls_out = (probs_dev, boards_dev, squares_dev)
+            job.probs_ready = torch.cuda.Event()
+            with torch.cuda.stream(down):
+                down.wait_event(done)
+                job.probs.copy_(probs_dev, non_blocking=True)
+                job.probs_ready.record()
+        job.batch = None
+        if self.quality:                                 # the device has this job's classifier queued: finish its scores meanwhile
+            t0 = time.perf_counter()
+            job.logits_ready.synchronize()
+            conf, dist = scores_finish(job.records.numpy().view(SCORE_RECORD).reshape(-1))
+            comp = mask_completenesses(job.half.numpy(), n_threads=self.n_host)
+            job.quality = [ExtractionQuality(confidence=float(conf[k]), quad_score=quadrangle_regularity(found_quads[k]),
+                                             completeness=float(comp[k]), distribution=float(dist[k])) for k in range(len(ids))]
+            self.clock("quality", t0)
+
+    def finish(self, job: Job) -> None:
+        """probabilities -> labels, FEN, pawn rule (one native call per job); the job's arrays go to its images' slots."""
+        ids, names, slots = job.ids, self.names, self.slots
+        t0 = time.perf_counter()
+        job.logits_ready.synchronize()
+        lg, mk = job.logits.numpy(), job.masks.numpy()
+        for k, i in enumerate(ids):
+            slots[i] = _ImageSlot(lg[k], mk[k], job.quads[k], job.quality[k] if job.quality else None)
+        if job.found:
+            job.probs_ready.synchronize()
+        self.clock("wait_probs_s", t0)
+        if not job.found:
+            return
+        t0 = time.perf_counter()
+        m = len(job.found)
+        probs = job.probs.numpy().reshape(m, 64, constants.NUM_CLASSES)
+        brd = job.boards.numpy()
+        fens, origs, _, fixes = decode_positions(probs, self.flip)
+        fix_lists: list[list] = [[] for _ in range(m)]
+        for b, sq, old, new in fixes:
+            fix_lists[b].append(pawn_rule_fix(names, sq, old, new))
+        for j, k in enumerate(job.found):
+            slot = slots[ids[k]]
+            slot.board = brd[j]
+            crops = self.cv.extract_squares(brd[j]) if self.return_crops else None
+            slot.position = PositionResult(fen=fens[j], original_fen=origs[j], model_probabilities=probs[j], squares=crops,
+                                           square_names=names, validation_fixes=fix_lists[j])
+        self.clock("decode_s", t0)
+
+    # ---- the software pipeline --------------------------------------------------------------------------------------------------
+    def issue(self, jobs: list[list[int]]) -> float:
+        """All jobs through the four stages; returns the host clock at which only the last job's ``finish`` was left.
+
+        The UNet of job k+1 is enqueued before the host works on job k, and the upload of job k+2 is issued behind the end of that
+        UNet.  Uses nothing of the call but the four stages: tests/test_batched_pipeline_cpu.py pins this ORDER with recorders."""
+        def retire(job):
+            self.finish(job)
+            job.release()                                # finish has synchronised the events behind every copy of the job
+
+        first = self.upload(jobs[0], sliced=True)
+        self.compute(first)                              # the first kernels are queued before anything else is staged
+        computed, uploaded, classified = first, None, None
+        if len(jobs) > 1:
+            uploaded = self.upload(jobs[1])              # nothing to hide behind yet: beside the (short) first job's UNet
+        for k in range(len(jobs)):
+            nxt = uploaded
+            if nxt is not None:
+                self.compute(nxt)
+                uploaded = self.upload(jobs[k + 2], gate=nxt.unet_done) if k + 2 < len(jobs) else None
+            self.classify(computed)
+            if classified is not None:
+                retire(classified)
+            classified, computed = computed, nxt
+        t_last = time.perf_counter()
+        retire(classified)
+        return t_last
+
+    def assemble(self) -> list[ChessVisionResult]:
+        t0 = time.perf_counter()
+        per_image = (time.time() - self.started) / len(self.slots)
+        results = []
+        for s in self.slots:
+            extraction = BoardExtractionResult(board_image=s.board, binary_mask=s.mask, quadrangle=s.quad, probabilities=s.logits)
+            results.append(ChessVisionResult(board_extraction=extraction, position=s.position, processing_time=per_image,
+                                             quality=s.quality))
+        self.clock("assemble_s", t0)
+        return results
+
+
+def process_images(cv, images, threshold, flip, fallback_quad, pipeline_chunk, return_crops, timings, first_job, last_job,
+                   quality) -> list[ChessVisionResult]:
+    """``ChessVision.process_images`` on the instance's native engines (arguments: see there)."""
+    started = time.time()
+    for image in images:
+        assert isinstance(image, np.ndarray) and image.dtype == np.uint8 and image.ndim == 3
+    if not images:
+        return []
+    _ = cv.board_extractor, cv.classifier
+    jobs = plan_jobs([im.shape for im in images], pipeline_chunk, first=int(first_job), last=int(last_job))
+    # A caller that chose no stream gets the instance's own compute stream, not the NULL stream: kernels queued on the legacy stream
+    # from one thread while other threads load models / run request slots was one of the two ingredients of the device faults of
+    # the round-6 soak (profiles/r06_tuning.md section 8).  Everything the call returns has been waited for through events when it
+    # ends, so nothing is left to order against the caller's stream.
+    own = torch.cuda.current_stream(cv.device) == torch.cuda.default_stream(cv.device)
+    with torch.cuda.stream(cv._pipeline_streams()[2]) if own else contextlib.nullcontext():
+        call = _Call(cv, images, threshold, flip, fallback_quad, return_crops, timings, quality, started)
+        t_last = call.issue(jobs)
+        call.eng.check_numerics()                        # one look at the numeric guard for the whole call
+        if call.eng_cls is not call.eng:
+            call.eng_cls.check_numerics()
+        call.tm["drain_s"] = time.perf_counter() - t_last    # last job: wait for its classifier, copies back, decode
+        results = call.assemble()
+        if timings is not None:
+            for name, a, b in call.gpu_events:
+                timings[name] = timings.get(name, 0.0) + a.elapsed_time(b)
+            timings["jobs"] = len(jobs)
+            timings["total_s"] = time.time() - started
+    return results

@@ -8,6 +8,8 @@ from __future__ import annotations
 import os
 from pathlib import Path
 
+import numpy as np
+
 # The reference resolves CVROOT to the repository that contains the package (constants.py:7).
 CVROOT = os.getenv("CVROOT", Path(__file__).resolve().parent.parent.as_posix())
 DATA_ROOT = Path(CVROOT) / "data"
@@ -23,6 +25,10 @@ BLACK_SQUARE_PATH = (DATA_ROOT / "squares" / "black_square.png").as_posix()
 INPUT_SIZE = (256, 256)        # UNet input (width, height)
 BOARD_SIZE = (512, 512)        # rectified board
 PIECE_SIZE = (64, 64)          # one square
+
+# the quadrangle of a photo that IS the board (``fallback_quad``): the whole 256-px mask, in the contour stage's vertex order
+WHOLE_MASK_QUADRANGLE = np.array([[[255, 0]], [[0, 0]], [[0, 255]], [[255, 255]]], dtype=np.int32)   # TR, TL, BL, BR
+WHOLE_MASK_QUADRANGLE.setflags(write=False)
 
 # class index -> FEN symbol; "f" marks an empty square
 LABEL_NAMES = list("BKNPQRbknpqr") + ["f"]

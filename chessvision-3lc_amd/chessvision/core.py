@@ -37,7 +37,7 @@ import torch
 from numpy.typing import NDArray
 
 from . import classical, constants, utils
-from .cv_types import BoardExtractionResult, ChessVisionResult, ExtractionQuality, PositionResult, ValidationFix
+from .cv_types import BoardExtractionResult, ChessVisionResult, PositionResult, ValidationFix, pawn_rule_fix
 from .fen import board_fen
 
 logger = logging.getLogger(__name__)
@@ -275,8 +275,7 @@ class ChessVision:
             extraction = BoardExtractionResult(board_image=None, binary_mask=r["mask"], quadrangle=None, probabilities=r["logits"])
             return ChessVisionResult(board_extraction=extraction, position=None, processing_time=time.time() - started)
         names = constants.SQUARE_NAMES_FLIPPED if flip else constants.SQUARE_NAMES_NORMAL
-        fixes = [ValidationFix(square_name=names[sq], original_piece=constants.LABEL_NAMES[old], corrected_piece=constants.LABEL_NAMES[new],
-                               rule_name="no_pawns_on_ends") for sq, old, new in r["fixes"]]
+        fixes = [pawn_rule_fix(names, *fix) for fix in r["fixes"]]
         extraction = BoardExtractionResult(board_image=r["board"], binary_mask=r["mask"], quadrangle=r["quadrangle"], probabilities=r["logits"])
         position = PositionResult(fen=r["fen"], original_fen=r["original_fen"], model_probabilities=r["probabilities"],
                                   squares=r["squares"], square_names=names, validation_fixes=fixes)
@@ -446,7 +445,7 @@ class ChessVision:
             binary_mask = st["mask"].numpy().copy()
             quadrangle = find_quadrangle(binary_mask)
             if quadrangle is None and fallback_quad:
-                quadrangle = np.array([[[255, 0]], [[0, 0]], [[0, 255]], [[255, 255]]], dtype=np.int32)   # TR, TL, BL, BR
+                quadrangle = constants.WHOLE_MASK_QUADRANGLE
             if quadrangle is None:
                 logger.info("Failed to extract board from image")
                 eng.check_numerics()                                          # synchronises: the logits have landed
@@ -484,36 +483,18 @@ class ChessVision:
             eng.check_numerics()                                              # synchronises
             probs = st["probs"].numpy().copy()
         fens, origs, _, fixes = decode_positions(probs[None], flip)
-        fix_list = [ValidationFix(square_name=names[sq], original_piece=constants.LABEL_NAMES[old],
-                                  corrected_piece=constants.LABEL_NAMES[new], rule_name="no_pawns_on_ends") for _, sq, old, new in fixes]
+        fix_list = [pawn_rule_fix(names, sq, old, new) for _, sq, old, new in fixes]
         return PositionResult(fen=fens[0], original_fen=origs[0], model_probabilities=probs, squares=squares, square_names=names,
                               validation_fixes=fix_list)
 
     def process_images(self, images: Sequence[NDArray[np.uint8]], threshold: float = 0.5, flip: bool = False,
                        fallback_quad: bool = False, pipeline_chunk: int = 64, return_crops: bool = True,
-                       timings: dict | None = None, first_job: int | None = None,
-                       last_job: int | None = None, quality: str | None = None) -> list[ChessVisionResult]:
-        """Batched pipeline: see ``_process_images_native`` (this wrapper adds the numeric-guard recovery: a call whose f16-based
-        engine reports a non-finite value is repeated as a whole on the exact-f32 instance, ``_recover``)."""
-        if quality not in (None, "logits", "sigmoid"):
-            raise ValueError(f"quality must be None, 'logits' or 'sigmoid', got {quality!r}")
-        return self._recover(lambda cv: cv._process_images_native(images, threshold, flip, fallback_quad, pipeline_chunk, return_crops,
-                                                                  timings, first_job, last_job, quality))
-
-    def _process_images_native(self, images: Sequence[NDArray[np.uint8]], threshold: float = 0.5, flip: bool = False,
-                               fallback_quad: bool = False, pipeline_chunk: int = 64, return_crops: bool = True,
-                               timings: dict | None = None, first_job: int | None = None,
-                               last_job: int | None = None, quality: str | None = None) -> list[ChessVisionResult]:
-        """Batched pipeline (new; the reference processes one image per call, core.py:152-195).
-
-        Images stay on the device between the two CNNs: INTER_AREA resize -> UNet (u8 in, logits + thresholded mask out);
-        only the 64 KB masks come back for the C++ contour stage; the quadrangles go back as 3x3 maps and ONE fused
-        warp+gray+flip+split kernel writes the classifier input; the classifier runs with softmax on device; labels, pawn
-        rule and FEN of a whole job are decoded by one native call.  Work is cut into jobs of up to ``pipeline_chunk``
-        equally sized images and software-pipelined: host->device copies run on their own stream out of a pinned staging
-        buffer filled by a few copy threads, device->host copies on a third stream behind events, and while the GPU runs
-        the UNet of job k+1 the host finds the quadrangles of job k and decodes job k-1.  Nothing on the host blocks the
-        compute stream.
+                       timings: dict | None = None, first_job: int = 16, last_job: int = 0,
+                       quality: str | None = None) -> list[ChessVisionResult]:
+        """Batched pipeline (``chessvision/batched.py``): the native stages of ``process_image``, cut into jobs of up to
+        ``pipeline_chunk`` equally sized images and software-pipelined; the first job of a call is cut to ``first_job`` images and
+        the last one to ``last_job`` (0: no split).  A call whose f16-based engine reports a non-finite value is repeated as a whole
+        on the exact-f32 instance (``_recover``).
 
         Results have the layout of ``process_image``; their arrays are views into the page-locked result buffers of the
         call (copy them if they must outlive a long-running server's memory budget).  ``PositionResult.squares`` carries the
@@ -528,270 +509,15 @@ class ChessVision:
         ``v > 0.5`` mask travel back behind the logits, and the host finishes the scores after the job's classifier has been queued.
         "logits" scores the raw logits (the reference's letter), "sigmoid" their sigmoid (what the column names promise).
         ``quad_score`` is that of the quadrangle found in the mask, in mask pixels; a fallback quadrangle scores 0 like none."""
-        started = time.time()
-        for image in images:
-            assert isinstance(image, np.ndarray) and image.dtype == np.uint8 and image.ndim == 3
-        if not images:
-            return []
-        _ = self.board_extractor, self.classifier
-        if (torch.cuda.current_stream(self.device) == torch.cuda.default_stream(self.device)
-                and os.environ.get("CHESSVISION_PIPE_OWN_STREAM", "1") != "0"):
-            # A caller that chose no stream gets the instance's own compute stream, not the NULL stream: kernels queued on the legacy
-            # stream from one thread while other threads load models / run request slots was one of the two ingredients of the device
-            # faults of the round-6 soak (profiles/r06_tuning.md section 8).  Everything the call returns has been waited for through
-            # events when it ends, so nothing is left to order against the caller's stream.
-            with torch.cuda.stream(self._pipeline_streams()[2]):
-                return self._process_images_native(images, threshold, flip, fallback_quad, pipeline_chunk, return_crops, timings,
-                                                   first_job, last_job, quality)
-        from concurrent.futures import ThreadPoolExecutor
+        if quality not in (None, "logits", "sigmoid"):
+            raise ValueError(f"quality must be None, 'logits' or 'sigmoid', got {quality!r}")
+        return self._recover(lambda cv: cv._process_images_native(images, threshold, flip, fallback_quad, pipeline_chunk, return_crops,
+                                                                  timings, first_job, last_job, quality))
 
-        from .distributed import host_threads
-        from .hip_backend import (SCORE_RECORD, board_homographies, decode_positions, find_quadrangles, mask_completenesses,
-                                  quadrangle_regularity, scores_finish)
+    def _process_images_native(self, *args) -> list[ChessVisionResult]:
+        from . import batched
 
-        n_host = host_threads()
-
-        eng, eng_cls = self._get_engine("unet"), self._get_engine("resnet18")
-        dev = self.device
-        n = len(images)
-        names = constants.SQUARE_NAMES_FLIPPED if flip else constants.SQUARE_NAMES_NORMAL
-        w, h = constants.BOARD_SIZE
-        groups: dict[tuple, list[int]] = {}
-        for i, im in enumerate(images):
-            groups.setdefault(im.shape, []).append(i)
-        step = max(1, int(pipeline_chunk))
-        jobs = [ids[k:k + step] for ids in groups.values() for k in range(0, len(ids), step)]
-        # Pipeline fill and drain are the only parts of a call the GPU does not overlap: nothing hides the staging + upload of the
-        # FIRST job, and after the last UNet the host still finds the LAST job's quadrangles before its classifier can start.  Both
-        # ends are therefore cut short (16 boards each by default; measured on MI355X, r03: 3578 -> 3658 boards/s for the short first
-        # job at 256 boards, although the UNet runs ~5 % slower on part-chunks); 0 switches a split off.
-        first = int(os.environ.get("CHESSVISION_PIPE_FIRST_JOB", "16")) if first_job is None else int(first_job)
-        last = int(os.environ.get("CHESSVISION_PIPE_LAST_JOB", "0")) if last_job is None else int(last_job)
-        if len(jobs) > 1 and 0 < first < len(jobs[0]):
-            jobs = [jobs[0][:first], jobs[0][first:]] + jobs[1:]
-        if len(jobs) > 2 and 0 < last and len(jobs[-1]) >= 2 * last:
-            jobs = jobs[:-1] + [jobs[-1][:-last], jobs[-1][-last:]]
-        tm = timings if timings is not None else {}
-        for key in ("stage_s", "wait_masks_s", "contours_s", "homography_s", "wait_probs_s", "decode_s", "assemble_s"):
-            tm.setdefault(key, 0.0)
-        if quality:
-            tm.setdefault("quality", 0.0)                    # host seconds of the score stage (its kernel: quality_ms)
-        gpu_events: list[tuple[str, torch.cuda.Event, torch.cuda.Event]] = []
-
-        def clock(key, t0):
-            tm[key] += time.perf_counter() - t0
-
-        def gpu_timed(name, fn):
-            if timings is None:
-                return fn()
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record()
-            out = fn()
-            b.record()
-            gpu_events.append((name, a, b))
-            return out
-
-        def pinned(shape, dtype):
-            return torch.empty(shape, dtype=dtype, pin_memory=True)
-
-        main = torch.cuda.current_stream(dev)
-        up, down = self._pipeline_streams()[:2]
-        pool = self._copy_pool
-        if pool is None:
-            pool = self._copy_pool = ThreadPoolExecutor(max_workers=min(16, n_host), thread_name_prefix="cv-stage")
-
-        def upload(ids, slice_upload=False, gate=None):      # host -> pinned staging -> device, on the upload stream
-            """``gate``: an event of the compute stream the copy must not start before.  Jobs are uploaded TWO ahead, gated on the
-            end of the previous job's UNet, so that the 50 MB copy runs beside the (short, HBM-light) warp + classifier phase instead
-            of beside a UNet, whose launches it slows by 4-7 % (r03_tuning.md step 17, r04_tuning.md)."""
-            t0 = time.perf_counter()
-            shape = images[ids[0]].shape
-            staged = pinned((len(ids),) + shape, torch.uint8)
-            view = staged.numpy()
-            with torch.cuda.stream(up):
-                batch = torch.empty((len(ids),) + shape, dtype=torch.uint8, device=dev)
-                if gate is not None:
-                    up.wait_event(gate)
-            # the first job of a call is staged and uploaded in slices of 16 images (the upload of a slice overlaps the host copies
-            # of the next one: nothing else hides that job's staging); later jobs are staged in one go behind the GPU's work
-            step_ = 16 if slice_upload else len(ids)
-
-            def copy_group(lo, hi):                          # one task per group of images: few Python-level dispatches, the
-                for k in range(lo, hi):                      # memcpys themselves run without the GIL
-                    np.copyto(view[k], images[ids[k]])
-
-            for k0 in range(0, len(ids), step_):
-                k1 = min(len(ids), k0 + step_)
-                per = max(1, -(-(k1 - k0) // 16))
-                list(pool.map(lambda lo: copy_group(lo, min(k1, lo + per)), range(k0, k1, per)))
-                with torch.cuda.stream(up):
-                    batch[k0:k1].copy_(staged[k0:k1], non_blocking=True)
-            clock("stage_s", t0)
-            with torch.cuda.stream(up):
-                arrived = torch.cuda.Event()
-                arrived.record()
-            return {"ids": ids, "batch": batch, "staged": staged, "arrived": arrived}
-
-        def compute(u):                                      # resize, UNet on the compute stream; masks start back
-            ids, batch = u["ids"], u["batch"]
-            main.wait_event(u["arrived"])
-            batch.record_stream(main)
-            tm.setdefault("first_enqueue_s", time.time() - started)      # host time until the first kernel of the call is queued
-            small = gpu_timed("resize_ms", lambda: eng.resize_area_u8(batch, (constants.INPUT_SIZE[1], constants.INPUT_SIZE[0])))
-            lg, mk = gpu_timed("unet_ms", lambda: eng.unet_forward_u8(small, threshold=threshold, want_mask=True))
-            scored = None
-            if quality:                                      # the score reductions, on the logits where the UNet left them
-                scored = gpu_timed("quality_ms", lambda: eng.extraction_scores_dev(lg, "none" if quality == "logits" else "sigmoid",
-                                                                                   want_mask=True))
-            done = torch.cuda.Event()
-            done.record()
-            st = {"ids": ids, "batch": batch, "logits": pinned((len(ids), 256, 256), torch.float32), "unet_done": done,
-                  "masks": pinned((len(ids), 256, 256), torch.uint8), "ev": torch.cuda.Event(), "keep": (lg, mk, u["staged"], scored)}
-            with torch.cuda.stream(down):
-                down.wait_event(done)
-                st["masks"].copy_(mk, non_blocking=True)     # masks first: the contour stage waits for them only
-                st["ev"].record()
-                st["logits"].copy_(lg[:, 0], non_blocking=True)
-                if scored is not None:
-                    st["records"] = pinned((len(ids), 64), torch.uint8)
-                    st["half"] = pinned((len(ids), 256, 256), torch.uint8)
-                    st["records"].copy_(scored[0], non_blocking=True)
-                    st["half"].copy_(scored[1].view(len(ids), 256, 256), non_blocking=True)
-                st["ev_logits"] = torch.cuda.Event()
-                st["ev_logits"].record()
-            return st
-
-        def classify(st):                                   # masks -> quadrangles (host) -> warp + split + classifier (device)
-            t0 = time.perf_counter()
-            st["ev"].synchronize()
-            clock("wait_masks_s", t0)
-            ids = st["ids"]
-            t0 = time.perf_counter()
-            found_quads = find_quadrangles(st["masks"].numpy(), n_threads=n_host)
-            clock("contours_s", t0)
-            t0 = time.perf_counter()
-            quads = []
-            for k, q in enumerate(found_quads):
-                if q is None and fallback_quad:
-                    q = np.array([[[255, 0]], [[0, 0]], [[0, 255]], [[255, 255]]], dtype=np.int32)   # TR, TL, BL, BR
-                shape = images[ids[k]].shape
-                quads.append(None if q is None else self._scale_quadrangle(q, (shape[0], shape[1])))
-            st["quads"] = quads
-            found = [k for k in range(len(ids)) if quads[k] is not None]
-            st["found"] = found
-            if found:
-                inv = board_homographies(np.stack([quads[k].reshape(4, 2) for k in found]), constants.BOARD_SIZE)
-                clock("homography_s", t0)
-                src = st["batch"] if len(found) == len(ids) else st["batch"][torch.as_tensor(found, device=dev)]
-                squares_dev, boards_dev = gpu_timed("warp_ms", lambda: eng.extract_squares_u8(src, inv))
-                warped = torch.cuda.Event()
-                warped.record()
-                st["boards"] = pinned((len(found), h, w), torch.uint8)
-                with torch.cuda.stream(down):                # the rectified boards travel back while the classifier runs
-                    down.wait_event(warped)
-                    st["boards"].copy_(boards_dev, non_blocking=True)
-                probs_dev = gpu_timed("resnet_ms", lambda: eng_cls.resnet18_forward_u8(squares_dev))
-                done = torch.cuda.Event()
-                done.record()
-                st["probs"] = pinned((len(found) * 64, constants.NUM_CLASSES), torch.float32)
-                st["keep2"] = (probs_dev, boards_dev, squares_dev)
-                with torch.cuda.stream(down):
-                    down.wait_event(done)
-                    st["probs"].copy_(probs_dev, non_blocking=True)
-                    st["ev2"] = torch.cuda.Event()
-                    st["ev2"].record()
-            else:
-                clock("homography_s", t0)
-            st["batch"] = None
-            if quality:                                      # the device has this job's classifier queued: finish its scores meanwhile
-                t0 = time.perf_counter()
-                st["ev_logits"].synchronize()
-                conf, dist = scores_finish(st["records"].numpy().view(SCORE_RECORD).reshape(-1))
-                comp = mask_completenesses(st["half"].numpy(), n_threads=n_host)
-                for k, i in enumerate(ids):
-                    quality_of[i] = ExtractionQuality(confidence=float(conf[k]), quad_score=quadrangle_regularity(found_quads[k]),
-                                                      completeness=float(comp[k]), distribution=float(dist[k]))
-                clock("quality", t0)
-            return st
-
-        logits_of: dict[int, NDArray[np.float32]] = {}
-        masks_of: dict[int, NDArray[np.uint8]] = {}
-        quads_of: dict[int, NDArray[np.float32] | None] = {}
-        boards: dict[int, NDArray[np.uint8]] = {}
-        positions: dict[int, PositionResult] = {}
-        quality_of: dict[int, ExtractionQuality] = {}
-
-        def finish(st):                                     # probabilities -> labels, FEN, pawn rule (one native call per job)
-            ids = st["ids"]
-            t0 = time.perf_counter()
-            st["ev_logits"].synchronize()
-            lg, mk = st["logits"].numpy(), st["masks"].numpy()
-            for k, i in enumerate(ids):
-                logits_of[i], masks_of[i], quads_of[i] = lg[k], mk[k], st["quads"][k]
-            if st["found"]:
-                st["ev2"].synchronize()
-                clock("wait_probs_s", t0)
-                t0 = time.perf_counter()
-                m = len(st["found"])
-                probs = st["probs"].numpy().reshape(m, 64, constants.NUM_CLASSES)
-                brd = st["boards"].numpy()
-                fens, origs, _, fixes = decode_positions(probs, flip)
-                fix_lists: list[list[ValidationFix]] = [[] for _ in range(m)]
-                for b, sq, old, new in fixes:
-                    fix_lists[b].append(ValidationFix(square_name=names[sq], original_piece=constants.LABEL_NAMES[old],
-                                                      corrected_piece=constants.LABEL_NAMES[new], rule_name="no_pawns_on_ends"))
-                for j, k in enumerate(st["found"]):
-                    boards[ids[k]] = brd[j]
-                    crops = self.extract_squares(brd[j]) if return_crops else None
-                    positions[ids[k]] = PositionResult(fen=fens[j], original_fen=origs[j], model_probabilities=probs[j],
-                                                       squares=crops, square_names=names, validation_fixes=fix_lists[j])
-                clock("decode_s", t0)
-            else:
-                clock("wait_probs_s", t0)
-            st["keep"] = st["keep2"] = None
-
-        # software pipeline over the jobs: the UNet of job k+1 is enqueued before the host works on job k, and the upload of job k+2
-        # is issued behind the end of that UNet (CHESSVISION_PIPE_PREFETCH=1 restores round 3's schedule: upload k+1 beside UNet k)
-        prefetch = int(os.environ.get("CHESSVISION_PIPE_PREFETCH", "2"))
-        ups = {0: upload(jobs[0], slice_upload=True)}
-        seg = compute(ups.pop(0))                            # the first kernels are queued before anything else is staged
-        if prefetch >= 2 and len(jobs) > 1:
-            ups[1] = upload(jobs[1])                         # nothing to hide behind yet: beside the (short) first job's UNet
-        cls = None
-        for k in range(len(jobs)):
-            nxt = None
-            if k + 1 < len(jobs):
-                if k + 1 not in ups:
-                    ups[k + 1] = upload(jobs[k + 1])
-                nxt = compute(ups.pop(k + 1))
-                if prefetch >= 2 and k + 2 < len(jobs):
-                    ups[k + 2] = upload(jobs[k + 2], gate=nxt["unet_done"])
-            cur = classify(seg)
-            if cls is not None:
-                finish(cls)
-            cls, seg = cur, nxt
-        t_last = time.perf_counter()
-        finish(cls)
-        eng.check_numerics()                               # one look at the numeric guard for the whole call
-        if eng_cls is not eng:
-            eng_cls.check_numerics()
-        tm["drain_s"] = time.perf_counter() - t_last       # last job: wait for its classifier, copies back, decode
-
-        t0 = time.perf_counter()
-        per_image = (time.time() - started) / n
-        results = []
-        for i in range(n):
-            extraction = BoardExtractionResult(board_image=boards.get(i), binary_mask=masks_of[i], quadrangle=quads_of[i],
-                                               probabilities=logits_of[i])
-            results.append(ChessVisionResult(board_extraction=extraction, position=positions.get(i),
-                                             processing_time=per_image, quality=quality_of.get(i)))
-        clock("assemble_s", t0)
-        if timings is not None:
-            for name, a, b in gpu_events:
-                tm[name] = tm.get(name, 0.0) + a.elapsed_time(b)
-            tm["jobs"] = len(jobs)
-            tm["total_s"] = time.time() - started
-        return results
+        return batched.process_images(self, *args)
 
     def _pipeline_streams(self):
         """(host->device, device->host, compute) streams of ``process_images``, created once per instance."""

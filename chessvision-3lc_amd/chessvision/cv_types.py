@@ -11,6 +11,8 @@ from dataclasses import dataclass, field
 import numpy as np
 from numpy.typing import NDArray
 
+from . import constants
+
 U8 = NDArray[np.uint8]
 F32 = NDArray[np.float32]
 
@@ -25,6 +27,12 @@ class ValidationFix:
     original_piece: str = _doc("symbol the classifier chose")
     corrected_piece: str = _doc("symbol after the rule fired")
     rule_name: str = _doc('rule identifier, e.g. "no_pawns_on_ends"')
+
+
+def pawn_rule_fix(square_names: list[str], square: int, old: int, new: int) -> ValidationFix:
+    """One correction of the pawn rule as the native decoders report it: square index, class index before and after."""
+    return ValidationFix(square_name=square_names[square], original_piece=constants.LABEL_NAMES[old],
+                         corrected_piece=constants.LABEL_NAMES[new], rule_name="no_pawns_on_ends")
 
 
 @dataclass

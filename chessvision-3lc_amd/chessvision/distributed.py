@@ -460,7 +460,7 @@ def process_images_sharded(cv, images: Sequence, threshold: float = 0.5, flip: b
     import time
 
     from . import constants
-    from .cv_types import BoardExtractionResult, ChessVisionResult, PositionResult, ValidationFix
+    from .cv_types import BoardExtractionResult, ChessVisionResult, PositionResult, pawn_rule_fix
     from .hip_backend import decode_positions
 
     rank = dist.get_rank() if dist.is_initialized() else 0
@@ -508,8 +508,7 @@ def process_images_sharded(cv, images: Sequence, threshold: float = 0.5, flip: b
         fens, origs, _, fixes = decode_positions(np.ascontiguousarray(g_probs[cls]), flip)
         fix_lists = [[] for _ in cls]
         for b, sq, old, new in fixes:
-            fix_lists[b].append(ValidationFix(square_name=names[sq], original_piece=constants.LABEL_NAMES[old],
-                                              corrected_piece=constants.LABEL_NAMES[new], rule_name="no_pawns_on_ends"))
+            fix_lists[b].append(pawn_rule_fix(names, sq, old, new))
     where = {i: j for j, i in enumerate(cls)}
     for i in remote:
         quad = g_quads[i, :8].reshape(4, 1, 2).copy() if g_quads[i, 8] > 0 else None

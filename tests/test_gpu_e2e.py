@@ -106,6 +106,34 @@ def test_process_images_matches_the_oracle_pipeline(cv_model):
     assert stats["mask_flips_inside_tolerance"] <= 2, stats
 
 
+def test_two_shapes_through_six_jobs_match_the_oracle_image_by_image(cv_model):
+    """Eleven photos of two shapes, interleaved, in jobs of at most 3 with both ends cut to 1: six jobs -- [0] [2,4] [6,8,9] [1,3,5] [7]
+    [10] (tests/test_batched_pipeline_cpu.py) -- so results are scattered back over the caller's order from a split first job, full
+    jobs of either shape and a split last job.  Result i must be image i's; the quality scores change nothing else."""
+    unet, resnet = _oracle_models()
+    images = [synthetic.board_photo(900 + s) for s in range(11)]
+    for k in (1, 3, 5, 7, 10):
+        images[k] = images[k][:384]                         # (384,512,3): the board is cut, most of these take the fallback quadrangle
+    kw = dict(pipeline_chunk=3, first_job=1, last_job=1, fallback_quad=True)
+    timings = {}
+    got = cv_model.process_images(images, timings=timings, **kw)
+    assert timings["jobs"] == 6 and len(got) == 11
+    ref = pipeline_ref.process_images(unet, resnet, images, fallback_quad=True)
+    stats = {"mask_flips_inside_tolerance": 0, "max_prob_err": 0.0, "fen_checked": 0}
+    for g, r, im in zip(got, ref, images):
+        _compare(g, r, stats, resnet, im)
+    assert all(g.position is not None and g.quality is None for g in got)
+    scored = cv_model.process_images(images, quality="sigmoid", **kw)
+    for g, s in zip(got, scored):
+        assert s.quality is not None
+        ge, se = g.board_extraction, s.board_extraction
+        for a, b in ((ge.probabilities, se.probabilities), (ge.binary_mask, se.binary_mask), (ge.quadrangle, se.quadrangle),
+                     (ge.board_image, se.board_image), (g.position.model_probabilities, s.position.model_probabilities)):
+            assert np.array_equal(a, b)
+        assert (g.position.fen, g.position.original_fen, g.position.validation_fixes) == \
+               (s.position.fen, s.position.original_fen, s.position.validation_fixes)
+
+
 def test_flip_and_threshold_variants_match_the_oracle(cv_model):
     unet, resnet = _oracle_models()
     images = _images(6, seed0=50)
