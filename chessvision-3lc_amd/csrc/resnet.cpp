@@ -307,8 +307,12 @@ static Status resnet_reserve(Engine& e, int n) {
     R.cap = want;
     const int S = want;
     R.taps.clear();
+    // f16r: a trunk tensor (pool output, block outputs) IS its unrounded f32 twin -- what the residual adds and the head read; the f16
+    // copy beside it is that tensor rounded once for the next convolution.  The taps report the twin: a tap of the copy is 2^-12 off
+    // the head's input, more than the head kernel's own error
+    auto trunk = [&](const Activation& a) { return a.want32 ? a.ref32(S) : a.ref(S); };
     if (e.dt == kF32) R.taps["act1"] = R.stem_out.ref(S);
-    R.taps["maxpool"] = R.pool_out.ref(S);
+    R.taps["maxpool"] = trunk(R.pool_out);
     for (int l = 0; l < 4; ++l) {
         for (int bi = 0; bi < R.arch->depth[l]; ++bi) {
             Engine::ResNet::Block& B = R.blocks[R.first[l] + bi];
@@ -319,10 +323,10 @@ static Status resnet_reserve(Engine& e, int n) {
             if (!chained) R.taps[p + ".act1"] = B.mid.ref(S);
             if (chained && bi < R.chain_nb - 1) {            // an inner chained block's output: its f32 twin (form 2) or nowhere outside the kernel (form 1)
                 if (chain_form() == 2) R.taps[p] = B.out.ref32(S);
-            } else R.taps[p] = B.out.ref(S);
+            } else R.taps[p] = trunk(B.out);
             if (B.has_down) R.taps[p + ".downsample"] = B.sc.only32 ? B.sc.ref32(S) : B.sc.ref(S);
         }
-        R.taps["layer" + std::to_string(l + 1)] = R.blocks[R.first[l + 1] - 1].out.ref(S);
+        R.taps["layer" + std::to_string(l + 1)] = trunk(R.blocks[R.first[l + 1] - 1].out);
     }
     return Status();
 }

@@ -194,6 +194,8 @@ int cv_softmax13(cv_engine_t* eng, const float* logits, int n, float* probs, voi
  * Tensors a fused launch never writes have no tap: under CV_PREC_F16R the ResNet's layer1 runs as ONE chained launch, so
  * "layer1.B.act1" of the chained blocks do not exist and the inner blocks' outputs ("layer1.0", and "layer1.1" for resnet34) are read
  * from their f32 twins (CV_ERR_INVALID naming CV_RESNET_CHAIN=0, the switch that runs layer1 layer by layer and materialises them);
+ * every other trunk tensor of that engine ("maxpool", the block outputs, "layerN") is likewise reported from its f32 twin, the tensor
+ * the residual adds and the head read -- the f16 copy beside it is the twin rounded once for the next convolution;
  * `model` is "unet" or the loaded ResNet's architecture name ("resnet18" | "resnet34"); the UNet's fused first two convolutions
  * (CV_FUSE_INC=0 to split them) likewise leave "inc.double_conv.2" unwritten at the throughput sizes. */
 int cv_get_activation(cv_engine_t* eng, const char* model, const char* name, float* out_host,
