@@ -25,8 +25,8 @@ import torch
 from . import constants
 from .cv_types import BoardExtractionResult, ChessVisionResult, ExtractionQuality, PositionResult, pawn_rule_fix
 from .distributed import host_threads
-from .hip_backend import (SCORE_RECORD, board_homographies, decode_positions, find_quadrangles, mask_completenesses,
-                          quadrangle_regularity, scores_finish)
+from .hip_backend import (SCORE_RECORD, SEG_RECORD, board_homographies, classification_scores, decode_positions, find_quadrangles,
+                          mask_completenesses, quadrangle_regularity, scores_finish, segmentation_scores_finish)
 
 _HOST_STAGES = ("stage_s", "wait_masks_s", "contours_s", "homography_s", "wait_probs_s", "decode_s", "assemble_s")
 
@@ -60,19 +60,23 @@ class Job:
     the allocating stream only, may hand its memory to a later job while the copy still reads it.  ``unet_out`` (read by the
     download stream up to ``logits_ready``) and ``cls_out`` (up to ``probs_ready``) exist for nothing else; ``release`` drops them
     once ``finish`` has synchronised both events.  ``batch`` is written by the upload stream and read by the compute stream: it is
-    handed over with ``record_stream`` and dropped as soon as its last kernel (the warp) is queued."""
+    handed over with ``record_stream`` and dropped as soon as its last kernel (the warp) is queued; ``labels`` (the label masks of
+    an evaluation call) likewise, dropped behind the segmentation-score kernel."""
     ids: list[int]
     # upload
     staged: torch.Tensor | None = None          # pinned source of the upload
     batch: torch.Tensor | None = None           # the photos on the device
-    arrived: torch.cuda.Event | None = None     # upload stream: the batch is there
+    label_staged: torch.Tensor | None = None    # pinned (n,256,256) u8 label masks (zero for an image without one), evaluation only
+    labels: torch.Tensor | None = None          # the label masks on the device
+    arrived: torch.cuda.Event | None = None     # upload stream: the batch (and the label masks) are there
     # compute
     unet_done: torch.cuda.Event | None = None   # compute stream: UNet (and scores) queued up to here; gates the upload two jobs on
-    unet_out: tuple | None = None               # device: logits, masks, score records -- held for the download stream
+    unet_out: tuple | None = None               # device: logits, masks, score records, segmentation records -- held for the download stream
     masks: torch.Tensor | None = None           # pinned (n,256,256) u8
     logits: torch.Tensor | None = None          # pinned (n,256,256) f32
     records: torch.Tensor | None = None         # pinned (n,64) u8 score records, ``quality`` only
     half: torch.Tensor | None = None            # pinned (n,256,256) u8 ``v > 0.5`` masks, ``quality`` only
+    seg_records: torch.Tensor | None = None     # pinned (n,64) u8 segmentation-score records, evaluation only
     masks_ready: torch.cuda.Event | None = None     # download stream: masks have landed
     logits_ready: torch.cuda.Event | None = None    # download stream: logits (and records, half) have landed
     # classify
@@ -85,7 +89,7 @@ class Job:
     probs_ready: torch.cuda.Event | None = None     # download stream: boards and probabilities have landed
 
     def release(self) -> None:
-        self.batch = self.unet_out = self.cls_out = None
+        self.batch = self.labels = self.unet_out = self.cls_out = None
 
 
 @dataclass(slots=True)
@@ -106,8 +110,9 @@ def _pinned(shape, dtype):
 class _Call:
     """The state one ``process_images`` call shares between its stages.  The compute stream is the CURRENT stream."""
 
-    def __init__(self, cv, images, threshold, flip, fallback_quad, return_crops, timings, quality, started):
+    def __init__(self, cv, images, threshold, flip, fallback_quad, return_crops, timings, quality, started, targets=None):
         self.cv, self.images, self.started = cv, images, started
+        self.targets = targets                           # evaluation.Targets of an evaluate_images call, else None
         self.threshold, self.flip, self.fallback_quad, self.return_crops, self.quality = threshold, flip, fallback_quad, return_crops, quality
         self.eng, self.eng_cls, self.dev = cv._get_engine("unet"), cv._get_engine("resnet18"), cv.device
         self.names = constants.SQUARE_NAMES_FLIPPED if flip else constants.SQUARE_NAMES_NORMAL
@@ -123,6 +128,8 @@ class _Call:
             self.tm.setdefault(key, 0.0)
         if quality:
             self.tm.setdefault("quality", 0.0)           # host seconds of the score stage (its kernel: quality_ms)
+        if targets is not None:
+            self.tm.setdefault("evaluation", 0.0)        # host seconds of the ground-truth scores (the kernel: seg_ms)
         self.gpu_events: list[tuple[str, torch.cuda.Event, torch.cuda.Event]] = []
         self.slots: list[_ImageSlot | None] = [None] * len(images)
 
@@ -168,6 +175,18 @@ class _Call:
             list(self.pool.map(lambda lo: copy_group(lo, min(k1, lo + per)), range(k0, k1, per)))
             with torch.cuda.stream(up):
                 job.batch[k0:k1].copy_(job.staged[k0:k1], non_blocking=True)
+        label_masks = [self.targets.masks[i] for i in ids] if self.targets is not None else []
+        if any(m is not None for m in label_masks):      # 64 KB per image beside its photo; an image without a mask gets zeros
+            job.label_staged = _pinned((len(ids), 256, 256), torch.uint8)
+            lview = job.label_staged.numpy()
+            for k, m in enumerate(label_masks):
+                if m is None:
+                    lview[k] = 0
+                else:
+                    np.copyto(lview[k], m)
+            with torch.cuda.stream(up):
+                job.labels = torch.empty((len(ids), 256, 256), dtype=torch.uint8, device=self.dev)
+                job.labels.copy_(job.label_staged, non_blocking=True)
         self.clock("stage_s", t0)
         with torch.cuda.stream(up):
             job.arrived = torch.cuda.Event()
@@ -186,9 +205,14 @@ class _Call:
         if self.quality:
             scored = self.gpu_timed("quality_ms", eng.extraction_scores_dev, lg, "none" if self.quality == "logits" else "sigmoid",
                                     want_mask=True)
+        seg = None
+        if job.labels is not None:                       # the ground-truth reductions, on the logits where the UNet left them
+            job.labels.record_stream(self.main)
+            seg = self.gpu_timed("seg_ms", eng.segmentation_scores_dev, lg, job.labels, self.threshold)
+            job.labels = None
         job.unet_done = torch.cuda.Event()
         job.unet_done.record()
-        job.unet_out = (lg, mk, scored)
+        job.unet_out = (lg, mk, scored, seg)
         job.logits, job.masks = _pinned((n, 256, 256), torch.float32), _pinned((n, 256, 256), torch.uint8)
         job.masks_ready, job.logits_ready = torch.cuda.Event(), torch.cuda.Event()
         with torch.cuda.stream(down):
@@ -200,6 +224,9 @@ class _Call:
                 job.records, job.half = _pinned((n, 64), torch.uint8), _pinned((n, 256, 256), torch.uint8)
                 job.records.copy_(scored[0], non_blocking=True)
                 job.half.copy_(scored[1].view(n, 256, 256), non_blocking=True)
+            if seg is not None:
+                job.seg_records = _pinned((n, 64), torch.uint8)
+                job.seg_records.copy_(seg, non_blocking=True)
             job.logits_ready.record()
 
     def classify(self, job: Job) -> None:
@@ -250,6 +277,16 @@ class _Call:
             job.quality = [ExtractionQuality(confidence=float(conf[k]), quad_score=quadrangle_regularity(found_quads[k]),
                                              completeness=float(comp[k]), distribution=float(dist[k])) for k in range(len(ids))]
             self.clock("quality", t0)
+        if job.seg_records is not None:                  # the same host gap: finish the segmentation scores
+            from .evaluation import SegmentationScores
+
+            t0 = time.perf_counter()
+            job.logits_ready.synchronize()
+            fin = segmentation_scores_finish(job.seg_records.numpy().view(SEG_RECORD).reshape(-1))
+            for k, i in enumerate(ids):
+                if self.targets.masks[i] is not None:
+                    self.targets.segmentation[i] = SegmentationScores(**{name: float(col[k]) for name, col in fin.items()})
+            self.clock("evaluation", t0)
 
     def finish(self, job: Job) -> None:
         """probabilities -> labels, FEN, pawn rule (one native call per job); the job's arrays go to its images' slots."""
@@ -268,7 +305,7 @@ class _Call:
         m = len(job.found)
         probs = job.probs.numpy().reshape(m, 64, constants.NUM_CLASSES)
         brd = job.boards.numpy()
-        fens, origs, _, fixes = decode_positions(probs, self.flip)
+        fens, origs, validated, fixes = decode_positions(probs, self.flip)
         fix_lists: list[list] = [[] for _ in range(m)]
         for b, sq, old, new in fixes:
             fix_lists[b].append(pawn_rule_fix(names, sq, old, new))
@@ -279,6 +316,34 @@ class _Call:
             slot.position = PositionResult(fen=fens[j], original_fen=origs[j], model_probabilities=probs[j], squares=crops,
                                            square_names=names, validation_fixes=fix_lists[j])
         self.clock("decode_s", t0)
+        if self.targets is not None:
+            t0 = time.perf_counter()
+            self.score_positions(job, probs, validated, fix_lists)
+            self.clock("evaluation", t0)
+
+    def score_positions(self, job: Job, probs, validated, fix_lists) -> None:
+        """The job's probabilities against the true placements (one native call): row i of a board is compared with the true piece
+        on ``square_names[i]``."""
+        from .evaluation import PositionScores, row_labels
+
+        true = self.targets.labels
+        sel = [j for j, k in enumerate(job.found) if true[job.ids[k]] is not None]
+        if not sel:
+            return
+        rows = np.stack([row_labels(true[job.ids[job.found[j]]], self.flip) for j in sel])
+        per_square, per_board = classification_scores(probs[sel], rows)
+        # once per job: the columns as arrays of their own (the records below hold rows of them), the accuracies as lists
+        predicted, valid = per_square["predicted"].astype(np.int8), validated[sel]
+        rank, conf, loss = (np.ascontiguousarray(per_square[name]) for name in ("rank", "confidence", "loss"))
+        top = (per_board["hits"][:, :3] / 64).tolist()
+        acc_o = (np.count_nonzero(predicted == rows, axis=1) / 64).tolist()
+        acc_v = (np.count_nonzero(valid == rows, axis=1) / 64).tolist()
+        mean_loss = per_board["mean_loss"].tolist()
+        for m, j in enumerate(sel):
+            self.targets.position[job.ids[job.found[j]]] = PositionScores(
+                top_k=tuple(top[m]), accuracy_original=acc_o[m], accuracy_validated=acc_v[m], mean_loss=mean_loss[m],
+                num_fixes=len(fix_lists[j]), true_labels=rows[m], predicted_labels=predicted[m], validated_labels=valid[m],
+                rank=rank[m], confidence=conf[m], loss=loss[m])
 
     # ---- the software pipeline --------------------------------------------------------------------------------------------------
     def issue(self, jobs: list[list[int]]) -> float:
@@ -321,8 +386,9 @@ class _Call:
 
 
 def process_images(cv, images, threshold, flip, fallback_quad, pipeline_chunk, return_crops, timings, first_job, last_job,
-                   quality) -> list[ChessVisionResult]:
-    """``ChessVision.process_images`` on the instance's native engines (arguments: see there)."""
+                   quality, targets=None) -> list[ChessVisionResult]:
+    """``ChessVision.process_images`` on the instance's native engines (arguments: see there).  ``targets`` (``evaluation.Targets``,
+    from ``ChessVision.evaluate_images``) additionally scores every job against its ground truth and leaves the records there."""
     started = time.time()
     for image in images:
         assert isinstance(image, np.ndarray) and image.dtype == np.uint8 and image.ndim == 3
@@ -336,7 +402,7 @@ def process_images(cv, images, threshold, flip, fallback_quad, pipeline_chunk, r
     # ends, so nothing is left to order against the caller's stream.
     own = torch.cuda.current_stream(cv.device) == torch.cuda.default_stream(cv.device)
     with torch.cuda.stream(cv._pipeline_streams()[2]) if own else contextlib.nullcontext():
-        call = _Call(cv, images, threshold, flip, fallback_quad, return_crops, timings, quality, started)
+        call = _Call(cv, images, threshold, flip, fallback_quad, return_crops, timings, quality, started, targets)
         t_last = call.issue(jobs)
         call.eng.check_numerics()                        # one look at the numeric guard for the whole call
         if call.eng_cls is not call.eng:

@@ -519,6 +519,31 @@ class ChessVision:
 
         return batched.process_images(self, *args)
 
+    def evaluate_images(self, images: Sequence[NDArray[np.uint8]], true_fens: Sequence[str | None] | None = None,
+                        label_masks: Sequence[NDArray[np.uint8] | None] | None = None, threshold: float = 0.5, flip: bool = False,
+                        fallback_quad: bool = False, pipeline_chunk: int = 64, timings: dict | None = None):
+        """``process_images`` plus the scores of every image against its ground truth (``chessvision/evaluation.py``): one call for
+        the loop of the reference's ``scripts/eval/evaluate.py:264-360`` and for the per-image ``loss`` / ``val_dice`` of its UNet
+        training side.  Returns an ``EvaluationReport``: ``results`` (exactly what ``process_images`` returns for these arguments),
+        one ``ImageEvaluation`` per image and the ``aggregate`` record.
+
+        ``true_fens`` / ``label_masks``: one entry per image, ``None`` for an unlabelled one; at least one of the two is required.
+        A FEN's piece-placement field is compared square by square (row i of the probabilities with the true piece on
+        ``square_names[i]``, so ``flip`` is followed); a label mask is a (256,256) uint8 array, "board" where non-zero.  A wrong
+        length, shape or dtype, or a malformed FEN, raises ``ValueError`` naming the image before anything is queued.
+
+        Per job the label masks travel to the device beside the photos, ONE more kernel runs right behind the UNet on the logits
+        where they are (``HipEngine.segmentation_scores_dev``), its 64-byte records come back behind the logits, and the job's
+        probabilities are scored by one native call right after its FENs are decoded.  An image with a FEN but no board found counts
+        as an extraction failure, not as a zero-accuracy board."""
+        from .evaluation import Targets
+
+        images = list(images)
+        targets = Targets(len(images), true_fens, label_masks)
+        results = self._recover(lambda cv: cv._process_images_native(images, threshold, flip, fallback_quad, pipeline_chunk, True,
+                                                                     timings, 16, 0, None, targets))
+        return targets.report(results)
+
     def _pipeline_streams(self):
         """(host->device, device->host, compute) streams of ``process_images``, created once per instance."""
         if self._streams is None:

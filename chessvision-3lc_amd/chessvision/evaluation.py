@@ -1,0 +1,293 @@
+"""Scores against ground truth: what the reference's evaluation side computes from the two networks' outputs and the labels.
+
+``scripts/eval/evaluate.py:264-360`` compares every ``process_image`` result with the true piece placement (square accuracy of
+``original_fen`` and ``fen``, top-1/2/3 accuracy of ``model_probabilities``, fixes, improvements, extraction failures) and averages
+them into its ``test_results`` record; ``scripts/train/unet_loss_collector.py:19-48`` writes a per-image ``loss`` = soft Dice loss +
+mean ``BCEWithLogitsLoss`` of the UNet's logits against the label mask; ``train_unet.py:333-338`` selects checkpoints by ``val_dice``.
+
+The functions below keep the reference's names and signatures and work on host arrays, without ``python-chess``: they are the
+readable forms and the test checkers.  ``ChessVision.evaluate_images`` does not come through them: there the per-pixel reductions
+run on the device, on the logits where the UNet left them (``HipEngine.segmentation_scores_dev``), and the per-square scores of a
+whole job come from one native call (``hip_backend.classification_scores``).
+
+Two readings are stated here because the reference leaves them open:
+
+* Dice.  The reference calls ``dice_loss(..., reduction="none")`` of a vendored Pytorch-UNet whose directory is empty in its tree.
+  Used here: upstream Pytorch-UNet's ``dice_coeff`` per image, ``(2 * inter + 1e-6) / (sets_sum + 1e-6)`` with ``sets_sum`` replaced
+  by ``2 * inter`` where it is 0.
+* Ties.  The reference ranks classes with ``np.argsort`` of the default kind, which numpy 2.2 does not keep stable for 13 float32
+  columns, so its order among EQUAL probabilities is undefined.  Used here: the stable order, rank of the true class t =
+  ``#{j: p_j > p_t} + #{j > t: p_j == p_t}``.  A square holding a NaN has rank 13: a miss at every k.
+"""
+from __future__ import annotations
+
+import math
+from collections.abc import Sequence
+from dataclasses import dataclass, field
+
+import numpy as np
+from numpy.typing import NDArray
+
+from . import constants
+from .cv_types import ChessVisionResult
+
+_EPS = 1e-6
+AGGREGATE_KEYS = ("top_1_accuracy_validated", "top_1_accuracy", "top_2_accuracy", "top_3_accuracy", "validation_fixes",
+                  "validation_improvements", "extraction_failures", "avg_time_per_prediction")
+
+
+# ---- the reference's host functions (evaluate.py:28-140) ---------------------------------------------------------------------------
+@dataclass
+class PositionAccuracy:
+    accuracy: float
+    num_correct: int
+    total_squares: int = 64
+
+
+@dataclass
+class TopKAccuracyResult:
+    k: int
+    accuracies: Sequence[float]
+
+    @property
+    def top_1(self) -> float:
+        return self.accuracies[0]
+
+    @property
+    def top_2(self) -> float:
+        return self.accuracies[1] if len(self.accuracies) > 1 else 0.0
+
+    @property
+    def top_3(self) -> float:
+        return self.accuracies[2] if len(self.accuracies) > 2 else 0.0
+
+
+def board_to_labels(fen: str) -> list[str]:
+    """Piece-placement field of a FEN (anything after the first space is ignored) -> 64 symbols in a8..h1 order, "f" for an empty
+    square.  ``ValueError`` for a malformed placement.  (The reference takes a ``chess.BaseBoard``; this form takes its FEN.)"""
+    ranks = str(fen).split(" ", 1)[0].split("/")
+    if len(ranks) != 8:
+        raise ValueError(f"malformed piece placement {fen!r}: {len(ranks)} ranks instead of 8")
+    labels: list[str] = []
+    for rank in ranks:
+        row: list[str] = []
+        for ch in rank:
+            if ch in "12345678":
+                row += ["f"] * int(ch)
+            elif ch != "f" and ch in constants.LABEL_INDICES:
+                row.append(ch)
+            else:
+                raise ValueError(f"malformed piece placement {fen!r}: unknown symbol {ch!r}")
+        if len(row) != 8:
+            raise ValueError(f"malformed piece placement {fen!r}: rank {rank!r} does not sum to 8 squares")
+        labels += row
+    return labels
+
+
+def label_indices(fen: str) -> NDArray[np.int8]:
+    """``board_to_labels`` as class indices (order of ``constants.LABEL_NAMES``): evaluate.py's ``get_validated_indices``."""
+    return np.array([constants.LABEL_INDICES[s] for s in board_to_labels(fen)], dtype=np.int8)
+
+
+def compute_position_accuracy(predicted_fen: str, true_fen: str) -> PositionAccuracy:
+    pred, true = board_to_labels(predicted_fen), board_to_labels(true_fen)
+    correct = sum(1 for p, t in zip(pred, true) if p == t)
+    return PositionAccuracy(accuracy=correct / 64, num_correct=correct)
+
+
+def true_class_ranks(model_probabilities: NDArray[np.float32], labels) -> NDArray[np.int32]:
+    """(64,13) probabilities, 64 true class indices given per row -> per row the number of classes ranked above the true one
+    (0 = the arg-max), ties in numpy's stable order; 13 for a row holding a NaN."""
+    p = np.asarray(model_probabilities, dtype=np.float32)
+    t = np.asarray(labels, dtype=np.int64)
+    pt = p[np.arange(p.shape[0]), t][:, None]
+    with np.errstate(invalid="ignore"):
+        rank = (p > pt).sum(axis=1) + ((p == pt) & (np.arange(p.shape[1])[None, :] > t[:, None])).sum(axis=1)
+    return np.where(np.isnan(p).any(axis=1), p.shape[1], rank).astype(np.int32)
+
+
+def compute_model_topk_accuracy(model_probabilities: NDArray[np.float32], true_fen: str, k: int = 3) -> TopKAccuracyResult:
+    """Fraction of squares whose true class is among the k most probable, for 1..k (evaluate.py:112-140).  Row i of the
+    probabilities is compared with square i of the FEN in a8..h1 order, as in the reference."""
+    rank = true_class_ranks(model_probabilities, label_indices(true_fen))
+    return TopKAccuracyResult(k=k, accuracies=[int((rank < j).sum()) / 64 for j in range(1, k + 1)])
+
+
+# ---- the records ---------------------------------------------------------------------------------------------------------------------
+@dataclass
+class SegmentationScores:
+    """One image's UNet output against its label mask."""
+    bce: float                 # mean over pixels of BCEWithLogitsLoss
+    dice_loss: float           # 1 - soft Dice of sigmoid(logits) and the mask
+    loss: float                # dice_loss + bce: the LossCollector's column
+    dice: float                # Dice of the thresholded mask and the label: the per-image val_dice (1 when both are empty)
+    iou: float                 # intersection over union of the two (1 when the union is empty)
+    pixel_accuracy: float
+
+
+@dataclass
+class PositionScores:
+    """One board's classifier output against its true placement.  The arrays have one entry per row of ``model_probabilities``
+    (``PositionResult.square_names`` order): the per-square columns of evaluate.py:327-343."""
+    top_k: tuple               # (top-1, top-2, top-3) accuracy of the raw probabilities
+    accuracy_original: float   # square accuracy of original_fen: the reference's top_1_accuracy
+    accuracy_validated: float  # square accuracy of fen: its top_1_accuracy_validated
+    mean_loss: float           # mean of -log(p_true)
+    num_fixes: int
+    true_labels: NDArray[np.int8]
+    predicted_labels: NDArray[np.int8]
+    validated_labels: NDArray[np.int8]
+    rank: NDArray[np.int32]
+    confidence: NDArray[np.float32]
+    loss: NDArray[np.float64]
+
+    @property
+    def top_1(self) -> float:
+        return self.top_k[0]
+
+    @property
+    def top_2(self) -> float:
+        return self.top_k[1]
+
+    @property
+    def top_3(self) -> float:
+        return self.top_k[2]
+
+
+@dataclass
+class ImageEvaluation:
+    segmentation: SegmentationScores | None      # None: no label mask was given for the image
+    position: PositionScores | None              # None: no FEN was given, or no board was found
+    extraction_failed: bool                      # no board was found (counted only among the images that have a FEN)
+
+
+@dataclass
+class EvaluationReport:
+    results: list[ChessVisionResult]
+    evaluations: list[ImageEvaluation]
+    aggregate: dict = field(default_factory=dict)
+
+
+# ---- host forms of the scores ------------------------------------------------------------------------------------------------------
+def _dice(inter: float, sets_sum: float) -> float:
+    if sets_sum == 0:
+        sets_sum = 2 * inter
+    return (2 * inter + _EPS) / (sets_sum + _EPS)
+
+
+def segmentation_scores(logits: NDArray[np.float32], label_mask: NDArray[np.uint8], threshold: float = 0.5) -> SegmentationScores:
+    """The six scores of ONE image in numpy: float64 sums of the float32 logits; the hard mask is ``sigmoid(x) > threshold`` with the
+    float32 sigmoid, as ``utils.create_binary_mask`` thresholds it.  A pixel is labelled "board" iff its mask value is non-zero."""
+    x32 = np.asarray(logits, dtype=np.float32).reshape(-1)
+    t = np.asarray(label_mask).reshape(-1) != 0
+    if x32.size != t.size or x32.size == 0:
+        raise ValueError("segmentation_scores expects one label per logit")
+    x = x32.astype(np.float64)
+    with np.errstate(over="ignore", invalid="ignore"):
+        bce = float(np.mean(np.maximum(x, 0) - x * t + np.log1p(np.exp(-np.abs(x)))))
+        v = 1.0 / (1.0 + np.exp(-x))
+        pred = (np.float32(1) / (np.float32(1) + np.exp(-x32))) > np.float32(threshold)
+        dice_loss = 1.0 - _dice(float((v * t).sum()), float(v.sum()) + int(t.sum()))     # v * t: a NaN pixel spoils the sum, labelled or not
+    n_label, n_pred, n_both = int(t.sum()), int(pred.sum()), int((pred & t).sum())
+    union = n_pred + n_label - n_both
+    return SegmentationScores(bce=bce, dice_loss=dice_loss, loss=dice_loss + bce, dice=_dice(n_both, n_pred + n_label),
+                              iou=1.0 if union == 0 else n_both / union,
+                              pixel_accuracy=(x.size - n_pred - n_label + 2 * n_both) / x.size)
+
+
+def row_labels(true_labels, flip: bool) -> NDArray[np.int8]:
+    """True class indices in a8..h1 order -> the order of the classifier's rows (``square_names``): reversed for a flipped board."""
+    t = np.asarray(true_labels, dtype=np.int8)
+    return t[::-1].copy() if flip else t
+
+
+def position_scores(model_probabilities: NDArray[np.float32], fen: str, original_fen: str, true_fen: str, num_fixes: int = 0,
+                    flip: bool = False) -> PositionScores:
+    """The record of ONE board on the host, in plain numpy (``evaluate_images`` gets the same from the native call).  Row i of the
+    probabilities is compared with the true piece on ``square_names[i]``: a8..h1, or h1..a8 with ``flip``."""
+    p = np.asarray(model_probabilities, dtype=np.float32)
+    true_rows = row_labels(label_indices(true_fen), flip)
+    rank = true_class_ranks(p, true_rows)
+    predicted = np.empty(64, dtype=np.int8)
+    for i in range(64):                                      # first maximum by ">" (cv_decode_positions); np.argmax but for NaN rows
+        best = 0
+        for k in range(1, 13):
+            if p[i, k] > p[i, best]:
+                best = k
+        predicted[i] = best
+    with np.errstate(divide="ignore", invalid="ignore"):
+        loss = -np.log(p[np.arange(64), true_rows.astype(np.int64)].astype(np.float64))
+    return PositionScores(top_k=tuple(int((rank < j).sum()) / 64 for j in (1, 2, 3)),
+                          accuracy_original=compute_position_accuracy(original_fen, true_fen).accuracy,
+                          accuracy_validated=compute_position_accuracy(fen, true_fen).accuracy,
+                          mean_loss=float(loss.sum() / 64.0), num_fixes=int(num_fixes), true_labels=true_rows,
+                          predicted_labels=predicted, validated_labels=row_labels(label_indices(fen), flip), rank=rank,
+                          confidence=np.max(p, axis=1), loss=loss)
+
+
+def aggregate(evaluations: Sequence[ImageEvaluation], processing_times: Sequence[float]) -> dict:
+    """evaluate.py:347-356's ``aggregate_data`` from the per-image records, with its arithmetic: the four accuracies are sums over the
+    successful extractions divided by their number (NaN when there are none), over the images that have a FEN; ``mean_loss``,
+    ``mean_dice`` and ``mean_iou`` are means over the images that had a label mask (NaN when there are none)."""
+    scored = [e for e in evaluations if e.position is not None]
+    failures = sum(1 for e in evaluations if e.extraction_failed)
+
+    def mean(values):
+        values = list(values)
+        return sum(values) / len(values) if values else math.nan
+
+    seg = [e.segmentation for e in evaluations if e.segmentation is not None]
+    times = list(processing_times)
+    return {
+        "top_1_accuracy_validated": mean(e.position.accuracy_validated for e in scored),
+        "top_1_accuracy": mean(e.position.accuracy_original for e in scored),
+        "top_2_accuracy": mean(e.position.top_k[1] for e in scored),
+        "top_3_accuracy": mean(e.position.top_k[2] for e in scored),
+        "validation_fixes": sum(e.position.num_fixes for e in scored),
+        "validation_improvements": sum(1 for e in scored if e.position.accuracy_validated > e.position.accuracy_original),
+        "extraction_failures": failures,
+        "avg_time_per_prediction": mean(times),
+        "mean_loss": mean(s.loss for s in seg),
+        "mean_dice": mean(s.dice for s in seg),
+        "mean_iou": mean(s.iou for s in seg),
+    }
+
+
+# ---- ground truth of one evaluate_images call --------------------------------------------------------------------------------------
+class Targets:
+    """Checked ground truth of a call, in the form the batched pipeline uses: per image the true class indices in a8..h1 order (or
+    None) and the (256,256) uint8 label mask (or None)."""
+
+    def __init__(self, n_images: int, true_fens=None, label_masks=None):
+        if true_fens is None and label_masks is None:
+            raise ValueError("evaluate_images needs ground truth: true_fens, label_masks or both")
+        self.fens: list = [None] * n_images if true_fens is None else list(true_fens)
+        self.masks: list = [None] * n_images if label_masks is None else list(label_masks)
+        if len(self.fens) != n_images:
+            raise ValueError(f"true_fens has {len(self.fens)} entries for {n_images} images")
+        if len(self.masks) != n_images:
+            raise ValueError(f"label_masks has {len(self.masks)} entries for {n_images} images")
+        self.labels: list = [None] * n_images
+        for i, fen in enumerate(self.fens):
+            if fen is None:
+                continue
+            try:
+                self.labels[i] = label_indices(fen)
+            except (ValueError, AttributeError, TypeError) as exc:
+                raise ValueError(f"image {i}: {exc}") from None
+        size = (constants.INPUT_SIZE[1], constants.INPUT_SIZE[0])
+        for i, m in enumerate(self.masks):
+            if m is None:
+                continue
+            if not isinstance(m, np.ndarray) or m.dtype != np.uint8 or m.shape != size:
+                what = f"{m.dtype} {m.shape}" if isinstance(m, np.ndarray) else type(m).__name__
+                raise ValueError(f"image {i}: a label mask must be a {size} uint8 array, got {what}")
+        self.segmentation: list = [None] * n_images      # filled by the pipeline: SegmentationScores / PositionScores per image
+        self.position: list = [None] * n_images
+
+    def report(self, results: list[ChessVisionResult]) -> EvaluationReport:
+        evaluations = [ImageEvaluation(segmentation=self.segmentation[i], position=self.position[i],
+                                       extraction_failed=self.labels[i] is not None and r.position is None)
+                       for i, r in enumerate(results)]
+        return EvaluationReport(results=results, evaluations=evaluations,
+                                aggregate=aggregate(evaluations, [r.processing_time for r in results]))

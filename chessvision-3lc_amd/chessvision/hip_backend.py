@@ -125,6 +125,10 @@ SYMBOLS = [
     ("cv_mask_completeness", _i, [_vp, _i, _i, ctypes.POINTER(ctypes.c_double)]),
     ("cv_mask_completenesses", _i, [_vp, _i, _i, _i, ctypes.POINTER(ctypes.c_double), _i]),
     ("cv_quadrangle_regularity", _i, [_fp, ctypes.POINTER(ctypes.c_double)]),
+    ("cv_segmentation_scores", _i, [_vp, _vp, _vp, _i, _i, _f, _vp, _vp]),
+    ("cv_segmentation_scores_finish", _i, [_vp, _i] + [ctypes.POINTER(ctypes.c_double)] * 6),
+    ("cv_fen_labels", _i, [ctypes.c_char_p, ctypes.POINTER(ctypes.c_int8)]),
+    ("cv_classification_scores", _i, [_fp, ctypes.POINTER(ctypes.c_int8), _i, _vp, _vp]),
 ]
 
 # cv_score_record_t (include/chessvision_hip.h): one 64-byte record per image
@@ -132,6 +136,14 @@ SCORE_RECORD = np.dtype({"names": ["hist", "above_half", "n_nan", "top_sum", "to
                          "formats": [("<i4", (10,)), "<i4", "<i4", "<f8", "<i4", "<i4"],
                          "offsets": [0, 40, 44, 48, 56, 60], "itemsize": 64})
 _TRANSFORMS = {"none": 0, "sigmoid": 1}
+# cv_seg_record_t, cv_square_score_t, cv_board_score_t (include/chessvision_hip.h)
+SEG_RECORD = np.dtype({"names": ["n_label", "n_pred", "n_both", "n_nan", "bce_sum", "sig_sum", "sig_label_sum", "count", "reserved"],
+                       "formats": ["<i4", "<i4", "<i4", "<i4", "<f8", "<f8", "<f8", "<i4", ("<i4", (5,))],
+                       "offsets": [0, 4, 8, 12, 16, 24, 32, 40, 44], "itemsize": 64})
+SQUARE_SCORE = np.dtype({"names": ["predicted", "rank", "confidence", "reserved", "loss"],
+                         "formats": ["<i4", "<i4", "<f4", "<i4", "<f8"], "offsets": [0, 4, 8, 12, 16], "itemsize": 24})
+BOARD_SCORE = np.dtype({"names": ["hits", "n_nan", "mean_loss"], "formats": [("<i4", (13,)), "<i4", "<f8"],
+                        "offsets": [0, 52, 56], "itemsize": 64})
 
 
 def trim_memory() -> int:
@@ -269,6 +281,46 @@ def scores_finish(records: np.ndarray):
     if r.size:
         _check(lib.cv_extraction_scores_finish(r.ctypes.data_as(_vp), int(r.size), conf.ctypes.data_as(dp), dist.ctypes.data_as(dp)))
     return conf, dist
+
+
+def segmentation_scores_finish(records: np.ndarray) -> dict:
+    """(N,) ``SEG_RECORD`` array -> {"bce", "dice_loss", "loss", "dice", "iou", "pixel_accuracy"}: (N,) float64 arrays
+    (``cv_segmentation_scores_finish``; the formulas are in include/chessvision_hip.h)."""
+    lib = load_library()
+    r = np.ascontiguousarray(records, dtype=SEG_RECORD).reshape(-1)
+    names = ("bce", "dice_loss", "loss", "dice", "iou", "pixel_accuracy")
+    out = {k: np.zeros(r.size, dtype=np.float64) for k in names}
+    dp = ctypes.POINTER(ctypes.c_double)
+    if r.size:
+        _check(lib.cv_segmentation_scores_finish(r.ctypes.data_as(_vp), int(r.size), *(out[k].ctypes.data_as(dp) for k in names)))
+    return out
+
+
+def fen_labels(fen: str) -> np.ndarray:
+    """Piece-placement field of a FEN -> (64,) int8 class indices in a8..h1 order (``cv_fen_labels``); ``HipBackendError`` naming
+    what is wrong with a malformed placement."""
+    lib = load_library()
+    labels = np.zeros(64, dtype=np.int8)
+    _check(lib.cv_fen_labels(str(fen).encode(), labels.ctypes.data_as(ctypes.POINTER(ctypes.c_int8))))
+    return labels
+
+
+def classification_scores(probabilities: np.ndarray, labels: np.ndarray):
+    """(N,64,13) float32 probabilities and (N,64) true class indices, given per row -> (per_square (N,64) ``SQUARE_SCORE``, per_board
+    (N,) ``BOARD_SCORE``) in one native call (``cv_classification_scores``, csrc/position.cpp)."""
+    lib = load_library()
+    p = np.ascontiguousarray(probabilities, dtype=np.float32)
+    if p.ndim != 3 or p.shape[1:] != (64, 13):
+        raise HipBackendError("classification_scores expects (N,64,13) float32 probabilities")
+    t = np.ascontiguousarray(labels, dtype=np.int8)
+    if t.shape != p.shape[:2]:
+        raise HipBackendError("classification_scores expects one label per row of the probabilities, (N,64)")
+    n = p.shape[0]
+    per_square, per_board = np.zeros((n, 64), dtype=SQUARE_SCORE), np.zeros(n, dtype=BOARD_SCORE)
+    if n:
+        _check(lib.cv_classification_scores(p.ctypes.data_as(_fp), t.ctypes.data_as(ctypes.POINTER(ctypes.c_int8)), n,
+                                            per_square.ctypes.data_as(_vp), per_board.ctypes.data_as(_vp)))
+    return per_square, per_board
 
 
 def mask_completeness(mask: np.ndarray) -> float:
@@ -550,6 +602,35 @@ class HipEngine:
         rec = records.cpu().numpy().view(SCORE_RECORD).reshape(-1)
         conf, dist = scores_finish(rec)
         return (rec, conf, dist, mask.cpu().numpy()) if want_mask else (rec, conf, dist)
+
+    def segmentation_scores_dev(self, logits: torch.Tensor, labels: torch.Tensor, threshold: float = 0.5) -> torch.Tensor:
+        """The device half of ``segmentation_scores``: launches the kernel on the current stream behind whatever produced ``logits``
+        ((N, ...) float32 on this device, contiguous) and ``labels`` (uint8, the same number of elements per image, contiguous; a
+        pixel is "board" iff its byte is non-zero) and returns the (N,64) uint8 device tensor of records.  Nothing is synchronised
+        or copied."""
+        if not isinstance(logits, torch.Tensor) or logits.dtype != torch.float32 or logits.device != self.device or logits.dim() < 1:
+            raise HipBackendError("segmentation_scores expects an (N, ...) float32 logits tensor on the engine's device")
+        if not isinstance(labels, torch.Tensor) or labels.dtype != torch.uint8 or labels.device != self.device or labels.dim() < 1:
+            raise HipBackendError("segmentation_scores expects an (N, ...) uint8 label tensor on the engine's device")
+        n = int(logits.shape[0])
+        count = int(logits.numel() // n) if n else 0
+        if int(labels.shape[0]) != n or labels.numel() != logits.numel():
+            raise HipBackendError("segmentation_scores expects one label byte per logit")
+        if n and not (logits.is_contiguous() and labels.is_contiguous()):
+            raise HipBackendError("segmentation_scores expects contiguous images")
+        if not np.isfinite(float(threshold)):
+            raise HipBackendError("segmentation_scores expects a finite threshold")
+        records = torch.empty((n, 64), dtype=torch.uint8, device=self.device)
+        _check(self._lib.cv_segmentation_scores(self._h, _ptr(logits), _ptr(labels), n, count, float(threshold), _ptr(records),
+                                                _stream_ptr(self.device)))
+        return records
+
+    def segmentation_scores(self, logits: torch.Tensor, labels: torch.Tensor, threshold: float = 0.5):
+        """-> (records, scores): per image the ``SEG_RECORD`` the kernel wrote (numpy) and the dict of float64 arrays
+        ``segmentation_scores_finish`` makes of them (bce, dice_loss, loss, dice, iou, pixel_accuracy).  Synchronises the current
+        stream."""
+        rec = self.segmentation_scores_dev(logits, labels, threshold).cpu().numpy().view(SEG_RECORD).reshape(-1)
+        return rec, segmentation_scores_finish(rec)
 
     def softmax13(self, logits: torch.Tensor) -> torch.Tensor:
         logits = logits.to(self.device, torch.float32).contiguous()

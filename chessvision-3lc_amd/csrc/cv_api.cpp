@@ -16,6 +16,9 @@
 namespace cv {
 void decode_positions(const float* probs, int n_boards, int flip, char* fen, char* original_fen, int8_t* labels,
                       int32_t* fixes, int32_t* n_fixes);
+const char* fen_labels(const char* fen, int8_t* labels);
+void classification_scores(const float* probs, const int8_t* labels, int n_boards, cv_square_score_t* per_square,
+                           cv_board_score_t* per_board);
 bool find_quadrangle(const uint8_t* mask, int h, int w, int32_t quad[8]);
 long find_contours_flat(const uint8_t* mask, int h, int w, bool tc89, int32_t* xy, long cap_pts, int32_t* counts, int32_t* holes,
                         long cap_contours);
@@ -33,6 +36,10 @@ double quadrangle_regularity(const float quad[8]);
 
 static_assert(sizeof(cv_score_record_t) == sizeof(cv::ScoreRecord) && offsetof(cv_score_record_t, top_sum) == offsetof(cv::ScoreRecord, top_sum) &&
               offsetof(cv_score_record_t, top_count) == offsetof(cv::ScoreRecord, top_count), "cv_score_record_t is the kernel's record");
+static_assert(sizeof(cv_seg_record_t) == sizeof(cv::SegRecord) && offsetof(cv_seg_record_t, bce_sum) == offsetof(cv::SegRecord, bce_sum) &&
+              offsetof(cv_seg_record_t, sig_label_sum) == offsetof(cv::SegRecord, sig_label_sum) &&
+              offsetof(cv_seg_record_t, count) == offsetof(cv::SegRecord, count), "cv_seg_record_t is the kernel's record");
+static_assert(sizeof(cv_square_score_t) == 24 && sizeof(cv_board_score_t) == 64, "layouts the Python binding mirrors");
 
 using namespace cv;
 
@@ -546,6 +553,66 @@ static int impl_cv_extraction_scores_finish(const cv_score_record_t* records, in
         }
         distribution[i] = 1.0 - entropy / std::log2(10.0);
     }
+    return CV_OK;
+}
+
+static int impl_cv_segmentation_scores(cv_engine_t* eng, const float* logits, const uint8_t* labels, int n, int count, float threshold,
+                                       cv_seg_record_t* records, void* stream) {
+    Status s = check_engine(eng);
+    if (!s.ok()) return finish(s);
+    if (!logits || !labels || !records) return finish(fail(CV_ERR_INVALID, "cv_segmentation_scores: null tensor"));
+    if (((uintptr_t)logits & 3u) || ((uintptr_t)records & 7u)) return finish(fail(CV_ERR_INVALID, "cv_segmentation_scores: logits must be 4-byte, records 8-byte aligned"));
+    if (n < 1) return finish(fail(CV_ERR_INVALID, "cv_segmentation_scores: n must be at least 1"));
+    if (count < 1 || count > (1 << 24)) return finish(fail(CV_ERR_INVALID, "cv_segmentation_scores: count must be in [1, 2^24]"));
+    if (!std::isfinite(threshold)) return finish(fail(CV_ERR_INVALID, "cv_segmentation_scores: threshold must be finite"));
+    DeviceGuard g(eng->impl.device);
+    hipError_t e = segmentation_scores(logits, labels, n, count, threshold, reinterpret_cast<SegRecord*>(records), (hipStream_t)stream);
+    if (e != hipSuccess) return finish(hip_fail(e, "segmentation_scores"));
+    return CV_OK;
+}
+
+// Pytorch-UNet's dice_coeff for one image: (2 * inter + eps) / (sets_sum + eps), sets_sum == 0 -> 2 * inter
+static double dice_of(double inter, double sets_sum) {
+    if (sets_sum == 0.0) sets_sum = 2.0 * inter;
+    return (2.0 * inter + 1e-6) / (sets_sum + 1e-6);
+}
+
+static int impl_cv_segmentation_scores_finish(const cv_seg_record_t* records, int n, double* bce, double* dice_loss, double* loss,
+                                              double* dice, double* iou, double* pixel_accuracy) {
+    if (n < 0 || (n > 0 && !records)) return finish(fail(CV_ERR_INVALID, "cv_segmentation_scores_finish: bad argument"));
+    for (int i = 0; i < n; ++i) {
+        const cv_seg_record_t& r = records[i];
+        if (r.count < 1) return finish(fail(CV_ERR_INVALID, "cv_segmentation_scores_finish: record " + std::to_string(i) + " has no pixels"));
+        const double b = r.bce_sum / (double)r.count;
+        const double dl = 1.0 - dice_of(r.sig_label_sum, r.sig_sum + (double)r.n_label);
+        const long long uni = (long long)r.n_pred + r.n_label - r.n_both;
+        if (bce) bce[i] = b;
+        if (dice_loss) dice_loss[i] = dl;
+        if (loss) loss[i] = dl + b;
+        if (dice) dice[i] = dice_of((double)r.n_both, (double)r.n_pred + (double)r.n_label);
+        if (iou) iou[i] = uni == 0 ? 1.0 : (double)r.n_both / (double)uni;
+        if (pixel_accuracy) pixel_accuracy[i] = (double)((long long)r.count - r.n_pred - r.n_label + 2LL * r.n_both) / (double)r.count;
+    }
+    return CV_OK;
+}
+
+static int impl_cv_fen_labels(const char* fen, int8_t* labels) {
+    if (!fen || !labels) return finish(fail(CV_ERR_INVALID, "cv_fen_labels: null argument"));
+    int8_t out[64];
+    const char* why = fen_labels(fen, out);
+    if (why) return finish(fail(CV_ERR_INVALID, std::string("cv_fen_labels: malformed piece placement (") + why + ")"));
+    std::memcpy(labels, out, 64);
+    return CV_OK;
+}
+
+static int impl_cv_classification_scores(const float* probs, const int8_t* labels, int n_boards, cv_square_score_t* per_square,
+                                         cv_board_score_t* per_board) {
+    if (n_boards < 0 || (n_boards > 0 && (!probs || !labels || !per_square || !per_board)))
+        return finish(fail(CV_ERR_INVALID, "cv_classification_scores: bad argument"));
+    for (size_t i = 0; i < (size_t)n_boards * 64; ++i)
+        if (labels[i] < 0 || labels[i] > 12)
+            return finish(fail(CV_ERR_INVALID, "cv_classification_scores: label " + std::to_string(i) + " is not a class index (0..12)"));
+    classification_scores(probs, labels, n_boards, per_square, per_board);
     return CV_OK;
 }
 
@@ -1188,4 +1255,29 @@ int cv_mask_completenesses(const uint8_t* masks, int n, int h, int w, double* sc
 
 int cv_quadrangle_regularity(const float* quad, double* score) {
     return guarded("cv_quadrangle_regularity", [&]() -> int { return impl_cv_quadrangle_regularity(quad, score); });
+}
+
+int cv_segmentation_scores(cv_engine_t* eng, const float* logits, const uint8_t* labels, int n, int count, float threshold,
+                           cv_seg_record_t* records, void* stream) {
+    return guarded("cv_segmentation_scores", [&]() -> int {
+        return impl_cv_segmentation_scores(eng, logits, labels, n, count, threshold, records, stream);
+    });
+}
+
+int cv_segmentation_scores_finish(const cv_seg_record_t* records, int n, double* bce, double* dice_loss, double* loss, double* dice,
+                                  double* iou, double* pixel_accuracy) {
+    return guarded("cv_segmentation_scores_finish", [&]() -> int {
+        return impl_cv_segmentation_scores_finish(records, n, bce, dice_loss, loss, dice, iou, pixel_accuracy);
+    });
+}
+
+int cv_fen_labels(const char* fen, int8_t* labels) {
+    return guarded("cv_fen_labels", [&]() -> int { return impl_cv_fen_labels(fen, labels); });
+}
+
+int cv_classification_scores(const float* probs, const int8_t* labels, int n_boards, cv_square_score_t* per_square,
+                             cv_board_score_t* per_board) {
+    return guarded("cv_classification_scores", [&]() -> int {
+        return impl_cv_classification_scores(probs, labels, n_boards, per_square, per_board);
+    });
 }

@@ -71,6 +71,23 @@ static_assert(sizeof(ScoreRecord) == 64, "one 64-byte record per image");
 hipError_t extraction_scores(const float* values, int n, int count, int transform, ScoreRecord* records, uint8_t* half_mask,
                              hipStream_t s);
 
+// Segmentation scores against a label mask (the per-image reductions behind the reference's LossCollector column, scripts/train/
+// unet_loss_collector.py:19-48, and train_unet.py's val_dice).  logits: n images of `count` contiguous float32 (4-byte aligned, 1 <=
+// count <= 2^24); labels: n x count uint8, any alignment, "board" iff the byte is non-zero; threshold finite.  One record per image:
+//   n_label / n_pred / n_both   label bytes != 0 / pixels with v > threshold, v = 1 / (1 + __expf(-x)) (outc_1x1's mask expression) / both
+//   n_nan                       NaN logits (each of them turns the three sums NaN)
+//   bce_sum                     float64 sum of the float32 terms max(x, 0) - x * t + log1pf(expf(-|x|)), t in {0, 1}
+//   sig_sum, sig_label_sum      float64 sums of v over all pixels / over the label pixels
+// Sums run in a fixed order (lane, wave shuffle tree, waves in order): bit-identical run to run.  Asynchronous on `s`; allocates nothing.
+struct SegRecord {
+    int32_t n_label, n_pred, n_both, n_nan;
+    double  bce_sum, sig_sum, sig_label_sum;
+    int32_t count, reserved[5];
+};
+static_assert(sizeof(SegRecord) == 64, "one 64-byte record per image");
+hipError_t segmentation_scores(const float* logits, const uint8_t* labels, int n, int count, float threshold, SegRecord* records,
+                               hipStream_t s);
+
 // MFMA lane-map probes used by cv_selftest_mfma (D = A*B^T with A:16xK, B:16xK row-major)
 hipError_t mfma_probe_f16(const half_t* a, const half_t* b, float* d, hipStream_t s);   // K = 32
 hipError_t mfma_probe_f32(const float* a, const float* b, float* d, hipStream_t s);     // K = 16

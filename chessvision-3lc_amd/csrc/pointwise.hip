@@ -1177,6 +1177,86 @@ __global__ __launch_bounds__(kScoreThreads) void extraction_scores_kernel(const 
     }
 }
 
+// ---- segmentation scores: the UNet's logits against a label mask ---------------------------------------------------------------
+// One workgroup of 16 waves per image, one sweep: the logits in 16-byte pieces (score_sweep's head / body / tail), the label bytes of
+// a body piece as one 4-byte load where the image's label stream is aligned there.  Counts are integers; the three sums are float64
+// per lane, a fixed shuffle tree per wave, then the waves in order through LDS -- no float atomics, a record is bit-identical run to
+// run.  A NaN logit turns all three sums NaN by itself (v * 0 is NaN for the unlabelled pixel too).
+__global__ __launch_bounds__(kScoreThreads) void segmentation_scores_kernel(const float* __restrict__ logits,
+                                                                            const uint8_t* __restrict__ labels, int count, float thr,
+                                                                            SegRecord* __restrict__ records) {
+    __shared__ double wsum[kScoreWaves][3];
+    __shared__ int wcnt[kScoreWaves][4];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const float* img = logits + (size_t)blockIdx.x * count;
+    const uint8_t* lab = labels + (size_t)blockIdx.x * count;
+    const int head = min(count, (int)(((16u - (unsigned)((uintptr_t)img & 15u)) & 15u) >> 2));
+    const int nvec = (count - head) >> 2;
+    const bool lab4 = (((uintptr_t)(lab + head)) & 3u) == 0;            // the body's label bytes come in four at a time
+    int c[4] = {0, 0, 0, 0};                                            // n_label, n_pred, n_both, n_nan
+    double bce = 0.0, sig = 0.0, sigl = 0.0;
+    score_sweep<0>(img, count, head, nvec, [&](const float* x, auto M, int at) {
+        constexpr int m = decltype(M)::value;
+        uint8_t t[m];
+        bool loaded = false;
+        if constexpr (m == 4) {
+            if (lab4) {
+                const uchar4 q = *reinterpret_cast<const uchar4*>(lab + at);
+                t[0] = q.x; t[1] = q.y; t[2] = q.z; t[3] = q.w;
+                loaded = true;
+            }
+        }
+        if (!loaded) {
+#pragma unroll
+            for (int j = 0; j < m; ++j) t[j] = lab[at + j];
+        }
+#pragma unroll
+        for (int j = 0; j < m; ++j) {
+            const float xv = x[j];
+            const bool on = t[j] != 0;
+            const float tf = on ? 1.f : 0.f;
+            const float v = score_value<1>(xv);               // the expression of outc_1x1_kernel's mask
+            const bool pred = v > thr;
+            c[0] += on;
+            c[1] += pred;
+            c[2] += on && pred;
+            c[3] += xv != xv;
+            const float term = (xv > 0.f ? xv : 0.f) - xv * tf + log1pf(expf(-fabsf(xv)));
+            bce += (double)term;
+            sig += (double)v;
+            sigl += (double)(v * tf);
+        }
+    });
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) {
+        bce += __shfl_down(bce, d);
+        sig += __shfl_down(sig, d);
+        sigl += __shfl_down(sigl, d);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) c[j] += __shfl_down(c[j], d);
+    }
+    if (lane == 0) {
+        wsum[wave][0] = bce; wsum[wave][1] = sig; wsum[wave][2] = sigl;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) wcnt[wave][j] = c[j];
+    }
+    __syncthreads();
+    if (tid == 0) {
+        SegRecord r;
+        double s[3] = {0.0, 0.0, 0.0};
+        int k[4] = {0, 0, 0, 0};
+        for (int w = 0; w < kScoreWaves; ++w) {
+            for (int j = 0; j < 3; ++j) s[j] += wsum[w][j];
+            for (int j = 0; j < 4; ++j) k[j] += wcnt[w][j];
+        }
+        r.n_label = k[0]; r.n_pred = k[1]; r.n_both = k[2]; r.n_nan = k[3];
+        r.bce_sum = s[0]; r.sig_sum = s[1]; r.sig_label_sum = s[2];
+        r.count = count;
+        for (int j = 0; j < 5; ++j) r.reserved[j] = 0;
+        records[blockIdx.x] = r;
+    }
+}
+
 // ---- MFMA lane-map probes (same fragment addressing as conv_igemm.hip) ---------------------------
 __global__ void mfma_probe_f16_kernel(const half_t* a, const half_t* b, float* d) {
     const int lane = threadIdx.x, q = lane >> 4, r = lane & 15;
@@ -1333,6 +1413,13 @@ hipError_t extraction_scores(const float* values, int n, int count, int transfor
         return hipErrorInvalidValue;
     if (transform) hipLaunchKernelGGL(extraction_scores_kernel<1>, dim3((unsigned)n), dim3(kScoreThreads), 0, s, values, count, records, half_mask);
     else hipLaunchKernelGGL(extraction_scores_kernel<0>, dim3((unsigned)n), dim3(kScoreThreads), 0, s, values, count, records, half_mask);
+    return hipGetLastError();
+}
+hipError_t segmentation_scores(const float* logits, const uint8_t* labels, int n, int count, float threshold, SegRecord* records,
+                               hipStream_t s) {
+    if (!logits || !labels || !records || n < 1 || count < 1 || count > (1 << 24) || ((uintptr_t)logits & 3u) || !(threshold - threshold == 0.f))
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL(segmentation_scores_kernel, dim3((unsigned)n), dim3(kScoreThreads), 0, s, logits, labels, count, threshold, records);
     return hipGetLastError();
 }
 hipError_t softmax13(const float* logits, int n, float* probs, hipStream_t s) {

@@ -5,8 +5,14 @@
 // decodes hundreds of boards per job; doing it per board in Python (argmax, list comprehensions, two FEN assemblies,
 // an argsort) cost more host time than the GPU needed for the CNNs.  Same results as the Python restatement
 // (chessvision/fen.py, core.py), which stays the readable version and the test checker.
+//
+// Also the host half of the ground-truth scores (evaluation): FEN -> true labels, and per-square rank / loss / top-k hits of the
+// probabilities against them (reference scripts/eval/evaluate.py:62-140).
+#include <cmath>
 #include <cstdint>
 #include <cstring>
+
+#include "../../include/chessvision_hip.h"      // plain C: the two score records
 
 namespace cv {
 
@@ -63,6 +69,64 @@ void decode_positions(const float* probs, int n_boards, int flip, char* fen, cha
         write_fen(lab, flip, fen + (size_t)b * 72);
     }
     *n_fixes = nf;
+}
+
+// Piece placement of a FEN (up to the first space) -> 64 class indices, a8..h1.  Returns nullptr, or what is wrong with the field.
+const char* fen_labels(const char* fen, int8_t* labels) {
+    int rank = 0, file = 0;
+    for (const char* p = fen; *p && *p != ' '; ++p) {
+        const char c = *p;
+        if (c == '/') {
+            if (file != 8) return "a rank does not sum to 8 squares";
+            if (++rank > 7) return "more than 8 ranks";
+            file = 0;
+        } else if (c >= '1' && c <= '8') {
+            const int run = c - '0';
+            if (file + run > 8) return "a rank does not sum to 8 squares";
+            for (int k = 0; k < run; ++k) labels[rank * 8 + file++] = 12;
+        } else {
+            const char* at = c == 'f' ? nullptr : (const char*)std::memchr(kLabels, c, 12);
+            if (!at) return "unknown piece symbol";
+            if (file >= 8) return "a rank does not sum to 8 squares";
+            labels[rank * 8 + file++] = (int8_t)(at - kLabels);
+        }
+    }
+    if (rank != 7) return "fewer than 8 ranks";
+    if (file != 8) return "a rank does not sum to 8 squares";
+    return nullptr;
+}
+
+// Per square: arg-max (as decode_positions), largest probability, rank and loss of the true class; per board: top-k hits, mean loss,
+// NaN squares.  rank = #{j: p_j > p_t} + #{j > t: p_j == p_t} -- the true class's place from the top of a STABLE ascending argsort
+// (among equal values the higher index sorts later, so it is nearer the top).  A square with a NaN anywhere has rank 13.
+void classification_scores(const float* probs, const int8_t* labels, int n_boards, cv_square_score_t* per_square,
+                           cv_board_score_t* per_board) {
+    for (int b = 0; b < n_boards; ++b) {
+        cv_board_score_t& bs = per_board[b];
+        std::memset(&bs, 0, sizeof(bs));
+        double total = 0.0;
+        for (int i = 0; i < 64; ++i) {
+            const float* p = probs + ((size_t)b * 64 + i) * 13;
+            const int t = labels[(size_t)b * 64 + i];
+            cv_square_score_t& sq = per_square[(size_t)b * 64 + i];
+            int best = 0, rank = 0;
+            bool nan = false;
+            for (int k = 0; k < 13; ++k) {
+                nan = nan || p[k] != p[k];
+                if (k && p[k] > p[best]) best = k;
+                rank += p[k] > p[t] || (k > t && p[k] == p[t]);
+            }
+            if (nan) { rank = 13; ++bs.n_nan; }
+            sq.predicted = best;
+            sq.rank = rank;
+            sq.confidence = nan ? std::nanf("") : p[best];   // np.max of a row with a NaN
+            sq.reserved = 0;
+            sq.loss = -std::log((double)p[t]);
+            total += sq.loss;
+            for (int k = rank; k < 13; ++k) ++bs.hits[k];
+        }
+        bs.mean_loss = total / 64.0;
+    }
 }
 
 }  // namespace cv

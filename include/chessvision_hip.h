@@ -338,6 +338,74 @@ int cv_mask_completenesses(const uint8_t* masks, int n, int h, int w, double* sc
  * - 0.5 std(angles) / (pi / 2), population standard deviations, in double.  Host only. */
 int cv_quadrangle_regularity(const float* quad, double* score);
 
+/* ---- ground-truth scores (additions under ABI 6; detect with dlsym(handle, "cv_segmentation_scores")) -------------------------- */
+/* What the reference's evaluation side computes against labels: the LossCollector's per-image `loss` = soft Dice loss + mean
+ * BCEWithLogitsLoss (scripts/train/unet_loss_collector.py:19-48), train_unet.py's val_dice (:333-338), and evaluate.py's per-square
+ * ranks and top-k hits (scripts/eval/evaluate.py:89-140, 264-360).  The per-pixel reductions run on the device, on the logits where
+ * the UNet left them; everything about the 64 x 13 probabilities is host code (they visit the host for the FEN anyway).
+ *
+ * cv_segmentation_scores: logits = n images of `count` contiguous float32 (DEVICE, 4-byte aligned -- an image need not be 16-byte
+ * aligned, `count` need not be a multiple of 4; 1 <= count <= 2^24, n >= 1); labels = n x count uint8 (DEVICE, any alignment), a pixel
+ * is "board" iff its byte is non-zero (the reference's masks are 0 / 255 and are divided by 255 before the loss); threshold finite.
+ * records: n records (DEVICE, 8-byte aligned).  Asynchronous on `stream`; allocates nothing and synchronises nothing.  A record is
+ * bit-identical run to run (integer counts; the float64 sums run in a fixed order, no float atomics).  Logits of +-inf are outside
+ * the contract (they give NaN sums where 0 * inf arises); a NaN logit is counted and makes all three sums NaN. */
+typedef struct cv_seg_record {
+    int32_t n_label;        /* label bytes != 0 */
+    int32_t n_pred;         /* pixels with v > threshold, v = 1 / (1 + exp(-x)) in the float32 expression the UNet's mask and
+                               cv_extraction_scores' transform 1 use: == count_nonzero(mask of cv_unet_forward_u8) bit for bit */
+    int32_t n_both;         /* pixels counted in both */
+    int32_t n_nan;          /* NaN logits */
+    double  bce_sum;        /* sum of the float32 terms max(x, 0) - x * t + log1pf(expf(-|x|)), t in {0, 1}; float64 sum */
+    double  sig_sum;        /* sum of v (float32 values, float64 sum) */
+    double  sig_label_sum;  /* sum of v over the label pixels */
+    int32_t count;
+    int32_t reserved[5];    /* 0; pads the record to 64 bytes */
+} cv_seg_record_t;
+int cv_segmentation_scores(cv_engine_t* eng, const float* logits, const uint8_t* labels, int n, int count, float threshold,
+                           cv_seg_record_t* records, void* stream);
+/* Records (HOST) -> six scores per image, n doubles each (any output may be NULL).  Needs no GPU and no engine.
+ *   bce            = bce_sum / count                                   BCEWithLogitsLoss(reduction="none").mean((-1, -2))
+ *   dice_loss      = 1 - (2 * sig_label_sum + 1e-6) / (S + 1e-6),  S = sig_sum + n_label, and S = 2 * sig_label_sum where S == 0
+ *   loss           = dice_loss + bce                                    the LossCollector's column
+ *   dice           = the same formula on the integer counts (n_both, n_pred + n_label): the per-image val_dice, 1 when both are empty
+ *   iou            = n_both / (n_pred + n_label - n_both), 1 when the union is empty
+ *   pixel_accuracy = (count - n_pred - n_label + 2 * n_both) / count
+ * The Dice form is a READING: the reference calls dice_loss(..., reduction="none") from a vendored Pytorch-UNet submodule whose
+ * directory is empty in the reference tree, so it could not be read.  This is upstream Pytorch-UNet's dice_coeff (epsilon 1e-6 in
+ * numerator and denominator, the sets_sum == 0 -> 2 * inter rule) applied per image. */
+int cv_segmentation_scores_finish(const cv_seg_record_t* records, int n, double* bce, double* dice_loss, double* loss, double* dice,
+                                  double* iou, double* pixel_accuracy);
+/* Piece-placement field of a FEN (anything after the first space is ignored) -> 64 class indices in a8..h1 order, classes in the
+ * order of constants.LABEL_NAMES = "BKNPQRbknpqrf" (12 = empty).  CV_ERR_INVALID with a message for a malformed placement: not 8
+ * ranks, a rank not summing to 8, an unknown symbol.  Host only. */
+int cv_fen_labels(const char* fen, int8_t* labels);
+/* probs: n_boards x 64 x 13 float32 (HOST); labels: n_boards x 64 true class indices (0..12), GIVEN PER ROW OF probs -- the caller
+ * maps rows to squares (a8..h1, or h1..a8 for a flipped board).  per_square: n_boards x 64 records; per_board: n_boards records.
+ *   predicted   the arg-max as cv_decode_positions computes it (first maximum)
+ *   confidence  the largest probability
+ *   rank        #{j: p_j > p_t} + #{j > t: p_j == p_t}: the position of the true class t from the top of np.argsort(kind="stable").
+ *               The reference's np.argsort uses the default kind, which numpy 2.2 does not keep stable for 13 float32 columns, so
+ *               its own order among EQUAL probabilities is undefined; this is the stable reading.  A square holding a NaN has rank 13
+ *               (a miss at every k) and is counted in n_nan.
+ *   loss        -log((double)p_t); +inf for 0
+ *   hits[k-1]   squares of the board with rank < k (top-k accuracy = hits[k-1] / 64); mean_loss: mean of the 64 losses
+ * Host only; needs no GPU and no engine. */
+typedef struct cv_square_score {
+    int32_t predicted;
+    int32_t rank;
+    float   confidence;
+    int32_t reserved;       /* 0 */
+    double  loss;
+} cv_square_score_t;
+typedef struct cv_board_score {
+    int32_t hits[13];
+    int32_t n_nan;          /* squares holding a NaN */
+    double  mean_loss;
+} cv_board_score_t;
+int cv_classification_scores(const float* probs, const int8_t* labels, int n_boards, cv_square_score_t* per_square,
+                             cv_board_score_t* per_board);
+
 /* ---- one image, host to host: the native form of ChessVision.process_image (core.py:152-195) ---------------------------------- */
 /* Everything a cgo / JNI / C++ host needs for the reference's per-image entry point in ONE call: INTER_AREA resize to 256x256
  * (core.py:212), UNet forward, sigmoid / threshold mask (core.py:273, utils.py:101-112), contours -> quadrangle (core.py:357-411),
