@@ -23,7 +23,7 @@ import numpy as np
 import torch
 
 from . import constants
-from .cv_types import BoardExtractionResult, ChessVisionResult, ExtractionQuality, PositionResult, pawn_rule_fix
+from .cv_types import BoardExtractionResult, ChessVisionResult, Embeddings, ExtractionQuality, PositionResult, pawn_rule_fix
 from .distributed import host_threads
 from .hip_backend import (SCORE_RECORD, SEG_RECORD, board_homographies, classification_scores, decode_positions, find_quadrangles,
                           mask_completenesses, quadrangle_regularity, scores_finish, segmentation_scores_finish)
@@ -61,7 +61,8 @@ class Job:
     download stream up to ``logits_ready``) and ``cls_out`` (up to ``probs_ready``) exist for nothing else; ``release`` drops them
     once ``finish`` has synchronised both events.  ``batch`` is written by the upload stream and read by the compute stream: it is
     handed over with ``record_stream`` and dropped as soon as its last kernel (the warp) is queued; ``labels`` (the label masks of
-    an evaluation call) likewise, dropped behind the segmentation-score kernel."""
+    an evaluation call) likewise, dropped behind the segmentation-score kernel.  The embeddings of an ``embeddings=True`` call ride in
+    ``unet_out`` / ``cls_out`` like every other device tensor the download stream reads."""
     ids: list[int]
     # upload
     staged: torch.Tensor | None = None          # pinned source of the upload
@@ -77,6 +78,7 @@ class Job:
     records: torch.Tensor | None = None         # pinned (n,64) u8 score records, ``quality`` only
     half: torch.Tensor | None = None            # pinned (n,256,256) u8 ``v > 0.5`` masks, ``quality`` only
     seg_records: torch.Tensor | None = None     # pinned (n,64) u8 segmentation-score records, evaluation only
+    unet_emb: torch.Tensor | None = None        # pinned (n,C) f32 bottleneck embeddings, ``embeddings`` only (behind logits_ready)
     masks_ready: torch.cuda.Event | None = None     # download stream: masks have landed
     logits_ready: torch.cuda.Event | None = None    # download stream: logits (and records, half) have landed
     # classify
@@ -86,6 +88,7 @@ class Job:
     cls_out: tuple | None = None                # device: probabilities, boards, squares -- held for the download stream
     boards: torch.Tensor | None = None          # pinned (found,512,512) u8
     probs: torch.Tensor | None = None           # pinned (found*64,13) f32
+    cls_emb: torch.Tensor | None = None         # pinned (found*64,512) f32 classifier embeddings, ``embeddings`` only (behind probs_ready)
     probs_ready: torch.cuda.Event | None = None     # download stream: boards and probabilities have landed
 
     def release(self) -> None:
@@ -101,6 +104,8 @@ class _ImageSlot:
     quality: ExtractionQuality | None
     board: np.ndarray | None = None
     position: PositionResult | None = None
+    unet_emb: np.ndarray | None = None
+    cls_emb: np.ndarray | None = None
 
 
 def _pinned(shape, dtype):
@@ -110,9 +115,11 @@ def _pinned(shape, dtype):
 class _Call:
     """The state one ``process_images`` call shares between its stages.  The compute stream is the CURRENT stream."""
 
-    def __init__(self, cv, images, threshold, flip, fallback_quad, return_crops, timings, quality, started, targets=None):
+    def __init__(self, cv, images, threshold, flip, fallback_quad, return_crops, timings, quality, started, targets=None,
+                 embeddings=False):
         self.cv, self.images, self.started = cv, images, started
         self.targets = targets                           # evaluation.Targets of an evaluate_images call, else None
+        self.embeddings = bool(embeddings)               # both forwards also pool their hook tensor (HipEngine: want_embedding)
         self.threshold, self.flip, self.fallback_quad, self.return_crops, self.quality = threshold, flip, fallback_quad, return_crops, quality
         self.eng, self.eng_cls, self.dev = cv._get_engine("unet"), cv._get_engine("resnet18"), cv.device
         self.names = constants.SQUARE_NAMES_FLIPPED if flip else constants.SQUARE_NAMES_NORMAL
@@ -200,7 +207,12 @@ class _Call:
         job.batch.record_stream(self.main)
         self.tm.setdefault("first_enqueue_s", time.time() - self.started)   # host time until the first kernel of the call is queued
         small = self.gpu_timed("resize_ms", eng.resize_area_u8, job.batch, (constants.INPUT_SIZE[1], constants.INPUT_SIZE[0]))
-        lg, mk = self.gpu_timed("unet_ms", eng.unet_forward_u8, small, threshold=self.threshold, want_mask=True)
+        emb = None
+        if self.embeddings:                              # the same forward plus one pooling launch per chunk, inside unet_ms
+            lg, mk, emb = self.gpu_timed("unet_ms", eng.unet_forward_u8, small, threshold=self.threshold, want_mask=True,
+                                         want_embedding=True)
+        else:
+            lg, mk = self.gpu_timed("unet_ms", eng.unet_forward_u8, small, threshold=self.threshold, want_mask=True)
         scored = None
         if self.quality:
             scored = self.gpu_timed("quality_ms", eng.extraction_scores_dev, lg, "none" if self.quality == "logits" else "sigmoid",
@@ -212,7 +224,7 @@ class _Call:
             job.labels = None
         job.unet_done = torch.cuda.Event()
         job.unet_done.record()
-        job.unet_out = (lg, mk, scored, seg)
+        job.unet_out = (lg, mk, scored, seg, emb)
         job.logits, job.masks = _pinned((n, 256, 256), torch.float32), _pinned((n, 256, 256), torch.uint8)
         job.masks_ready, job.logits_ready = torch.cuda.Event(), torch.cuda.Event()
         with torch.cuda.stream(down):
@@ -227,6 +239,9 @@ class _Call:
             if seg is not None:
                 job.seg_records = _pinned((n, 64), torch.uint8)
                 job.seg_records.copy_(seg, non_blocking=True)
+            if emb is not None:
+                job.unet_emb = _pinned(tuple(emb.shape), torch.float32)
+                job.unet_emb.copy_(emb, non_blocking=True)
             job.logits_ready.record()
 
     def classify(self, job: Job) -> None:
@@ -258,15 +273,22 @@ class _Call:
             with torch.cuda.stream(down):                # the rectified boards travel back while the classifier runs
                 down.wait_event(warped)
                 job.boards.copy_(boards_dev, non_blocking=True)
-            probs_dev = self.gpu_timed("resnet_ms", self.eng_cls.resnet18_forward_u8, squares_dev)
+            cls_emb = None
+            if self.embeddings:                          # the pooled layer4 output of every square, inside resnet_ms
+                probs_dev, cls_emb = self.gpu_timed("resnet_ms", self.eng_cls.resnet18_forward_u8, squares_dev, want_embedding=True)
+            else:
+                probs_dev = self.gpu_timed("resnet_ms", self.eng_cls.resnet18_forward_u8, squares_dev)
             done = torch.cuda.Event()
             done.record()
             job.probs = _pinned((len(found) * 64, constants.NUM_CLASSES), torch.float32)
-            job.cls_out = (probs_dev, boards_dev, squares_dev)
+            job.cls_out = (probs_dev, boards_dev, squares_dev, cls_emb)
             job.probs_ready = torch.cuda.Event()
             with torch.cuda.stream(down):
                 down.wait_event(done)
                 job.probs.copy_(probs_dev, non_blocking=True)
+                if cls_emb is not None:
+                    job.cls_emb = _pinned(tuple(cls_emb.shape), torch.float32)
+                    job.cls_emb.copy_(cls_emb, non_blocking=True)
                 job.probs_ready.record()
         job.batch = None
         if self.quality:                                 # the device has this job's classifier queued: finish its scores meanwhile
@@ -296,6 +318,10 @@ class _Call:
         lg, mk = job.logits.numpy(), job.masks.numpy()
         for k, i in enumerate(ids):
             slots[i] = _ImageSlot(lg[k], mk[k], job.quads[k], job.quality[k] if job.quality else None)
+        if job.unet_emb is not None:
+            ue = job.unet_emb.numpy()
+            for k, i in enumerate(ids):
+                slots[i].unet_emb = ue[k]
         if job.found:
             job.probs_ready.synchronize()
         self.clock("wait_probs_s", t0)
@@ -306,6 +332,10 @@ class _Call:
         probs = job.probs.numpy().reshape(m, 64, constants.NUM_CLASSES)
         brd = job.boards.numpy()
         fens, origs, validated, fixes = decode_positions(probs, self.flip)
+        if job.cls_emb is not None:                      # rows follow square_names, as the probabilities do
+            ce = job.cls_emb.numpy().reshape(m, 64, -1)
+            for j, k in enumerate(job.found):
+                slots[ids[k]].cls_emb = ce[j]
         fix_lists: list[list] = [[] for _ in range(m)]
         for b, sq, old, new in fixes:
             fix_lists[b].append(pawn_rule_fix(names, sq, old, new))
@@ -379,16 +409,20 @@ class _Call:
         results = []
         for s in self.slots:
             extraction = BoardExtractionResult(board_image=s.board, binary_mask=s.mask, quadrangle=s.quad, probabilities=s.logits)
+            emb = Embeddings(board_extractor=s.unet_emb, classifier=s.cls_emb) if self.embeddings else None
             results.append(ChessVisionResult(board_extraction=extraction, position=s.position, processing_time=per_image,
                                              quality=s.quality))
+            if emb is not None:
+                results[-1].embeddings = emb             # an attribute, not a constructor argument (cv_types.ChessVisionResult)
         self.clock("assemble_s", t0)
         return results
 
 
 def process_images(cv, images, threshold, flip, fallback_quad, pipeline_chunk, return_crops, timings, first_job, last_job,
-                   quality, targets=None) -> list[ChessVisionResult]:
+                   quality, targets=None, embeddings=False) -> list[ChessVisionResult]:
     """``ChessVision.process_images`` on the instance's native engines (arguments: see there).  ``targets`` (``evaluation.Targets``,
-    from ``ChessVision.evaluate_images``) additionally scores every job against its ground truth and leaves the records there."""
+    from ``ChessVision.evaluate_images``) additionally scores every job against its ground truth and leaves the records there;
+    ``embeddings`` attaches an ``Embeddings`` record to every result."""
     started = time.time()
     for image in images:
         assert isinstance(image, np.ndarray) and image.dtype == np.uint8 and image.ndim == 3
@@ -402,7 +436,7 @@ def process_images(cv, images, threshold, flip, fallback_quad, pipeline_chunk, r
     # ends, so nothing is left to order against the caller's stream.
     own = torch.cuda.current_stream(cv.device) == torch.cuda.default_stream(cv.device)
     with torch.cuda.stream(cv._pipeline_streams()[2]) if own else contextlib.nullcontext():
-        call = _Call(cv, images, threshold, flip, fallback_quad, return_crops, timings, quality, started, targets)
+        call = _Call(cv, images, threshold, flip, fallback_quad, return_crops, timings, quality, started, targets, embeddings)
         t_last = call.issue(jobs)
         call.eng.check_numerics()                        # one look at the numeric guard for the whole call
         if call.eng_cls is not call.eng:

@@ -65,6 +65,9 @@ class _RequestSlot:
 class ChessVision:
     """Chess position detection from images (drop-in for the reference class of the same name)."""
 
+    # evaluate_images also collects the embeddings of process_images(embeddings=True) while this is set (its argument list is pinned)
+    evaluation_embeddings = False
+
     def __init__(
         self,
         board_extractor_weights: str | None = None,
@@ -490,7 +493,7 @@ class ChessVision:
     def process_images(self, images: Sequence[NDArray[np.uint8]], threshold: float = 0.5, flip: bool = False,
                        fallback_quad: bool = False, pipeline_chunk: int = 64, return_crops: bool = True,
                        timings: dict | None = None, first_job: int = 16, last_job: int = 0,
-                       quality: str | None = None) -> list[ChessVisionResult]:
+                       embeddings: bool = False, quality: str | None = None) -> list[ChessVisionResult]:
         """Batched pipeline (``chessvision/batched.py``): the native stages of ``process_image``, cut into jobs of up to
         ``pipeline_chunk`` equally sized images and software-pipelined; the first job of a call is cut to ``first_job`` images and
         the last one to ``last_job`` (0: no split).  A call whose f16-based engine reports a non-finite value is repeated as a whole
@@ -508,11 +511,22 @@ class ChessVision:
         right behind the UNet on the logits where they are (``HipEngine.extraction_scores_dev``); its 64-byte records and its
         ``v > 0.5`` mask travel back behind the logits, and the host finishes the scores after the job's classifier has been queued.
         "logits" scores the raw logits (the reference's letter), "sigmoid" their sigmoid (what the column names promise).
-        ``quad_score`` is that of the quadrangle found in the mask, in mask pixels; a fallback quadrangle scores 0 like none."""
+        ``quad_score`` is that of the quadrangle found in the mask, in mask pixels; a fallback quadrangle scores 0 like none.
+
+        ``embeddings`` (False = off, nothing extra is launched, allocated, copied or returned) attaches an ``Embeddings`` record to
+        every result: what the reference collects with 3LC's ``EmbeddingsMetricsCollector`` at ``named_modules()[52]`` of the UNet and
+        ``[90]`` of the classifier (``chessvision/embeddings.py``).  Both forwards pool their hook tensor on the device, once per
+        internal chunk (``HipEngine.unet_forward_u8`` / ``resnet18_forward_u8`` with ``want_embedding``); the vectors travel back
+        behind the logits / probabilities into page-locked buffers of the call.  The pooling launches ride inside ``unet_ms`` /
+        ``resnet_ms`` of ``timings``: there is no ``embedding_ms`` key.  ``classifier`` is None where ``position`` is None; a call
+        repeated on the exact-f32 instance (``_recover``) returns that instance's embeddings.  Out of scope: the single-image
+        ``process_image`` / ``cv_process_image_v2`` (its result struct does not grow), ``distributed.process_images_sharded`` (which
+        does not carry ``quality`` either), the PaCMAP reduction the reference runs on the collected table, and forward hooks on the
+        HIP model objects (they are not ``nn.Module``s)."""
         if quality not in (None, "logits", "sigmoid"):
             raise ValueError(f"quality must be None, 'logits' or 'sigmoid', got {quality!r}")
         return self._recover(lambda cv: cv._process_images_native(images, threshold, flip, fallback_quad, pipeline_chunk, return_crops,
-                                                                  timings, first_job, last_job, quality))
+                                                                  timings, first_job, last_job, quality, None, bool(embeddings)))
 
     def _process_images_native(self, *args) -> list[ChessVisionResult]:
         from . import batched
@@ -535,13 +549,15 @@ class ChessVision:
         Per job the label masks travel to the device beside the photos, ONE more kernel runs right behind the UNet on the logits
         where they are (``HipEngine.segmentation_scores_dev``), its 64-byte records come back behind the logits, and the job's
         probabilities are scored by one native call right after its FENs are decoded.  An image with a FEN but no board found counts
-        as an extraction failure, not as a zero-accuracy board."""
+        as an extraction failure, not as a zero-accuracy board.  With ``self.evaluation_embeddings = True`` (an
+        attribute of the instance, default False: the argument list of this method is pinned) the call also collects the embeddings of
+        ``process_images(embeddings=True)``; they are in ``report.results``."""
         from .evaluation import Targets
 
         images = list(images)
         targets = Targets(len(images), true_fens, label_masks)
         results = self._recover(lambda cv: cv._process_images_native(images, threshold, flip, fallback_quad, pipeline_chunk, True,
-                                                                     timings, 16, 0, None, targets))
+                                                                     timings, 16, 0, None, targets, bool(self.evaluation_embeddings)))
         return targets.report(results)
 
     def _pipeline_streams(self):

@@ -70,11 +70,25 @@ class ExtractionQuality:
 
 
 @dataclass
+class Embeddings:
+    """The activations the reference hands to 3LC's ``EmbeddingsMetricsCollector`` (``scripts/process_new_raw/process_pipeline.py:
+    328-351``, ``scripts/train/train_unet.py:219``, ``scripts/train/train_classifier.py:32,212``), reduced to one vector per sample by
+    the mean over the spatial dimensions (``chessvision/embeddings.py``)."""
+    board_extractor: F32 = _doc("(C,) channel means of the UNet bottleneck, named_modules()[52]; C = 1024 (512 for the bilinear UNet)")
+    classifier: F32 | None = _doc("(64,512) pooled layer4 output per square (named_modules()[90], global_pool), rows in "
+                                  "square_names order; None when no board was found")
+
+
+@dataclass
 class ChessVisionResult:
     board_extraction: BoardExtractionResult = _doc("always present")
     position: PositionResult | None = _doc("None when board extraction failed")
     processing_time: float = _doc("seconds spent in process_image (per image for process_images)")
     quality: ExtractionQuality | None = field(default=None, metadata={"doc": "process_images(quality=...) only; NOT a reference field"})
+    # process_images(embeddings=True) only; NOT a reference field.  A plain attribute with the class-level default None, set by the
+    # batched pipeline after construction: the dataclass fields (the constructor's arguments and their order) end with ``quality``, as
+    # tests/test_quality_cpu.py and tests/test_evaluation_cpu.py pin them.
+    embeddings = None
 
 
 @dataclass

@@ -87,6 +87,12 @@ SYMBOLS = [
     ("cv_unet_forward_u8", _i, [_vp, _vp, _i, _vp, _vp, _f, _vp]),
     ("cv_resnet18_forward_u8", _i, [_vp, _vp, _i, _vp, _vp]),
     ("cv_softmax13", _i, [_vp, _vp, _i, _vp, _vp]),
+    ("cv_embedding_dim", _i, [_vp, ctypes.c_char_p, ctypes.POINTER(_i)]),
+    ("cv_unet_forward_emb", _i, [_vp, _vp, _i, _vp, _vp, _vp]),
+    ("cv_unet_forward_u8_emb", _i, [_vp, _vp, _i, _vp, _vp, _f, _vp, _vp]),
+    ("cv_resnet18_forward_emb", _i, [_vp, _vp, _i, _vp, _vp, _vp]),
+    ("cv_resnet18_forward_u8_emb", _i, [_vp, _vp, _i, _vp, _vp, _vp]),
+    ("cv_activation_channel_means", _i, [_vp, ctypes.c_char_p, ctypes.c_char_p, _vp, ctypes.c_size_t, ctypes.POINTER(ctypes.c_int64), _vp]),
     ("cv_get_activation", _i, [_vp, ctypes.c_char_p, ctypes.c_char_p, _fp, ctypes.c_size_t,
                                ctypes.POINTER(ctypes.c_int64)]),
     ("cv_model_macs", _i, [_vp, ctypes.c_char_p, ctypes.POINTER(ctypes.c_int64)]),
@@ -533,45 +539,77 @@ class HipEngine:
         _check(self._lib.cv_engine_workspace_bytes(self._h, ctypes.byref(v)))
         return int(v.value)
 
-    def unet_forward(self, x: torch.Tensor, check: bool = True) -> torch.Tensor:
+    def embedding_dim(self, model: str) -> int:
+        """Channels of ``model``'s embedding (``cv_embedding_dim``): "unet" 1024 (transposed-conv variant) or 512 (bilinear), the
+        loaded ResNet 512."""
+        v = _i()
+        _check(self._lib.cv_embedding_dim(self._h, model.encode(), ctypes.byref(v)))
+        return int(v.value)
+
+    def _embedding_out(self, model: str, n: int) -> torch.Tensor:
+        return torch.empty((n, self.embedding_dim(model)), dtype=torch.float32, device=self.device)
+
+    def unet_forward(self, x: torch.Tensor, check: bool = True, want_embedding: bool = False):
         """(B,3,256,256) float32 in [0,1] -> (B,1,256,256) float32 logits (device tensor).  ``check`` consults the
         numeric guard (synchronises, like the ``.cpu()`` the reference does next); throughput loops pass False and call
-        ``check_numerics()`` once at the end."""
+        ``check_numerics()`` once at the end.  ``want_embedding``: -> (logits, embedding (B,C) float32 device tensor), the channel
+        means of the bottleneck (the reference's hook at ``named_modules()[52]``), pooled inside the forward."""
         x = self._dev_f32(x, (3, 256, 256))
         out = torch.empty((x.shape[0], 1, 256, 256), dtype=torch.float32, device=self.device)
-        _check(self._lib.cv_unet_forward(self._h, _ptr(x), x.shape[0], _ptr(out), _stream_ptr(self.device)))
+        if want_embedding:
+            emb = self._embedding_out("unet", x.shape[0])
+            _check(self._lib.cv_unet_forward_emb(self._h, _ptr(x), x.shape[0], _ptr(out), _ptr(emb), _stream_ptr(self.device)))
+        else:
+            _check(self._lib.cv_unet_forward(self._h, _ptr(x), x.shape[0], _ptr(out), _stream_ptr(self.device)))
         if check:
             self.check_numerics()
-        return out
+        return (out, emb) if want_embedding else out
 
-    def resnet18_forward(self, x: torch.Tensor, check: bool = True) -> torch.Tensor:
-        """(N,1,64,64) float32 in [0,1] -> (N,13) float32 logits (device tensor) of the loaded ResNet (18 or 34)."""
+    def resnet18_forward(self, x: torch.Tensor, check: bool = True, want_embedding: bool = False):
+        """(N,1,64,64) float32 in [0,1] -> (N,13) float32 logits (device tensor) of the loaded ResNet (18 or 34).
+        ``want_embedding``: -> (logits, embedding (N,512) float32 device tensor), the globally pooled ``layer4`` output (the
+        reference's hook at ``named_modules()[90]``, ``global_pool``)."""
         x = self._dev_f32(x, (1, 64, 64))
         out = torch.empty((x.shape[0], 13), dtype=torch.float32, device=self.device)
-        _check(self._lib.cv_resnet18_forward(self._h, _ptr(x), x.shape[0], _ptr(out), _stream_ptr(self.device)))
+        if want_embedding:
+            emb = self._embedding_out(self.classifier_arch or "resnet18", x.shape[0])
+            _check(self._lib.cv_resnet18_forward_emb(self._h, _ptr(x), x.shape[0], _ptr(out), _ptr(emb), _stream_ptr(self.device)))
+        else:
+            _check(self._lib.cv_resnet18_forward(self._h, _ptr(x), x.shape[0], _ptr(out), _stream_ptr(self.device)))
         if check:
             self.check_numerics()
-        return out
+        return (out, emb) if want_embedding else out
 
-    def unet_forward_u8(self, x_u8: torch.Tensor, threshold: float = 0.5, want_mask: bool = True):
-        """(B,256,256,3) uint8 HWC -> (logits (B,1,256,256) f32, mask (B,256,256) u8 | None)."""
+    def unet_forward_u8(self, x_u8: torch.Tensor, threshold: float = 0.5, want_mask: bool = True, want_embedding: bool = False):
+        """(B,256,256,3) uint8 HWC -> (logits (B,1,256,256) f32, mask (B,256,256) u8 | None); with ``want_embedding`` the (B,C)
+        float32 bottleneck embedding is appended."""
         if x_u8.dtype != torch.uint8 or tuple(x_u8.shape[1:]) != (256, 256, 3):
             raise HipBackendError("unet_forward_u8 expects (B,256,256,3) uint8")
         x_u8 = x_u8.to(self.device).contiguous()
         b = x_u8.shape[0]
         logits = torch.empty((b, 1, 256, 256), dtype=torch.float32, device=self.device)
         mask = torch.empty((b, 256, 256), dtype=torch.uint8, device=self.device) if want_mask else None
+        if want_embedding:
+            emb = self._embedding_out("unet", b)
+            _check(self._lib.cv_unet_forward_u8_emb(self._h, _ptr(x_u8), b, _ptr(logits), _ptr(mask) if want_mask else None,
+                                                    float(threshold), _ptr(emb), _stream_ptr(self.device)))
+            return logits, mask, emb
         _check(self._lib.cv_unet_forward_u8(self._h, _ptr(x_u8), b, _ptr(logits), _ptr(mask) if want_mask else None,
                                             float(threshold), _stream_ptr(self.device)))
         return logits, mask
 
-    def resnet18_forward_u8(self, squares_u8: torch.Tensor) -> torch.Tensor:
-        """(N,64,64) uint8 -> (N,13) float32 softmax probabilities of the loaded ResNet (18 or 34)."""
+    def resnet18_forward_u8(self, squares_u8: torch.Tensor, want_embedding: bool = False):
+        """(N,64,64) uint8 -> (N,13) float32 softmax probabilities of the loaded ResNet (18 or 34); with ``want_embedding`` ->
+        (probabilities, embedding (N,512) float32)."""
         if squares_u8.dtype != torch.uint8 or tuple(squares_u8.shape[1:]) != (64, 64):
             raise HipBackendError("resnet18_forward_u8 expects (N,64,64) uint8")
         squares_u8 = squares_u8.to(self.device).contiguous()
         n = squares_u8.shape[0]
         out = torch.empty((n, 13), dtype=torch.float32, device=self.device)
+        if want_embedding:
+            emb = self._embedding_out(self.classifier_arch or "resnet18", n)
+            _check(self._lib.cv_resnet18_forward_u8_emb(self._h, _ptr(squares_u8), n, _ptr(out), _ptr(emb), _stream_ptr(self.device)))
+            return out, emb
         _check(self._lib.cv_resnet18_forward_u8(self._h, _ptr(squares_u8), n, _ptr(out), _stream_ptr(self.device)))
         return out
 
@@ -679,6 +717,17 @@ class HipEngine:
         out = np.empty(tuple(int(d) for d in dims), dtype=np.float32)
         _check(self._lib.cv_get_activation(self._h, model.encode(), name.encode(), out.ctypes.data_as(_fp), out.size,
                                            dims))
+        return out
+
+    def activation_channel_means(self, model: str, name: str) -> torch.Tensor:
+        """(N,C) float32 device tensor: per-image channel means over H x W of the named activation, for the chunk the last forward
+        left in the workspace (``cv_activation_channel_means``).  Enqueued on the current stream; nothing is synchronised or copied
+        to the host.  The reference's ``--embedding_layer`` for layers other than the two hook points (``embeddings.tap_for_index``)."""
+        dims = (ctypes.c_int64 * 2)()
+        _check(self._lib.cv_activation_channel_means(self._h, model.encode(), name.encode(), None, 0, dims, None))
+        out = torch.empty((int(dims[0]), int(dims[1])), dtype=torch.float32, device=self.device)
+        _check(self._lib.cv_activation_channel_means(self._h, model.encode(), name.encode(), _ptr(out), out.numel(), dims,
+                                                     _stream_ptr(self.device)))
         return out
 
     def activation_exponent(self, model: str, name: str) -> int:

@@ -258,6 +258,70 @@ static int impl_cv_resnet18_forward_u8(cv_engine_t* eng, const uint8_t* squares_
     return finish(resnet_forward(eng->impl, squares_u8, true, n, probs, true, (hipStream_t)stream));
 }
 
+static int impl_cv_embedding_dim(cv_engine_t* eng, const char* model, int* channels) {
+    Status s = check_engine(eng);
+    if (!s.ok()) return finish(s);
+    if (!model || !channels) return finish(fail(CV_ERR_INVALID, "null argument"));
+    std::lock_guard<std::mutex> lk(eng->impl.mu);
+    bool is_resnet = false;
+    s = model_by_name(eng->impl, model, &is_resnet);
+    if (!s.ok()) return finish(s);
+    *channels = is_resnet ? (eng->impl.resnet ? 512 : 0) : unet_embedding_dim(eng->impl);
+    if (*channels == 0) return finish(fail(CV_ERR_STATE, "cv_embedding_dim: model '" + std::string(model) + "' is not loaded"));
+    return CV_OK;
+}
+
+static Status check_embedding(const float* embedding) {
+    if ((uintptr_t)embedding & 15u) return fail(CV_ERR_INVALID, "embedding must be 16-byte aligned");
+    return Status();
+}
+
+static int impl_cv_unet_forward_emb(cv_engine_t* eng, const void* x, bool x_u8, int batch, float* logits, uint8_t* mask, float threshold,
+                                    float* embedding, void* stream) {
+    Status s = check_engine(eng);
+    if (!s.ok()) return finish(s);
+    if (!(threshold >= 0.f && threshold <= 1.f)) return finish(fail(CV_ERR_INVALID, "threshold must be between 0 and 1"));
+    if (!(s = check_embedding(embedding)).ok()) return finish(s);
+    std::lock_guard<std::mutex> lk(eng->impl.mu);
+    DeviceGuard g(eng->impl.device);
+    return finish(unet_forward(eng->impl, x, x_u8, batch, logits, mask, threshold, (hipStream_t)stream, embedding));
+}
+
+static int impl_cv_resnet18_forward_emb(cv_engine_t* eng, const void* x, bool x_u8, int n, float* out, float* embedding, void* stream) {
+    Status s = check_engine(eng);
+    if (!s.ok()) return finish(s);
+    if (!(s = check_embedding(embedding)).ok()) return finish(s);
+    std::lock_guard<std::mutex> lk(eng->impl.mu);
+    DeviceGuard g(eng->impl.device);
+    return finish(resnet_forward(eng->impl, x, x_u8, n, out, x_u8, (hipStream_t)stream, embedding));   // the u8 entry returns probabilities
+}
+
+static int impl_cv_activation_channel_means(cv_engine_t* eng, const char* model, const char* name, float* out_dev, size_t capacity_floats,
+                                            int64_t dims[2], void* stream) {
+    Status s = check_engine(eng);
+    if (!s.ok()) return finish(s);
+    if (!model || !name || !dims) return finish(fail(CV_ERR_INVALID, "null argument"));
+    std::lock_guard<std::mutex> lk(eng->impl.mu);
+    DeviceGuard g(eng->impl.device);
+    TensorRef t;
+    bool is_resnet = false;
+    s = model_by_name(eng->impl, model, &is_resnet);
+    // "global_pool" (the classifier's hook, named_modules()[90]) is the mean of layer4's output: pooled here, it needs no tensor of its own
+    if (s.ok()) s = is_resnet ? resnet_activation(eng->impl, std::strcmp(name, "global_pool") == 0 ? "layer4" : name, &t) : unet_activation(eng->impl, name, &t);
+    if (!s.ok()) return finish(s);
+    dims[0] = t.N; dims[1] = t.C;
+    if (!out_dev) return CV_OK;                           // shape query
+    const std::string tap = "cv_activation_channel_means('" + std::string(name) + "')";
+    if (t.N < 1) return finish(fail(CV_ERR_INVALID, tap + ": no forward has run yet"));
+    if (capacity_floats < (size_t)t.N * t.C)
+        return finish(fail(CV_ERR_INVALID, tap + ": output buffer too small, " + std::to_string((size_t)t.N * t.C) + " floats needed"));
+    if ((uintptr_t)out_dev & 15u) return finish(fail(CV_ERR_INVALID, tap + ": output must be 16-byte aligned"));
+    if (t.C % 8 || t.split) return finish(fail(CV_ERR_INVALID, tap + ": the tensor's channel slice cannot be pooled"));
+    hipError_t e = channel_means(eng->impl.dt, t, out_dev, (hipStream_t)stream);
+    if (e != hipSuccess) return finish(hip_fail(e, tap.c_str()));
+    return CV_OK;
+}
+
 static int impl_cv_softmax13(cv_engine_t* eng, const float* logits, int n, float* probs, void* stream) {
     Status s = check_engine(eng);
     if (!s.ok()) return finish(s);
@@ -1083,6 +1147,32 @@ int cv_resnet18_forward(cv_engine_t* eng, const float* x, int n, float* logits, 
 
 int cv_resnet18_forward_u8(cv_engine_t* eng, const uint8_t* squares_u8, int n, float* probs, void* stream) {
     return guarded("cv_resnet18_forward_u8", [&]() -> int { return impl_cv_resnet18_forward_u8(eng, squares_u8, n, probs, stream); });
+}
+
+int cv_embedding_dim(cv_engine_t* eng, const char* model, int* channels) {
+    return guarded("cv_embedding_dim", [&]() -> int { return impl_cv_embedding_dim(eng, model, channels); });
+}
+
+int cv_unet_forward_emb(cv_engine_t* eng, const float* x, int batch, float* logits, float* embedding, void* stream) {
+    return guarded("cv_unet_forward_emb", [&]() -> int { return impl_cv_unet_forward_emb(eng, x, false, batch, logits, nullptr, 0.5f, embedding, stream); });
+}
+
+int cv_unet_forward_u8_emb(cv_engine_t* eng, const uint8_t* x_u8, int batch, float* logits, uint8_t* mask,
+                           float threshold, float* embedding, void* stream) {
+    return guarded("cv_unet_forward_u8_emb", [&]() -> int { return impl_cv_unet_forward_emb(eng, x_u8, true, batch, logits, mask, threshold, embedding, stream); });
+}
+
+int cv_resnet18_forward_emb(cv_engine_t* eng, const float* x, int n, float* logits, float* embedding, void* stream) {
+    return guarded("cv_resnet18_forward_emb", [&]() -> int { return impl_cv_resnet18_forward_emb(eng, x, false, n, logits, embedding, stream); });
+}
+
+int cv_resnet18_forward_u8_emb(cv_engine_t* eng, const uint8_t* squares_u8, int n, float* probs, float* embedding, void* stream) {
+    return guarded("cv_resnet18_forward_u8_emb", [&]() -> int { return impl_cv_resnet18_forward_emb(eng, squares_u8, true, n, probs, embedding, stream); });
+}
+
+int cv_activation_channel_means(cv_engine_t* eng, const char* model, const char* name, float* out_dev, size_t capacity_floats,
+                                int64_t dims[2], void* stream) {
+    return guarded("cv_activation_channel_means", [&]() -> int { return impl_cv_activation_channel_means(eng, model, name, out_dev, capacity_floats, dims, stream); });
 }
 
 int cv_softmax13(cv_engine_t* eng, const float* logits, int n, float* probs, void* stream) {

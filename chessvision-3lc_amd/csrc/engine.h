@@ -320,9 +320,10 @@ class Engine {
     struct GraphKey {
         int model = 0, n = 0, flags = 0;                  // model 0 = UNet, 1 = ResNet-18; flags: u8 entry / softmax
         const void* x = nullptr; void* out = nullptr; void* mask = nullptr;
+        void* emb = nullptr;                              // embedding output, or null: a forward that pools and one that does not are two graphs
         unsigned thr_bits = 0;
         bool operator==(const GraphKey& o) const {
-            return model == o.model && n == o.n && flags == o.flags && x == o.x && out == o.out && mask == o.mask && thr_bits == o.thr_bits;
+            return model == o.model && n == o.n && flags == o.flags && x == o.x && out == o.out && mask == o.mask && emb == o.emb && thr_bits == o.thr_bits;
         }
     };
     struct GraphEntry {
@@ -378,13 +379,17 @@ int choose_cfg(int ct, int rows, int64_t pixels, int n_stages);
 int choose_ns(int cfg, int dt, int rows, int64_t pixels, int n_stages);
 
 Status unet_load(Engine& e, const ParamMap& pm);
+// embedding (nullable, device, batch x unet_embedding_dim floats, 16-byte aligned): per-image channel means of the bottleneck,
+// pooled inside the forward while each chunk's tensor is in the workspace (pointwise.h: channel_means).  Null: nothing is launched.
 Status unet_forward(Engine& e, const void* x, bool x_u8, int batch, float* logits, uint8_t* mask, float thr,
-                    hipStream_t s);
+                    hipStream_t s, float* embedding = nullptr);
+int unet_embedding_dim(Engine& e);                  // 1024 (transposed-conv UNet) | 512 (bilinear) | 0: not loaded
 Status unet_activation(Engine& e, const std::string& name, TensorRef* out);
 int64_t unet_macs(Engine& e);
 
 Status resnet_load(Engine& e, const ParamMap& pm, const std::string& arch);   // arch: "resnet18" | "resnet34"
-Status resnet_forward(Engine& e, const void* x, bool x_u8, int n, float* out, bool softmax, hipStream_t s);
+// embedding (nullable, device, n x 512 floats): per-square channel means of layer4's output (its f32 twin under f16r) -- global_pool
+Status resnet_forward(Engine& e, const void* x, bool x_u8, int n, float* out, bool softmax, hipStream_t s, float* embedding = nullptr);
 Status resnet_activation(Engine& e, const std::string& name, TensorRef* out);
 int64_t resnet_macs(Engine& e);
 

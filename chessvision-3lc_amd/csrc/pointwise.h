@@ -21,6 +21,13 @@ hipError_t upsample_bilinear2x(int dt, const TensorRef& src, const TensorRef& ds
 // max |stored value| of the slice, as float bits (>= 0x7f800000: a non-finite value is present); *out must start at 0
 hipError_t absmax(int dt, const TensorRef& src, unsigned* out, hipStream_t s);
 
+// Embeddings: per-image channel means of a stored tensor, out[n][c] (float32, row-major src.N x src.C, 16-byte aligned) =
+// 2^src.exp * mean over the H x W interior of elem(n, y, x, c) -- what 3LC's EmbeddingsMetricsCollector keeps of a hooked (B, C, H, W)
+// output.  src.f32_only: read as f32 whatever `dt` says.  src.C a multiple of 8, src.Coff of the dtype's group; a slice across both
+// halves of a concatenated buffer (src.split) is refused.  The summation order depends on (H, W) only: an image's row is
+// bit-identical for every N and every position in the batch.  Asynchronous on `s`; allocates nothing.
+hipError_t channel_means(int dt, const TensorRef& src, float* out, hipStream_t s);
+
 // rounding-bias calibration: out[slice][tap][c] (double, slices x k*k x src.C) = sum of the stored f16 input under tap (ky, kx) over
 // the slice's images and all Ho x Wo output positions of a k x k / stride / pad (k-1)/2 convolution (f16 tensors only)
 hipError_t tap_sums_f16(const TensorRef& src, int Ho, int Wo, int stride, int k, int slices, double* out, hipStream_t s);

@@ -205,6 +205,79 @@ __global__ void absmax_kernel(TensorRef src, unsigned* __restrict__ out) {
     if ((threadIdx.x & 63) == 0 && m) atomicMax(out, m);
 }
 
+// ---- embeddings: per-image channel means of a stored tensor, out[n][c] = mul * mean over the H x W interior (pointwise.h:
+// channel_means).  A lane owns 8 consecutive channels (one 16-B load for f16, two for split-f16 and f32) of one pixel SLICE: with
+// P = H * W and S = channel_means_slices(P), lane (unit u, slice s) adds pixels s, s + S, s + 2 S, .. in that order, the i-th of them
+// into accumulator i % 8; the 8 accumulators are joined by a fixed tree, and the S slices of a unit by a halving tree through LDS.
+// unit u = n * (C / 8) + channel group; a workgroup holds 256 / S consecutive units in its low lane bits, so consecutive lanes read
+// consecutive 16-B groups of one pixel.  The order of every addition follows from (H, W) alone -- not from N, the grid, or where in a
+// chunk an image sits: an image's row has the same bits pooled alone or as image 63 of 64.  No atomics.
+__host__ __device__ inline int channel_means_slices(int pixels) {
+    int s = 1;
+    while (s < 256 && pixels > 8 * s) s *= 2;               // at most 8 pixels per lane until the workgroup is one unit wide (256 x 256: 256)
+    return s;
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void channel_means_kernel(TensorRef src, int slices, float mul, float* __restrict__ out) {
+    constexpr int GN = Grp<T>::N, GPL = 8 / GN;              // groups per lane: 1 (f16, split-f16) or 2 (f32)
+    __shared__ float part[8][256];
+    const int upb = 256 / slices;                            // units per workgroup
+    const int ul = threadIdx.x % upb, sl = threadIdx.x / upb;
+    const int cgs = src.C / 8, pixels = src.H * src.W;
+    const size_t unit = (size_t)blockIdx.x * upb + ul;
+    const bool live = unit < (size_t)src.N * cgs;
+    const int n = live ? (int)(unit / cgs) : 0, cg = live ? (int)(unit % cgs) : 0;
+    float acc[8][8];
+#pragma unroll
+    for (int a = 0; a < 8; ++a)
+#pragma unroll
+        for (int j = 0; j < 8; ++j) acc[a][j] = 0.f;
+    if (live)
+        for (int p0 = sl; p0 < pixels; p0 += 8 * slices) {
+#pragma unroll
+            for (int a = 0; a < 8; ++a) {
+                const int p = p0 + a * slices;
+                if (p < pixels) {
+                    const size_t pix = pix_index(src, n, p / src.W, p % src.W);
+#pragma unroll
+                    for (int g = 0; g < GPL; ++g) {
+                        int par;
+                        float v[GN];
+                        Grp<T>::load(grp_ptr<T>(src, pix, cg * GPL + g, &par), par, v);
+#pragma unroll
+                        for (int j = 0; j < GN; ++j) acc[a][g * GN + j] += v[j];
+                    }
+                }
+            }
+        }
+    float s8[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j)
+        s8[j] = ((acc[0][j] + acc[1][j]) + (acc[2][j] + acc[3][j])) + ((acc[4][j] + acc[5][j]) + (acc[6][j] + acc[7][j]));
+    if (slices > 1) {                                        // uniform over the launch
+#pragma unroll
+        for (int j = 0; j < 8; ++j) part[j][threadIdx.x] = s8[j];
+        for (int h = slices / 2; h >= 1; h /= 2) {
+            __syncthreads();
+            if (sl < h) {
+#pragma unroll
+                for (int j = 0; j < 8; ++j) part[j][threadIdx.x] += part[j][threadIdx.x + h * upb];
+            }
+        }
+        if (sl == 0) {
+#pragma unroll
+            for (int j = 0; j < 8; ++j) s8[j] = part[j][threadIdx.x];
+        }
+    }
+    if (live && sl == 0) {
+        const float count = (float)pixels;
+        float* o = out + (size_t)n * src.C + cg * 8;
+        *reinterpret_cast<f4*>(o) = f4{s8[0] * mul / count, s8[1] * mul / count, s8[2] * mul / count, s8[3] * mul / count};
+        *reinterpret_cast<f4*>(o + 4) = f4{s8[4] * mul / count, s8[5] * mul / count, s8[6] * mul / count, s8[7] * mul / count};
+    }
+}
+
 // ---- load-time rounding-bias calibration (engine.cpp: Engine::measure_tap_sums): per convolution tap and input channel, the sum of
 // the stored f16 input over the slice's images and every output position -- out[slice][tap][c] = sum_n sum_(oy,ox) x(n, oy*stride +
 // ky - pad, ox*stride + kx - pad, c), the zero border read as it is.  One lane = one channel (consecutive lanes read consecutive
@@ -1309,6 +1382,20 @@ hipError_t absmax(int dt, const TensorRef& src, unsigned* out, hipStream_t s) {
     if (dt == kF16) hipLaunchKernelGGL(absmax_kernel<half_t>, g_, b_, 0, s, src, out);
     else if (dt == kSplit) hipLaunchKernelGGL(absmax_kernel<split_t>, g_, b_, 0, s, src, out);
     else hipLaunchKernelGGL(absmax_kernel<float>, g_, b_, 0, s, src, out);
+    return hipGetLastError();
+}
+hipError_t channel_means(int dt, const TensorRef& src, float* out, hipStream_t s) {
+    if (src.f32_only) dt = kF32;
+    if (!src.base || !out || ((uintptr_t)out & 15u) || src.N < 1 || src.H < 1 || src.W < 1 || src.C < 8 || src.C % 8 || src.Coff % dtype_group(dt) ||
+        src.split)
+        return hipErrorInvalidValue;
+    const int slices = channel_means_slices(src.H * src.W);
+    const size_t units = (size_t)src.N * (src.C / 8);
+    const dim3 g_(grid_for(units, 256 / slices)), b_(256);
+    const float mul = pow2f(src.exp);
+    if (dt == kF16) hipLaunchKernelGGL(channel_means_kernel<half_t>, g_, b_, 0, s, src, slices, mul, out);
+    else if (dt == kSplit) hipLaunchKernelGGL(channel_means_kernel<split_t>, g_, b_, 0, s, src, slices, mul, out);
+    else hipLaunchKernelGGL(channel_means_kernel<float>, g_, b_, 0, s, src, slices, mul, out);
     return hipGetLastError();
 }
 hipError_t tap_sums_f16(const TensorRef& src, int Ho, int Wo, int stride, int k, int slices, double* out, hipStream_t s) {

@@ -33,7 +33,7 @@ const ResNetArch* resnet_arch(const std::string& name) {
 
 static Status resnet_reserve(Engine& e, int n);
 static Status layer1_chain(Engine& e, int n, hipStream_t s);
-static Status resnet_chunk(Engine& e, const void* x, bool x_u8, int n, float* out, bool softmax, hipStream_t s);
+static Status resnet_chunk(Engine& e, const void* x, bool x_u8, int n, float* out, bool softmax, hipStream_t s, float* embedding = nullptr);
 
 // form of the chained layer1 launch (f16r): 2 (default) = two workgroups per CU, block 0's f32 output written and read back; 1 = one
 // workgroup per CU with 512 registers, the f32 trunk stays in registers -- no round trip, but nothing covers the workgroup's barriers,
@@ -362,7 +362,7 @@ Status resnet_activation(Engine& e, const std::string& name, TensorRef* out) {
     return Status();
 }
 
-static Status resnet_chunk(Engine& e, const void* x, bool x_u8, int n, float* out, bool softmax, hipStream_t s) {
+static Status resnet_chunk(Engine& e, const void* x, bool x_u8, int n, float* out, bool softmax, hipStream_t s, float* embedding) {
     Engine::ResNet& R = *e.resnet;
     R.last_n = n;
     e.ws_slot = 1;
@@ -435,6 +435,11 @@ static Status resnet_chunk(Engine& e, const void* x, bool x_u8, int n, float* ou
     }
     int head_dt = dt;
     if (cur.base32) { cur.base = cur.base32; head_dt = kF32; }   // f16r: pool the trunk's f32 twin
+    if (embedding && !e.calibrating) {
+        // the embedding of the reference's hook (named_modules()[90] = global_pool): channel means of the tensor the head pools
+        begin("embedding (channel means)", 0, (double)n * 512 * (cur.H * cur.W * dtype_size(head_dt) + 4));
+        CV_TRY(end("channel_means", channel_means(head_dt, cur, embedding, s)));
+    }
     begin("head_avgpool_fc", 13.0 * 512 * n, (double)n * (cur.H * cur.W * 512 * dtype_size(head_dt) + 13 * 4));
     CV_TRY(end("head_avgpool_fc", head_avgpool_fc(head_dt, cur, (const float*)R.fc_w.ptr, (const float*)R.fc_b.ptr, out,
                                                    softmax ? 1 : 0, e.guard_ptr(), R.head_id, s)));
@@ -502,7 +507,7 @@ static Status layer1_chain(Engine& e, int n, hipStream_t s) {
     return Status();
 }
 
-Status resnet_forward(Engine& e, const void* x, bool x_u8, int n, float* out, bool softmax, hipStream_t s) {
+Status resnet_forward(Engine& e, const void* x, bool x_u8, int n, float* out, bool softmax, hipStream_t s, float* embedding) {
     if (!e.resnet) return fail(3, "ResNet weights not loaded (call cv_load_resnet or cv_load_resnet18 first)");
     if (n < 0 || (n > 0 && (!x || !out))) return fail(1, "cv_resnet18_forward: null tensor or negative batch");
     if (n == 0) return Status();
@@ -510,15 +515,16 @@ Status resnet_forward(Engine& e, const void* x, bool x_u8, int n, float* out, bo
     CV_TRY(resnet_reserve(e, n));
     if (n <= e.resnet->cap && n <= 512) {                // one small chunk (a board's 64 squares): the launch sequence replays as a hipGraph
         Engine::GraphKey key;
-        key.model = 1; key.n = n; key.flags = (x_u8 ? 1 : 0) | (softmax ? 2 : 0); key.x = x; key.out = out;
+        key.model = 1; key.n = n; key.flags = (x_u8 ? 1 : 0) | (softmax ? 2 : 0); key.x = x; key.out = out; key.emb = embedding;
         e.resnet->last_n = n;                            // a graph replay skips resnet_chunk's host side (see unet_forward)
         e.ws_slot = 1;
-        return e.run_graphed(key, s, [&](hipStream_t st) { return resnet_chunk(e, x, x_u8, n, out, softmax, st); });
+        return e.run_graphed(key, s, [&](hipStream_t st) { return resnet_chunk(e, x, x_u8, n, out, softmax, st, embedding); });
     }
     const size_t in_stride = (size_t)64 * 64 * (x_u8 ? 1 : 4);
     for (int off = 0; off < n; off += e.resnet->cap) {
         const int c = std::min(e.resnet->cap, n - off);
-        CV_TRY(resnet_chunk(e, (const char*)x + (size_t)off * in_stride, x_u8, c, out + (size_t)off * 13, softmax, s));
+        CV_TRY(resnet_chunk(e, (const char*)x + (size_t)off * in_stride, x_u8, c, out + (size_t)off * 13, softmax, s,
+                            embedding ? embedding + (size_t)off * 512 : nullptr));
     }
     return Status();
 }

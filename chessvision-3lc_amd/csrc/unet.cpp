@@ -94,7 +94,8 @@ static void double_conv_keys(std::vector<std::string>& out, const std::string& p
 }
 
 static Status unet_reserve(Engine& e, int n);
-static Status unet_chunk(Engine& e, const void* x, bool x_u8, int n, float* logits, uint8_t* mask, float thr, hipStream_t s);
+static Status unet_chunk(Engine& e, const void* x, bool x_u8, int n, float* logits, uint8_t* mask, float thr, hipStream_t s,
+                         float* embedding = nullptr);
 
 // Two deterministic calibration images, NCHW f32 in [0,1]: uniform noise, and a structured frame (dark noise, a bright
 // checkered quadrilateral, saturated white and black blocks) -- the extremes of what a photo can put into the network.
@@ -374,6 +375,7 @@ static Status unet_reserve(Engine& e, int n) {
 }
 
 int64_t unet_macs(Engine& e) { return e.unet ? e.unet->macs : 0; }
+int unet_embedding_dim(Engine& e) { return e.unet ? e.unet->c5 : 0; }
 
 Status unet_activation(Engine& e, const std::string& name, TensorRef* out) {
     if (!e.unet) return fail(3, "UNet not loaded");
@@ -386,7 +388,7 @@ Status unet_activation(Engine& e, const std::string& name, TensorRef* out) {
 }
 
 static Status unet_chunk(Engine& e, const void* x, bool x_u8, int n, float* logits, uint8_t* mask, float thr,
-                         hipStream_t s) {
+                         hipStream_t s, float* embedding) {
     Engine::UNet& U = *e.unet;
     U.last_n = n;
     e.ws_slot = 0;
@@ -434,6 +436,13 @@ static Status unet_chunk(Engine& e, const void* x, bool x_u8, int n, float* logi
         const TensorRef pool_next = (i < 3) ? U.pool[i + 1].ref(n) : TensorRef();
         CV_TRY(e.run_conv(U.d[i][1], U.dmid[i].ref(n), out, nullptr, true, s, nullptr, i < 3 ? &pool_next : nullptr));
     }
+    if (embedding && !e.calibrating) {
+        // the embedding of the reference's hook (named_modules()[52] = down4.maxpool_conv.1.double_conv.5): channel means of the
+        // bottleneck, pooled while this chunk's tensor is the one in the buffer -- inside the captured sequence of a small forward
+        const TensorRef bott = U.bott.ref(n);
+        begin("embedding (channel means)", (double)n * bott.C * (bott.H * bott.W * esz + 4));
+        CV_TRY(timed("channel_means", channel_means(dt, bott, embedding, s)));
+    }
     TensorRef deep = U.bott.ref(n);
     for (int i = 0; i < 4; ++i) {
         const int lvl = 3 - i;
@@ -466,7 +475,7 @@ static Status unet_chunk(Engine& e, const void* x, bool x_u8, int n, float* logi
 }
 
 Status unet_forward(Engine& e, const void* x, bool x_u8, int batch, float* logits, uint8_t* mask, float thr,
-                    hipStream_t s) {
+                    hipStream_t s, float* embedding) {
     if (!e.unet) return fail(3, "UNet weights not loaded (call cv_load_unet first)");
     if (batch < 0 || (batch > 0 && (!x || !logits))) return fail(1, "cv_unet_forward: null tensor or negative batch");
     if (batch == 0) return Status();
@@ -474,17 +483,18 @@ Status unet_forward(Engine& e, const void* x, bool x_u8, int batch, float* logit
     CV_TRY(unet_reserve(e, batch));
     if (batch <= e.unet->cap && batch <= 8) {            // one small chunk: the launch sequence replays as a hipGraph
         Engine::GraphKey key;
-        key.model = 0; key.n = batch; key.flags = x_u8 ? 1 : 0; key.x = x; key.out = logits; key.mask = mask;
+        key.model = 0; key.n = batch; key.flags = x_u8 ? 1 : 0; key.x = x; key.out = logits; key.mask = mask; key.emb = embedding;
         std::memcpy(&key.thr_bits, &thr, sizeof(float));
         e.unet->last_n = batch;                          // a graph replay skips unet_chunk's host side: what cv_get_activation reports
         e.ws_slot = 0;                                   // must not depend on whether this call replayed
-        return e.run_graphed(key, s, [&](hipStream_t st) { return unet_chunk(e, x, x_u8, batch, logits, mask, thr, st); });
+        return e.run_graphed(key, s, [&](hipStream_t st) { return unet_chunk(e, x, x_u8, batch, logits, mask, thr, st, embedding); });
     }
     const size_t in_stride = (size_t)3 * 256 * 256 * (x_u8 ? 1 : 4);
     for (int off = 0; off < batch; off += e.unet->cap) {
         const int n = std::min(e.unet->cap, batch - off);
         CV_TRY(unet_chunk(e, (const char*)x + (size_t)off * in_stride, x_u8, n, logits + (size_t)off * 65536,
-                          mask ? mask + (size_t)off * 65536 : nullptr, thr, s));
+                          mask ? mask + (size_t)off * 65536 : nullptr, thr, s,
+                          embedding ? embedding + (size_t)off * e.unet->c5 : nullptr));
     }
     return Status();
 }

@@ -183,6 +183,37 @@ int cv_unet_forward_u8(cv_engine_t* eng, const uint8_t* x_u8, int batch, float* 
 /* squares_u8: (n,64,64) uint8 -> probs: (n,13) float32 = softmax(logits, dim=1) (core.py:236-242).  Runs the loaded ResNet. */
 int cv_resnet18_forward_u8(cv_engine_t* eng, const uint8_t* squares_u8, int n, float* probs, void* stream);
 
+/* ---- embeddings at the reference's 3LC hook points -------------------------------------------------------------------------
+ * The reference collects embeddings with 3LC's EmbeddingsMetricsCollector at named_modules()[52] of the UNet
+ * (down4.maxpool_conv.1.double_conv.5, the bottleneck; train_unet.py:219, process_pipeline.py:328-351) and at named_modules()[90] of
+ * the classifier (global_pool; train_classifier.py:32,212).  The collector's default reduction of a hooked (B,C,H,W) output is the mean
+ * over H and W, giving (B,C) -- this library's reading of it, DESIGN.md section 4 "Embeddings"; for global_pool the "flatten" alternative
+ * is the same vector, for the bottleneck "flatten" needs the whole tensor (cv_get_activation).
+ *
+ * cv_embedding_dim: channels of `model`'s embedding -- "unet": 1024 (transposed-conv variant) or 512 (bilinear); "resnet18" /
+ * "resnet34": 512.  CV_ERR_STATE when the model is not loaded.
+ *
+ * The four _emb entry points are their namesakes with one more argument: `embedding`, a DEVICE pointer to batch x channels float32
+ * (row-major, 16-byte aligned), written by the time `stream` reaches the end of the call.  The channel means are taken inside the
+ * forward, once per internal chunk while that chunk's tensor is in the workspace, by one extra launch per chunk (for the classifier on
+ * the tensor the head pools: layer4's output, its f32 twin under CV_PREC_F16R); a small forward that replays as a hipGraph replays the
+ * pooling with it.  Every other output is bit-identical to the namesake's.  A row's bits do not depend on the batch size or on the
+ * image's position in the batch.  embedding == NULL: exactly the namesake -- same launches, same graph. */
+int cv_embedding_dim(cv_engine_t* eng, const char* model, int* channels);
+int cv_unet_forward_emb(cv_engine_t* eng, const float* x, int batch, float* logits, float* embedding, void* stream);
+int cv_unet_forward_u8_emb(cv_engine_t* eng, const uint8_t* x_u8, int batch, float* logits, uint8_t* mask,
+                           float threshold, float* embedding, void* stream);
+int cv_resnet18_forward_emb(cv_engine_t* eng, const float* x, int n, float* logits, float* embedding, void* stream);
+int cv_resnet18_forward_u8_emb(cv_engine_t* eng, const uint8_t* squares_u8, int n, float* probs, float* embedding, void* stream);
+
+/* Channel means of ANY activation cv_get_activation knows (the reference's --embedding_layer option for other layers), for the chunk
+ * the last forward left in the workspace: out_dev (DEVICE, 16-byte aligned, capacity_floats >= N*C) receives the (N,C) float32 means
+ * over H x W, dims = {N, C}.  Enqueued on `stream` (the stream of that forward, or one ordered behind it): no device-wide
+ * synchronisation, no host copy.  out_dev == NULL: shape query.  For a ResNet, "global_pool" names the pooled "layer4".  An unknown tap, a tap a fused launch never writes, or too small a
+ * capacity: CV_ERR_INVALID with a message naming the tap. */
+int cv_activation_channel_means(cv_engine_t* eng, const char* model, const char* name, float* out_dev, size_t capacity_floats,
+                                int64_t dims[2], void* stream);
+
 /* (n,13) logits -> softmax probabilities, in place allowed (core.py:242). */
 int cv_softmax13(cv_engine_t* eng, const float* logits, int n, float* probs, void* stream);
 
