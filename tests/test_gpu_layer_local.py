@@ -10,6 +10,8 @@ the fused last-conv + OutConv, the chained layer1 of f16r, and the kernels witho
 
 Every exposed tap is either checked or in the stated absent set of its engine (layer_local.expected_absent); a tap missing outside that
 set, or exposed inside it, fails the case.  The bars are layer_local.BARS (none is new); max-pools and aliases are bit-exact.
+The cases at ``unet_chunk=2`` / ``resnet_chunk=128`` are followed by the small-batch forms of the DEFAULT chunk sizes
+(``LAYER_LOCAL_AT_DEFAULT_CHUNK``, frozen from the census of tests/test_gpu_batch_sweep.py, whose tripwire keeps the list complete).
 Each case appends its per-edge figures to the parity report of test_gpu_models.py (``_record``); profiles/layer_local_parity.md is made
 from them.
 """
@@ -181,6 +183,88 @@ def test_resnet_stem_and_head_past_2048_squares_in_one_chunk(resnet_engine_4096)
     res = _check(tag, _resnet_taps(eng, arch, out, "logits"), x, sd, prec, picks, ll.expected_absent(sd, prec, chain_form=CHAIN_FORM),
                  only={"act1", "maxpool", "logits"})
     assert [r["edge"] for r in res] == (["act1"] if prec == "f32" else []) + ["maxpool", "logits"]
+    eng.check_numerics()
+
+
+# ---- the launch forms of the DEFAULT chunk sizes ------------------------------------------------------------------------------------
+# The cases above run engines packed for chunks of 2 images / 128 (4096) squares.  The production engines pack for 64 / 16384: wide
+# layers carry 256-row weights and fall back per launch, so a small batch takes other forms there.  This list is frozen from the census of
+# tests/test_gpu_batch_sweep.py: per (model, precision, variant) N = 1 / n = 64 and the smallest member of every other census class that
+# begins at a size small enough to download every tap (UNet N <= 4, ResNet n <= 256).  The sweep's tripwire fails when the planner grows
+# a small-batch form that is not here.
+LAYER_LOCAL_AT_DEFAULT_CHUNK = tuple(
+    # every N up to 8 is a launch form of its own (split-K factors, 8 x 16 / 16 x 16 patches, the transposed convs' tiles)
+    [("unet", prec, variant, n) for prec, variant in (("f32", "convT"), ("f32", "bilinear"), ("f16x3", "convT"), ("f16x3", "bilinear"),
+                                                      ("f16", "convT")) for n in (1, 2, 3, 4)]
+    # 64 = one board; 63 shares its class under f16r only; every other swept size up to 256 begins a class
+    + [("resnet18", prec, "", n) for prec in ("f32", "f16x3", "f16", "f16r") for n in (1, 7, 63, 64, 100, 128, 192, 256)]
+    + [("resnet34", "f16x3", "", n) for n in (1, 7, 63, 64, 65, 100, 256)]
+    + [("resnet34", "f16r", "", n) for n in (1, 7, 63, 64, 100, 256)])
+
+
+class _OneEngineAtATime:
+    """The default-chunk engine of (model, precision, variant), built on first use and closed when another is asked for."""
+
+    def __init__(self):
+        self.key, self.eng, self.sd = None, None, None
+
+    def get(self, model, prec, variant):
+        from chessvision.hip_backend import HipEngine
+
+        if self.key != (model, prec, variant):
+            self.close()
+            for var in ("CHESSVISION_HIP_UNET_CHUNK", "CHESSVISION_HIP_RESNET_CHUNK"):
+                assert var not in os.environ, f"{var} is set: this case is about the library's own chunk sizes"
+            eng = HipEngine(precision=prec)
+            if model == "unet":
+                sd = synth.make_unet(seed=1, bilinear=variant == "bilinear").state_dict()
+                eng.load_unet(sd)
+            else:
+                sd = _resnet(model).state_dict()
+                eng.load_resnet({k: v for k, v in sd.items() if not k.endswith("num_batches_tracked")}, model)
+            self.key, self.eng, self.sd = (model, prec, variant), eng, sd
+        return self.eng, self.sd
+
+    def close(self):
+        if self.eng is not None:
+            eng, self.eng, self.key = self.eng, None, None
+            try:
+                eng.check_numerics()
+            finally:
+                eng.close()
+
+
+@pytest.fixture(scope="module")
+def default_chunk_engines():
+    holder = _OneEngineAtATime()
+    yield holder
+    holder.close()
+
+
+@pytest.mark.parametrize("model, prec, variant, n", LAYER_LOCAL_AT_DEFAULT_CHUNK,
+                         ids=[f"{m}-{p}{'-' + v if v else ''}-{n}" for m, p, v, n in LAYER_LOCAL_AT_DEFAULT_CHUNK])
+def test_default_chunk_small_batch_forms_every_tapped_layer_matches_float64(default_chunk_engines, monkeypatch, model, prec, variant, n):
+    """One forward of ``n`` at the default chunk size, three times on fixed buffers (every listed size is one the engine replays as a
+    hipGraph); then every tap as in the cases above: the last image of the batch, or its last 72 squares."""
+    monkeypatch.delenv("CHESSVISION_HIP_UNET_CHUNK", raising=False)
+    monkeypatch.delenv("CHESSVISION_HIP_RESNET_CHUNK", raising=False)
+    eng, sd = default_chunk_engines.get(model, prec, variant)
+    tag = {"model": model, "variant": variant, "prec": prec, "case": f"default_chunk_{n}"}
+    if model == "unet":
+        x = ll.unet_f32(ll.unet_images_u8(20 + n, ["photo", "border", "photo", "random"][4 - n:]))       # the checked (last) image: random bytes
+        x_dev, out = x.cuda(), torch.empty((n, 1, 256, 256), device="cuda")
+        _repeat_on_fixed_buffers(eng, "cv_unet_forward", x_dev, n, out)
+        assert eng.activation("unet", "inc").shape[0] == n
+        _check(tag, _unet_taps(eng, out.cpu().numpy()), x, sd, prec, [n - 1], ll.expected_absent(sd, prec))
+    else:
+        first = max(0, n - 72)
+        specials = {i: kind for i, kind in ll.specials_from(max(0, n - 40)).items() if i < n}
+        x = ll.squares_f32(ll.squares_u8(30 + n, n, specials))
+        x_dev, out = x.cuda(), torch.empty((n, 13), device="cuda")
+        _repeat_on_fixed_buffers(eng, "cv_resnet18_forward", x_dev, n, out)
+        assert eng.activation(model, "maxpool").shape[0] == n
+        _check(tag, _resnet_taps(eng, model, out.cpu().numpy(), "logits"), x, sd, prec, range(first, n),
+               ll.expected_absent(sd, prec, chain_form=CHAIN_FORM))
     eng.check_numerics()
 
 
