@@ -1,6 +1,7 @@
 """The batched pipeline behind ``ChessVision.process_images`` (new; the reference processes one image per call, core.py:152-195).
 
-Images stay on the device between the two CNNs: INTER_AREA resize -> UNet (u8 in, logits + thresholded mask out); only the 64 KB
+Images stay on the device between the two CNNs: INTER_AREA resize -> UNet (u8 in, logits + thresholded mask out; with
+``resize="antialias"`` the enrichment job's antialiased bilinear resize to float32 and the UNet's float entry); only the 64 KB
 masks come back for the C++ contour stage; the quadrangles go back as 3x3 maps and ONE fused warp+gray+flip+split kernel writes the
 classifier input; the classifier runs with softmax on device; labels, pawn rule and FEN of a whole job are decoded by one native
 call.  Work is cut into jobs of up to ``pipeline_chunk`` equally sized images (``plan_jobs``) and software-pipelined
@@ -28,6 +29,7 @@ from .distributed import host_threads
 from .hip_backend import (SCORE_RECORD, SEG_RECORD, board_homographies, classification_scores, decode_positions, find_quadrangles,
                           mask_completenesses, quadrangle_regularity, scores_finish, segmentation_scores_finish)
 
+RESIZE_MODES = ("area", "antialias")
 _HOST_STAGES = ("stage_s", "wait_masks_s", "contours_s", "homography_s", "wait_probs_s", "decode_s", "assemble_s")
 
 
@@ -116,8 +118,9 @@ class _Call:
     """The state one ``process_images`` call shares between its stages.  The compute stream is the CURRENT stream."""
 
     def __init__(self, cv, images, threshold, flip, fallback_quad, return_crops, timings, quality, started, targets=None,
-                 embeddings=False):
+                 embeddings=False, resize="area"):
         self.cv, self.images, self.started = cv, images, started
+        self.resize = resize                             # "area" | "antialias": how a photo becomes the UNet's input (forward)
         self.targets = targets                           # evaluation.Targets of an evaluate_images call, else None
         self.embeddings = bool(embeddings)               # both forwards also pool their hook tensor (HipEngine: want_embedding)
         self.threshold, self.flip, self.fallback_quad, self.return_crops, self.quality = threshold, flip, fallback_quad, return_crops, quality
@@ -200,19 +203,28 @@ class _Call:
             job.arrived.record()
         return job
 
+    def forward(self, batch):
+        """The photos of one job -> (logits, mask, embedding | None) in the call's resize mode: "area" is INTER_AREA to bytes and the
+        u8 UNet entry (``process_image``'s arithmetic, reference core.py:212); "antialias" is the antialiased bilinear resize to
+        float32 NCHW and the float UNet entry (the enrichment job's arithmetic, process_pipeline.py:340-344).  Two engine calls either
+        way, under the same two timing keys."""
+        eng, size = self.eng, (constants.INPUT_SIZE[1], constants.INPUT_SIZE[0])
+        if self.resize == "antialias":
+            small, unet = self.gpu_timed("resize_ms", eng.resize_antialias_f32, batch, size), eng.unet_forward_mask
+        else:
+            small, unet = self.gpu_timed("resize_ms", eng.resize_area_u8, batch, size), eng.unet_forward_u8
+        if self.embeddings:                              # the same forward plus one pooling launch per chunk, inside unet_ms
+            return self.gpu_timed("unet_ms", unet, small, threshold=self.threshold, want_mask=True, want_embedding=True)
+        lg, mk = self.gpu_timed("unet_ms", unet, small, threshold=self.threshold, want_mask=True)
+        return lg, mk, None
+
     def compute(self, job: Job) -> None:
         """resize + UNet (+ the score reductions, on the logits where the UNet left them) on the compute stream; masks start back."""
         n, eng, down = len(job.ids), self.eng, self.down
         self.main.wait_event(job.arrived)
         job.batch.record_stream(self.main)
         self.tm.setdefault("first_enqueue_s", time.time() - self.started)   # host time until the first kernel of the call is queued
-        small = self.gpu_timed("resize_ms", eng.resize_area_u8, job.batch, (constants.INPUT_SIZE[1], constants.INPUT_SIZE[0]))
-        emb = None
-        if self.embeddings:                              # the same forward plus one pooling launch per chunk, inside unet_ms
-            lg, mk, emb = self.gpu_timed("unet_ms", eng.unet_forward_u8, small, threshold=self.threshold, want_mask=True,
-                                         want_embedding=True)
-        else:
-            lg, mk = self.gpu_timed("unet_ms", eng.unet_forward_u8, small, threshold=self.threshold, want_mask=True)
+        lg, mk, emb = self.forward(job.batch)
         scored = None
         if self.quality:
             scored = self.gpu_timed("quality_ms", eng.extraction_scores_dev, lg, "none" if self.quality == "logits" else "sigmoid",
@@ -419,11 +431,14 @@ class _Call:
 
 
 def process_images(cv, images, threshold, flip, fallback_quad, pipeline_chunk, return_crops, timings, first_job, last_job,
-                   quality, targets=None, embeddings=False) -> list[ChessVisionResult]:
+                   quality, targets=None, embeddings=False, resize="area") -> list[ChessVisionResult]:
     """``ChessVision.process_images`` on the instance's native engines (arguments: see there).  ``targets`` (``evaluation.Targets``,
     from ``ChessVision.evaluate_images``) additionally scores every job against its ground truth and leaves the records there;
-    ``embeddings`` attaches an ``Embeddings`` record to every result."""
+    ``embeddings`` attaches an ``Embeddings`` record to every result; ``resize`` ("area" | "antialias") chooses how a photo becomes
+    the UNet's input (``_Call.forward``)."""
     started = time.time()
+    if resize not in RESIZE_MODES:
+        raise ValueError(f"resize must be one of {RESIZE_MODES}, got {resize!r}")
     for image in images:
         assert isinstance(image, np.ndarray) and image.dtype == np.uint8 and image.ndim == 3
     if not images:
@@ -436,7 +451,8 @@ def process_images(cv, images, threshold, flip, fallback_quad, pipeline_chunk, r
     # ends, so nothing is left to order against the caller's stream.
     own = torch.cuda.current_stream(cv.device) == torch.cuda.default_stream(cv.device)
     with torch.cuda.stream(cv._pipeline_streams()[2]) if own else contextlib.nullcontext():
-        call = _Call(cv, images, threshold, flip, fallback_quad, return_crops, timings, quality, started, targets, embeddings)
+        call = _Call(cv, images, threshold, flip, fallback_quad, return_crops, timings, quality, started, targets, embeddings,
+                     resize)
         t_last = call.issue(jobs)
         call.eng.check_numerics()                        # one look at the numeric guard for the whole call
         if call.eng_cls is not call.eng:

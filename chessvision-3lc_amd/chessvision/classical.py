@@ -113,6 +113,59 @@ def resize_area(image: NDArray[np.uint8], size: tuple[int, int]) -> NDArray[np.u
     return out if image.ndim == 3 else out[:, :, 0]
 
 
+# ---- antialiased bilinear resize (v2.Resize((256, 256), antialias=True) on a float image, process_pipeline.py:340-344) ----
+def antialias_taps(src: int, dst: int):
+    """One axis of ATen's antialiased bilinear resize (``_compute_indices_min_size_weights_aa`` with the triangle filter): with
+    ``scale = src / dst`` the filter's support is ``max(scale, 1)`` source pixels either side of ``center = scale * (i + 0.5)``;
+    output ``i`` reads source ``first[i] .. first[i] + count[i] - 1`` with weights ``max(0, 1 - |(j + first - center + 0.5) /
+    support|)`` divided by their sum.  Computed in float64, weights stored as float32 -- the arithmetic of ``resize_antialias_table``
+    in ``csrc/pipeline.hip``.  Returns (first (dst,) int64, count (dst,) int64, weights (dst, max count) float32, unused tail 0)."""
+    scale = src / dst
+    support = max(scale, 1.0)
+    inv = 1.0 / support
+    first, rows = [], []
+    for i in range(dst):
+        center = scale * (i + 0.5)
+        lo = max(int(center - support + 0.5), 0)
+        hi = min(int(center + support + 0.5), src)
+        wt = [max(0.0, 1.0 - abs((j + lo - center + 0.5) * inv)) for j in range(hi - lo)]
+        total = 0.0
+        for v in wt:
+            total += v
+        first.append(lo)
+        rows.append([v / total for v in wt])
+    count = np.array([len(r) for r in rows], dtype=np.int64)
+    weights = np.zeros((dst, int(count.max())), dtype=np.float32)
+    for i, r in enumerate(rows):
+        weights[i, :len(r)] = r
+    return np.array(first, dtype=np.int64), count, weights
+
+
+def resize_antialias(image: NDArray[np.uint8], size: tuple[int, int]) -> NDArray[np.float32]:
+    """``torch.nn.functional.interpolate(u8.float() / 255, (height, width), mode="bilinear", antialias=True, align_corners=False)``
+    for one (H,W,C) uint8 image and ``size = (width, height)``, as (C,height,width) float32 in [0,1]: what the reference's enrichment
+    job feeds its UNet (``v2.Resize((256, 256), antialias=True)`` on a float image).  Pixel = ``float32(u8) / 255``, horizontal
+    pass first, both passes in float32 with the taps of ``antialias_taps`` added in ascending order, multiplies and adds unfused;
+    channels as given.  Enlarging is two-tap bilinear, equal sizes give ``u8 / 255`` exactly.  The device kernel
+    (``HipEngine.resize_antialias_f32``) performs the same operations in the same order; this is its checker, and what a caller
+    feeds a model object that is not the HIP one (``process_images`` itself runs on the native engines only)."""
+    w_out, h_out = size
+    img = image if image.ndim == 3 else image[:, :, None]
+    h, w, _ = img.shape
+    xf, xc, xw = antialias_taps(w, w_out)
+    yf, yc, yw = antialias_taps(h, h_out)
+    src = img.astype(np.float32) / np.float32(255.0)
+    rows = np.zeros((h, w_out, img.shape[2]), dtype=np.float32)              # horizontal pass of every source row
+    for k in range(xw.shape[1]):
+        live = xc > k
+        rows[:, live] = rows[:, live] + src[:, xf[live] + k] * xw[live, k][None, :, None]
+    out = np.zeros((h_out, w_out, img.shape[2]), dtype=np.float32)
+    for k in range(yw.shape[1]):
+        live = yc > k
+        out[live] = out[live] + rows[yf[live] + k] * yw[live, k][:, None, None]
+    return np.ascontiguousarray(out.transpose(2, 0, 1))
+
+
 # ---- contours (cv2.findContours(mask, RETR_CCOMP, CHAIN_APPROX_TC89_KCOS), core.py:360) ----------------
 def _trace_border(f: NDArray[np.bool_], start: tuple[int, int], prev: tuple[int, int]) -> NDArray[np.int32]:
     """Suzuki-Abe border following (step 3 of Algorithm 1) from ``start`` with ``prev`` the background pixel

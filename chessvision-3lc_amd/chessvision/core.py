@@ -67,6 +67,8 @@ class ChessVision:
 
     # evaluate_images also collects the embeddings of process_images(embeddings=True) while this is set (its argument list is pinned)
     evaluation_embeddings = False
+    # ... and resizes the way process_images(resize=...) does ("area" | "antialias")
+    evaluation_resize = "area"
 
     def __init__(
         self,
@@ -492,7 +494,7 @@ class ChessVision:
 
     def process_images(self, images: Sequence[NDArray[np.uint8]], threshold: float = 0.5, flip: bool = False,
                        fallback_quad: bool = False, pipeline_chunk: int = 64, return_crops: bool = True,
-                       timings: dict | None = None, first_job: int = 16, last_job: int = 0,
+                       timings: dict | None = None, first_job: int = 16, last_job: int = 0, resize: str = "area",
                        embeddings: bool = False, quality: str | None = None) -> list[ChessVisionResult]:
         """Batched pipeline (``chessvision/batched.py``): the native stages of ``process_image``, cut into jobs of up to
         ``pipeline_chunk`` equally sized images and software-pipelined; the first job of a call is cut to ``first_job`` images and
@@ -522,11 +524,32 @@ class ChessVision:
         repeated on the exact-f32 instance (``_recover``) returns that instance's embeddings.  Out of scope: the single-image
         ``process_image`` / ``cv_process_image_v2`` (its result struct does not grow), ``distributed.process_images_sharded`` (which
         does not carry ``quality`` either), the PaCMAP reduction the reference runs on the collected table, and forward hooks on the
-        HIP model objects (they are not ``nn.Module``s)."""
+        HIP model objects (they are not ``nn.Module``s).
+
+        ``resize`` ("area" = the default: nothing changes, no new launch, allocation or copy) chooses how a photo becomes the UNet's
+        256 x 256 input.  "area" is ``process_image``'s way, ``cv2.resize(INTER_AREA)`` to bytes (reference core.py:212).
+        "antialias" is the enrichment job's way (``v2.Resize((256, 256), antialias=True)`` on a float image,
+        process_pipeline.py:340-344): ``F.interpolate(u8.float() / 255, (256, 256), mode="bilinear", antialias=True,
+        align_corners=False)``, computed per job by one kernel (``HipEngine.resize_antialias_f32``) into float32 NCHW that the UNet's
+        float entry takes (``HipEngine.unet_forward_mask``) -- no rounding to bytes in between, so logits, scores, embeddings and
+        now and then a mask pixel are those of the reference's table, not ``process_image``'s.  The warp still reads the
+        full-resolution u8 photo, and ``resize_ms`` / ``unet_ms`` of ``timings`` keep their meaning.  Any other value raises
+        ``ValueError`` before anything is launched; a call repeated on the exact-f32 instance keeps its mode.  Out of scope: the
+        single-image ``process_image`` / ``extract_board`` / ``cv_process_image_v2`` (the core.py:212 path: they stay INTER_AREA),
+        ``distributed.process_images_sharded``, torchvision's uint8 path (fixed-point weights), PIL's resize (train_unet.py:52), and
+        float-tensor inputs, including the job's ``(x * 255).astype(uint8)`` round trip of the photo."""
         if quality not in (None, "logits", "sigmoid"):
             raise ValueError(f"quality must be None, 'logits' or 'sigmoid', got {quality!r}")
+        self._check_resize(resize)
         return self._recover(lambda cv: cv._process_images_native(images, threshold, flip, fallback_quad, pipeline_chunk, return_crops,
-                                                                  timings, first_job, last_job, quality, None, bool(embeddings)))
+                                                                  timings, first_job, last_job, quality, None, bool(embeddings), resize))
+
+    @staticmethod
+    def _check_resize(resize) -> None:
+        from .batched import RESIZE_MODES
+
+        if resize not in RESIZE_MODES:
+            raise ValueError(f"resize must be one of {RESIZE_MODES}, got {resize!r}")
 
     def _process_images_native(self, *args) -> list[ChessVisionResult]:
         from . import batched
@@ -551,13 +574,17 @@ class ChessVision:
         probabilities are scored by one native call right after its FENs are decoded.  An image with a FEN but no board found counts
         as an extraction failure, not as a zero-accuracy board.  With ``self.evaluation_embeddings = True`` (an
         attribute of the instance, default False: the argument list of this method is pinned) the call also collects the embeddings of
-        ``process_images(embeddings=True)``; they are in ``report.results``."""
+        ``process_images(embeddings=True)``; they are in ``report.results``.  ``self.evaluation_resize`` ("area" by default) is
+        ``process_images``'s ``resize`` in the same way."""
         from .evaluation import Targets
 
+        resize = self.evaluation_resize
+        self._check_resize(resize)
         images = list(images)
         targets = Targets(len(images), true_fens, label_masks)
         results = self._recover(lambda cv: cv._process_images_native(images, threshold, flip, fallback_quad, pipeline_chunk, True,
-                                                                     timings, 16, 0, None, targets, bool(self.evaluation_embeddings)))
+                                                                     timings, 16, 0, None, targets, bool(self.evaluation_embeddings),
+                                                                     resize))
         return targets.report(results)
 
     def _pipeline_streams(self):

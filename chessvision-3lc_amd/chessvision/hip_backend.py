@@ -112,6 +112,8 @@ SYMBOLS = [
     ("cv_find_contours", _i, [_vp, _i, _i, _i, ctypes.POINTER(ctypes.c_int32), ctypes.c_int64, ctypes.POINTER(ctypes.c_int32),
                               ctypes.POINTER(ctypes.c_int32), ctypes.c_int64, ctypes.POINTER(ctypes.c_int64)]),
     ("cv_resize_area_u8", _i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _i, _vp]),
+    ("cv_resize_antialias_f32", _i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _i, _vp]),
+    ("cv_unet_forward_mask", _i, [_vp, _vp, _i, _vp, _vp, _f, _vp, _vp]),
     ("cv_extract_squares_u8", _i, [_vp, _vp, _i, _i, _i, ctypes.POINTER(ctypes.c_double), _vp, _vp, _vp]),
     ("cv_extract_squares_u8_dev", _i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
     ("cv_engine_workspace_bytes", _i, [_vp, ctypes.POINTER(ctypes.c_size_t)]),
@@ -598,6 +600,20 @@ class HipEngine:
                                             float(threshold), _stream_ptr(self.device)))
         return logits, mask
 
+    def unet_forward_mask(self, x: torch.Tensor, threshold: float = 0.5, want_mask: bool = True, want_embedding: bool = False):
+        """The float-input sibling of ``unet_forward_u8``: (B,3,256,256) float32 NCHW in [0,1] (what ``resize_antialias_f32``
+        writes) -> (logits (B,1,256,256) f32, mask (B,256,256) u8 | None); with ``want_embedding`` the (B,C) float32 bottleneck
+        embedding is appended.  Logits and embedding are ``unet_forward``'s bit for bit.  Like ``unet_forward_u8`` it does not
+        consult the numeric guard: the batched pipeline calls ``check_numerics()`` once per call."""
+        x = self._dev_f32(x, (3, 256, 256))
+        b = x.shape[0]
+        logits = torch.empty((b, 1, 256, 256), dtype=torch.float32, device=self.device)
+        mask = torch.empty((b, 256, 256), dtype=torch.uint8, device=self.device) if want_mask else None
+        emb = self._embedding_out("unet", b) if want_embedding else None
+        _check(self._lib.cv_unet_forward_mask(self._h, _ptr(x), b, _ptr(logits), _ptr(mask) if want_mask else None, float(threshold),
+                                              _ptr(emb) if want_embedding else None, _stream_ptr(self.device)))
+        return (logits, mask, emb) if want_embedding else (logits, mask)
+
     def resnet18_forward_u8(self, squares_u8: torch.Tensor, want_embedding: bool = False):
         """(N,64,64) uint8 -> (N,13) float32 softmax probabilities of the loaded ResNet (18 or 34); with ``want_embedding`` ->
         (probabilities, embedding (N,512) float32)."""
@@ -686,6 +702,20 @@ class HipEngine:
         out = torch.empty((n, out_hw[0], out_hw[1], c), dtype=torch.uint8, device=self.device)
         _check(self._lib.cv_resize_area_u8(self._h, _ptr(images), n, h, w, c, _ptr(out), out_hw[0], out_hw[1],
                                            _stream_ptr(self.device)))
+        return out
+
+    def resize_antialias_f32(self, images: torch.Tensor, out_hw=(256, 256)) -> torch.Tensor:
+        """(N,H,W,C) uint8 HWC, C in 1..4 -> (N,C,out_h,out_w) float32 NCHW in [0,1]: the antialiased bilinear resize of the
+        reference's enrichment job, ``F.interpolate(u8.float() / 255, out_hw, mode="bilinear", antialias=True,
+        align_corners=False)`` (``classical.resize_antialias`` is the host form).  One launch on the current stream."""
+        if images.dtype != torch.uint8 or images.dim() != 4 or not 1 <= images.shape[3] <= 4:
+            raise HipBackendError("resize_antialias_f32 expects (N,H,W,C) uint8 with 1 to 4 channels")
+        images = images.to(self.device).contiguous()
+        n, h, w, c = images.shape
+        out = torch.empty((n, c, out_hw[0], out_hw[1]), dtype=torch.float32, device=self.device)
+        if n:
+            _check(self._lib.cv_resize_antialias_f32(self._h, _ptr(images), n, h, w, c, _ptr(out), out_hw[0], out_hw[1],
+                                                     _stream_ptr(self.device)))
         return out
 
     def extract_squares_u8(self, images: torch.Tensor, inverse_maps: np.ndarray, want_boards: bool = True):

@@ -26,6 +26,10 @@ hipError_t resize_area_u8(const uint8_t* src, int n, int h, int w, int c, uint8_
 void resize_area_table(int ssize, int dsize, std::vector<int>& ofs, std::vector<int>& si, std::vector<float>& alpha);
 hipError_t resize_area_u8_tab(const uint8_t* src, int n, int h, int w, int c, uint8_t* dst, int oh, int ow, const int* xofs,
                               const int* xsi, const float* xa, const int* yofs, const int* ysi, const float* ya, hipStream_t s);
+void resize_antialias_table(int ssize, int dsize, std::vector<int>& first, std::vector<int>& count, std::vector<float>& weights, int* stride);
+hipError_t resize_antialias_f32(const uint8_t* src, int n, int h, int w, int c, float* dst, int oh, int ow, const int* xfirst,
+                                const int* xcount, const float* xw, int xstride, const int* yfirst, const int* ycount, const float* yw,
+                                int ystride, hipStream_t s);
 hipError_t extract_squares_u8(const uint8_t* images, int n, int h, int w, const double* inv, uint8_t* squares,
                               uint8_t* boards, hipStream_t s);
 hipError_t extract_squares_u8_one(const uint8_t* image, int h, int w, const double* inv_host, uint8_t* squares, uint8_t* board, hipStream_t s);
@@ -741,6 +745,49 @@ static int impl_cv_resize_area_u8(cv_engine_t* eng, const uint8_t* src, int n, i
     return finish(resize_on_stream(eng->impl, src, n, h, w_, channels, dst, out_h, out_w, (hipStream_t)stream));
 }
 
+// antialiased bilinear resize to float32 NCHW with the engine's cached tap tables (caller holds the engine mutex)
+static Status resize_antialias_on_stream(Engine& en, const uint8_t* src, int n, int h, int w_, int channels, float* dst, int out_h, int out_w,
+                                         hipStream_t st) {
+    const int geom[4] = {h, w_, out_h, out_w};
+    if (std::memcmp(en.aa_geom, geom, sizeof geom) != 0) {
+        if (capture_flag()) return fail(CV_ERR_STATE, "resize tables rebuilt during graph capture");
+        std::vector<int> xf, xc, yf, yc;
+        std::vector<float> xw, yw;
+        int xs = 0, ys = 0;
+        resize_antialias_table(w_, out_w, xf, xc, xw, &xs);
+        resize_antialias_table(h, out_h, yf, yc, yw, &ys);
+        CV_HIP(hipStreamSynchronize(st));                              // a launch in flight may still read the previous tables
+        std::vector<char> blob;
+        auto put = [&](const void* p, size_t nbytes) { const size_t at = blob.size(); blob.resize(at + ((nbytes + 15) & ~(size_t)15)); std::memcpy(blob.data() + at, p, nbytes); return at; };
+        const size_t off[6] = {put(xf.data(), xf.size() * 4), put(xc.data(), xc.size() * 4), put(xw.data(), xw.size() * 4),
+                               put(yf.data(), yf.size() * 4), put(yc.data(), yc.size() * 4), put(yw.data(), yw.size() * 4)};
+        en.aa_geom[0] = 0;                                             // no geometry while the upload can still fail
+        CV_TRY(en.aa_tabs.upload(blob.data(), blob.size()));
+        for (int i = 0; i < 6; ++i) en.aa_off[i] = off[i];
+        en.aa_stride[0] = xs; en.aa_stride[1] = ys;
+        std::memcpy(en.aa_geom, geom, sizeof geom);
+    }
+    const char* base = (const char*)en.aa_tabs.ptr;
+    const hipError_t e = resize_antialias_f32(src, n, h, w_, channels, dst, out_h, out_w, (const int*)(base + en.aa_off[0]),
+                                              (const int*)(base + en.aa_off[1]), (const float*)(base + en.aa_off[2]), en.aa_stride[0],
+                                              (const int*)(base + en.aa_off[3]), (const int*)(base + en.aa_off[4]),
+                                              (const float*)(base + en.aa_off[5]), en.aa_stride[1], st);
+    if (e != hipSuccess) return hip_fail(e, "resize_antialias_f32");
+    return Status();
+}
+
+static int impl_cv_resize_antialias_f32(cv_engine_t* eng, const uint8_t* src, int n, int h, int w_, int channels, float* dst, int out_h,
+                                        int out_w, void* stream) {
+    Status s = check_engine(eng);
+    if (!s.ok()) return finish(s);
+    if (!src || !dst || n <= 0 || h <= 0 || w_ <= 0 || channels < 1 || channels > 4 || out_h <= 0 || out_w <= 0 || ((uintptr_t)dst & 3u) ||
+        out_h > 65535 * 16)
+        return finish(fail(CV_ERR_INVALID, "cv_resize_antialias_f32: bad argument"));
+    DeviceGuard g(eng->impl.device);
+    std::lock_guard<std::mutex> lk(eng->impl.mu);
+    return finish(resize_antialias_on_stream(eng->impl, src, n, h, w_, channels, dst, out_h, out_w, (hipStream_t)stream));
+}
+
 static int impl_cv_extract_squares_u8(cv_engine_t* eng, const uint8_t* images, int n, int h, int w_, const double* inv_host,
                           uint8_t* squares, uint8_t* boards, void* stream) {
     Status s = check_engine(eng);
@@ -1162,6 +1209,11 @@ int cv_unet_forward_u8_emb(cv_engine_t* eng, const uint8_t* x_u8, int batch, flo
     return guarded("cv_unet_forward_u8_emb", [&]() -> int { return impl_cv_unet_forward_emb(eng, x_u8, true, batch, logits, mask, threshold, embedding, stream); });
 }
 
+int cv_unet_forward_mask(cv_engine_t* eng, const float* x, int batch, float* logits, uint8_t* mask, float threshold, float* embedding,
+                         void* stream) {
+    return guarded("cv_unet_forward_mask", [&]() -> int { return impl_cv_unet_forward_emb(eng, x, false, batch, logits, mask, threshold, embedding, stream); });
+}
+
 int cv_resnet18_forward_emb(cv_engine_t* eng, const float* x, int n, float* logits, float* embedding, void* stream) {
     return guarded("cv_resnet18_forward_emb", [&]() -> int { return impl_cv_resnet18_forward_emb(eng, x, false, n, logits, embedding, stream); });
 }
@@ -1238,6 +1290,11 @@ int cv_find_quadrangles(const uint8_t* masks, int n, int h, int w, int32_t* quad
 int cv_resize_area_u8(cv_engine_t* eng, const uint8_t* src, int n, int h, int w_, int channels, uint8_t* dst, int out_h,
                       int out_w, void* stream) {
     return guarded("cv_resize_area_u8", [&]() -> int { return impl_cv_resize_area_u8(eng, src, n, h, w_, channels, dst, out_h, out_w, stream); });
+}
+
+int cv_resize_antialias_f32(cv_engine_t* eng, const uint8_t* src, int n, int h, int w_, int channels, float* dst, int out_h,
+                            int out_w, void* stream) {
+    return guarded("cv_resize_antialias_f32", [&]() -> int { return impl_cv_resize_antialias_f32(eng, src, n, h, w_, channels, dst, out_h, out_w, stream); });
 }
 
 int cv_extract_squares_u8(cv_engine_t* eng, const uint8_t* images, int n, int h, int w_, const double* inv_host,

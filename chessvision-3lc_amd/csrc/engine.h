@@ -288,6 +288,10 @@ class Engine {
     DeviceBuffer area_tabs;                             // INTER_AREA tables of the last fractional resize geometry (cv_resize_area_u8)
     long long area_key = -1;
     size_t area_off[6] = {0, 0, 0, 0, 0, 0};
+    DeviceBuffer aa_tabs;                               // tap tables of the last antialiased resize geometry (cv_resize_antialias_f32)
+    int aa_geom[4] = {0, 0, 0, 0};                      // (h, w, out_h, out_w) the tables were built for; all 0: none yet
+    size_t aa_off[6] = {0, 0, 0, 0, 0, 0};
+    int aa_stride[2] = {0, 0};
 
     // numeric guard: one device word, 0xffffffff = clean, else the lowest id of a layer that stored a non-finite value
     DeviceBuffer guard;

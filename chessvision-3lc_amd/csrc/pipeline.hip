@@ -1,6 +1,7 @@
 // pipeline.hip -- device versions of the classical stages either side of the CNNs.
 //
 //   resize_area_u8     cv2.resize(image, (256,256), INTER_AREA)                          reference core.py:212
+//   resize_antialias_f32  v2.Resize((256,256), antialias=True) on a float image          reference process_pipeline.py:340-344
 //   extract_squares_u8 cv2.warpPerspective(image, M, (512,512)) -> cvtColor(BGR2GRAY) -> flip(.., 1) ->
 //                      ChessVision.extract_squares                                        reference utils.py:131-132,
 //                                                                                         core.py:298-300, 419-439
@@ -162,6 +163,128 @@ __global__ void resize_area_u8_kernel(const uint8_t* __restrict__ src, int n, in
     }
     const double v = rint(acc);
     dst[idx] = (uint8_t)(v < 0.0 ? 0.0 : v > 255.0 ? 255.0 : v);
+}
+
+// ---- antialiased bilinear resize (what the reference's enrichment job feeds its UNet) ----------------------------------------
+// torch.nn.functional.interpolate(u8.float() / 255, (oh, ow), mode="bilinear", antialias=True, align_corners=False), which is what
+// torchvision's v2.Resize((256, 256), antialias=True) runs on a float image (reference scripts/process_new_raw/process_pipeline.py:
+// 340-344): a separable triangle filter whose support grows with the scale factor, horizontal pass first, both passes in float32.
+// The per-axis tap tables (first source index, tap count, normalised weights: ATen's _compute_indices_min_size_weights_aa) come
+// from the host (resize_antialias_table below).  (n,h,w,c) u8 HWC in, (n,c,oh,ow) float32 NCHW out, channels as given.
+//
+// One launch.  A workgroup owns a 64 x 16 output tile of one image, all channels.  It walks the source rows its tile needs in slabs
+// of as many rows as fit the LDS block: the horizontal pass writes a slab's rows (tile columns only, channels interleaved) to LDS
+// -- a lane keeps one (column, channel) and walks the rows, so its taps are loop-invariant (in registers when an axis has at most 4)
+// and consecutive lanes read consecutive channels of neighbouring taps: a wave's byte loads fall into a few cache lines --, then
+// every lane adds the slab's share of the vertical taps of its outputs (lane = one column, 4 rows, all channels; LDS reads at a
+// stride of c dwords, conflict-free for c = 1 and 3) to accumulators that live in registers across slabs.  Slabs ascend, so every
+// output adds its taps in ascending order whatever the slab size: the order of additions depends on the geometry alone, there
+// are no atomics, and an image gives the same bits alone and inside a batch.  32 KB of LDS per workgroup: a 512 -> 256 tile
+// (34 rows x 64 x 3 floats) is one slab, and the CU holds several workgroups.  Multiplies and adds stay unfused: the numpy form
+// (chessvision/classical.py: resize_antialias) computes the same bits.
+struct AaTabs { const int* xfirst; const int* xcount; const float* xw; int xstride; const int* yfirst; const int* ycount; const float* yw; int ystride; };
+constexpr int kAaTileW = 64, kAaTileH = 16, kAaLdsFloats = 8192;
+
+// float(p) / 255.0f without the division sequence: one refinement step on p * fl(1 / 255) (the residual fma(-q, 255, p) is exact).
+// Bit-equal to the IEEE quotient for each of the 256 byte values (a multiply alone is wrong for 126 of them); the 256 -> 256 case of
+// tests/test_gpu_resize_antialias.py sends every byte value through it.
+__device__ __forceinline__ float unit_from_byte(uint8_t p) {
+    const float x = (float)p, r = 1.0f / 255.0f;
+    const float q = x * r;
+    return __builtin_fmaf(__builtin_fmaf(-q, 255.0f, x), r, q);
+}
+
+template <int C>
+__global__ __launch_bounds__(256) void resize_antialias_kernel(const uint8_t* __restrict__ src, int h, int w, float* __restrict__ dst,
+                                                               int oh, int ow, AaTabs t) {
+#pragma clang fp contract(off)
+    __shared__ float rows[kAaLdsFloats];
+    const int ox0 = blockIdx.x * kAaTileW, oy0 = blockIdx.y * kAaTileH;
+    const int tw = min(kAaTileW, ow - ox0), th = min(kAaTileH, oh - oy0);
+    const size_t img = blockIdx.z;
+    const uint8_t* s = src + img * (size_t)h * w * C;
+    const int twc = tw * C;
+    const int slab = kAaLdsFloats / twc;                                  // >= 32 source rows (tw <= 64, C <= 4)
+    const int r_lo = t.yfirst[oy0], r_hi = t.yfirst[oy0 + th - 1] + t.ycount[oy0 + th - 1];   // first / count never decrease with the row
+    // horizontal pass: a lane keeps ONE (column, channel) of the tile and walks source rows, so its taps are loop-invariant; when the
+    // tile's row is narrower than the workgroup, groups of twc lanes take the rows in turn
+    const int groups = 256 / twc, hg = threadIdx.x / twc, hcol = threadIdx.x - hg * twc;
+    const int hx = ox0 + hcol / C, hch = hcol % C;
+    const int xcnt = t.xcount[hx];
+    const float* wx = t.xw + (size_t)hx * t.xstride;
+    const uint8_t* hp = s + (size_t)t.xfirst[hx] * C + hch;
+    const bool few = t.xstride <= 4;                                      // the workload's case (factor <= 2): weights and offsets in registers
+    float w4[4];
+    int o4[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {                                          // a tap past the count re-reads the last one with weight 0: a + x * 0 = a
+        w4[j] = few && j < xcnt ? wx[j] : 0.f;
+        o4[j] = min(j, xcnt - 1) * C;
+    }
+    // vertical pass: lane = one output column, rows oy0 + tq + 4k, all channels; tq is the wave's number, so rows and weights are scalar
+    const int tx = threadIdx.x & 63, tq = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    float acc[4][C];
+    int yf[4], yc[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int oy = oy0 + tq + 4 * k;
+        yf[k] = oy < oh ? t.yfirst[oy] : 0;
+        yc[k] = oy < oh ? t.ycount[oy] : 0;
+#pragma unroll
+        for (int ch = 0; ch < C; ++ch) acc[k][ch] = 0.f;
+    }
+    for (int s0 = r_lo; s0 < r_hi; s0 += slab) {
+        const int s1 = min(r_hi, s0 + slab);
+        const int nrows = s1 - s0;
+        if (hg < groups && few) {
+            for (int r = hg; r < nrows; r += 4 * groups) {                 // four rows at a time: 16 byte loads in flight per lane
+                uint8_t b[4][4];
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {                              // a row past the slab re-reads the slab's last row; it is not stored
+                    const uint8_t* p = hp + (size_t)(s0 + min(r + u * groups, nrows - 1)) * w * C;
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) b[u][j] = p[o4[j]];
+                }
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    float a = 0.f;
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) a = a + unit_from_byte(b[u][j]) * w4[j];
+                    if (r + u * groups < nrows) rows[(r + u * groups) * twc + hcol] = a;
+                }
+            }
+        } else if (hg < groups) {
+            for (int r = hg; r < nrows; r += groups) {
+                const uint8_t* p = hp + (size_t)(s0 + r) * w * C;
+                float a = 0.f;
+                for (int j = 0; j < xcnt; ++j) a = a + unit_from_byte(p[(size_t)j * C]) * wx[j];
+                rows[r * twc + hcol] = a;
+            }
+        }
+        __syncthreads();
+        if (tx < tw) {                                                     // this slab's share of every output's taps, ascending
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const int j0 = max(yf[k], s0), j1 = min(yf[k] + yc[k], s1);
+                const float* wy = t.yw + (size_t)(oy0 + tq + 4 * k) * t.ystride;
+                for (int r = j0; r < j1; ++r) {
+                    const float wgt = wy[r - yf[k]];
+                    const float* hrow = rows + (r - s0) * twc + tx * C;
+#pragma unroll
+                    for (int ch = 0; ch < C; ++ch) acc[k][ch] = acc[k][ch] + hrow[ch] * wgt;
+                }
+            }
+        }
+        __syncthreads();                                                   // the next slab overwrites the rows
+    }
+    if (tx >= tw) return;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int oy = oy0 + tq + 4 * k;
+        if (oy >= oh) continue;
+#pragma unroll
+        for (int ch = 0; ch < C; ++ch) dst[((img * C + ch) * oh + oy) * (size_t)ow + ox0 + tx] = acc[k][ch];
+    }
 }
 
 // ---- warp + gray + flip + 64-way split --------------------------------------------------------------------
@@ -350,6 +473,54 @@ hipError_t resize_area_u8(const uint8_t* src, int n, int h, int w, int c, uint8_
                        double2{1.0 / isx, isx}, double2{1.0 / isy, isy});
     return hipGetLastError();
 }
+
+// host side of the antialiased resize: the taps of one axis, ATen's _compute_indices_min_size_weights_aa with the triangle filter
+// (computed in double, weights normalised and then stored as float; chessvision/classical.py: antialias_taps is the same arithmetic).
+// first / count: per destination index; weights: dsize rows of *stride floats, a row's unused tail is 0.
+void resize_antialias_table(int ssize, int dsize, std::vector<int>& first, std::vector<int>& count, std::vector<float>& weights, int* stride) {
+#pragma clang fp contract(off)
+    const double scale = (double)ssize / dsize;
+    const double support = scale > 1.0 ? scale : 1.0, inv = 1.0 / support;
+    first.assign(dsize, 0); count.assign(dsize, 0);
+    int widest = 1;
+    for (int i = 0; i < dsize; ++i) {
+        const double center = scale * (i + 0.5);
+        const int lo = (int)(center - support + 0.5), hi = (int)(center + support + 0.5);
+        first[i] = lo > 0 ? lo : 0;
+        count[i] = (hi < ssize ? hi : ssize) - first[i];
+        widest = count[i] > widest ? count[i] : widest;
+    }
+    *stride = widest;
+    weights.assign((size_t)dsize * widest, 0.f);
+    std::vector<double> wt(widest);
+    for (int i = 0; i < dsize; ++i) {
+        const double center = scale * (i + 0.5);
+        double total = 0.0;
+        for (int j = 0; j < count[i]; ++j) {
+            const double v = 1.0 - std::fabs((j + first[i] - center + 0.5) * inv);
+            wt[j] = v > 0.0 ? v : 0.0;
+            total += wt[j];
+        }
+        for (int j = 0; j < count[i]; ++j) weights[(size_t)i * widest + j] = (float)(wt[j] / total);
+    }
+}
+
+// tables: device pointers (built by the caller with resize_antialias_table and uploaded once per geometry)
+hipError_t resize_antialias_f32(const uint8_t* src, int n, int h, int w, int c, float* dst, int oh, int ow, const int* xfirst,
+                                const int* xcount, const float* xw, int xstride, const int* yfirst, const int* ycount, const float* yw,
+                                int ystride, hipStream_t s) {
+    const unsigned gx = (unsigned)((ow + kAaTileW - 1) / kAaTileW), gy = (unsigned)((oh + kAaTileH - 1) / kAaTileH);
+    if (c < 1 || c > 4 || gy > 65535u) return hipErrorInvalidValue;
+    const AaTabs t{xfirst, xcount, xw, xstride, yfirst, ycount, yw, ystride};
+    auto kernel = c == 1 ? resize_antialias_kernel<1> : c == 2 ? resize_antialias_kernel<2> : c == 3 ? resize_antialias_kernel<3> : resize_antialias_kernel<4>;
+    for (int off = 0; off < n; off += 32768) {                             // grid.z = images
+        const int cnt = n - off < 32768 ? n - off : 32768;
+        hipLaunchKernelGGL(kernel, dim3(gx, gy, (unsigned)cnt), dim3(256), 0, s, src + (size_t)off * h * w * c, h, w,
+                           dst + (size_t)off * c * oh * ow, oh, ow, t);
+    }
+    return hipGetLastError();
+}
+
 hipError_t extract_squares_u8(const uint8_t* images, int n, int h, int w, const double* inv, uint8_t* squares,
                               uint8_t* boards, hipStream_t s) {
     WarpMatrix none;

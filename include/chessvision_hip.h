@@ -203,6 +203,11 @@ int cv_embedding_dim(cv_engine_t* eng, const char* model, int* channels);
 int cv_unet_forward_emb(cv_engine_t* eng, const float* x, int batch, float* logits, float* embedding, void* stream);
 int cv_unet_forward_u8_emb(cv_engine_t* eng, const uint8_t* x_u8, int batch, float* logits, uint8_t* mask,
                            float threshold, float* embedding, void* stream);
+/* The float-input sibling of cv_unet_forward_u8(_emb): x as for cv_unet_forward, mask (nullable) and threshold as for
+ * cv_unet_forward_u8, embedding (nullable) as for cv_unet_forward_emb.  Logits and embedding are bit-identical to cv_unet_forward(_emb)'s
+ * on the same x. */
+int cv_unet_forward_mask(cv_engine_t* eng, const float* x, int batch, float* logits, uint8_t* mask, float threshold,
+                         float* embedding, void* stream);
 int cv_resnet18_forward_emb(cv_engine_t* eng, const float* x, int n, float* logits, float* embedding, void* stream);
 int cv_resnet18_forward_u8_emb(cv_engine_t* eng, const uint8_t* squares_u8, int n, float* probs, float* embedding, void* stream);
 
@@ -297,6 +302,17 @@ int cv_find_contours(const uint8_t* mask, int h, int w, int method, int32_t* xy,
  * box mean with round-half-up for integer shrink factors, coverage-weighted mean otherwise.  DEVICE pointers. */
 int cv_resize_area_u8(cv_engine_t* eng, const uint8_t* src, int n, int h, int w, int channels, uint8_t* dst,
                       int out_h, int out_w, void* stream);
+
+/* (n,h,w,channels) uint8 HWC -> (n,channels,out_h,out_w) float32 NCHW in [0,1]: the antialiased bilinear resize the reference's
+ * enrichment job puts in front of its UNet (v2.Resize((256,256), antialias=True) on a float image, process_pipeline.py:340-344 =
+ * torch.nn.functional.interpolate(u8.float() / 255, size, mode="bilinear", antialias=True, align_corners=False)).  A separable
+ * triangle filter with ATen's taps (support max(in/out, 1) per axis, weights normalised), pixel = float(u8) / 255.0f, horizontal pass
+ * first, both passes in float32, taps added in ascending order; enlarging is two-tap bilinear, equal sizes are the identity.
+ * channels 1..4, taken as given; any h, w >= 1.  DEVICE pointers, dst 4-byte aligned; one launch, asynchronous on `stream` (the tap
+ * tables of a new geometry are built on the host and uploaded once).  An image's bits do not depend on the batch around it.  The
+ * output is what cv_unet_forward / cv_unet_forward_mask take. */
+int cv_resize_antialias_f32(cv_engine_t* eng, const uint8_t* src, int n, int h, int w, int channels, float* dst,
+                            int out_h, int out_w, void* stream);
 
 /* Quadrangles -> the matrices of the board warp, host side, in OpenCV's order of operations (utils.extract_perspective,
  * utils.py:115-132: cv2.getPerspectiveTransform(approx, dest) with dest = (0,0), (w,0), (w,h), (0,h); cv2.warpPerspective then
