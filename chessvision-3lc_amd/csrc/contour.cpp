@@ -19,6 +19,8 @@
 #include <utility>
 #include <vector>
 
+#include "host_stages.h"
+
 // the float / double roundings of the restated OpenCV arithmetic are part of the result: no fused multiply-add anywhere here
 #pragma clang fp contract(off)
 

@@ -5,38 +5,16 @@
 #include <cmath>
 #include <cstddef>
 #include <cstring>
+#include <initializer_list>
 #include <new>
 #include <stdexcept>
 #include <thread>
 
 #include "engine.h"
+#include "host_stages.h"
 #include "models.h"
+#include "pipeline.h"
 #include "pointwise.h"
-
-namespace cv {
-void decode_positions(const float* probs, int n_boards, int flip, char* fen, char* original_fen, int8_t* labels,
-                      int32_t* fixes, int32_t* n_fixes);
-const char* fen_labels(const char* fen, int8_t* labels);
-void classification_scores(const float* probs, const int8_t* labels, int n_boards, cv_square_score_t* per_square,
-                           cv_board_score_t* per_board);
-bool find_quadrangle(const uint8_t* mask, int h, int w, int32_t quad[8]);
-long find_contours_flat(const uint8_t* mask, int h, int w, bool tc89, int32_t* xy, long cap_pts, int32_t* counts, int32_t* holes,
-                        long cap_contours);
-hipError_t resize_area_u8(const uint8_t* src, int n, int h, int w, int c, uint8_t* dst, int oh, int ow, hipStream_t s);
-void resize_area_table(int ssize, int dsize, std::vector<int>& ofs, std::vector<int>& si, std::vector<float>& alpha);
-hipError_t resize_area_u8_tab(const uint8_t* src, int n, int h, int w, int c, uint8_t* dst, int oh, int ow, const int* xofs,
-                              const int* xsi, const float* xa, const int* yofs, const int* ysi, const float* ya, hipStream_t s);
-void resize_antialias_table(int ssize, int dsize, std::vector<int>& first, std::vector<int>& count, std::vector<float>& weights, int* stride);
-hipError_t resize_antialias_f32(const uint8_t* src, int n, int h, int w, int c, float* dst, int oh, int ow, const int* xfirst,
-                                const int* xcount, const float* xw, int xstride, const int* yfirst, const int* ycount, const float* yw,
-                                int ystride, hipStream_t s);
-hipError_t extract_squares_u8(const uint8_t* images, int n, int h, int w, const double* inv, uint8_t* squares,
-                              uint8_t* boards, hipStream_t s);
-hipError_t extract_squares_u8_one(const uint8_t* image, int h, int w, const double* inv_host, uint8_t* squares, uint8_t* board, hipStream_t s);
-void board_homographies(const float* quads, int n, int out_w, int out_h, double* forward, double* inverse);
-double mask_completeness(const uint8_t* mask, int h, int w);
-double quadrangle_regularity(const float quad[8]);
-}  // namespace cv
 
 static_assert(sizeof(cv_score_record_t) == sizeof(cv::ScoreRecord) && offsetof(cv_score_record_t, top_sum) == offsetof(cv::ScoreRecord, top_sum) &&
               offsetof(cv_score_record_t, top_count) == offsetof(cv::ScoreRecord, top_count), "cv_score_record_t is the kernel's record");
@@ -51,6 +29,7 @@ struct cv_engine {
     Engine impl;
 };
 
+// ---- what two or more entry points share (may throw: std::vector / std::map / std::string allocations) ----------------------
 namespace {
 
 struct DeviceGuard {                       // every entry point runs on the engine's device
@@ -59,13 +38,12 @@ struct DeviceGuard {                       // every entry point runs on the engi
     ~DeviceGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
 };
 
-int finish(const Status& s) { return s.code; }
-
 // No C++ exception may unwind through the C boundary (ctypes / cgo callers would abort): every entry point runs inside
 // this wrapper.  The out-of-memory message fits the small-string buffer, so reporting it allocates nothing.
 template <class F> int guarded(const char* what, F&& body) noexcept {
     try {
-        return body();
+        const Status s = body();
+        return s.code;
     } catch (const std::bad_alloc&) {
         try { set_error("out of memory"); } catch (...) {}
         return CV_ERR_NOMEM;
@@ -103,122 +81,32 @@ Status check_engine(cv_engine_t* eng) {
     return Status();
 }
 
-}  // namespace
-
-// ---- implementations (may throw: std::vector / std::map / std::string allocations) ------------------------------
-
-static int impl_cv_device_count(int* count) {
-    if (!count) return finish(fail(CV_ERR_INVALID, "null count"));
-    hipError_t e = hipGetDeviceCount(count);
-    if (e != hipSuccess) { *count = 0; return finish(hip_fail(e, "hipGetDeviceCount")); }
-    return CV_OK;
-}
-
-static int impl_cv_engine_create(int device, int precision, cv_engine_t** out) {
-    if (!out) return finish(fail(CV_ERR_INVALID, "null out pointer"));
-    *out = nullptr;
-    if (precision != CV_PREC_F32 && precision != CV_PREC_F16 && precision != CV_PREC_F16X3 && precision != CV_PREC_F16R)
-        return finish(fail(CV_ERR_INVALID, "unknown precision"));
-    static_assert((int)CV_PREC_F32 == (int)kF32 && (int)CV_PREC_F16 == (int)kF16 && (int)CV_PREC_F16X3 == (int)kSplit, "enum values must match");
-    int count = 0;
-    hipError_t e = hipGetDeviceCount(&count);
-    if (e != hipSuccess || count <= 0)
-        return finish(fail(CV_ERR_HIP, std::string("no HIP device available: ") + (e != hipSuccess ? hipGetErrorString(e) : "device count is 0")));
-    if (device < 0 || device >= count) return finish(fail(CV_ERR_INVALID, "device ordinal out of range"));
-    DeviceGuard g(device);
-    hipDeviceProp_t prop;
-    if ((e = hipGetDeviceProperties(&prop, device)) != hipSuccess) return finish(hip_fail(e, "hipGetDeviceProperties"));
-    if (std::string(prop.gcnArchName).rfind("gfx950", 0) != 0)
-        return finish(fail(CV_ERR_STATE, std::string("libchessvision_hip is built for gfx950 (MI355X); device is ") + prop.gcnArchName));
-    {
-        // the dynamic-LDS limits of the conv kernels are raised ONCE per device and process, under a lock: repeating hipFuncSetAttribute
-        // at every engine creation while other threads launch those very kernels (request slots: replicas are loaded in the background
-        // of a serving instance) is not something the runtime promises to survive
-        static std::mutex prep_mu;
-        static bool prepared[64] = {};
-        std::lock_guard<std::mutex> lk(prep_mu);
-        if (device >= 64 || !prepared[device]) {
-            if ((e = conv_igemm_prepare()) != hipSuccess) return finish(hip_fail(e, "conv_igemm_prepare"));
-            if ((e = conv_halo_prepare()) != hipSuccess) return finish(hip_fail(e, "conv_halo_prepare"));
-            if ((e = conv1x1_lds_prepare()) != hipSuccess) return finish(hip_fail(e, "conv1x1_lds_prepare"));
-            if (device < 64) prepared[device] = true;
-        }
-    }
-    cv_engine* eng = new (std::nothrow) cv_engine();
-    if (!eng) return finish(fail(CV_ERR_NOMEM, "out of host memory"));
-    eng->impl.device = device;
-    eng->impl.dt = precision == CV_PREC_F16R ? (int)kF16 : precision;   // CV_PREC_F32 / F16 / F16X3 values equal cv::DType
-    eng->impl.trunk32 = precision == CV_PREC_F16R;
-    Status gs = eng->impl.guard_init();
-    if (!gs.ok()) { delete eng; return finish(gs); }
-    *out = eng;
-    return CV_OK;
-}
-
-static int impl_cv_engine_destroy(cv_engine_t* eng) {
-    if (!eng) return CV_OK;
-    {
-        DeviceGuard g(eng->impl.device);                // every block of the engine goes back to the cache under ITS device
-        (void)device_synchronize();
-        ReleaseAlreadySynced quiescent;                 // nothing can be queued on a dying engine's buffers from here on
-        eng->impl.unet.reset();
-        eng->impl.resnet.reset();
-        delete eng;
-    }
-    return CV_OK;
-}
-
-static int impl_cv_engine_set_chunk(cv_engine_t* eng, int unet_images, int resnet_squares) {
-    Status s = check_engine(eng);
-    if (!s.ok()) return finish(s);
-    std::lock_guard<std::mutex> lk(eng->impl.mu);
-    if (eng->impl.unet || eng->impl.resnet) return finish(fail(CV_ERR_STATE, "cv_engine_set_chunk must precede cv_load_*"));
-    if (unet_images < 0 || resnet_squares < 0) return finish(fail(CV_ERR_INVALID, "negative chunk"));
-    if (unet_images) eng->impl.unet_chunk = unet_images;
-    if (resnet_squares) eng->impl.resnet_chunk = resnet_squares;
-    return CV_OK;
-}
-
 // Model loads are serialised process-wide.  A load packs, uploads and calibrates through the legacy stream (hundreds of synchronous
 // allocations, fills and copies, calibration forwards on stream 0); two of them side by side in one process -- a second instance created
 // while another loads, or beside the background replica of a request slot -- ended in a GPU memory access fault in 50-80 % of the
 // soak runs (tests/dev/slots_soak.py; forwards beside ONE load never did, in any number of runs).  Loads take seconds and happen once
 // per engine: one at a time costs nothing.
-static std::mutex& load_mutex() {
+std::mutex& load_mutex() {
     static std::mutex mu;
     return mu;
 }
 
-static int impl_cv_load_unet(cv_engine_t* eng, const cv_param_t* params, int n_params) {
-    Status s = check_engine(eng);
-    if (!s.ok()) return finish(s);
-    std::lock_guard<std::mutex> load_lk(load_mutex());
-    std::lock_guard<std::mutex> lk(eng->impl.mu);
-    DeviceGuard g(eng->impl.device);
-    ParamMap pm;
-    s = to_map(params, n_params, pm);
-    if (s.ok()) s = unet_load(eng->impl, pm);
-    return finish(s);
-}
-
-static int impl_cv_load_resnet(cv_engine_t* eng, const char* arch, const cv_param_t* params, int n_params) {
-    Status s = check_engine(eng);
-    if (!s.ok()) return finish(s);
+Status load_resnet(cv_engine_t* eng, const char* arch, const cv_param_t* params, int n_params) {
+    CV_TRY(check_engine(eng));
     if (!arch || !resnet_arch(arch))
-        return finish(fail(CV_ERR_INVALID, "cv_load_resnet: arch must be 'resnet18' or 'resnet34', got " +
-                                               (arch ? "'" + std::string(arch) + "'" : std::string("NULL"))));
+        return fail(CV_ERR_INVALID, "cv_load_resnet: arch must be 'resnet18' or 'resnet34', got " +
+                                        (arch ? "'" + std::string(arch) + "'" : std::string("NULL")));
     std::lock_guard<std::mutex> load_lk(load_mutex());
     std::lock_guard<std::mutex> lk(eng->impl.mu);
     DeviceGuard g(eng->impl.device);
     ParamMap pm;
-    s = to_map(params, n_params, pm);
-    if (s.ok()) s = resnet_load(eng->impl, pm, arch);
-    return finish(s);
+    CV_TRY(to_map(params, n_params, pm));
+    return resnet_load(eng->impl, pm, arch);
 }
 
 // by-name entry points: "unet" | the loaded ResNet's architecture name.  Sets *is_resnet; a known name of a model that is not the loaded
 // one fails with CV_ERR_STATE naming what is loaded, an unknown name with CV_ERR_INVALID.
-static Status model_by_name(const Engine& e, const char* model, bool* is_resnet) {
+Status model_by_name(const Engine& e, const char* model, bool* is_resnet) {
     *is_resnet = false;
     if (std::strcmp(model, "unet") == 0) return Status();
     if (!resnet_arch(model)) return fail(CV_ERR_INVALID, "model must be 'unet', 'resnet18' or 'resnet34'");
@@ -228,274 +116,56 @@ static Status model_by_name(const Engine& e, const char* model, bool* is_resnet)
     return Status();
 }
 
-static int impl_cv_unet_forward(cv_engine_t* eng, const float* x, int batch, float* logits, void* stream) {
-    Status s = check_engine(eng);
-    if (!s.ok()) return finish(s);
-    std::lock_guard<std::mutex> lk(eng->impl.mu);
-    DeviceGuard g(eng->impl.device);
-    return finish(unet_forward(eng->impl, x, false, batch, logits, nullptr, 0.5f, (hipStream_t)stream));
-}
-
-static int impl_cv_unet_forward_u8(cv_engine_t* eng, const uint8_t* x_u8, int batch, float* logits, uint8_t* mask,
-                       float threshold, void* stream) {
-    Status s = check_engine(eng);
-    if (!s.ok()) return finish(s);
-    if (!(threshold >= 0.f && threshold <= 1.f)) return finish(fail(CV_ERR_INVALID, "threshold must be between 0 and 1"));
-    std::lock_guard<std::mutex> lk(eng->impl.mu);
-    DeviceGuard g(eng->impl.device);
-    return finish(unet_forward(eng->impl, x_u8, true, batch, logits, mask, threshold, (hipStream_t)stream));
-}
-
-static int impl_cv_resnet18_forward(cv_engine_t* eng, const float* x, int n, float* logits, void* stream) {
-    Status s = check_engine(eng);
-    if (!s.ok()) return finish(s);
-    std::lock_guard<std::mutex> lk(eng->impl.mu);
-    DeviceGuard g(eng->impl.device);
-    return finish(resnet_forward(eng->impl, x, false, n, logits, false, (hipStream_t)stream));
-}
-
-static int impl_cv_resnet18_forward_u8(cv_engine_t* eng, const uint8_t* squares_u8, int n, float* probs, void* stream) {
-    Status s = check_engine(eng);
-    if (!s.ok()) return finish(s);
-    std::lock_guard<std::mutex> lk(eng->impl.mu);
-    DeviceGuard g(eng->impl.device);
-    return finish(resnet_forward(eng->impl, squares_u8, true, n, probs, true, (hipStream_t)stream));
-}
-
-static int impl_cv_embedding_dim(cv_engine_t* eng, const char* model, int* channels) {
-    Status s = check_engine(eng);
-    if (!s.ok()) return finish(s);
-    if (!model || !channels) return finish(fail(CV_ERR_INVALID, "null argument"));
-    std::lock_guard<std::mutex> lk(eng->impl.mu);
+// the tensor `name` of the model `model`, as it stands after the model's last forward (caller holds the engine mutex)
+Status activation_by_name(Engine& e, const char* model, const char* name, TensorRef* t) {
     bool is_resnet = false;
-    s = model_by_name(eng->impl, model, &is_resnet);
-    if (!s.ok()) return finish(s);
-    *channels = is_resnet ? (eng->impl.resnet ? 512 : 0) : unet_embedding_dim(eng->impl);
-    if (*channels == 0) return finish(fail(CV_ERR_STATE, "cv_embedding_dim: model '" + std::string(model) + "' is not loaded"));
-    return CV_OK;
+    CV_TRY(model_by_name(e, model, &is_resnet));
+    return is_resnet ? resnet_activation(e, name, t) : unet_activation(e, name, t);
 }
 
-static Status check_embedding(const float* embedding) {
+Status check_embedding(const float* embedding) {
     if ((uintptr_t)embedding & 15u) return fail(CV_ERR_INVALID, "embedding must be 16-byte aligned");
     return Status();
 }
 
-static int impl_cv_unet_forward_emb(cv_engine_t* eng, const void* x, bool x_u8, int batch, float* logits, uint8_t* mask, float threshold,
-                                    float* embedding, void* stream) {
-    Status s = check_engine(eng);
-    if (!s.ok()) return finish(s);
-    if (!(threshold >= 0.f && threshold <= 1.f)) return finish(fail(CV_ERR_INVALID, "threshold must be between 0 and 1"));
-    if (!(s = check_embedding(embedding)).ok()) return finish(s);
+// the five cv_unet_forward* entry points; those without a mask, a threshold or an embedding pass null, 0.5 and null
+Status unet_entry(cv_engine_t* eng, const void* x, bool x_u8, int batch, float* logits, uint8_t* mask, float threshold, float* embedding,
+                  void* stream) {
+    CV_TRY(check_engine(eng));
+    if (!(threshold >= 0.f && threshold <= 1.f)) return fail(CV_ERR_INVALID, "threshold must be between 0 and 1");
+    CV_TRY(check_embedding(embedding));
     std::lock_guard<std::mutex> lk(eng->impl.mu);
     DeviceGuard g(eng->impl.device);
-    return finish(unet_forward(eng->impl, x, x_u8, batch, logits, mask, threshold, (hipStream_t)stream, embedding));
+    return unet_forward(eng->impl, x, x_u8, batch, logits, mask, threshold, (hipStream_t)stream, embedding);
 }
 
-static int impl_cv_resnet18_forward_emb(cv_engine_t* eng, const void* x, bool x_u8, int n, float* out, float* embedding, void* stream) {
-    Status s = check_engine(eng);
-    if (!s.ok()) return finish(s);
-    if (!(s = check_embedding(embedding)).ok()) return finish(s);
+// the four cv_resnet18_forward* entry points; the u8 entries return probabilities, the float entries logits
+Status resnet_entry(cv_engine_t* eng, const void* x, bool x_u8, int n, float* out, float* embedding, void* stream) {
+    CV_TRY(check_engine(eng));
+    CV_TRY(check_embedding(embedding));
     std::lock_guard<std::mutex> lk(eng->impl.mu);
     DeviceGuard g(eng->impl.device);
-    return finish(resnet_forward(eng->impl, x, x_u8, n, out, x_u8, (hipStream_t)stream, embedding));   // the u8 entry returns probabilities
-}
-
-static int impl_cv_activation_channel_means(cv_engine_t* eng, const char* model, const char* name, float* out_dev, size_t capacity_floats,
-                                            int64_t dims[2], void* stream) {
-    Status s = check_engine(eng);
-    if (!s.ok()) return finish(s);
-    if (!model || !name || !dims) return finish(fail(CV_ERR_INVALID, "null argument"));
-    std::lock_guard<std::mutex> lk(eng->impl.mu);
-    DeviceGuard g(eng->impl.device);
-    TensorRef t;
-    bool is_resnet = false;
-    s = model_by_name(eng->impl, model, &is_resnet);
-    // "global_pool" (the classifier's hook, named_modules()[90]) is the mean of layer4's output: pooled here, it needs no tensor of its own
-    if (s.ok()) s = is_resnet ? resnet_activation(eng->impl, std::strcmp(name, "global_pool") == 0 ? "layer4" : name, &t) : unet_activation(eng->impl, name, &t);
-    if (!s.ok()) return finish(s);
-    dims[0] = t.N; dims[1] = t.C;
-    if (!out_dev) return CV_OK;                           // shape query
-    const std::string tap = "cv_activation_channel_means('" + std::string(name) + "')";
-    if (t.N < 1) return finish(fail(CV_ERR_INVALID, tap + ": no forward has run yet"));
-    if (capacity_floats < (size_t)t.N * t.C)
-        return finish(fail(CV_ERR_INVALID, tap + ": output buffer too small, " + std::to_string((size_t)t.N * t.C) + " floats needed"));
-    if ((uintptr_t)out_dev & 15u) return finish(fail(CV_ERR_INVALID, tap + ": output must be 16-byte aligned"));
-    if (t.C % 8 || t.split) return finish(fail(CV_ERR_INVALID, tap + ": the tensor's channel slice cannot be pooled"));
-    hipError_t e = channel_means(eng->impl.dt, t, out_dev, (hipStream_t)stream);
-    if (e != hipSuccess) return finish(hip_fail(e, tap.c_str()));
-    return CV_OK;
-}
-
-static int impl_cv_softmax13(cv_engine_t* eng, const float* logits, int n, float* probs, void* stream) {
-    Status s = check_engine(eng);
-    if (!s.ok()) return finish(s);
-    if (n < 0 || (n > 0 && (!logits || !probs))) return finish(fail(CV_ERR_INVALID, "cv_softmax13: null tensor"));
-    if (n == 0) return CV_OK;
-    DeviceGuard g(eng->impl.device);
-    hipError_t e = softmax13(logits, n, probs, (hipStream_t)stream);
-    if (e != hipSuccess) return finish(hip_fail(e, "softmax13"));
-    return CV_OK;
-}
-
-static int impl_cv_get_activation(cv_engine_t* eng, const char* model, const char* name, float* out_host, size_t out_capacity,
-                      int64_t dims[4]) {
-    Status s = check_engine(eng);
-    if (!s.ok()) return finish(s);
-    if (!model || !name || !dims) return finish(fail(CV_ERR_INVALID, "null argument"));
-    std::lock_guard<std::mutex> lk(eng->impl.mu);
-    DeviceGuard g(eng->impl.device);
-    TensorRef t;
-    bool is_resnet = false;
-    s = model_by_name(eng->impl, model, &is_resnet);
-    if (s.ok()) s = is_resnet ? resnet_activation(eng->impl, name, &t) : unet_activation(eng->impl, name, &t);
-    if (!s.ok()) return finish(s);
-    dims[0] = t.N; dims[1] = t.C; dims[2] = t.H; dims[3] = t.W;
-    const size_t numel = (size_t)t.N * t.C * t.H * t.W;
-    if (!out_host) return CV_OK;                          // shape query
-    if (out_capacity < numel) return finish(fail(CV_ERR_INVALID, "output buffer too small"));
-    DeviceBuffer tmp;
-    s = tmp.alloc(numel * sizeof(float), false);
-    if (!s.ok()) return finish(s);
-    hipError_t e = device_synchronize();
-    if (e == hipSuccess) e = unpack_nchw_f32(t.f32_only ? (int)kF32 : eng->impl.dt, t, (float*)tmp.ptr, nullptr);
-    if (e == hipSuccess) e = sync_memcpy(out_host, tmp.ptr, numel * sizeof(float), hipMemcpyDeviceToHost);
-    if (e != hipSuccess) return finish(hip_fail(e, "cv_get_activation"));
-    return CV_OK;
-}
-
-static int impl_cv_model_macs(cv_engine_t* eng, const char* model, int64_t* macs) {
-    Status s = check_engine(eng);
-    if (!s.ok()) return finish(s);
-    if (!model || !macs) return finish(fail(CV_ERR_INVALID, "null argument"));
-    bool is_resnet = false;
-    s = model_by_name(eng->impl, model, &is_resnet);
-    if (!s.ok()) return finish(s);
-    *macs = is_resnet ? resnet_macs(eng->impl) : unet_macs(eng->impl);
-    if (*macs == 0) return finish(fail(CV_ERR_STATE, "model not loaded"));
-    return CV_OK;
-}
-
-static int impl_cv_profile_convs(cv_engine_t* eng, const char* model, const void* x, int batch, void* out, int iters,
-                     void* stream, float* conv_ms_total, int* conv_launches, float* all_ms_total) {
-    Status s = check_engine(eng);
-    if (!s.ok()) return finish(s);
-    if (!model || iters <= 0) return finish(fail(CV_ERR_INVALID, "bad profile arguments"));
-    std::lock_guard<std::mutex> lk(eng->impl.mu);
-    DeviceGuard g(eng->impl.device);
-    Engine& e = eng->impl;
-    bool is_resnet = false;
-    s = model_by_name(e, model, &is_resnet);
-    if (!s.ok()) return finish(s);
-    e.prof_clear();
-    e.profiling = true;
-    const bool is_unet = !is_resnet;
-    for (int i = 0; i < iters && s.ok(); ++i) {
-        if (is_unet) s = unet_forward(e, x, false, batch, (float*)out, nullptr, 0.5f, (hipStream_t)stream);
-        else s = resnet_forward(e, x, false, batch, (float*)out, false, (hipStream_t)stream);
-    }
-    e.profiling = false;
-    if (s.ok()) s = e.prof_collect();
-    if (!s.ok()) { e.prof_clear(); return finish(s); }
-    float conv = 0.f, all = 0.f;
-    int n = 0;
-    for (auto& pe : e.prof) { all += pe.ms; if (pe.is_conv) { conv += pe.ms; ++n; } }
-    if (conv_ms_total) *conv_ms_total = conv;
-    if (conv_launches) *conv_launches = n;
-    if (all_ms_total) *all_ms_total = all;
-    return CV_OK;
-}
-
-static int impl_cv_profile_entry(cv_engine_t* eng, int index, char* name, int name_cap, float* ms, double* macs, int* is_conv) {
-    Status s = check_engine(eng);
-    if (!s.ok()) return finish(s);
-    std::lock_guard<std::mutex> lk(eng->impl.mu);
-    if (index < 0 || index >= (int)eng->impl.prof.size()) return finish(fail(CV_ERR_INVALID, "profile index out of range"));
-    const ProfileEntry& pe = eng->impl.prof[index];
-    if (name && name_cap > 0) { std::strncpy(name, pe.name.c_str(), name_cap - 1); name[name_cap - 1] = 0; }
-    if (ms) *ms = pe.ms;
-    if (macs) *macs = pe.macs;
-    if (is_conv) *is_conv = pe.is_conv ? 1 : 0;
-    return CV_OK;
+    return resnet_forward(eng->impl, x, x_u8, n, out, x_u8, (hipStream_t)stream, embedding);
 }
 
 // ---- single-layer entry points (parity tests) -------------------------------------------------------
-static int round_up(int v, int m) { return (v + m - 1) / m * m; }
-
-static int impl_cv_op_conv2d(cv_engine_t* eng, const float* x, int n, int cin, int h, int w_, const float* w_host, int cout,
-                 int k, int stride, const float* scale_host, const float* shift_host, const float* residual,
-                 int relu, float* y, void* stream) {
-    Status s = check_engine(eng);
-    if (!s.ok()) return finish(s);
-    if (!x || !w_host || !y || n <= 0 || cin <= 0 || cout <= 0 || h <= 0 || w_ <= 0 || stride <= 0)
-        return finish(fail(CV_ERR_INVALID, "cv_op_conv2d: bad argument"));
-    std::lock_guard<std::mutex> lk(eng->impl.mu);
-    DeviceGuard g(eng->impl.device);
-    Engine& e = eng->impl;
-    hipStream_t st = (hipStream_t)stream;
-    const int pad = (k - 1) / 2;
-    const int ho = (h + 2 * pad - k) / stride + 1, wo = (w_ + 2 * pad - k) / stride + 1;
-    const int cinPad = round_up(cin, 8);
-    std::vector<float> ones(cout, 1.f), zeros(cout, 0.f);
-    ConvLayer L;
-    e.ws_slot = 0;
-    s = L.build_conv("op_conv2d", e.dt, w_host, cout, cin, k, stride, scale_host ? scale_host : ones.data(),
-                     shift_host ? shift_host : zeros.data(), cinPad, (int64_t)n * ho * wo, (ho == wo) ? ho : 0);
-    if (!s.ok()) return finish(s);
-    Activation ax, ay, ar;
-    if ((s = ax.create(n, h, w_, cinPad, e.dt)).ok() && (s = ay.create(n, ho, wo, cout, e.dt)).ok()) {
-        hipError_t err = pack_nchw_f32(e.dt, x, cin, ax.ref(n), e.guard_ptr(), st);
-        TensorRef rr;
-        if (err == hipSuccess && residual) {
-            s = ar.create(n, ho, wo, cout, e.dt);
-            if (s.ok()) { err = pack_nchw_f32(e.dt, residual, cout, ar.ref(n), e.guard_ptr(), st); rr = ar.ref(n); }
-        }
-        if (s.ok() && err == hipSuccess) s = e.run_conv(L, ax.ref(n), ay.ref(n), residual ? &rr : nullptr, relu != 0, st);
-        if (s.ok() && err == hipSuccess) err = unpack_nchw_f32(e.dt, ay.ref(n), y, st);
-        if (s.ok() && err == hipSuccess) err = hipStreamSynchronize(st);
-        if (s.ok() && err != hipSuccess) s = hip_fail(err, "cv_op_conv2d");
-    }
-    return finish(s);
-}
-
-static int impl_cv_op_conv_transpose2x2(cv_engine_t* eng, const float* x, int n, int cin, int h, int w_, const float* w_host,
-                            int cout, const float* bias_host, float* y, void* stream) {
-    Status s = check_engine(eng);
-    if (!s.ok()) return finish(s);
-    if (!x || !w_host || !y || !bias_host || n <= 0) return finish(fail(CV_ERR_INVALID, "cv_op_conv_transpose2x2: bad argument"));
-    std::lock_guard<std::mutex> lk(eng->impl.mu);
-    DeviceGuard g(eng->impl.device);
-    Engine& e = eng->impl;
-    hipStream_t st = (hipStream_t)stream;
-    ConvLayer L;
-    e.ws_slot = 0;
-    s = L.build_convT("op_convT", e.dt, w_host, cin, cout, bias_host, (int64_t)n * h * w_);
-    if (!s.ok()) return finish(s);
-    Activation ax, ay;
-    if ((s = ax.create(n, h, w_, cin, e.dt)).ok() && (s = ay.create(n, 2 * h, 2 * w_, cout, e.dt)).ok()) {
-        hipError_t err = pack_nchw_f32(e.dt, x, cin, ax.ref(n), e.guard_ptr(), st);
-        if (err == hipSuccess) s = e.run_conv(L, ax.ref(n), ay.ref(n), nullptr, false, st);
-        if (s.ok() && err == hipSuccess) err = unpack_nchw_f32(e.dt, ay.ref(n), y, st);
-        if (s.ok() && err == hipSuccess) err = hipStreamSynchronize(st);
-        if (s.ok() && err != hipSuccess) s = hip_fail(err, "cv_op_conv_transpose2x2");
-    }
-    return finish(s);
-}
+int round_up(int v, int m) { return (v + m - 1) / m * m; }
 
 typedef hipError_t (*pool_fn)(int, const TensorRef&, const TensorRef&, hipStream_t);
-static hipError_t upsample_plain(int dt, const TensorRef& a, const TensorRef& b, hipStream_t s) {
+hipError_t upsample_plain(int dt, const TensorRef& a, const TensorRef& b, hipStream_t s) {
     return upsample_bilinear2x(dt, a, b, nullptr, 0u, s);
 }
-static int pool_like(cv_engine_t* eng, const float* x, int n, int c, int h, int w_, int ho, int wo, float* y,
-                     void* stream, pool_fn fn, const char* what) {
-    Status s = check_engine(eng);
-    if (!s.ok()) return finish(s);
-    if (!x || !y || n <= 0 || c <= 0 || h <= 0 || w_ <= 0 || ho <= 0 || wo <= 0) return finish(fail(CV_ERR_INVALID, std::string(what) + ": bad argument"));
+Status pool_like(cv_engine_t* eng, const float* x, int n, int c, int h, int w_, int ho, int wo, float* y, void* stream, pool_fn fn,
+                 const char* what) {
+    CV_TRY(check_engine(eng));
+    if (!x || !y || n <= 0 || c <= 0 || h <= 0 || w_ <= 0 || ho <= 0 || wo <= 0) return fail(CV_ERR_INVALID, std::string(what) + ": bad argument");
     std::lock_guard<std::mutex> lk(eng->impl.mu);
     DeviceGuard g(eng->impl.device);
     Engine& e = eng->impl;
     hipStream_t st = (hipStream_t)stream;
     const int cp = round_up(c, 8);
     Activation ax, ay;
+    Status s;
     if ((s = ax.create(n, h, w_, cp, e.dt)).ok() && (s = ay.create(n, ho, wo, cp, e.dt)).ok()) {
         hipError_t err = pack_nchw_f32(e.dt, x, c, ax.ref(n), e.guard_ptr(), st);
         if (err == hipSuccess) err = fn(e.dt, ax.ref(n), ay.ref(n), st);
@@ -503,230 +173,58 @@ static int pool_like(cv_engine_t* eng, const float* x, int n, int c, int h, int 
         if (err == hipSuccess) err = hipStreamSynchronize(st);
         if (err != hipSuccess) s = hip_fail(err, what);
     }
-    return finish(s);
-}
-
-// conv 1x1 C -> 1 + bias (+ sigmoid / threshold mask): the stand-alone OutConv kernel, as a single-layer entry point
-static int impl_cv_op_outc_1x1(cv_engine_t* eng, const float* x, int n, int c, int h, int w_, const float* w_host, const float* bias_host,
-                               float threshold, float* logits, uint8_t* mask, void* stream) {
-    Status s = check_engine(eng);
-    if (!s.ok()) return finish(s);
-    if (!x || !w_host || !bias_host || !logits || n <= 0 || c <= 0 || h <= 0 || w_ <= 0)
-        return finish(fail(CV_ERR_INVALID, "cv_op_outc_1x1: bad argument"));
-    std::lock_guard<std::mutex> lk(eng->impl.mu);
-    DeviceGuard g(eng->impl.device);
-    Engine& e = eng->impl;
-    hipStream_t st = (hipStream_t)stream;
-    const int cp = round_up(c, 8);
-    const int lpp = cp / dtype_group(e.dt);
-    if (lpp > 64 || (lpp & (lpp - 1))) return finish(fail(CV_ERR_INVALID, "cv_op_outc_1x1: channel count must give a power-of-two lane group <= 64"));
-    std::vector<float> wpad(cp, 0.f);
-    std::copy(w_host, w_host + c, wpad.begin());
-    Activation ax;
-    DeviceBuffer dw, db;
-    if ((s = ax.create(n, h, w_, cp, e.dt)).ok() && (s = dw.upload(wpad.data(), cp * sizeof(float))).ok() &&
-        (s = db.upload(bias_host, sizeof(float))).ok()) {
-        hipError_t err = pack_nchw_f32(e.dt, x, c, ax.ref(n), e.guard_ptr(), st);
-        if (err == hipSuccess)
-            err = outc_1x1(e.dt, ax.ref(n), (const float*)dw.ptr, (const float*)db.ptr, logits, mask, threshold, e.guard_ptr(),
-                           e.register_layer("op_outc_1x1"), st);
-        if (err == hipSuccess) err = hipStreamSynchronize(st);
-        if (err != hipSuccess) s = hip_fail(err, "cv_op_outc_1x1");
-    }
-    return finish(s);
-}
-
-static int impl_cv_op_maxpool2x2(cv_engine_t* eng, const float* x, int n, int c, int h, int w_, float* y, void* stream) {
-    return pool_like(eng, x, n, c, h, w_, h / 2, w_ / 2, y, stream, maxpool2x2, "cv_op_maxpool2x2");
-}
-static int impl_cv_op_maxpool3x3s2(cv_engine_t* eng, const float* x, int n, int c, int h, int w_, float* y, void* stream) {
-    return pool_like(eng, x, n, c, h, w_, (h + 2 - 3) / 2 + 1, (w_ + 2 - 3) / 2 + 1, y, stream, maxpool3x3s2, "cv_op_maxpool3x3s2");
-}
-static int impl_cv_op_upsample_bilinear2x(cv_engine_t* eng, const float* x, int n, int c, int h, int w_, float* y, void* stream) {
-    return pool_like(eng, x, n, c, h, w_, 2 * h, 2 * w_, y, stream, upsample_plain, "cv_op_upsample_bilinear2x");
+    return s;
 }
 
 // ---- classical stages either side of the CNNs -----------------------------------------
-static int impl_cv_find_quadrangle(const uint8_t* mask, int h, int w, int32_t quad[8], int* found) {
-    if (!mask || !quad || !found || h <= 0 || w <= 0) return finish(fail(CV_ERR_INVALID, "cv_find_quadrangle: bad argument"));
-    *found = find_quadrangle(mask, h, w, quad) ? 1 : 0;
-    return CV_OK;
+// Host threads for `n` masks.  A mask takes ~50 us since round 4 (run-based labelling): starting a thread costs about as much, so every
+// thread gets at least eight masks (64 masks: 8 threads; a single board: none), and there are never more than 32.
+int mask_threads(int n, int n_threads) {
+    const int nt = n_threads > 0 ? n_threads : (int)std::thread::hardware_concurrency();
+    return std::max(1, std::min(nt, std::min((n + 7) / 8, 32)));
 }
 
-static int impl_cv_find_contours(const uint8_t* mask, int h, int w, int method, int32_t* xy, int64_t cap_points, int32_t* counts,
-                                 int32_t* holes, int64_t cap_contours, int64_t* n_contours) {
-    if (!mask || !xy || !counts || !holes || !n_contours || h <= 0 || w <= 0 || cap_points < 0 || cap_contours < 0 ||
-        (method != 0 && method != 1))
-        return finish(fail(CV_ERR_INVALID, "cv_find_contours: bad argument"));
-    const long n = find_contours_flat(mask, h, w, method == 1, xy, (long)cap_points, counts, holes, (long)cap_contours);
-    if (n < 0) return finish(fail(CV_ERR_INVALID, "cv_find_contours: output capacity too small"));
-    *n_contours = n;
-    return CV_OK;
-}
-
-static int impl_cv_find_quadrangles(const uint8_t* masks, int n, int h, int w, int32_t* quads, int32_t* found, int n_threads) {
-    if (!masks || !quads || !found || n < 0 || h <= 0 || w <= 0) return finish(fail(CV_ERR_INVALID, "cv_find_quadrangles: bad argument"));
-    int nt = n_threads > 0 ? n_threads : (int)std::thread::hardware_concurrency();
-    // a mask takes ~50 us since round 4 (run-based labelling): starting a thread costs about as much, so every thread gets at least
-    // eight masks (64 masks: 8 threads; a single board: none)
-    nt = std::max(1, std::min(nt, std::min((n + 7) / 8, 32)));
-    auto work = [&](int t) {
-        for (int i = t; i < n; i += nt)
-            found[i] = find_quadrangle(masks + (size_t)i * h * w, h, w, quads + (size_t)i * 8) ? 1 : 0;
-    };
-    if (nt == 1) { work(0); return CV_OK; }
-    std::vector<std::thread> pool;
-    for (int t = 0; t < nt; ++t) pool.emplace_back(work, t);
-    for (auto& th : pool) th.join();
-    return CV_OK;
-}
-
-// contiguous slices of [0, n) on up to `nt` host threads (the quality scores: every item costs about the same)
-template <class F> static void parallel_slices(int n, int nt, F&& work) {
+// contiguous slices of [0, n) on up to `nt` host threads (every item costs about the same)
+template <class F> void parallel_slices(int n, int nt, F&& work) {
     if (nt <= 1) { work(0, n); return; }
     std::vector<std::thread> pool;
     for (int t = 0; t < nt; ++t) pool.emplace_back([&work, n, nt, t] { work((int)((long long)n * t / nt), (int)((long long)n * (t + 1) / nt)); });
     for (auto& th : pool) th.join();
 }
 
-static int impl_cv_extraction_scores(cv_engine_t* eng, const float* values, int n, int count, int transform, cv_score_record_t* records,
-                                     uint8_t* half_mask, void* stream) {
-    Status s = check_engine(eng);
-    if (!s.ok()) return finish(s);
-    if (!values || !records) return finish(fail(CV_ERR_INVALID, "cv_extraction_scores: null tensor"));
-    if (((uintptr_t)values & 3u) || ((uintptr_t)records & 7u)) return finish(fail(CV_ERR_INVALID, "cv_extraction_scores: values must be 4-byte, records 8-byte aligned"));
-    if (n < 1) return finish(fail(CV_ERR_INVALID, "cv_extraction_scores: n must be at least 1"));
-    if (count < 4 || count > (1 << 24)) return finish(fail(CV_ERR_INVALID, "cv_extraction_scores: count must be in [4, 2^24]"));
-    if (transform != 0 && transform != 1) return finish(fail(CV_ERR_INVALID, "cv_extraction_scores: transform must be 0 (as given) or 1 (sigmoid)"));
-    DeviceGuard g(eng->impl.device);
-    hipError_t e = extraction_scores(values, n, count, transform, reinterpret_cast<ScoreRecord*>(records), half_mask, (hipStream_t)stream);
-    if (e != hipSuccess) return finish(hip_fail(e, "extraction_scores"));
-    return CV_OK;
-}
-
-static int impl_cv_extraction_scores_finish(const cv_score_record_t* records, int n, double* confidence, double* distribution) {
-    if (n < 0 || (n > 0 && (!records || !confidence || !distribution))) return finish(fail(CV_ERR_INVALID, "cv_extraction_scores_finish: bad argument"));
-    const double nan = std::nan("");
-    for (int i = 0; i < n; ++i) {
-        const cv_score_record_t& r = records[i];
-        // numpy's sort puts NaN last, so one NaN in the image reaches the top quarter and the mean
-        confidence[i] = r.n_nan > 0 || r.top_count <= 0 ? nan : 2.0 * r.top_sum / (double)r.top_count;
-        long long total = 0;
-        for (int b = 0; b < 10; ++b) total += r.hist[b];
-        if (total == 0) { distribution[i] = nan; continue; }           // 0 / 0 in the reference's hist / sum(hist)
-        double entropy = 0.0;
-        for (int b = 0; b < 10; ++b) {
-            const double p = (double)r.hist[b] / (double)total;
-            entropy -= p * std::log2(p + 1e-10);
-        }
-        distribution[i] = 1.0 - entropy / std::log2(10.0);
-    }
-    return CV_OK;
-}
-
-static int impl_cv_segmentation_scores(cv_engine_t* eng, const float* logits, const uint8_t* labels, int n, int count, float threshold,
-                                       cv_seg_record_t* records, void* stream) {
-    Status s = check_engine(eng);
-    if (!s.ok()) return finish(s);
-    if (!logits || !labels || !records) return finish(fail(CV_ERR_INVALID, "cv_segmentation_scores: null tensor"));
-    if (((uintptr_t)logits & 3u) || ((uintptr_t)records & 7u)) return finish(fail(CV_ERR_INVALID, "cv_segmentation_scores: logits must be 4-byte, records 8-byte aligned"));
-    if (n < 1) return finish(fail(CV_ERR_INVALID, "cv_segmentation_scores: n must be at least 1"));
-    if (count < 1 || count > (1 << 24)) return finish(fail(CV_ERR_INVALID, "cv_segmentation_scores: count must be in [1, 2^24]"));
-    if (!std::isfinite(threshold)) return finish(fail(CV_ERR_INVALID, "cv_segmentation_scores: threshold must be finite"));
-    DeviceGuard g(eng->impl.device);
-    hipError_t e = segmentation_scores(logits, labels, n, count, threshold, reinterpret_cast<SegRecord*>(records), (hipStream_t)stream);
-    if (e != hipSuccess) return finish(hip_fail(e, "segmentation_scores"));
-    return CV_OK;
+Status mask_completenesses(const uint8_t* masks, int n, int h, int w, double* scores, int n_threads) {
+    if (!masks || !scores || n < 0 || h <= 0 || w <= 0) return fail(CV_ERR_INVALID, "cv_mask_completenesses: bad argument");
+    parallel_slices(n, mask_threads(n, n_threads), [&](int lo, int hi) {
+        for (int i = lo; i < hi; ++i) scores[i] = mask_completeness(masks + (size_t)i * h * w, h, w);
+    });
+    return Status();
 }
 
 // Pytorch-UNet's dice_coeff for one image: (2 * inter + eps) / (sets_sum + eps), sets_sum == 0 -> 2 * inter
-static double dice_of(double inter, double sets_sum) {
+double dice_of(double inter, double sets_sum) {
     if (sets_sum == 0.0) sets_sum = 2.0 * inter;
     return (2.0 * inter + 1e-6) / (sets_sum + 1e-6);
 }
 
-static int impl_cv_segmentation_scores_finish(const cv_seg_record_t* records, int n, double* bce, double* dice_loss, double* loss,
-                                              double* dice, double* iou, double* pixel_accuracy) {
-    if (n < 0 || (n > 0 && !records)) return finish(fail(CV_ERR_INVALID, "cv_segmentation_scores_finish: bad argument"));
-    for (int i = 0; i < n; ++i) {
-        const cv_seg_record_t& r = records[i];
-        if (r.count < 1) return finish(fail(CV_ERR_INVALID, "cv_segmentation_scores_finish: record " + std::to_string(i) + " has no pixels"));
-        const double b = r.bce_sum / (double)r.count;
-        const double dl = 1.0 - dice_of(r.sig_label_sum, r.sig_sum + (double)r.n_label);
-        const long long uni = (long long)r.n_pred + r.n_label - r.n_both;
-        if (bce) bce[i] = b;
-        if (dice_loss) dice_loss[i] = dl;
-        if (loss) loss[i] = dl + b;
-        if (dice) dice[i] = dice_of((double)r.n_both, (double)r.n_pred + (double)r.n_label);
-        if (iou) iou[i] = uni == 0 ? 1.0 : (double)r.n_both / (double)uni;
-        if (pixel_accuracy) pixel_accuracy[i] = (double)((long long)r.count - r.n_pred - r.n_label + 2LL * r.n_both) / (double)r.count;
-    }
-    return CV_OK;
-}
-
-static int impl_cv_fen_labels(const char* fen, int8_t* labels) {
-    if (!fen || !labels) return finish(fail(CV_ERR_INVALID, "cv_fen_labels: null argument"));
-    int8_t out[64];
-    const char* why = fen_labels(fen, out);
-    if (why) return finish(fail(CV_ERR_INVALID, std::string("cv_fen_labels: malformed piece placement (") + why + ")"));
-    std::memcpy(labels, out, 64);
-    return CV_OK;
-}
-
-static int impl_cv_classification_scores(const float* probs, const int8_t* labels, int n_boards, cv_square_score_t* per_square,
-                                         cv_board_score_t* per_board) {
-    if (n_boards < 0 || (n_boards > 0 && (!probs || !labels || !per_square || !per_board)))
-        return finish(fail(CV_ERR_INVALID, "cv_classification_scores: bad argument"));
-    for (size_t i = 0; i < (size_t)n_boards * 64; ++i)
-        if (labels[i] < 0 || labels[i] > 12)
-            return finish(fail(CV_ERR_INVALID, "cv_classification_scores: label " + std::to_string(i) + " is not a class index (0..12)"));
-    classification_scores(probs, labels, n_boards, per_square, per_board);
-    return CV_OK;
-}
-
-static int impl_cv_mask_completenesses(const uint8_t* masks, int n, int h, int w, double* scores, int n_threads) {
-    if (!masks || !scores || n < 0 || h <= 0 || w <= 0) return finish(fail(CV_ERR_INVALID, "cv_mask_completenesses: bad argument"));
-    int nt = n_threads > 0 ? n_threads : (int)std::thread::hardware_concurrency();
-    nt = std::max(1, std::min(nt, std::min((n + 7) / 8, 32)));          // as cv_find_quadrangles: at least eight masks per thread
-    parallel_slices(n, nt, [&](int lo, int hi) {
-        for (int i = lo; i < hi; ++i) scores[i] = mask_completeness(masks + (size_t)i * h * w, h, w);
-    });
-    return CV_OK;
-}
-
-static int impl_cv_quadrangle_regularity(const float* quad, double* score) {
-    if (!score) return finish(fail(CV_ERR_INVALID, "cv_quadrangle_regularity: null score"));
-    *score = quad ? quadrangle_regularity(quad) : 0.0;
-    return CV_OK;
-}
-
 // INTER_AREA on `st` with the engine's cached tables for fractional shrinks (caller holds the engine mutex)
-static Status resize_on_stream(Engine& en, const uint8_t* src, int n, int h, int w_, int channels, uint8_t* dst, int out_h, int out_w, hipStream_t st) {
+Status resize_on_stream(Engine& en, const uint8_t* src, int n, int h, int w_, int channels, uint8_t* dst, int out_h, int out_w, hipStream_t st) {
     hipError_t e;
     const bool integer = h % out_h == 0 && w_ % out_w == 0;
     if (!integer && out_h <= h && out_w <= w_ && channels <= 4) {
         // fractional shrink: OpenCV's float32 table form; the two tables are built once per geometry and stay on the device
-        const long long key = (((long long)h * 65536 + w_) * 65536 + out_h) * 65536 + out_w;
-        if (en.area_key != key) {
-            if (capture_flag()) return fail(CV_ERR_STATE, "resize tables rebuilt during graph capture");
+        ResizeTables& tabs = en.area_tabs;
+        const int geom[4] = {h, w_, out_h, out_w};
+        if (std::memcmp(tabs.geom, geom, sizeof geom) != 0) {
             std::vector<int> xo, xs, yo, ys;
             std::vector<float> xa, ya;
             resize_area_table(w_, out_w, xo, xs, xa);
             resize_area_table(h, out_h, yo, ys, ya);
-            CV_HIP(hipStreamSynchronize(st));                          // a launch in flight may still read the previous tables
-            std::vector<char> blob;
-            auto put = [&](const void* p, size_t nbytes) { const size_t at = blob.size(); blob.resize(at + ((nbytes + 15) & ~(size_t)15)); std::memcpy(blob.data() + at, p, nbytes); return at; };
-            const size_t o0 = put(xo.data(), xo.size() * 4), o1 = put(xs.data(), xs.size() * 4), o2 = put(xa.data(), xa.size() * 4);
-            const size_t o3 = put(yo.data(), yo.size() * 4), o4 = put(ys.data(), ys.size() * 4), o5 = put(ya.data(), ya.size() * 4);
-            CV_TRY(en.area_tabs.upload(blob.data(), blob.size()));
-            const size_t off[6] = {o0, o1, o2, o3, o4, o5};
-            for (int i = 0; i < 6; ++i) en.area_off[i] = off[i];
-            en.area_key = key;
+            CV_TRY(tabs.replace(geom, st, xo, xs, xa, yo, ys, ya));
         }
-        const char* base = (const char*)en.area_tabs.ptr;
-        e = resize_area_u8_tab(src, n, h, w_, channels, dst, out_h, out_w, (const int*)(base + en.area_off[0]), (const int*)(base + en.area_off[1]),
-                               (const float*)(base + en.area_off[2]), (const int*)(base + en.area_off[3]), (const int*)(base + en.area_off[4]),
-                               (const float*)(base + en.area_off[5]), st);
+        const char* base = (const char*)tabs.buf.ptr;
+        e = resize_area_u8_tab(src, n, h, w_, channels, dst, out_h, out_w, (const int*)(base + tabs.off[0]), (const int*)(base + tabs.off[1]),
+                               (const float*)(base + tabs.off[2]), (const int*)(base + tabs.off[3]), (const int*)(base + tabs.off[4]),
+                               (const float*)(base + tabs.off[5]), st);
     } else {
         e = resize_area_u8(src, n, h, w_, channels, dst, out_h, out_w, st);
     }
@@ -734,110 +232,56 @@ static Status resize_on_stream(Engine& en, const uint8_t* src, int n, int h, int
     return Status();
 }
 
-static int impl_cv_resize_area_u8(cv_engine_t* eng, const uint8_t* src, int n, int h, int w_, int channels, uint8_t* dst, int out_h,
-                      int out_w, void* stream) {
-    Status s = check_engine(eng);
-    if (!s.ok()) return finish(s);
-    if (!src || !dst || n <= 0 || h <= 0 || w_ <= 0 || channels <= 0 || out_h <= 0 || out_w <= 0)
-        return finish(fail(CV_ERR_INVALID, "cv_resize_area_u8: bad argument"));
-    DeviceGuard g(eng->impl.device);
-    std::lock_guard<std::mutex> lk(eng->impl.mu);
-    return finish(resize_on_stream(eng->impl, src, n, h, w_, channels, dst, out_h, out_w, (hipStream_t)stream));
-}
-
 // antialiased bilinear resize to float32 NCHW with the engine's cached tap tables (caller holds the engine mutex)
-static Status resize_antialias_on_stream(Engine& en, const uint8_t* src, int n, int h, int w_, int channels, float* dst, int out_h, int out_w,
-                                         hipStream_t st) {
+Status resize_antialias_on_stream(Engine& en, const uint8_t* src, int n, int h, int w_, int channels, float* dst, int out_h, int out_w,
+                                  hipStream_t st) {
+    ResizeTables& tabs = en.aa_tabs;
     const int geom[4] = {h, w_, out_h, out_w};
-    if (std::memcmp(en.aa_geom, geom, sizeof geom) != 0) {
-        if (capture_flag()) return fail(CV_ERR_STATE, "resize tables rebuilt during graph capture");
+    if (std::memcmp(tabs.geom, geom, sizeof geom) != 0) {
         std::vector<int> xf, xc, yf, yc;
         std::vector<float> xw, yw;
         int xs = 0, ys = 0;
         resize_antialias_table(w_, out_w, xf, xc, xw, &xs);
         resize_antialias_table(h, out_h, yf, yc, yw, &ys);
-        CV_HIP(hipStreamSynchronize(st));                              // a launch in flight may still read the previous tables
-        std::vector<char> blob;
-        auto put = [&](const void* p, size_t nbytes) { const size_t at = blob.size(); blob.resize(at + ((nbytes + 15) & ~(size_t)15)); std::memcpy(blob.data() + at, p, nbytes); return at; };
-        const size_t off[6] = {put(xf.data(), xf.size() * 4), put(xc.data(), xc.size() * 4), put(xw.data(), xw.size() * 4),
-                               put(yf.data(), yf.size() * 4), put(yc.data(), yc.size() * 4), put(yw.data(), yw.size() * 4)};
-        en.aa_geom[0] = 0;                                             // no geometry while the upload can still fail
-        CV_TRY(en.aa_tabs.upload(blob.data(), blob.size()));
-        for (int i = 0; i < 6; ++i) en.aa_off[i] = off[i];
-        en.aa_stride[0] = xs; en.aa_stride[1] = ys;
-        std::memcpy(en.aa_geom, geom, sizeof geom);
+        CV_TRY(tabs.replace(geom, st, xf, xc, xw, yf, yc, yw, xs, ys));
     }
-    const char* base = (const char*)en.aa_tabs.ptr;
-    const hipError_t e = resize_antialias_f32(src, n, h, w_, channels, dst, out_h, out_w, (const int*)(base + en.aa_off[0]),
-                                              (const int*)(base + en.aa_off[1]), (const float*)(base + en.aa_off[2]), en.aa_stride[0],
-                                              (const int*)(base + en.aa_off[3]), (const int*)(base + en.aa_off[4]),
-                                              (const float*)(base + en.aa_off[5]), en.aa_stride[1], st);
+    const char* base = (const char*)tabs.buf.ptr;
+    const hipError_t e = resize_antialias_f32(src, n, h, w_, channels, dst, out_h, out_w, (const int*)(base + tabs.off[0]),
+                                              (const int*)(base + tabs.off[1]), (const float*)(base + tabs.off[2]), tabs.stride[0],
+                                              (const int*)(base + tabs.off[3]), (const int*)(base + tabs.off[4]),
+                                              (const float*)(base + tabs.off[5]), tabs.stride[1], st);
     if (e != hipSuccess) return hip_fail(e, "resize_antialias_f32");
     return Status();
 }
 
-static int impl_cv_resize_antialias_f32(cv_engine_t* eng, const uint8_t* src, int n, int h, int w_, int channels, float* dst, int out_h,
-                                        int out_w, void* stream) {
-    Status s = check_engine(eng);
-    if (!s.ok()) return finish(s);
-    if (!src || !dst || n <= 0 || h <= 0 || w_ <= 0 || channels < 1 || channels > 4 || out_h <= 0 || out_w <= 0 || ((uintptr_t)dst & 3u) ||
-        out_h > 65535 * 16)
-        return finish(fail(CV_ERR_INVALID, "cv_resize_antialias_f32: bad argument"));
-    DeviceGuard g(eng->impl.device);
-    std::lock_guard<std::mutex> lk(eng->impl.mu);
-    return finish(resize_antialias_on_stream(eng->impl, src, n, h, w_, channels, dst, out_h, out_w, (hipStream_t)stream));
-}
-
-static int impl_cv_extract_squares_u8(cv_engine_t* eng, const uint8_t* images, int n, int h, int w_, const double* inv_host,
-                          uint8_t* squares, uint8_t* boards, void* stream) {
-    Status s = check_engine(eng);
-    if (!s.ok()) return finish(s);
-    if (!images || !inv_host || !squares || n <= 0 || h <= 0 || w_ <= 0)
-        return finish(fail(CV_ERR_INVALID, "cv_extract_squares_u8: bad argument"));
-    if ((size_t)h * (size_t)w_ > ((size_t)1 << 30)) return finish(fail(CV_ERR_INVALID, "cv_extract_squares_u8: image too large (32-bit byte offsets)"));
-    if (((uintptr_t)squares & 3) || ((uintptr_t)boards & 3)) return finish(fail(CV_ERR_INVALID, "cv_extract_squares_u8: outputs must be 4-byte aligned"));
-    std::lock_guard<std::mutex> lk(eng->impl.mu);
-    DeviceGuard g(eng->impl.device);
-    Engine& e = eng->impl;
-    const size_t bytes = (size_t)n * 9 * sizeof(double);
-    if (e.scratch.bytes < bytes) { s = e.scratch.alloc(bytes, false); if (!s.ok()) return finish(s); }
-    hipStream_t st = (hipStream_t)stream;
-    hipError_t err = hipMemcpyAsync(e.scratch.ptr, inv_host, bytes, hipMemcpyHostToDevice, st);
-    if (err == hipSuccess) err = extract_squares_u8(images, n, h, w_, (const double*)e.scratch.ptr, squares, boards, st);
-    if (err == hipSuccess) err = hipStreamSynchronize(st);       // inv_host may be reused by the caller; scratch by the next call
-    if (err != hipSuccess) return finish(hip_fail(err, "extract_squares_u8"));
-    return CV_OK;
-}
-
 // range calibration as data: the per-tensor exponents of a model, in the fixed order of its activation list (two per tensor: the
 // tensor's exponent and the second half's exponent of a concatenated buffer)
-static int impl_cv_engine_calibration(cv_engine_t* eng, const char* model, int32_t* exps, int capacity, int* count, int import) {
-    Status s = check_engine(eng);
-    if (!s.ok()) return finish(s);
-    if (!model || !count) return finish(fail(CV_ERR_INVALID, "null argument"));
+Status engine_calibration(cv_engine_t* eng, const char* model, int32_t* exps, int capacity, int* count, int import) {
+    CV_TRY(check_engine(eng));
+    if (!model || !count) return fail(CV_ERR_INVALID, "null argument");
     std::lock_guard<std::mutex> lk(eng->impl.mu);
     DeviceGuard g(eng->impl.device);
     Engine& e = eng->impl;
     std::vector<Activation*>* acts = nullptr;
     bool is_resnet = false;
-    s = model_by_name(e, model, &is_resnet);
-    if (!s.ok()) return finish(s.code == CV_ERR_INVALID ? fail(CV_ERR_STATE, "model must be a loaded 'unet', 'resnet18' or 'resnet34'") : s);
+    const Status s = model_by_name(e, model, &is_resnet);
+    if (!s.ok()) return s.code == CV_ERR_INVALID ? fail(CV_ERR_STATE, "model must be a loaded 'unet', 'resnet18' or 'resnet34'") : s;
     if (!is_resnet && e.unet) acts = &e.unet->acts;
     else if (is_resnet && e.resnet) acts = &e.resnet->acts;
-    else return finish(fail(CV_ERR_STATE, "model must be a loaded 'unet', 'resnet18' or 'resnet34'"));
+    else return fail(CV_ERR_STATE, "model must be a loaded 'unet', 'resnet18' or 'resnet34'");
     const int n = 2 * (int)acts->size();
     if (!import) {
         *count = n;
-        if (!exps) return CV_OK;                                  // size query
-        if (capacity < n) return finish(fail(CV_ERR_INVALID, "calibration buffer too small"));
+        if (!exps) return Status();                               // size query
+        if (capacity < n) return fail(CV_ERR_INVALID, "calibration buffer too small");
         for (size_t i = 0; i < acts->size(); ++i) { exps[2 * i] = (*acts)[i]->exp; exps[2 * i + 1] = (*acts)[i]->exp2; }
-        return CV_OK;
+        return Status();
     }
-    if (!exps || capacity != n) return finish(fail(CV_ERR_INVALID, "calibration vector does not match this model (" + std::to_string(n) + " entries expected)"));
-    if (e.dt == kF32) return CV_OK;                               // the f32 engine stores real values: nothing to set
+    if (!exps || capacity != n) return fail(CV_ERR_INVALID, "calibration vector does not match this model (" + std::to_string(n) + " entries expected)");
+    if (e.dt == kF32) return Status();                            // the f32 engine stores real values: nothing to set
     // validate the WHOLE vector before the first write: a rejected import leaves the engine exactly as it was
     for (int i = 0; i < n; ++i)
-        if (exps[i] < -60 || exps[i] > 60) return finish(fail(CV_ERR_INVALID, "exponent out of range (entry " + std::to_string(i) + ")"));
+        if (exps[i] < -60 || exps[i] > 60) return fail(CV_ERR_INVALID, "exponent out of range (entry " + std::to_string(i) + ")");
     bool changed = false;
     for (size_t i = 0; i < acts->size(); ++i) {
         Activation* a = (*acts)[i];
@@ -848,36 +292,36 @@ static int impl_cv_engine_calibration(cv_engine_t* eng, const char* model, int32
     }
     if (changed) {                                                // the layers re-fold their epilogue constants at their next launch
         hipError_t he = device_synchronize();
-        if (he != hipSuccess) return finish(hip_fail(he, "cv_engine_import_calibration"));
+        if (he != hipSuccess) return hip_fail(he, "cv_engine_import_calibration");
         e.graph_invalidate();
         e.graph_clear();
     }
     *count = changed ? 1 : 0;
-    return CV_OK;
-}
-
-static int impl_cv_board_homographies(const float* quads, int n, int out_w, int out_h, double* forward, double* inverse) {
-    if (n < 0 || out_w <= 0 || out_h <= 0 || (n > 0 && (!quads || (!forward && !inverse))))
-        return finish(fail(CV_ERR_INVALID, "cv_board_homographies: bad argument"));
-    board_homographies(quads, n, out_w, out_h, forward, inverse);
-    return CV_OK;
+    return Status();
 }
 
 // ---- one image, host to host ---------------------------------------------------------------------------------------------
-static Status resize_on_stream(Engine& en, const uint8_t* src, int n, int h, int w_, int channels, uint8_t* dst, int out_h, int out_w, hipStream_t st);
+// A copy in flight on a side stream must not outlive the call that issued it.  Armed when the copy is issued, this waits for the side
+// stream on the host at whatever exit the call takes; disarmed once the caller's stream has joined the side stream on the device and
+// has itself been synchronised, so that the success path pays no second host synchronisation.
+struct SideStreamJoin {
+    hipStream_t side = nullptr;
+    void arm(hipStream_t s) { side = s; }
+    void disarm() { side = nullptr; }
+    ~SideStreamJoin() { if (side) (void)hipStreamSynchronize(side); }
+};
 
-static int impl_cv_process_image(cv_engine_t* ue, cv_engine_t* ce, const uint8_t* image, int h, int w_, float threshold, int flip,
-                                 int fallback_quad, cv_image_result_t* out, size_t out_size, void* stream) {
+Status process_image(cv_engine_t* ue, cv_engine_t* ce, const uint8_t* image, int h, int w_, float threshold, int flip, int fallback_quad,
+                     cv_image_result_t* out, size_t out_size, void* stream) {
     // the caller's struct may be the shorter one of an earlier ABI: nothing at or beyond out_size is touched
     if (out && out_size < offsetof(cv_image_result_t, n_fixes) + sizeof(int32_t))
-        return finish(fail(CV_ERR_INVALID, "cv_process_image: result struct smaller than the ABI 3 layout"));
+        return fail(CV_ERR_INVALID, "cv_process_image: result struct smaller than the ABI 3 layout");
     uint8_t* const out_squares = (out && out_size >= offsetof(cv_image_result_t, squares) + sizeof(uint8_t*)) ? out->squares : nullptr;
-    Status s = check_engine(ue);
-    if (s.ok()) s = check_engine(ce);
-    if (!s.ok()) return finish(s);
-    if (!image || !out || h <= 0 || w_ <= 0 || (size_t)h * w_ > ((size_t)1 << 28)) return finish(fail(CV_ERR_INVALID, "cv_process_image: bad argument"));
-    if (!(threshold >= 0.f && threshold <= 1.f)) return finish(fail(CV_ERR_INVALID, "threshold must be between 0 and 1"));
-    if (ue->impl.device != ce->impl.device) return finish(fail(CV_ERR_STATE, "cv_process_image: both engines must live on one device"));
+    CV_TRY(check_engine(ue));
+    CV_TRY(check_engine(ce));
+    if (!image || !out || h <= 0 || w_ <= 0 || (size_t)h * w_ > ((size_t)1 << 28)) return fail(CV_ERR_INVALID, "cv_process_image: bad argument");
+    if (!(threshold >= 0.f && threshold <= 1.f)) return fail(CV_ERR_INVALID, "threshold must be between 0 and 1");
+    if (ue->impl.device != ce->impl.device) return fail(CV_ERR_STATE, "cv_process_image: both engines must live on one device");
     Engine& U = ue->impl;
     Engine& C = ce->impl;
     hipStream_t st = (hipStream_t)stream;
@@ -885,68 +329,66 @@ static int impl_cv_process_image(cv_engine_t* ue, cv_engine_t* ce, const uint8_t
     out->found = 0;
     out->n_fixes = 0;
     const size_t img_b = (size_t)h * w_ * 3, small_b = 256 * 256 * 3, lg_b = 65536 * sizeof(float), mk_b = 65536, sq_b = 64 * 4096,
-                 bd_b = 512 * 512, pr_b = 64 * 13 * sizeof(float), inv_b = 9 * sizeof(double);
-    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    // host block: image | mask | logits | board | probs | inv          device block: image | small | logits | mask | squares | board | probs | inv
-    const size_t h_off[6] = {0, up(img_b), up(img_b) + up(mk_b), up(img_b) + up(mk_b) + up(lg_b), up(img_b) + up(mk_b) + up(lg_b) + up(bd_b),
-                             up(img_b) + up(mk_b) + up(lg_b) + up(bd_b) + up(pr_b)};
-    const size_t h_guard = h_off[5] + up(inv_b);              // two guard words (extractor, classifier)
-    const size_t h_need = h_guard + 256;
-    size_t d_off[8];
+                 bd_b = 512 * 512, pr_b = 64 * 13 * sizeof(float), inv_b = 9 * sizeof(double), gd_b = 2 * sizeof(unsigned);
+    // both staging blocks are carved into pieces that start on 256-byte boundaries; returns the size of the block
+    auto carve = [](std::initializer_list<size_t> sizes, size_t* off) {
+        size_t at = 0;
+        for (size_t b : sizes) { *off++ = at; at += (b + 255) & ~(size_t)255; }
+        return at;
+    };
+    size_t h_off[7], d_off[6];
+    // host block: image | mask | logits | board | probs | inv | two guard words (extractor, classifier)
+    const size_t h_need = carve({img_b, mk_b, lg_b, bd_b, pr_b, inv_b, gd_b}, h_off);
+    // device block: image | small | logits | squares | board | inv
+    const size_t d_need = carve({img_b, small_b, lg_b, sq_b, bd_b, inv_b}, d_off);
     std::lock_guard<std::mutex> pipe_lock(U.pipe_mu);   // one request at a time per extractor engine: the staging blocks are shared
     {
-        const size_t sizes[8] = {img_b, small_b, lg_b, mk_b, sq_b, bd_b, pr_b, inv_b};
-        size_t at = 0;
-        for (int i = 0; i < 8; ++i) { d_off[i] = at; at += up(sizes[i]); }
         std::unique_lock<std::mutex> lk(U.mu);
         if (U.pipe_host_bytes < h_need) {
             hipError_t e = hipStreamSynchronize(st);
-            if (e != hipSuccess) return finish(hip_fail(e, "cv_process_image"));
+            if (e != hipSuccess) return hip_fail(e, "cv_process_image");
             if (U.pipe_host) block_release(U.pipe_host, U.pipe_host_cap, true);
             U.pipe_host = nullptr; U.pipe_host_bytes = 0; U.pipe_host_cap = 0;
             e = block_alloc(&U.pipe_host, h_need, &U.pipe_host_cap, true);
-            if (e != hipSuccess) { U.pipe_host = nullptr; return finish(fail(CV_ERR_NOMEM, std::string("hipHostMalloc: ") + hipGetErrorString(e))); }
+            if (e != hipSuccess) { U.pipe_host = nullptr; return fail(CV_ERR_NOMEM, std::string("hipHostMalloc: ") + hipGetErrorString(e)); }
             U.pipe_host_bytes = h_need;
         }
-        if (U.pipe_dev.bytes < at) {
+        if (U.pipe_dev.bytes < d_need) {
             hipError_t e = hipStreamSynchronize(st);
-            if (e != hipSuccess) return finish(hip_fail(e, "cv_process_image"));
+            if (e != hipSuccess) return hip_fail(e, "cv_process_image");
             U.graph_invalidate();
-            s = U.pipe_dev.alloc(at, false);
-            if (!s.ok()) return finish(s);
+            CV_TRY(U.pipe_dev.alloc(d_need, false));
         }
     }
     char* hb = (char*)U.pipe_host;
     char* db = (char*)U.pipe_dev.ptr;
     uint8_t* d_img = (uint8_t*)(db + d_off[0]); uint8_t* d_small = (uint8_t*)(db + d_off[1]); float* d_lg = (float*)(db + d_off[2]);
-    uint8_t* d_mk = (uint8_t*)(db + d_off[3]); uint8_t* d_sq = (uint8_t*)(db + d_off[4]); uint8_t* d_bd = (uint8_t*)(db + d_off[5]);
-    float* d_pr = (float*)(db + d_off[6]);
+    uint8_t* d_sq = (uint8_t*)(db + d_off[3]); uint8_t* d_bd = (uint8_t*)(db + d_off[4]);
     uint8_t* h_img = (uint8_t*)(hb + h_off[0]); uint8_t* h_mk = (uint8_t*)(hb + h_off[1]); float* h_lg = (float*)(hb + h_off[2]);
     uint8_t* h_bd = (uint8_t*)(hb + h_off[3]); float* h_pr = (float*)(hb + h_off[4]); double* h_inv = (double*)(hb + h_off[5]);
-    unsigned* h_gd = (unsigned*)(hb + h_guard);
+    unsigned* h_gd = (unsigned*)(hb + h_off[6]);
 
-    // The mask (64 KB) and the probabilities (3.3 KB) are written by their kernels straight into the page-locked block, which the device
-    // sees under its host address: over PCIe inside the kernel instead of a copy operation behind it (-18 us per call for the mask, same-box
-    // A/B in profiles/r05_tuning.md section 14).  CV_PI_HOSTMASK=0 / CV_PI_HOSTOUT=0 restore the device buffers + copies.
-    static const bool host_mask = [] { const char* v = std::getenv("CV_PI_HOSTMASK"); return !(v && v[0] == '0'); }();
     std::memcpy(h_img, image, img_b);
     hipError_t e = hipMemcpyAsync(d_img, h_img, img_b, hipMemcpyHostToDevice, st);
-    if (e != hipSuccess) return finish(hip_fail(e, "cv_process_image: upload"));
+    if (e != hipSuccess) return hip_fail(e, "cv_process_image: upload");
+    Status s;
     {
+        // The mask (64 KB) and the probabilities (3.3 KB) are written by their kernels straight into the page-locked block, which the
+        // device sees under its host address: over PCIe inside the kernel instead of a copy operation behind it (-18 us per call for the
+        // mask, same-box A/B in profiles/r05_tuning.md section 14).
         std::lock_guard<std::mutex> lk(U.mu);
         s = resize_on_stream(U, d_img, 1, h, w_, 3, d_small, 256, 256, st);
-        if (s.ok()) s = unet_forward(U, d_small, true, 1, d_lg, host_mask ? h_mk : d_mk, threshold, st);
+        if (s.ok()) s = unet_forward(U, d_small, true, 1, d_lg, h_mk, threshold, st);
     }
-    if (!s.ok()) return finish(s);
-    e = host_mask ? hipSuccess : hipMemcpyAsync(h_mk, d_mk, mk_b, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess && !U.pipe_event) e = hipEventCreateWithFlags(&U.pipe_event, hipEventDisableTiming);
+    if (!s.ok()) return s;
+    if (!U.pipe_event) e = hipEventCreateWithFlags(&U.pipe_event, hipEventDisableTiming);
     if (e == hipSuccess) e = hipEventRecord(U.pipe_event, st);
     if (e == hipSuccess) e = hipMemcpyAsync(h_lg, d_lg, lg_b, hipMemcpyDeviceToHost, st);     // travels while the host finds the quadrangle
     if (e == hipSuccess) e = hipEventSynchronize(U.pipe_event);
-    if (e != hipSuccess) return finish(hip_fail(e, "cv_process_image: mask"));
+    if (e != hipSuccess) return hip_fail(e, "cv_process_image: mask");
     if (out->mask) std::memcpy(out->mask, h_mk, mk_b);
     int32_t quad[8];
-    bool side_busy = false, side_joined = false;             // a download is in flight on U.pipe_side: every exit below waits for it
+    SideStreamJoin side;                                     // the board's download on U.pipe_side: every exit below waits for it
     bool found = find_quadrangle(h_mk, 256, 256, quad);
     if (!found && fallback_quad) {
         const int32_t whole[8] = {255, 0, 0, 0, 0, 255, 255, 255};            // TR, TL, BL, BR of the mask
@@ -962,31 +404,25 @@ static int impl_cv_process_image(cv_engine_t* ue, cv_engine_t* ce, const uint8_t
         e = extract_squares_u8_one(d_img, h, w_, h_inv, d_sq, d_bd, st);   // the matrix travels in the kernel arguments
         // the rectified board (256 KB) goes home on a side stream while the classifier runs: behind the classifier on `st` it was 16 us
         // at the end of every call
-        static const bool side_on = [] { const char* v = std::getenv("CV_PI_SIDE"); return !(v && v[0] == '0'); }();
-        static const bool host_out = [] { const char* v = std::getenv("CV_PI_HOSTOUT"); return !(v && v[0] == '0'); }();
-        if (side_on) {
-            if (e == hipSuccess && !U.pipe_side) e = hipStreamCreateWithFlags(&U.pipe_side, hipStreamNonBlocking);
-            if (e == hipSuccess && !U.pipe_event2) e = hipEventCreateWithFlags(&U.pipe_event2, hipEventDisableTiming);
-            if (e == hipSuccess) e = hipEventRecord(U.pipe_event2, st);
-            if (e == hipSuccess) e = hipStreamWaitEvent(U.pipe_side, U.pipe_event2, 0);
-            if (e == hipSuccess) e = hipMemcpyAsync(h_bd, d_bd, bd_b, hipMemcpyDeviceToHost, U.pipe_side);
-            side_busy = e == hipSuccess;
-            if (e == hipSuccess && !U.pipe_event3) e = hipEventCreateWithFlags(&U.pipe_event3, hipEventDisableTiming);
-            if (e == hipSuccess) e = hipEventRecord(U.pipe_event3, U.pipe_side);
-        }
-        if (e != hipSuccess) { if (side_busy) (void)hipStreamSynchronize(U.pipe_side); return finish(hip_fail(e, "cv_process_image: warp")); }
+        if (e == hipSuccess && !U.pipe_side) e = hipStreamCreateWithFlags(&U.pipe_side, hipStreamNonBlocking);
+        if (e == hipSuccess && !U.pipe_event2) e = hipEventCreateWithFlags(&U.pipe_event2, hipEventDisableTiming);
+        if (e == hipSuccess) e = hipEventRecord(U.pipe_event2, st);
+        if (e == hipSuccess) e = hipStreamWaitEvent(U.pipe_side, U.pipe_event2, 0);
+        if (e == hipSuccess) e = hipMemcpyAsync(h_bd, d_bd, bd_b, hipMemcpyDeviceToHost, U.pipe_side);
+        if (e == hipSuccess) side.arm(U.pipe_side);
+        if (e == hipSuccess && !U.pipe_event3) e = hipEventCreateWithFlags(&U.pipe_event3, hipEventDisableTiming);
+        if (e == hipSuccess) e = hipEventRecord(U.pipe_event3, U.pipe_side);
+        if (e != hipSuccess) return hip_fail(e, "cv_process_image: warp");
         {
             std::lock_guard<std::mutex> lk(C.mu);
             // the 64 x 13 probabilities are written by the head kernel straight into the page-locked block (device-visible under
             // its host address): 3.3 KB over PCIe inside the kernel instead of one more copy operation at the end of the stream
-            s = resnet_forward(C, d_sq, true, 64, host_out ? h_pr : d_pr, true, st);
+            s = resnet_forward(C, d_sq, true, 64, h_pr, true, st);
         }
-        if (!s.ok()) { if (side_busy) (void)hipStreamSynchronize(U.pipe_side); return finish(s); }
-        e = host_out ? hipSuccess : hipMemcpyAsync(h_pr, d_pr, pr_b, hipMemcpyDeviceToHost, st);
+        if (!s.ok()) return s;
         // the side stream joins `st` on the DEVICE (the download finished long before the classifier): one host synchronisation per call
-        if (e == hipSuccess && side_busy) { e = hipStreamWaitEvent(st, U.pipe_event3, 0); side_joined = e == hipSuccess; }
-        if (e == hipSuccess && !side_busy) e = hipMemcpyAsync(h_bd, d_bd, bd_b, hipMemcpyDeviceToHost, st);
-        if (e != hipSuccess) { if (side_busy) (void)hipStreamSynchronize(U.pipe_side); return finish(hip_fail(e, "cv_process_image: download")); }
+        e = hipStreamWaitEvent(st, U.pipe_event3, 0);
+        if (e != hipSuccess) return hip_fail(e, "cv_process_image: download");
     }
     {   // the numeric guards ride with the downloads into page-locked memory; ONE synchronisation, then both words are judged
         std::lock_guard<std::mutex> lk(U.mu);
@@ -997,10 +433,10 @@ static int impl_cv_process_image(cv_engine_t* ue, cv_engine_t* ce, const uint8_t
         std::lock_guard<std::mutex> lk(C.mu);
         s = C.guard_read_async(h_gd + 1, st);
     }
-    if (!s.ok()) { if (side_busy) (void)hipStreamSynchronize(U.pipe_side); return finish(s); }
+    if (!s.ok()) return s;
     e = hipStreamSynchronize(st);                           // everything above has landed afterwards
-    if (side_busy && !side_joined) { const hipError_t e2 = hipStreamSynchronize(U.pipe_side); if (e == hipSuccess) e = e2; }
-    if (e != hipSuccess) return finish(hip_fail(e, "cv_process_image: synchronise"));
+    if (e != hipSuccess) return hip_fail(e, "cv_process_image: synchronise");
+    side.disarm();                                          // ... the board too: `st` waited for it on the device
     {
         std::lock_guard<std::mutex> lk(U.mu);
         s = U.guard_eval(h_gd[0]);
@@ -1009,9 +445,9 @@ static int impl_cv_process_image(cv_engine_t* ue, cv_engine_t* ce, const uint8_t
         std::lock_guard<std::mutex> lk(C.mu);
         s = C.guard_eval(h_gd[1]);
     }
-    if (!s.ok()) return finish(s);
+    if (!s.ok()) return s;
     if (out->logits) std::memcpy(out->logits, h_lg, lg_b);
-    if (!found) return CV_OK;
+    if (!found) return Status();
     if (out->board) std::memcpy(out->board, h_bd, bd_b);
     if (out_squares)                                         // extract_squares (core.py:419-439) on the host copy: 4096 rows of 64 bytes
         for (int r = 0; r < 8; ++r)
@@ -1023,120 +459,10 @@ static int impl_cv_process_image(cv_engine_t* ue, cv_engine_t* ce, const uint8_t
     decode_positions(h_pr, 1, flip, out->fen, out->original_fen, labels, out->fixes, &out->n_fixes);
     if (out->labels) std::memcpy(out->labels, labels, sizeof(labels));
     out->found = 1;
-    return CV_OK;
+    return Status();
 }
 
-static int impl_cv_profile_entry_bytes(cv_engine_t* eng, int index, double* bytes) {
-    Status s = check_engine(eng);
-    if (!s.ok()) return finish(s);
-    std::lock_guard<std::mutex> lk(eng->impl.mu);
-    if (!bytes || index < 0 || index >= (int)eng->impl.prof.size()) return finish(fail(CV_ERR_INVALID, "profile index out of range"));
-    *bytes = eng->impl.prof[index].bytes;
-    return CV_OK;
-}
-
-static int impl_cv_profile_entry_kernel(cv_engine_t* eng, int index, char* kernel, int kernel_cap) {
-    Status s = check_engine(eng);
-    if (!s.ok()) return finish(s);
-    std::lock_guard<std::mutex> lk(eng->impl.mu);
-    if (!kernel || kernel_cap <= 0 || index < 0 || index >= (int)eng->impl.prof.size()) return finish(fail(CV_ERR_INVALID, "profile index out of range"));
-    const std::string& k = eng->impl.prof[index].kernel;
-    const size_t n = std::min(k.size(), (size_t)kernel_cap - 1);
-    std::memcpy(kernel, k.data(), n);
-    kernel[n] = 0;
-    return CV_OK;
-}
-
-static int impl_cv_engine_numeric_status(cv_engine_t* eng, void* stream) {
-    Status s = check_engine(eng);
-    if (!s.ok()) return finish(s);
-    std::lock_guard<std::mutex> lk(eng->impl.mu);
-    DeviceGuard g(eng->impl.device);
-    return finish(eng->impl.guard_check((hipStream_t)stream));
-}
-
-static int impl_cv_engine_workspace_bytes(cv_engine_t* eng, size_t* bytes) {
-    Status s = check_engine(eng);
-    if (!s.ok()) return finish(s);
-    if (!bytes) return finish(fail(CV_ERR_INVALID, "null argument"));
-    std::lock_guard<std::mutex> lk(eng->impl.mu);
-    *bytes = eng->impl.workspace_bytes();
-    return CV_OK;
-}
-
-static int impl_cv_get_activation_exponent(cv_engine_t* eng, const char* model, const char* name, int* exponent) {
-    Status s = check_engine(eng);
-    if (!s.ok()) return finish(s);
-    if (!model || !name || !exponent) return finish(fail(CV_ERR_INVALID, "null argument"));
-    std::lock_guard<std::mutex> lk(eng->impl.mu);
-    TensorRef t;
-    bool is_resnet = false;
-    s = model_by_name(eng->impl, model, &is_resnet);
-    if (s.ok()) s = is_resnet ? resnet_activation(eng->impl, name, &t) : unet_activation(eng->impl, name, &t);
-    if (!s.ok()) return finish(s);
-    *exponent = t.exp;
-    return CV_OK;
-}
-
-static int impl_cv_decode_positions(const float* probs, int n_boards, int flip, char* fen, char* original_fen, int8_t* labels,
-                                    int32_t* fixes, int32_t* n_fixes) {
-    if (n_boards < 0 || (n_boards > 0 && (!probs || !fen || !original_fen || !labels || !fixes || !n_fixes)))
-        return finish(fail(CV_ERR_INVALID, "cv_decode_positions: bad argument"));
-    decode_positions(probs, n_boards, flip, fen, original_fen, labels, fixes, n_fixes);
-    return CV_OK;
-}
-
-static int impl_cv_extract_squares_u8_dev(cv_engine_t* eng, const uint8_t* images, int n, int h, int w_, const double* inv_dev,
-                                          uint8_t* squares, uint8_t* boards, void* stream) {
-    Status s = check_engine(eng);
-    if (!s.ok()) return finish(s);
-    if (!images || !inv_dev || !squares || n <= 0 || h <= 0 || w_ <= 0)
-        return finish(fail(CV_ERR_INVALID, "cv_extract_squares_u8_dev: bad argument"));
-    if ((size_t)h * (size_t)w_ > ((size_t)1 << 30)) return finish(fail(CV_ERR_INVALID, "cv_extract_squares_u8_dev: image too large (32-bit byte offsets)"));
-    if (((uintptr_t)squares & 3) || ((uintptr_t)boards & 3) || ((uintptr_t)inv_dev & 7))
-        return finish(fail(CV_ERR_INVALID, "cv_extract_squares_u8_dev: outputs must be 4-byte aligned, matrices 8-byte aligned"));
-    DeviceGuard g(eng->impl.device);
-    hipError_t err = extract_squares_u8(images, n, h, w_, inv_dev, squares, boards, (hipStream_t)stream);
-    if (err != hipSuccess) return finish(hip_fail(err, "extract_squares_u8"));
-    return CV_OK;
-}
-
-static int impl_cv_selftest_mfma(cv_engine_t* eng, float* max_err_f16, float* max_err_f32) {
-    Status s = check_engine(eng);
-    if (!s.ok()) return finish(s);
-    DeviceGuard g(eng->impl.device);
-    // asymmetric integer-valued operands: exact in f16 and f32, so the expected error is exactly 0
-    _Float16 a16[16 * 32], b16[16 * 32];
-    float a32[16 * 16], b32[16 * 16], ref16[256], ref32[256], got[256];
-    for (int i = 0; i < 16; ++i)
-        for (int k = 0; k < 32; ++k) { a16[i * 32 + k] = (_Float16)(float)((i * 3 + k * 5) % 7 - 3); b16[i * 32 + k] = (_Float16)(float)((i * 5 + k * 2 + 1) % 9 - 4); }
-    for (int i = 0; i < 16; ++i)
-        for (int k = 0; k < 16; ++k) { a32[i * 16 + k] = (float)((i * 3 + k * 5) % 7 - 3); b32[i * 16 + k] = (float)((i * 5 + k * 2 + 1) % 9 - 4); }
-    for (int i = 0; i < 16; ++i)
-        for (int j = 0; j < 16; ++j) {
-            float s16 = 0, s32 = 0;
-            for (int k = 0; k < 32; ++k) s16 += (float)a16[i * 32 + k] * (float)b16[j * 32 + k];
-            for (int k = 0; k < 16; ++k) s32 += a32[i * 16 + k] * b32[j * 16 + k];
-            ref16[i * 16 + j] = s16; ref32[i * 16 + j] = s32;
-        }
-    DeviceBuffer da, db, dd;
-    hipError_t e = hipSuccess;
-    float err16 = 0.f, err32 = 0.f;
-    if (!(s = da.upload(a16, sizeof(a16))).ok() || !(s = db.upload(b16, sizeof(b16))).ok() || !(s = dd.alloc(sizeof(got), true)).ok()) return finish(s);
-    e = mfma_probe_f16((const half_t*)da.ptr, (const half_t*)db.ptr, (float*)dd.ptr, nullptr);
-    if (e == hipSuccess) e = sync_memcpy(got, dd.ptr, sizeof(got), hipMemcpyDeviceToHost);
-    if (e != hipSuccess) return finish(hip_fail(e, "mfma_probe_f16"));
-    for (int i = 0; i < 256; ++i) err16 = std::max(err16, std::fabs(got[i] - ref16[i]));
-    if (!(s = da.upload(a32, sizeof(a32))).ok() || !(s = db.upload(b32, sizeof(b32))).ok()) return finish(s);
-    e = mfma_probe_f32((const float*)da.ptr, (const float*)db.ptr, (float*)dd.ptr, nullptr);
-    if (e == hipSuccess) e = sync_memcpy(got, dd.ptr, sizeof(got), hipMemcpyDeviceToHost);
-    if (e != hipSuccess) return finish(hip_fail(e, "mfma_probe_f32"));
-    for (int i = 0; i < 256; ++i) err32 = std::max(err32, std::fabs(got[i] - ref32[i]));
-    if (max_err_f16) *max_err_f16 = err16;
-    if (max_err_f32) *max_err_f32 = err32;
-    return CV_OK;
-}
-
+}  // namespace
 
 // ---- the exported C surface: every entry point is exception-tight -----------------------------------------------
 extern "C" {
@@ -1145,286 +471,736 @@ int cv_abi_version(void) { return CV_ABI_VERSION; }
 const char* cv_last_error(void) { return get_error(); }
 
 int cv_device_count(int* count) {
-    return guarded("cv_device_count", [&]() -> int { return impl_cv_device_count(count); });
+    return guarded("cv_device_count", [&]() -> Status {
+        if (!count) return fail(CV_ERR_INVALID, "null count");
+        hipError_t e = hipGetDeviceCount(count);
+        if (e != hipSuccess) { *count = 0; return hip_fail(e, "hipGetDeviceCount"); }
+        return Status();
+    });
 }
+
 int cv_trim_memory(size_t* bytes_freed) {
-    return guarded("cv_trim_memory", [&]() -> int {
+    return guarded("cv_trim_memory", [&]() -> Status {
         const size_t n = block_cache_trim();
         if (bytes_freed) *bytes_freed = n;
-        return CV_OK;
+        return Status();
     });
 }
 
 int cv_engine_create(int device, int precision, cv_engine_t** out) {
-    return guarded("cv_engine_create", [&]() -> int { return impl_cv_engine_create(device, precision, out); });
+    return guarded("cv_engine_create", [&]() -> Status {
+        if (!out) return fail(CV_ERR_INVALID, "null out pointer");
+        *out = nullptr;
+        if (precision != CV_PREC_F32 && precision != CV_PREC_F16 && precision != CV_PREC_F16X3 && precision != CV_PREC_F16R)
+            return fail(CV_ERR_INVALID, "unknown precision");
+        static_assert((int)CV_PREC_F32 == (int)kF32 && (int)CV_PREC_F16 == (int)kF16 && (int)CV_PREC_F16X3 == (int)kSplit, "enum values must match");
+        int count = 0;
+        hipError_t e = hipGetDeviceCount(&count);
+        if (e != hipSuccess || count <= 0)
+            return fail(CV_ERR_HIP, std::string("no HIP device available: ") + (e != hipSuccess ? hipGetErrorString(e) : "device count is 0"));
+        if (device < 0 || device >= count) return fail(CV_ERR_INVALID, "device ordinal out of range");
+        DeviceGuard g(device);
+        hipDeviceProp_t prop;
+        if ((e = hipGetDeviceProperties(&prop, device)) != hipSuccess) return hip_fail(e, "hipGetDeviceProperties");
+        if (std::string(prop.gcnArchName).rfind("gfx950", 0) != 0)
+            return fail(CV_ERR_STATE, std::string("libchessvision_hip is built for gfx950 (MI355X); device is ") + prop.gcnArchName);
+        {
+            // the dynamic-LDS limits of the conv kernels are raised ONCE per device and process, under a lock: repeating hipFuncSetAttribute
+            // at every engine creation while other threads launch those very kernels (request slots: replicas are loaded in the background
+            // of a serving instance) is not something the runtime promises to survive
+            static std::mutex prep_mu;
+            static bool prepared[64] = {};
+            std::lock_guard<std::mutex> lk(prep_mu);
+            if (device >= 64 || !prepared[device]) {
+                if ((e = conv_igemm_prepare()) != hipSuccess) return hip_fail(e, "conv_igemm_prepare");
+                if ((e = conv_halo_prepare()) != hipSuccess) return hip_fail(e, "conv_halo_prepare");
+                if ((e = conv1x1_lds_prepare()) != hipSuccess) return hip_fail(e, "conv1x1_lds_prepare");
+                if (device < 64) prepared[device] = true;
+            }
+        }
+        cv_engine* eng = new (std::nothrow) cv_engine();
+        if (!eng) return fail(CV_ERR_NOMEM, "out of host memory");
+        eng->impl.device = device;
+        eng->impl.dt = precision == CV_PREC_F16R ? (int)kF16 : precision;   // CV_PREC_F32 / F16 / F16X3 values equal cv::DType
+        eng->impl.trunk32 = precision == CV_PREC_F16R;
+        const Status gs = eng->impl.guard_init();
+        if (!gs.ok()) { delete eng; return gs; }
+        *out = eng;
+        return Status();
+    });
 }
 
 int cv_engine_destroy(cv_engine_t* eng) {
-    return guarded("cv_engine_destroy", [&]() -> int { return impl_cv_engine_destroy(eng); });
+    return guarded("cv_engine_destroy", [&]() -> Status {
+        if (!eng) return Status();
+        DeviceGuard g(eng->impl.device);                // every block of the engine goes back to the cache under ITS device
+        (void)device_synchronize();
+        ReleaseAlreadySynced quiescent;                 // nothing can be queued on a dying engine's buffers from here on
+        eng->impl.unet.reset();
+        eng->impl.resnet.reset();
+        delete eng;
+        return Status();
+    });
 }
 
 int cv_engine_set_chunk(cv_engine_t* eng, int unet_images, int resnet_squares) {
-    return guarded("cv_engine_set_chunk", [&]() -> int { return impl_cv_engine_set_chunk(eng, unet_images, resnet_squares); });
+    return guarded("cv_engine_set_chunk", [&]() -> Status {
+        CV_TRY(check_engine(eng));
+        std::lock_guard<std::mutex> lk(eng->impl.mu);
+        if (eng->impl.unet || eng->impl.resnet) return fail(CV_ERR_STATE, "cv_engine_set_chunk must precede cv_load_*");
+        if (unet_images < 0 || resnet_squares < 0) return fail(CV_ERR_INVALID, "negative chunk");
+        if (unet_images) eng->impl.unet_chunk = unet_images;
+        if (resnet_squares) eng->impl.resnet_chunk = resnet_squares;
+        return Status();
+    });
 }
 
 int cv_load_unet(cv_engine_t* eng, const cv_param_t* params, int n_params) {
-    return guarded("cv_load_unet", [&]() -> int { return impl_cv_load_unet(eng, params, n_params); });
+    return guarded("cv_load_unet", [&]() -> Status {
+        CV_TRY(check_engine(eng));
+        std::lock_guard<std::mutex> load_lk(load_mutex());
+        std::lock_guard<std::mutex> lk(eng->impl.mu);
+        DeviceGuard g(eng->impl.device);
+        ParamMap pm;
+        CV_TRY(to_map(params, n_params, pm));
+        return unet_load(eng->impl, pm);
+    });
 }
 
 int cv_load_resnet(cv_engine_t* eng, const char* arch, const cv_param_t* params, int n_params) {
-    return guarded("cv_load_resnet", [&]() -> int { return impl_cv_load_resnet(eng, arch, params, n_params); });
+    return guarded("cv_load_resnet", [&]() -> Status { return load_resnet(eng, arch, params, n_params); });
 }
 
 int cv_load_resnet18(cv_engine_t* eng, const cv_param_t* params, int n_params) {
-    return guarded("cv_load_resnet18", [&]() -> int { return impl_cv_load_resnet(eng, "resnet18", params, n_params); });
+    return guarded("cv_load_resnet18", [&]() -> Status { return load_resnet(eng, "resnet18", params, n_params); });
 }
 
 int cv_unet_forward(cv_engine_t* eng, const float* x, int batch, float* logits, void* stream) {
-    return guarded("cv_unet_forward", [&]() -> int { return impl_cv_unet_forward(eng, x, batch, logits, stream); });
+    return guarded("cv_unet_forward", [&]() -> Status { return unet_entry(eng, x, false, batch, logits, nullptr, 0.5f, nullptr, stream); });
 }
 
 int cv_unet_forward_u8(cv_engine_t* eng, const uint8_t* x_u8, int batch, float* logits, uint8_t* mask,
                        float threshold, void* stream) {
-    return guarded("cv_unet_forward_u8", [&]() -> int { return impl_cv_unet_forward_u8(eng, x_u8, batch, logits, mask, threshold, stream); });
-}
-
-int cv_resnet18_forward(cv_engine_t* eng, const float* x, int n, float* logits, void* stream) {
-    return guarded("cv_resnet18_forward", [&]() -> int { return impl_cv_resnet18_forward(eng, x, n, logits, stream); });
-}
-
-int cv_resnet18_forward_u8(cv_engine_t* eng, const uint8_t* squares_u8, int n, float* probs, void* stream) {
-    return guarded("cv_resnet18_forward_u8", [&]() -> int { return impl_cv_resnet18_forward_u8(eng, squares_u8, n, probs, stream); });
-}
-
-int cv_embedding_dim(cv_engine_t* eng, const char* model, int* channels) {
-    return guarded("cv_embedding_dim", [&]() -> int { return impl_cv_embedding_dim(eng, model, channels); });
+    return guarded("cv_unet_forward_u8", [&]() -> Status { return unet_entry(eng, x_u8, true, batch, logits, mask, threshold, nullptr, stream); });
 }
 
 int cv_unet_forward_emb(cv_engine_t* eng, const float* x, int batch, float* logits, float* embedding, void* stream) {
-    return guarded("cv_unet_forward_emb", [&]() -> int { return impl_cv_unet_forward_emb(eng, x, false, batch, logits, nullptr, 0.5f, embedding, stream); });
+    return guarded("cv_unet_forward_emb", [&]() -> Status { return unet_entry(eng, x, false, batch, logits, nullptr, 0.5f, embedding, stream); });
 }
 
 int cv_unet_forward_u8_emb(cv_engine_t* eng, const uint8_t* x_u8, int batch, float* logits, uint8_t* mask,
                            float threshold, float* embedding, void* stream) {
-    return guarded("cv_unet_forward_u8_emb", [&]() -> int { return impl_cv_unet_forward_emb(eng, x_u8, true, batch, logits, mask, threshold, embedding, stream); });
+    return guarded("cv_unet_forward_u8_emb", [&]() -> Status { return unet_entry(eng, x_u8, true, batch, logits, mask, threshold, embedding, stream); });
 }
 
 int cv_unet_forward_mask(cv_engine_t* eng, const float* x, int batch, float* logits, uint8_t* mask, float threshold, float* embedding,
                          void* stream) {
-    return guarded("cv_unet_forward_mask", [&]() -> int { return impl_cv_unet_forward_emb(eng, x, false, batch, logits, mask, threshold, embedding, stream); });
+    return guarded("cv_unet_forward_mask", [&]() -> Status { return unet_entry(eng, x, false, batch, logits, mask, threshold, embedding, stream); });
+}
+
+int cv_resnet18_forward(cv_engine_t* eng, const float* x, int n, float* logits, void* stream) {
+    return guarded("cv_resnet18_forward", [&]() -> Status { return resnet_entry(eng, x, false, n, logits, nullptr, stream); });
+}
+
+int cv_resnet18_forward_u8(cv_engine_t* eng, const uint8_t* squares_u8, int n, float* probs, void* stream) {
+    return guarded("cv_resnet18_forward_u8", [&]() -> Status { return resnet_entry(eng, squares_u8, true, n, probs, nullptr, stream); });
 }
 
 int cv_resnet18_forward_emb(cv_engine_t* eng, const float* x, int n, float* logits, float* embedding, void* stream) {
-    return guarded("cv_resnet18_forward_emb", [&]() -> int { return impl_cv_resnet18_forward_emb(eng, x, false, n, logits, embedding, stream); });
+    return guarded("cv_resnet18_forward_emb", [&]() -> Status { return resnet_entry(eng, x, false, n, logits, embedding, stream); });
 }
 
 int cv_resnet18_forward_u8_emb(cv_engine_t* eng, const uint8_t* squares_u8, int n, float* probs, float* embedding, void* stream) {
-    return guarded("cv_resnet18_forward_u8_emb", [&]() -> int { return impl_cv_resnet18_forward_emb(eng, squares_u8, true, n, probs, embedding, stream); });
+    return guarded("cv_resnet18_forward_u8_emb", [&]() -> Status { return resnet_entry(eng, squares_u8, true, n, probs, embedding, stream); });
+}
+
+int cv_embedding_dim(cv_engine_t* eng, const char* model, int* channels) {
+    return guarded("cv_embedding_dim", [&]() -> Status {
+        CV_TRY(check_engine(eng));
+        if (!model || !channels) return fail(CV_ERR_INVALID, "null argument");
+        std::lock_guard<std::mutex> lk(eng->impl.mu);
+        bool is_resnet = false;
+        CV_TRY(model_by_name(eng->impl, model, &is_resnet));
+        *channels = is_resnet ? (eng->impl.resnet ? 512 : 0) : unet_embedding_dim(eng->impl);
+        if (*channels == 0) return fail(CV_ERR_STATE, "cv_embedding_dim: model '" + std::string(model) + "' is not loaded");
+        return Status();
+    });
 }
 
 int cv_activation_channel_means(cv_engine_t* eng, const char* model, const char* name, float* out_dev, size_t capacity_floats,
                                 int64_t dims[2], void* stream) {
-    return guarded("cv_activation_channel_means", [&]() -> int { return impl_cv_activation_channel_means(eng, model, name, out_dev, capacity_floats, dims, stream); });
+    return guarded("cv_activation_channel_means", [&]() -> Status {
+        CV_TRY(check_engine(eng));
+        if (!model || !name || !dims) return fail(CV_ERR_INVALID, "null argument");
+        std::lock_guard<std::mutex> lk(eng->impl.mu);
+        DeviceGuard g(eng->impl.device);
+        TensorRef t;
+        // "global_pool" (the classifier's hook, named_modules()[90]) is the mean of layer4's output: pooled here, it needs no tensor of
+        // its own.  The UNet has no tensor of that name.
+        const bool pooled_layer4 = std::strcmp(name, "global_pool") == 0 && std::strcmp(model, "unet") != 0;
+        CV_TRY(activation_by_name(eng->impl, model, pooled_layer4 ? "layer4" : name, &t));
+        dims[0] = t.N; dims[1] = t.C;
+        if (!out_dev) return Status();                        // shape query
+        const std::string tap = "cv_activation_channel_means('" + std::string(name) + "')";
+        if (t.N < 1) return fail(CV_ERR_INVALID, tap + ": no forward has run yet");
+        if (capacity_floats < (size_t)t.N * t.C)
+            return fail(CV_ERR_INVALID, tap + ": output buffer too small, " + std::to_string((size_t)t.N * t.C) + " floats needed");
+        if ((uintptr_t)out_dev & 15u) return fail(CV_ERR_INVALID, tap + ": output must be 16-byte aligned");
+        if (t.C % 8 || t.split) return fail(CV_ERR_INVALID, tap + ": the tensor's channel slice cannot be pooled");
+        hipError_t e = channel_means(eng->impl.dt, t, out_dev, (hipStream_t)stream);
+        if (e != hipSuccess) return hip_fail(e, tap.c_str());
+        return Status();
+    });
 }
 
 int cv_softmax13(cv_engine_t* eng, const float* logits, int n, float* probs, void* stream) {
-    return guarded("cv_softmax13", [&]() -> int { return impl_cv_softmax13(eng, logits, n, probs, stream); });
+    return guarded("cv_softmax13", [&]() -> Status {
+        CV_TRY(check_engine(eng));
+        if (n < 0 || (n > 0 && (!logits || !probs))) return fail(CV_ERR_INVALID, "cv_softmax13: null tensor");
+        if (n == 0) return Status();
+        DeviceGuard g(eng->impl.device);
+        hipError_t e = softmax13(logits, n, probs, (hipStream_t)stream);
+        if (e != hipSuccess) return hip_fail(e, "softmax13");
+        return Status();
+    });
 }
 
 int cv_get_activation(cv_engine_t* eng, const char* model, const char* name, float* out_host, size_t out_capacity,
                       int64_t dims[4]) {
-    return guarded("cv_get_activation", [&]() -> int { return impl_cv_get_activation(eng, model, name, out_host, out_capacity, dims); });
+    return guarded("cv_get_activation", [&]() -> Status {
+        CV_TRY(check_engine(eng));
+        if (!model || !name || !dims) return fail(CV_ERR_INVALID, "null argument");
+        std::lock_guard<std::mutex> lk(eng->impl.mu);
+        DeviceGuard g(eng->impl.device);
+        TensorRef t;
+        CV_TRY(activation_by_name(eng->impl, model, name, &t));
+        dims[0] = t.N; dims[1] = t.C; dims[2] = t.H; dims[3] = t.W;
+        const size_t numel = (size_t)t.N * t.C * t.H * t.W;
+        if (!out_host) return Status();                       // shape query
+        if (out_capacity < numel) return fail(CV_ERR_INVALID, "output buffer too small");
+        DeviceBuffer tmp;
+        CV_TRY(tmp.alloc(numel * sizeof(float), false));
+        hipError_t e = device_synchronize();
+        if (e == hipSuccess) e = unpack_nchw_f32(t.f32_only ? (int)kF32 : eng->impl.dt, t, (float*)tmp.ptr, nullptr);
+        if (e == hipSuccess) e = sync_memcpy(out_host, tmp.ptr, numel * sizeof(float), hipMemcpyDeviceToHost);
+        if (e != hipSuccess) return hip_fail(e, "cv_get_activation");
+        return Status();
+    });
+}
+
+int cv_get_activation_exponent(cv_engine_t* eng, const char* model, const char* name, int* exponent) {
+    return guarded("cv_get_activation_exponent", [&]() -> Status {
+        CV_TRY(check_engine(eng));
+        if (!model || !name || !exponent) return fail(CV_ERR_INVALID, "null argument");
+        std::lock_guard<std::mutex> lk(eng->impl.mu);
+        TensorRef t;
+        CV_TRY(activation_by_name(eng->impl, model, name, &t));
+        *exponent = t.exp;
+        return Status();
+    });
 }
 
 int cv_model_macs(cv_engine_t* eng, const char* model, int64_t* macs) {
-    return guarded("cv_model_macs", [&]() -> int { return impl_cv_model_macs(eng, model, macs); });
+    return guarded("cv_model_macs", [&]() -> Status {
+        CV_TRY(check_engine(eng));
+        if (!model || !macs) return fail(CV_ERR_INVALID, "null argument");
+        bool is_resnet = false;
+        CV_TRY(model_by_name(eng->impl, model, &is_resnet));
+        *macs = is_resnet ? resnet_macs(eng->impl) : unet_macs(eng->impl);
+        if (*macs == 0) return fail(CV_ERR_STATE, "model not loaded");
+        return Status();
+    });
 }
 
 int cv_profile_convs(cv_engine_t* eng, const char* model, const void* x, int batch, void* out, int iters,
                      void* stream, float* conv_ms_total, int* conv_launches, float* all_ms_total) {
-    return guarded("cv_profile_convs", [&]() -> int { return impl_cv_profile_convs(eng, model, x, batch, out, iters, stream, conv_ms_total, conv_launches, all_ms_total); });
+    return guarded("cv_profile_convs", [&]() -> Status {
+        CV_TRY(check_engine(eng));
+        if (!model || iters <= 0) return fail(CV_ERR_INVALID, "bad profile arguments");
+        std::lock_guard<std::mutex> lk(eng->impl.mu);
+        DeviceGuard g(eng->impl.device);
+        Engine& e = eng->impl;
+        bool is_resnet = false;
+        CV_TRY(model_by_name(e, model, &is_resnet));
+        e.prof_clear();
+        e.profiling = true;
+        Status s;
+        for (int i = 0; i < iters && s.ok(); ++i) {
+            if (is_resnet) s = resnet_forward(e, x, false, batch, (float*)out, false, (hipStream_t)stream);
+            else s = unet_forward(e, x, false, batch, (float*)out, nullptr, 0.5f, (hipStream_t)stream);
+        }
+        e.profiling = false;
+        if (s.ok()) s = e.prof_collect();
+        if (!s.ok()) { e.prof_clear(); return s; }
+        float conv = 0.f, all = 0.f;
+        int n = 0;
+        for (auto& pe : e.prof) { all += pe.ms; if (pe.is_conv) { conv += pe.ms; ++n; } }
+        if (conv_ms_total) *conv_ms_total = conv;
+        if (conv_launches) *conv_launches = n;
+        if (all_ms_total) *all_ms_total = all;
+        return Status();
+    });
 }
 
 int cv_profile_entry(cv_engine_t* eng, int index, char* name, int name_cap, float* ms, double* macs, int* is_conv) {
-    return guarded("cv_profile_entry", [&]() -> int { return impl_cv_profile_entry(eng, index, name, name_cap, ms, macs, is_conv); });
+    return guarded("cv_profile_entry", [&]() -> Status {
+        CV_TRY(check_engine(eng));
+        std::lock_guard<std::mutex> lk(eng->impl.mu);
+        if (index < 0 || index >= (int)eng->impl.prof.size()) return fail(CV_ERR_INVALID, "profile index out of range");
+        const ProfileEntry& pe = eng->impl.prof[index];
+        if (name && name_cap > 0) { std::strncpy(name, pe.name.c_str(), name_cap - 1); name[name_cap - 1] = 0; }
+        if (ms) *ms = pe.ms;
+        if (macs) *macs = pe.macs;
+        if (is_conv) *is_conv = pe.is_conv ? 1 : 0;
+        return Status();
+    });
+}
+
+int cv_profile_entry_bytes(cv_engine_t* eng, int index, double* bytes) {
+    return guarded("cv_profile_entry_bytes", [&]() -> Status {
+        CV_TRY(check_engine(eng));
+        std::lock_guard<std::mutex> lk(eng->impl.mu);
+        if (!bytes || index < 0 || index >= (int)eng->impl.prof.size()) return fail(CV_ERR_INVALID, "profile index out of range");
+        *bytes = eng->impl.prof[index].bytes;
+        return Status();
+    });
+}
+
+int cv_profile_entry_kernel(cv_engine_t* eng, int index, char* kernel, int kernel_cap) {
+    return guarded("cv_profile_entry_kernel", [&]() -> Status {
+        CV_TRY(check_engine(eng));
+        std::lock_guard<std::mutex> lk(eng->impl.mu);
+        if (!kernel || kernel_cap <= 0 || index < 0 || index >= (int)eng->impl.prof.size()) return fail(CV_ERR_INVALID, "profile index out of range");
+        const std::string& k = eng->impl.prof[index].kernel;
+        const size_t n = std::min(k.size(), (size_t)kernel_cap - 1);
+        std::memcpy(kernel, k.data(), n);
+        kernel[n] = 0;
+        return Status();
+    });
+}
+
+int cv_engine_numeric_status(cv_engine_t* eng, void* stream) {
+    return guarded("cv_engine_numeric_status", [&]() -> Status {
+        CV_TRY(check_engine(eng));
+        std::lock_guard<std::mutex> lk(eng->impl.mu);
+        DeviceGuard g(eng->impl.device);
+        return eng->impl.guard_check((hipStream_t)stream);
+    });
+}
+
+int cv_engine_workspace_bytes(cv_engine_t* eng, size_t* bytes) {
+    return guarded("cv_engine_workspace_bytes", [&]() -> Status {
+        CV_TRY(check_engine(eng));
+        if (!bytes) return fail(CV_ERR_INVALID, "null argument");
+        std::lock_guard<std::mutex> lk(eng->impl.mu);
+        *bytes = eng->impl.workspace_bytes();
+        return Status();
+    });
+}
+
+int cv_engine_export_calibration(cv_engine_t* eng, const char* model, int32_t* exps, int capacity, int* count) {
+    return guarded("cv_engine_export_calibration", [&]() -> Status { return engine_calibration(eng, model, exps, capacity, count, 0); });
+}
+
+int cv_engine_import_calibration(cv_engine_t* eng, const char* model, const int32_t* exps, int count, int* changed) {
+    return guarded("cv_engine_import_calibration", [&]() -> Status {
+        int ch = 0;
+        const Status s = engine_calibration(eng, model, const_cast<int32_t*>(exps), count, &ch, 1);
+        if (changed) *changed = ch;
+        return s;
+    });
 }
 
 int cv_op_conv2d(cv_engine_t* eng, const float* x, int n, int cin, int h, int w_, const float* w_host, int cout,
                  int k, int stride, const float* scale_host, const float* shift_host, const float* residual,
                  int relu, float* y, void* stream) {
-    return guarded("cv_op_conv2d", [&]() -> int { return impl_cv_op_conv2d(eng, x, n, cin, h, w_, w_host, cout, k, stride, scale_host, shift_host, residual, relu, y, stream); });
+    return guarded("cv_op_conv2d", [&]() -> Status {
+        CV_TRY(check_engine(eng));
+        if (!x || !w_host || !y || n <= 0 || cin <= 0 || cout <= 0 || h <= 0 || w_ <= 0 || stride <= 0)
+            return fail(CV_ERR_INVALID, "cv_op_conv2d: bad argument");
+        std::lock_guard<std::mutex> lk(eng->impl.mu);
+        DeviceGuard g(eng->impl.device);
+        Engine& e = eng->impl;
+        hipStream_t st = (hipStream_t)stream;
+        const int pad = (k - 1) / 2;
+        const int ho = (h + 2 * pad - k) / stride + 1, wo = (w_ + 2 * pad - k) / stride + 1;
+        const int cinPad = round_up(cin, 8);
+        std::vector<float> ones(cout, 1.f), zeros(cout, 0.f);
+        ConvLayer L;
+        e.ws_slot = 0;
+        CV_TRY(L.build_conv("op_conv2d", e.dt, w_host, cout, cin, k, stride, scale_host ? scale_host : ones.data(),
+                            shift_host ? shift_host : zeros.data(), cinPad, (int64_t)n * ho * wo, (ho == wo) ? ho : 0));
+        Activation ax, ay, ar;
+        Status s;
+        if ((s = ax.create(n, h, w_, cinPad, e.dt)).ok() && (s = ay.create(n, ho, wo, cout, e.dt)).ok()) {
+            hipError_t err = pack_nchw_f32(e.dt, x, cin, ax.ref(n), e.guard_ptr(), st);
+            TensorRef rr;
+            if (err == hipSuccess && residual) {
+                s = ar.create(n, ho, wo, cout, e.dt);
+                if (s.ok()) { err = pack_nchw_f32(e.dt, residual, cout, ar.ref(n), e.guard_ptr(), st); rr = ar.ref(n); }
+            }
+            if (s.ok() && err == hipSuccess) s = e.run_conv(L, ax.ref(n), ay.ref(n), residual ? &rr : nullptr, relu != 0, st);
+            if (s.ok() && err == hipSuccess) err = unpack_nchw_f32(e.dt, ay.ref(n), y, st);
+            if (s.ok() && err == hipSuccess) err = hipStreamSynchronize(st);
+            if (s.ok() && err != hipSuccess) s = hip_fail(err, "cv_op_conv2d");
+        }
+        return s;
+    });
 }
 
 int cv_op_conv_transpose2x2(cv_engine_t* eng, const float* x, int n, int cin, int h, int w_, const float* w_host,
                             int cout, const float* bias_host, float* y, void* stream) {
-    return guarded("cv_op_conv_transpose2x2", [&]() -> int { return impl_cv_op_conv_transpose2x2(eng, x, n, cin, h, w_, w_host, cout, bias_host, y, stream); });
+    return guarded("cv_op_conv_transpose2x2", [&]() -> Status {
+        CV_TRY(check_engine(eng));
+        if (!x || !w_host || !y || !bias_host || n <= 0) return fail(CV_ERR_INVALID, "cv_op_conv_transpose2x2: bad argument");
+        std::lock_guard<std::mutex> lk(eng->impl.mu);
+        DeviceGuard g(eng->impl.device);
+        Engine& e = eng->impl;
+        hipStream_t st = (hipStream_t)stream;
+        ConvLayer L;
+        e.ws_slot = 0;
+        CV_TRY(L.build_convT("op_convT", e.dt, w_host, cin, cout, bias_host, (int64_t)n * h * w_));
+        Activation ax, ay;
+        Status s;
+        if ((s = ax.create(n, h, w_, cin, e.dt)).ok() && (s = ay.create(n, 2 * h, 2 * w_, cout, e.dt)).ok()) {
+            hipError_t err = pack_nchw_f32(e.dt, x, cin, ax.ref(n), e.guard_ptr(), st);
+            if (err == hipSuccess) s = e.run_conv(L, ax.ref(n), ay.ref(n), nullptr, false, st);
+            if (s.ok() && err == hipSuccess) err = unpack_nchw_f32(e.dt, ay.ref(n), y, st);
+            if (s.ok() && err == hipSuccess) err = hipStreamSynchronize(st);
+            if (s.ok() && err != hipSuccess) s = hip_fail(err, "cv_op_conv_transpose2x2");
+        }
+        return s;
+    });
+}
+
+// conv 1x1 C -> 1 + bias (+ sigmoid / threshold mask): the stand-alone OutConv kernel, as a single-layer entry point
+int cv_op_outc_1x1(cv_engine_t* eng, const float* x, int n, int c, int h, int w_, const float* w_host, const float* bias_host,
+                   float threshold, float* logits, uint8_t* mask, void* stream) {
+    return guarded("cv_op_outc_1x1", [&]() -> Status {
+        CV_TRY(check_engine(eng));
+        if (!x || !w_host || !bias_host || !logits || n <= 0 || c <= 0 || h <= 0 || w_ <= 0)
+            return fail(CV_ERR_INVALID, "cv_op_outc_1x1: bad argument");
+        std::lock_guard<std::mutex> lk(eng->impl.mu);
+        DeviceGuard g(eng->impl.device);
+        Engine& e = eng->impl;
+        hipStream_t st = (hipStream_t)stream;
+        const int cp = round_up(c, 8);
+        const int lpp = cp / dtype_group(e.dt);
+        if (lpp > 64 || (lpp & (lpp - 1))) return fail(CV_ERR_INVALID, "cv_op_outc_1x1: channel count must give a power-of-two lane group <= 64");
+        std::vector<float> wpad(cp, 0.f);
+        std::copy(w_host, w_host + c, wpad.begin());
+        Activation ax;
+        DeviceBuffer dw, db;
+        Status s;
+        if ((s = ax.create(n, h, w_, cp, e.dt)).ok() && (s = dw.upload(wpad.data(), cp * sizeof(float))).ok() &&
+            (s = db.upload(bias_host, sizeof(float))).ok()) {
+            hipError_t err = pack_nchw_f32(e.dt, x, c, ax.ref(n), e.guard_ptr(), st);
+            if (err == hipSuccess)
+                err = outc_1x1(e.dt, ax.ref(n), (const float*)dw.ptr, (const float*)db.ptr, logits, mask, threshold, e.guard_ptr(),
+                               e.register_layer("op_outc_1x1"), st);
+            if (err == hipSuccess) err = hipStreamSynchronize(st);
+            if (err != hipSuccess) s = hip_fail(err, "cv_op_outc_1x1");
+        }
+        return s;
+    });
 }
 
 int cv_op_maxpool2x2(cv_engine_t* eng, const float* x, int n, int c, int h, int w_, float* y, void* stream) {
-    return guarded("cv_op_maxpool2x2", [&]() -> int { return impl_cv_op_maxpool2x2(eng, x, n, c, h, w_, y, stream); });
+    return guarded("cv_op_maxpool2x2", [&]() -> Status { return pool_like(eng, x, n, c, h, w_, h / 2, w_ / 2, y, stream, maxpool2x2, "cv_op_maxpool2x2"); });
 }
 
 int cv_op_maxpool3x3s2(cv_engine_t* eng, const float* x, int n, int c, int h, int w_, float* y, void* stream) {
-    return guarded("cv_op_maxpool3x3s2", [&]() -> int { return impl_cv_op_maxpool3x3s2(eng, x, n, c, h, w_, y, stream); });
+    return guarded("cv_op_maxpool3x3s2", [&]() -> Status {
+        return pool_like(eng, x, n, c, h, w_, (h + 2 - 3) / 2 + 1, (w_ + 2 - 3) / 2 + 1, y, stream, maxpool3x3s2, "cv_op_maxpool3x3s2");
+    });
 }
 
 int cv_op_upsample_bilinear2x(cv_engine_t* eng, const float* x, int n, int c, int h, int w_, float* y, void* stream) {
-    return guarded("cv_op_upsample_bilinear2x", [&]() -> int { return impl_cv_op_upsample_bilinear2x(eng, x, n, c, h, w_, y, stream); });
+    return guarded("cv_op_upsample_bilinear2x", [&]() -> Status {
+        return pool_like(eng, x, n, c, h, w_, 2 * h, 2 * w_, y, stream, upsample_plain, "cv_op_upsample_bilinear2x");
+    });
+}
+
+int cv_selftest_mfma(cv_engine_t* eng, float* max_err_f16, float* max_err_f32) {
+    return guarded("cv_selftest_mfma", [&]() -> Status {
+        CV_TRY(check_engine(eng));
+        DeviceGuard g(eng->impl.device);
+        // asymmetric integer-valued operands: exact in f16 and f32, so the expected error is exactly 0
+        _Float16 a16[16 * 32], b16[16 * 32];
+        float a32[16 * 16], b32[16 * 16], ref16[256], ref32[256], got[256];
+        for (int i = 0; i < 16; ++i)
+            for (int k = 0; k < 32; ++k) { a16[i * 32 + k] = (_Float16)(float)((i * 3 + k * 5) % 7 - 3); b16[i * 32 + k] = (_Float16)(float)((i * 5 + k * 2 + 1) % 9 - 4); }
+        for (int i = 0; i < 16; ++i)
+            for (int k = 0; k < 16; ++k) { a32[i * 16 + k] = (float)((i * 3 + k * 5) % 7 - 3); b32[i * 16 + k] = (float)((i * 5 + k * 2 + 1) % 9 - 4); }
+        for (int i = 0; i < 16; ++i)
+            for (int j = 0; j < 16; ++j) {
+                float s16 = 0, s32 = 0;
+                for (int k = 0; k < 32; ++k) s16 += (float)a16[i * 32 + k] * (float)b16[j * 32 + k];
+                for (int k = 0; k < 16; ++k) s32 += a32[i * 16 + k] * b32[j * 16 + k];
+                ref16[i * 16 + j] = s16; ref32[i * 16 + j] = s32;
+            }
+        DeviceBuffer da, db, dd;
+        float err16 = 0.f, err32 = 0.f;
+        CV_TRY(da.upload(a16, sizeof(a16)));
+        CV_TRY(db.upload(b16, sizeof(b16)));
+        CV_TRY(dd.alloc(sizeof(got), true));
+        hipError_t e = mfma_probe_f16((const half_t*)da.ptr, (const half_t*)db.ptr, (float*)dd.ptr, nullptr);
+        if (e == hipSuccess) e = sync_memcpy(got, dd.ptr, sizeof(got), hipMemcpyDeviceToHost);
+        if (e != hipSuccess) return hip_fail(e, "mfma_probe_f16");
+        for (int i = 0; i < 256; ++i) err16 = std::max(err16, std::fabs(got[i] - ref16[i]));
+        CV_TRY(da.upload(a32, sizeof(a32)));
+        CV_TRY(db.upload(b32, sizeof(b32)));
+        e = mfma_probe_f32((const float*)da.ptr, (const float*)db.ptr, (float*)dd.ptr, nullptr);
+        if (e == hipSuccess) e = sync_memcpy(got, dd.ptr, sizeof(got), hipMemcpyDeviceToHost);
+        if (e != hipSuccess) return hip_fail(e, "mfma_probe_f32");
+        for (int i = 0; i < 256; ++i) err32 = std::max(err32, std::fabs(got[i] - ref32[i]));
+        if (max_err_f16) *max_err_f16 = err16;
+        if (max_err_f32) *max_err_f32 = err32;
+        return Status();
+    });
 }
 
 int cv_find_quadrangle(const uint8_t* mask, int h, int w, int32_t quad[8], int* found) {
-    return guarded("cv_find_quadrangle", [&]() -> int { return impl_cv_find_quadrangle(mask, h, w, quad, found); });
+    return guarded("cv_find_quadrangle", [&]() -> Status {
+        if (!mask || !quad || !found || h <= 0 || w <= 0) return fail(CV_ERR_INVALID, "cv_find_quadrangle: bad argument");
+        *found = find_quadrangle(mask, h, w, quad) ? 1 : 0;
+        return Status();
+    });
 }
 
 int cv_find_contours(const uint8_t* mask, int h, int w, int method, int32_t* xy, int64_t cap_points, int32_t* counts,
                      int32_t* holes, int64_t cap_contours, int64_t* n_contours) {
-    return guarded("cv_find_contours", [&]() -> int {
-        return impl_cv_find_contours(mask, h, w, method, xy, cap_points, counts, holes, cap_contours, n_contours);
+    return guarded("cv_find_contours", [&]() -> Status {
+        if (!mask || !xy || !counts || !holes || !n_contours || h <= 0 || w <= 0 || cap_points < 0 || cap_contours < 0 ||
+            (method != 0 && method != 1))
+            return fail(CV_ERR_INVALID, "cv_find_contours: bad argument");
+        const long n = find_contours_flat(mask, h, w, method == 1, xy, (long)cap_points, counts, holes, (long)cap_contours);
+        if (n < 0) return fail(CV_ERR_INVALID, "cv_find_contours: output capacity too small");
+        *n_contours = n;
+        return Status();
     });
 }
 
 int cv_find_quadrangles(const uint8_t* masks, int n, int h, int w, int32_t* quads, int32_t* found, int n_threads) {
-    return guarded("cv_find_quadrangles", [&]() -> int { return impl_cv_find_quadrangles(masks, n, h, w, quads, found, n_threads); });
-}
-
-int cv_resize_area_u8(cv_engine_t* eng, const uint8_t* src, int n, int h, int w_, int channels, uint8_t* dst, int out_h,
-                      int out_w, void* stream) {
-    return guarded("cv_resize_area_u8", [&]() -> int { return impl_cv_resize_area_u8(eng, src, n, h, w_, channels, dst, out_h, out_w, stream); });
-}
-
-int cv_resize_antialias_f32(cv_engine_t* eng, const uint8_t* src, int n, int h, int w_, int channels, float* dst, int out_h,
-                            int out_w, void* stream) {
-    return guarded("cv_resize_antialias_f32", [&]() -> int { return impl_cv_resize_antialias_f32(eng, src, n, h, w_, channels, dst, out_h, out_w, stream); });
-}
-
-int cv_extract_squares_u8(cv_engine_t* eng, const uint8_t* images, int n, int h, int w_, const double* inv_host,
-                          uint8_t* squares, uint8_t* boards, void* stream) {
-    return guarded("cv_extract_squares_u8", [&]() -> int { return impl_cv_extract_squares_u8(eng, images, n, h, w_, inv_host, squares, boards, stream); });
-}
-
-int cv_engine_export_calibration(cv_engine_t* eng, const char* model, int32_t* exps, int capacity, int* count) {
-    return guarded("cv_engine_export_calibration", [&]() -> int { return impl_cv_engine_calibration(eng, model, exps, capacity, count, 0); });
-}
-
-int cv_engine_import_calibration(cv_engine_t* eng, const char* model, const int32_t* exps, int count, int* changed) {
-    return guarded("cv_engine_import_calibration", [&]() -> int {
-        int ch = 0;
-        const int rc = impl_cv_engine_calibration(eng, model, const_cast<int32_t*>(exps), count, &ch, 1);
-        if (changed) *changed = ch;
-        return rc;
+    return guarded("cv_find_quadrangles", [&]() -> Status {
+        if (!masks || !quads || !found || n < 0 || h <= 0 || w <= 0) return fail(CV_ERR_INVALID, "cv_find_quadrangles: bad argument");
+        parallel_slices(n, mask_threads(n, n_threads), [&](int lo, int hi) {
+            for (int i = lo; i < hi; ++i) found[i] = find_quadrangle(masks + (size_t)i * h * w, h, w, quads + (size_t)i * 8) ? 1 : 0;
+        });
+        return Status();
     });
 }
 
-int cv_process_image_v2(cv_engine_t* unet_engine, cv_engine_t* classifier_engine, const uint8_t* image, int h, int w, float threshold,
-                        int flip, int fallback_quad, cv_image_result_t* out, size_t out_size, void* stream) {
-    return guarded("cv_process_image_v2", [&]() -> int {
-        return impl_cv_process_image(unet_engine, classifier_engine, image, h, w, threshold, flip, fallback_quad, out, out_size, stream);
+int cv_mask_completeness(const uint8_t* mask, int h, int w, double* score) {
+    return guarded("cv_mask_completeness", [&]() -> Status { return mask_completenesses(mask, 1, h, w, score, 1); });
+}
+
+int cv_mask_completenesses(const uint8_t* masks, int n, int h, int w, double* scores, int n_threads) {
+    return guarded("cv_mask_completenesses", [&]() -> Status { return mask_completenesses(masks, n, h, w, scores, n_threads); });
+}
+
+int cv_quadrangle_regularity(const float* quad, double* score) {
+    return guarded("cv_quadrangle_regularity", [&]() -> Status {
+        if (!score) return fail(CV_ERR_INVALID, "cv_quadrangle_regularity: null score");
+        *score = quad ? quadrangle_regularity(quad) : 0.0;
+        return Status();
     });
 }
-
-int cv_process_image(cv_engine_t* unet_engine, cv_engine_t* classifier_engine, const uint8_t* image, int h, int w, float threshold,
-                     int flip, int fallback_quad, cv_image_result_t* out, void* stream) {
-    return guarded("cv_process_image", [&]() -> int {      // the struct of ABI 3 / 4: `squares` did not exist
-        return impl_cv_process_image(unet_engine, classifier_engine, image, h, w, threshold, flip, fallback_quad, out,
-                                     offsetof(cv_image_result_t, squares), stream);
-    });
-}
-
-int cv_board_homographies(const float* quads, int n, int out_w, int out_h, double* forward, double* inverse) {
-    return guarded("cv_board_homographies", [&]() -> int { return impl_cv_board_homographies(quads, n, out_w, out_h, forward, inverse); });
-}
-
-int cv_selftest_mfma(cv_engine_t* eng, float* max_err_f16, float* max_err_f32) {
-    return guarded("cv_selftest_mfma", [&]() -> int { return impl_cv_selftest_mfma(eng, max_err_f16, max_err_f32); });
-}
-
-int cv_op_outc_1x1(cv_engine_t* eng, const float* x, int n, int c, int h, int w_, const float* w_host, const float* bias_host,
-                   float threshold, float* logits, uint8_t* mask, void* stream) {
-    return guarded("cv_op_outc_1x1", [&]() -> int {
-        return impl_cv_op_outc_1x1(eng, x, n, c, h, w_, w_host, bias_host, threshold, logits, mask, stream);
-    });
-}
-
-int cv_profile_entry_bytes(cv_engine_t* eng, int index, double* bytes) {
-    return guarded("cv_profile_entry_bytes", [&]() -> int { return impl_cv_profile_entry_bytes(eng, index, bytes); });
-}
-
-int cv_profile_entry_kernel(cv_engine_t* eng, int index, char* kernel, int kernel_cap) {
-    return guarded("cv_profile_entry_kernel", [&]() -> int { return impl_cv_profile_entry_kernel(eng, index, kernel, kernel_cap); });
-}
-
-int cv_engine_numeric_status(cv_engine_t* eng, void* stream) {
-    return guarded("cv_engine_numeric_status", [&]() -> int { return impl_cv_engine_numeric_status(eng, stream); });
-}
-
-int cv_engine_workspace_bytes(cv_engine_t* eng, size_t* bytes) {
-    return guarded("cv_engine_workspace_bytes", [&]() -> int { return impl_cv_engine_workspace_bytes(eng, bytes); });
-}
-
-int cv_get_activation_exponent(cv_engine_t* eng, const char* model, const char* name, int* exponent) {
-    return guarded("cv_get_activation_exponent", [&]() -> int { return impl_cv_get_activation_exponent(eng, model, name, exponent); });
-}
-
-int cv_decode_positions(const float* probs, int n_boards, int flip, char* fen, char* original_fen, int8_t* labels,
-                        int32_t* fixes, int32_t* n_fixes) {
-    return guarded("cv_decode_positions", [&]() -> int {
-        return impl_cv_decode_positions(probs, n_boards, flip, fen, original_fen, labels, fixes, n_fixes);
-    });
-}
-
-int cv_extract_squares_u8_dev(cv_engine_t* eng, const uint8_t* images, int n, int h, int w_, const double* inv_dev,
-                              uint8_t* squares, uint8_t* boards, void* stream) {
-    return guarded("cv_extract_squares_u8_dev", [&]() -> int {
-        return impl_cv_extract_squares_u8_dev(eng, images, n, h, w_, inv_dev, squares, boards, stream);
-    });
-}
-
-}  // extern "C"
 
 int cv_extraction_scores(cv_engine_t* eng, const float* values, int n, int count, int transform, cv_score_record_t* records,
                          uint8_t* half_mask, void* stream) {
-    return guarded("cv_extraction_scores", [&]() -> int {
-        return impl_cv_extraction_scores(eng, values, n, count, transform, records, half_mask, stream);
+    return guarded("cv_extraction_scores", [&]() -> Status {
+        CV_TRY(check_engine(eng));
+        if (!values || !records) return fail(CV_ERR_INVALID, "cv_extraction_scores: null tensor");
+        if (((uintptr_t)values & 3u) || ((uintptr_t)records & 7u)) return fail(CV_ERR_INVALID, "cv_extraction_scores: values must be 4-byte, records 8-byte aligned");
+        if (n < 1) return fail(CV_ERR_INVALID, "cv_extraction_scores: n must be at least 1");
+        if (count < 4 || count > (1 << 24)) return fail(CV_ERR_INVALID, "cv_extraction_scores: count must be in [4, 2^24]");
+        if (transform != 0 && transform != 1) return fail(CV_ERR_INVALID, "cv_extraction_scores: transform must be 0 (as given) or 1 (sigmoid)");
+        DeviceGuard g(eng->impl.device);
+        hipError_t e = extraction_scores(values, n, count, transform, reinterpret_cast<ScoreRecord*>(records), half_mask, (hipStream_t)stream);
+        if (e != hipSuccess) return hip_fail(e, "extraction_scores");
+        return Status();
     });
 }
 
 int cv_extraction_scores_finish(const cv_score_record_t* records, int n, double* confidence, double* distribution) {
-    return guarded("cv_extraction_scores_finish", [&]() -> int { return impl_cv_extraction_scores_finish(records, n, confidence, distribution); });
-}
-
-int cv_mask_completeness(const uint8_t* mask, int h, int w, double* score) {
-    return guarded("cv_mask_completeness", [&]() -> int { return impl_cv_mask_completenesses(mask, 1, h, w, score, 1); });
-}
-
-int cv_mask_completenesses(const uint8_t* masks, int n, int h, int w, double* scores, int n_threads) {
-    return guarded("cv_mask_completenesses", [&]() -> int { return impl_cv_mask_completenesses(masks, n, h, w, scores, n_threads); });
-}
-
-int cv_quadrangle_regularity(const float* quad, double* score) {
-    return guarded("cv_quadrangle_regularity", [&]() -> int { return impl_cv_quadrangle_regularity(quad, score); });
+    return guarded("cv_extraction_scores_finish", [&]() -> Status {
+        if (n < 0 || (n > 0 && (!records || !confidence || !distribution))) return fail(CV_ERR_INVALID, "cv_extraction_scores_finish: bad argument");
+        const double nan = std::nan("");
+        for (int i = 0; i < n; ++i) {
+            const cv_score_record_t& r = records[i];
+            // numpy's sort puts NaN last, so one NaN in the image reaches the top quarter and the mean
+            confidence[i] = r.n_nan > 0 || r.top_count <= 0 ? nan : 2.0 * r.top_sum / (double)r.top_count;
+            long long total = 0;
+            for (int b = 0; b < 10; ++b) total += r.hist[b];
+            if (total == 0) { distribution[i] = nan; continue; }           // 0 / 0 in the reference's hist / sum(hist)
+            double entropy = 0.0;
+            for (int b = 0; b < 10; ++b) {
+                const double p = (double)r.hist[b] / (double)total;
+                entropy -= p * std::log2(p + 1e-10);
+            }
+            distribution[i] = 1.0 - entropy / std::log2(10.0);
+        }
+        return Status();
+    });
 }
 
 int cv_segmentation_scores(cv_engine_t* eng, const float* logits, const uint8_t* labels, int n, int count, float threshold,
                            cv_seg_record_t* records, void* stream) {
-    return guarded("cv_segmentation_scores", [&]() -> int {
-        return impl_cv_segmentation_scores(eng, logits, labels, n, count, threshold, records, stream);
+    return guarded("cv_segmentation_scores", [&]() -> Status {
+        CV_TRY(check_engine(eng));
+        if (!logits || !labels || !records) return fail(CV_ERR_INVALID, "cv_segmentation_scores: null tensor");
+        if (((uintptr_t)logits & 3u) || ((uintptr_t)records & 7u)) return fail(CV_ERR_INVALID, "cv_segmentation_scores: logits must be 4-byte, records 8-byte aligned");
+        if (n < 1) return fail(CV_ERR_INVALID, "cv_segmentation_scores: n must be at least 1");
+        if (count < 1 || count > (1 << 24)) return fail(CV_ERR_INVALID, "cv_segmentation_scores: count must be in [1, 2^24]");
+        if (!std::isfinite(threshold)) return fail(CV_ERR_INVALID, "cv_segmentation_scores: threshold must be finite");
+        DeviceGuard g(eng->impl.device);
+        hipError_t e = segmentation_scores(logits, labels, n, count, threshold, reinterpret_cast<SegRecord*>(records), (hipStream_t)stream);
+        if (e != hipSuccess) return hip_fail(e, "segmentation_scores");
+        return Status();
     });
 }
 
 int cv_segmentation_scores_finish(const cv_seg_record_t* records, int n, double* bce, double* dice_loss, double* loss, double* dice,
                                   double* iou, double* pixel_accuracy) {
-    return guarded("cv_segmentation_scores_finish", [&]() -> int {
-        return impl_cv_segmentation_scores_finish(records, n, bce, dice_loss, loss, dice, iou, pixel_accuracy);
+    return guarded("cv_segmentation_scores_finish", [&]() -> Status {
+        if (n < 0 || (n > 0 && !records)) return fail(CV_ERR_INVALID, "cv_segmentation_scores_finish: bad argument");
+        for (int i = 0; i < n; ++i) {
+            const cv_seg_record_t& r = records[i];
+            if (r.count < 1) return fail(CV_ERR_INVALID, "cv_segmentation_scores_finish: record " + std::to_string(i) + " has no pixels");
+            const double b = r.bce_sum / (double)r.count;
+            const double dl = 1.0 - dice_of(r.sig_label_sum, r.sig_sum + (double)r.n_label);
+            const long long uni = (long long)r.n_pred + r.n_label - r.n_both;
+            if (bce) bce[i] = b;
+            if (dice_loss) dice_loss[i] = dl;
+            if (loss) loss[i] = dl + b;
+            if (dice) dice[i] = dice_of((double)r.n_both, (double)r.n_pred + (double)r.n_label);
+            if (iou) iou[i] = uni == 0 ? 1.0 : (double)r.n_both / (double)uni;
+            if (pixel_accuracy) pixel_accuracy[i] = (double)((long long)r.count - r.n_pred - r.n_label + 2LL * r.n_both) / (double)r.count;
+        }
+        return Status();
     });
 }
 
 int cv_fen_labels(const char* fen, int8_t* labels) {
-    return guarded("cv_fen_labels", [&]() -> int { return impl_cv_fen_labels(fen, labels); });
+    return guarded("cv_fen_labels", [&]() -> Status {
+        if (!fen || !labels) return fail(CV_ERR_INVALID, "cv_fen_labels: null argument");
+        int8_t out[64];
+        const char* why = fen_labels(fen, out);
+        if (why) return fail(CV_ERR_INVALID, std::string("cv_fen_labels: malformed piece placement (") + why + ")");
+        std::memcpy(labels, out, 64);
+        return Status();
+    });
 }
 
 int cv_classification_scores(const float* probs, const int8_t* labels, int n_boards, cv_square_score_t* per_square,
                              cv_board_score_t* per_board) {
-    return guarded("cv_classification_scores", [&]() -> int {
-        return impl_cv_classification_scores(probs, labels, n_boards, per_square, per_board);
+    return guarded("cv_classification_scores", [&]() -> Status {
+        if (n_boards < 0 || (n_boards > 0 && (!probs || !labels || !per_square || !per_board)))
+            return fail(CV_ERR_INVALID, "cv_classification_scores: bad argument");
+        for (size_t i = 0; i < (size_t)n_boards * 64; ++i)
+            if (labels[i] < 0 || labels[i] > 12)
+                return fail(CV_ERR_INVALID, "cv_classification_scores: label " + std::to_string(i) + " is not a class index (0..12)");
+        classification_scores(probs, labels, n_boards, per_square, per_board);
+        return Status();
     });
 }
+
+int cv_decode_positions(const float* probs, int n_boards, int flip, char* fen, char* original_fen, int8_t* labels,
+                        int32_t* fixes, int32_t* n_fixes) {
+    return guarded("cv_decode_positions", [&]() -> Status {
+        if (n_boards < 0 || (n_boards > 0 && (!probs || !fen || !original_fen || !labels || !fixes || !n_fixes)))
+            return fail(CV_ERR_INVALID, "cv_decode_positions: bad argument");
+        decode_positions(probs, n_boards, flip, fen, original_fen, labels, fixes, n_fixes);
+        return Status();
+    });
+}
+
+int cv_board_homographies(const float* quads, int n, int out_w, int out_h, double* forward, double* inverse) {
+    return guarded("cv_board_homographies", [&]() -> Status {
+        if (n < 0 || out_w <= 0 || out_h <= 0 || (n > 0 && (!quads || (!forward && !inverse))))
+            return fail(CV_ERR_INVALID, "cv_board_homographies: bad argument");
+        board_homographies(quads, n, out_w, out_h, forward, inverse);
+        return Status();
+    });
+}
+
+int cv_resize_area_u8(cv_engine_t* eng, const uint8_t* src, int n, int h, int w_, int channels, uint8_t* dst, int out_h,
+                      int out_w, void* stream) {
+    return guarded("cv_resize_area_u8", [&]() -> Status {
+        CV_TRY(check_engine(eng));
+        if (!src || !dst || n <= 0 || h <= 0 || w_ <= 0 || channels <= 0 || out_h <= 0 || out_w <= 0)
+            return fail(CV_ERR_INVALID, "cv_resize_area_u8: bad argument");
+        DeviceGuard g(eng->impl.device);
+        std::lock_guard<std::mutex> lk(eng->impl.mu);
+        return resize_on_stream(eng->impl, src, n, h, w_, channels, dst, out_h, out_w, (hipStream_t)stream);
+    });
+}
+
+int cv_resize_antialias_f32(cv_engine_t* eng, const uint8_t* src, int n, int h, int w_, int channels, float* dst, int out_h,
+                            int out_w, void* stream) {
+    return guarded("cv_resize_antialias_f32", [&]() -> Status {
+        CV_TRY(check_engine(eng));
+        if (!src || !dst || n <= 0 || h <= 0 || w_ <= 0 || channels < 1 || channels > 4 || out_h <= 0 || out_w <= 0 || ((uintptr_t)dst & 3u) ||
+            out_h > 65535 * 16)
+            return fail(CV_ERR_INVALID, "cv_resize_antialias_f32: bad argument");
+        DeviceGuard g(eng->impl.device);
+        std::lock_guard<std::mutex> lk(eng->impl.mu);
+        return resize_antialias_on_stream(eng->impl, src, n, h, w_, channels, dst, out_h, out_w, (hipStream_t)stream);
+    });
+}
+
+int cv_extract_squares_u8(cv_engine_t* eng, const uint8_t* images, int n, int h, int w_, const double* inv_host,
+                          uint8_t* squares, uint8_t* boards, void* stream) {
+    return guarded("cv_extract_squares_u8", [&]() -> Status {
+        CV_TRY(check_engine(eng));
+        if (!images || !inv_host || !squares || n <= 0 || h <= 0 || w_ <= 0)
+            return fail(CV_ERR_INVALID, "cv_extract_squares_u8: bad argument");
+        if ((size_t)h * (size_t)w_ > ((size_t)1 << 30)) return fail(CV_ERR_INVALID, "cv_extract_squares_u8: image too large (32-bit byte offsets)");
+        if (((uintptr_t)squares & 3) || ((uintptr_t)boards & 3)) return fail(CV_ERR_INVALID, "cv_extract_squares_u8: outputs must be 4-byte aligned");
+        std::lock_guard<std::mutex> lk(eng->impl.mu);
+        DeviceGuard g(eng->impl.device);
+        Engine& e = eng->impl;
+        const size_t bytes = (size_t)n * 9 * sizeof(double);
+        if (e.scratch.bytes < bytes) CV_TRY(e.scratch.alloc(bytes, false));
+        hipStream_t st = (hipStream_t)stream;
+        hipError_t err = hipMemcpyAsync(e.scratch.ptr, inv_host, bytes, hipMemcpyHostToDevice, st);
+        if (err == hipSuccess) err = extract_squares_u8(images, n, h, w_, (const double*)e.scratch.ptr, squares, boards, st);
+        if (err == hipSuccess) err = hipStreamSynchronize(st);       // inv_host may be reused by the caller; scratch by the next call
+        if (err != hipSuccess) return hip_fail(err, "extract_squares_u8");
+        return Status();
+    });
+}
+
+int cv_extract_squares_u8_dev(cv_engine_t* eng, const uint8_t* images, int n, int h, int w_, const double* inv_dev,
+                              uint8_t* squares, uint8_t* boards, void* stream) {
+    return guarded("cv_extract_squares_u8_dev", [&]() -> Status {
+        CV_TRY(check_engine(eng));
+        if (!images || !inv_dev || !squares || n <= 0 || h <= 0 || w_ <= 0)
+            return fail(CV_ERR_INVALID, "cv_extract_squares_u8_dev: bad argument");
+        if ((size_t)h * (size_t)w_ > ((size_t)1 << 30)) return fail(CV_ERR_INVALID, "cv_extract_squares_u8_dev: image too large (32-bit byte offsets)");
+        if (((uintptr_t)squares & 3) || ((uintptr_t)boards & 3) || ((uintptr_t)inv_dev & 7))
+            return fail(CV_ERR_INVALID, "cv_extract_squares_u8_dev: outputs must be 4-byte aligned, matrices 8-byte aligned");
+        DeviceGuard g(eng->impl.device);
+        hipError_t err = extract_squares_u8(images, n, h, w_, inv_dev, squares, boards, (hipStream_t)stream);
+        if (err != hipSuccess) return hip_fail(err, "extract_squares_u8");
+        return Status();
+    });
+}
+
+int cv_process_image_v2(cv_engine_t* unet_engine, cv_engine_t* classifier_engine, const uint8_t* image, int h, int w, float threshold,
+                        int flip, int fallback_quad, cv_image_result_t* out, size_t out_size, void* stream) {
+    return guarded("cv_process_image_v2", [&]() -> Status {
+        return process_image(unet_engine, classifier_engine, image, h, w, threshold, flip, fallback_quad, out, out_size, stream);
+    });
+}
+
+int cv_process_image(cv_engine_t* unet_engine, cv_engine_t* classifier_engine, const uint8_t* image, int h, int w, float threshold,
+                     int flip, int fallback_quad, cv_image_result_t* out, void* stream) {
+    return guarded("cv_process_image", [&]() -> Status {      // the struct of ABI 3 / 4: `squares` did not exist
+        return process_image(unet_engine, classifier_engine, image, h, w, threshold, flip, fallback_quad, out,
+                             offsetof(cv_image_result_t, squares), stream);
+    });
+}
+
+}  // extern "C"

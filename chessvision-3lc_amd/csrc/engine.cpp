@@ -256,6 +256,27 @@ Status DeviceBuffer::upload(const void* host, size_t n) {
     return Status();
 }
 
+Status ResizeTables::replace(const int geom_[4], hipStream_t st, const std::vector<int>& x0, const std::vector<int>& x1, const std::vector<float>& x2,
+                             const std::vector<int>& y0, const std::vector<int>& y1, const std::vector<float>& y2, int xstride, int ystride) {
+    if (capture_flag()) return fail(3, "resize tables rebuilt during graph capture");
+    CV_HIP(hipStreamSynchronize(st));
+    std::vector<char> blob;
+    const void* const data[6] = {x0.data(), x1.data(), x2.data(), y0.data(), y1.data(), y2.data()};
+    const size_t count[6] = {x0.size(), x1.size(), x2.size(), y0.size(), y1.size(), y2.size()};
+    size_t at[6];
+    for (int i = 0; i < 6; ++i) {                         // ints and floats alike: four bytes per element
+        at[i] = blob.size();
+        blob.resize(at[i] + ((count[i] * 4 + 15) & ~(size_t)15));
+        std::memcpy(blob.data() + at[i], data[i], count[i] * 4);
+    }
+    std::memset(geom, 0, sizeof geom);                    // no geometry while the upload can still fail
+    CV_TRY(buf.upload(blob.data(), blob.size()));
+    std::memcpy(off, at, sizeof off);
+    stride[0] = xstride; stride[1] = ystride;
+    std::memcpy(geom, geom_, sizeof geom);
+    return Status();
+}
+
 Status Activation::reserve(int cap_) {
     std::vector<Activation*> one{this};
     return reserve_all(one, cap_);

@@ -115,6 +115,19 @@ struct DeviceBuffer {
     }
 };
 
+// The per-axis tables of the last geometry a device resize served (x: offset / count / weight arrays, then the same three for y), in
+// one device block, each array 16-byte aligned.  A resize compares `geom` with its own and calls replace() only when they differ.
+struct ResizeTables {
+    int geom[4] = {0, 0, 0, 0};                     // (h, w, out_h, out_w) the tables were built for; all 0: none
+    DeviceBuffer buf;
+    size_t off[6] = {0, 0, 0, 0, 0, 0};             // byte offsets of the six arrays in `buf`
+    int stride[2] = {0, 0};                         // weights per output element, x and y (antialias tables; unused by INTER_AREA)
+    // Waits for `st` first (a launch in flight may still read the previous tables); refused during graph capture.  `geom` is recorded
+    // only once the upload succeeded: after a failure the next resize rebuilds instead of trusting tables that are gone.
+    Status replace(const int geom_[4], hipStream_t st, const std::vector<int>& x0, const std::vector<int>& x1, const std::vector<float>& x2,
+                   const std::vector<int>& y0, const std::vector<int>& y1, const std::vector<float>& y2, int xstride = 0, int ystride = 0);
+};
+
 // a PHWC activation buffer sized for `cap` images
 //
 // Range scaling (f16 / split-f16 engines): the buffer holds real_value * 2^-exp.  f16 carries 5 exponent bits, and the lo
@@ -285,13 +298,8 @@ class Engine {
     hipEvent_t pipe_event2 = nullptr;               // cv_process_image: "the rectified board exists" -> its download on pipe_side beside the classifier
     hipStream_t pipe_side = nullptr;
     hipEvent_t pipe_event3 = nullptr;               // cv_process_image: "the board is home" (side stream) -> joined into the caller's stream on the device
-    DeviceBuffer area_tabs;                             // INTER_AREA tables of the last fractional resize geometry (cv_resize_area_u8)
-    long long area_key = -1;
-    size_t area_off[6] = {0, 0, 0, 0, 0, 0};
-    DeviceBuffer aa_tabs;                               // tap tables of the last antialiased resize geometry (cv_resize_antialias_f32)
-    int aa_geom[4] = {0, 0, 0, 0};                      // (h, w, out_h, out_w) the tables were built for; all 0: none yet
-    size_t aa_off[6] = {0, 0, 0, 0, 0, 0};
-    int aa_stride[2] = {0, 0};
+    ResizeTables area_tabs;                             // INTER_AREA tables of the last fractional resize geometry (cv_resize_area_u8)
+    ResizeTables aa_tabs;                               // tap tables of the last antialiased resize geometry (cv_resize_antialias_f32)
 
     // numeric guard: one device word, 0xffffffff = clean, else the lowest id of a layer that stored a non-finite value
     DeviceBuffer guard;

@@ -15,6 +15,7 @@
 #include <cstring>
 
 #include "engine.h"
+#include "host_stages.h"
 
 namespace cv {
 

@@ -24,6 +24,8 @@
 #include <cstdlib>
 #include <vector>
 
+#include "pipeline.h"
+
 namespace cv {
 
 typedef uint64_t __attribute__((aligned(1))) u64_unaligned;

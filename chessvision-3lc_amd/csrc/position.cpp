@@ -12,7 +12,7 @@
 #include <cstdint>
 #include <cstring>
 
-#include "../../include/chessvision_hip.h"      // plain C: the two score records
+#include "host_stages.h"
 
 namespace cv {
 

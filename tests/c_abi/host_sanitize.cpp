@@ -15,12 +15,7 @@
 #include <limits>
 #include <vector>
 
-namespace cv {
-void decode_positions(const float* probs, int n_boards, int flip, char* fen, char* original_fen, int8_t* labels, int32_t* fixes, int32_t* n_fixes);
-bool find_quadrangle(const uint8_t* mask, int h, int w, int32_t quad[8]);
-long find_contours_flat(const uint8_t* mask, int h, int w, bool tc89, int32_t* xy, long cap_pts, int32_t* counts, int32_t* holes, long cap_contours);
-void board_homographies(const float* quads, int n, int out_w, int out_h, double* forward, double* inverse);
-}  // namespace cv
+#include "../../chessvision-3lc_amd/csrc/host_stages.h"      // the declarations the three units themselves are compiled against
 
 #ifdef WITH_ORACLE
 // the independent plain-C restatement of the same OpenCV chain (oracle/c_ref/contours_ref.c, raster-scan relabelling instead of border

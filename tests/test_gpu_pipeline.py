@@ -108,6 +108,12 @@ def test_device_resize_matches_host_restatement(engines):
         odd = rng.integers(0, 256, (2, h, w, 3), dtype=np.uint8)
         got = engines["f32"].resize_area_u8(torch.from_numpy(odd), (256, 256)).cpu().numpy()
         assert np.array_equal(got, np.stack([classical.resize_area(im, (256, 256)) for im in odd])), (h, w)
+    # the engine keeps the tables of ONE geometry: another input shape, another output size, then the first geometry again (new pixels)
+    for shape, out in (((2, 37, 53, 3), 16), ((2, 53, 37, 3), 16), ((2, 37, 53, 3), 24), ((2, 37, 53, 3), 16)):
+        odd = rng.integers(0, 256, shape, dtype=np.uint8)
+        got = engines["f32"].resize_area_u8(torch.from_numpy(odd), (out, out)).cpu().numpy()
+        assert np.array_equal(got, np.stack([classical.resize_area(im, (out, out)) for im in odd])), (shape, out)
+        assert np.array_equal(got[0], cref.resize_area(odd[0], (out, out))), (shape, out)
 
 
 def test_device_resize_enlarging_matches_host_and_oracle(engines):

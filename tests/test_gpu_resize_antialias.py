@@ -65,6 +65,15 @@ def test_other_output_sizes_and_channel_counts(engines):
         got = eng.resize_antialias_f32(torch.from_numpy(batch), (oh, ow)).cpu().numpy()
         for k in range(2):
             assert _same_bits(got[k], classical.resize_antialias(batch[k], (ow, oh))), (h, w, c, oh, ow)
+    # the engine keeps the tables of ONE geometry: another input shape, another output size, then the first geometry again (new pixels)
+    for (h, w), out in (((37, 53), 16), ((53, 37), 16), ((37, 53), 24), ((37, 53), 16)):
+        batch = rng.integers(0, 256, (2, h, w, 3), dtype=np.uint8)
+        got = eng.resize_antialias_f32(torch.from_numpy(batch), (out, out)).cpu().numpy()
+        err, bar = float(np.abs(got.astype(np.float64) - aref.torch_resize(batch, out)).max()), aref.bar(h, w, out)
+        print(f"AA device {h}x{w} -> {out}: err {err:.3e} bar {bar:.3e}")
+        assert np.isfinite(got).all() and err <= bar, (h, w, out, err, bar)
+        for k in range(2):
+            assert _same_bits(got[k], classical.resize_antialias(batch[k], (out, out))), (h, w, out)
     with pytest.raises(Exception, match="resize_antialias_f32"):
         eng.resize_antialias_f32(torch.zeros((1, 8, 8, 5), dtype=torch.uint8))
     with pytest.raises(Exception, match="resize_antialias_f32"):
