@@ -30,6 +30,10 @@ PIECE_SIZE = (64, 64)          # one square
 WHOLE_MASK_QUADRANGLE = np.array([[[255, 0]], [[0, 0]], [[0, 255]], [[255, 255]]], dtype=np.int32)   # TR, TL, BL, BR
 WHOLE_MASK_QUADRANGLE.setflags(write=False)
 
+# the classifier's training normalisation (mean, std) of the gray square in [0, 1]: Normalize([0.564], [0.246]) in the reference's
+# scripts/train/train_classifier.py:41,50.  process_image / classify_position do NOT apply it (core.py:237 divides by 255 only).
+CLASSIFIER_NORMALIZATION = (0.564, 0.246)
+
 # class index -> FEN symbol; "f" marks an empty square
 LABEL_NAMES = list("BKNPQRbknpqr") + ["f"]
 NUM_CLASSES = len(LABEL_NAMES)

@@ -587,6 +587,81 @@ class ChessVision:
                                                                      resize))
         return targets.report(results)
 
+    def evaluate_squares(self, squares: NDArray[np.uint8], labels=None, normalize="train", batch_size: int = 512,
+                         embeddings: bool = False):
+        """The classifier's validation pass over a table of squares: one call for ``validate()`` and the ``tlc.collect_metrics`` pass
+        of the reference's ``scripts/train/train_classifier.py`` (:90-111, :274-292).  Returns a ``SquaresReport``
+        (``chessvision/evaluation.py``): per square ``predicted``, ``confidence``, ``loss``, ``correct`` and ``rank``, optionally
+        ``embeddings`` (N,512), and ``aggregate`` (``val_loss``, ``val_acc``, top-k hits, confusion matrix ...).
+
+        ``squares``: (N,64,64) uint8, gray.  ``labels``: N class indices (-1 or None = unlabelled), label names in
+        ``constants.LABEL_NAMES`` order or the reference's folder names ("_b" for "b"), or None: then ``loss`` is NaN and ``rank``
+        -1 everywhere.  ``normalize``: "train" = ``constants.CLASSIFIER_NORMALIZATION``, the ``Normalize`` of the reference's
+        ``val_transforms``; a (mean, std) pair; or None = the plain ``/255`` of ``classify_position``.  The transform runs inside
+        the stem kernel, bit for bit ``ToTensor`` + ``Normalize``.
+
+        The squares go up through page-locked staging in pieces of at most one engine chunk, the forward runs on the whole piece,
+        the logits never visit the host: one more kernel makes a 32-byte record per square (``HipEngine.square_records_dev``) and
+        only the records and the embeddings come back.  ``batch_size`` ONLY shapes the ``val_loss`` average (the mean over
+        consecutive batches of each batch's mean loss, as ``validate()`` forms it); it does NOT split the forward, because a
+        forward's bits depend on its batch shape.  A call whose f16-based engine reports a non-finite value is repeated on the
+        exact-f32 instance (``_recover``).  A classifier that is not a HIP model raises ``TypeError``.  Out of scope: crops that are
+        not 64 x 64 gray (PIL's ``Resize`` / ``Grayscale``), the training transforms, 3LC itself."""
+        from .evaluation import square_label_indices
+
+        if not self._native(self.classifier):
+            raise TypeError("evaluate_squares needs the HIP classifier (HipPieceClassifier); there is no other path")
+        sq = np.asarray(squares)
+        if sq.dtype != np.uint8 or sq.ndim != 3 or sq.shape[1:] != (constants.PIECE_SIZE[1], constants.PIECE_SIZE[0]):
+            raise ValueError(f"evaluate_squares expects (N,64,64) uint8 squares, got {sq.dtype} {sq.shape}")
+        lab = square_label_indices(labels, sq.shape[0])
+        if normalize is None:
+            norm = (0.0, 1.0)                                # (v - 0) / 1 == v bit for bit: the /255 input, logits out
+        elif isinstance(normalize, str):
+            if normalize != "train":
+                raise ValueError(f"normalize must be 'train', a (mean, std) pair or None, got {normalize!r}")
+            norm = constants.CLASSIFIER_NORMALIZATION
+        else:
+            norm = (float(normalize[0]), float(normalize[1]))
+            if len(normalize) != 2 or not (np.isfinite(norm[0]) and np.isfinite(norm[1]) and norm[1] > 0):
+                raise ValueError(f"normalize must be a finite (mean, std) pair with std > 0, got {normalize!r}")
+        return self._recover(lambda cv: cv._evaluate_squares_native(sq, lab, norm, int(batch_size), bool(embeddings)))
+
+    def _evaluate_squares_native(self, sq, lab, norm, batch_size: int, embeddings: bool):
+        from .evaluation import SquareScores, SquaresReport
+        from .hip_backend import SQUARE_RECORD, square_records_finish
+
+        eng = self.classifier.engine
+        n = int(sq.shape[0])
+        piece = max(1, min(int(eng.resnet_chunk), n))
+        labelled = bool((lab >= 0).any())
+        with self._native_lock, torch.no_grad():
+            pin = lambda s, d: torch.empty(s, dtype=d, pin_memory=True)      # noqa: E731
+            stage = [pin((piece, 64, 64), torch.uint8) for _ in range(2 if n > piece else 1)]
+            sent = [None] * len(stage)                       # the upload that last read each staging buffer
+            rec_host = pin((n, SQUARE_RECORD.itemsize), torch.uint8)
+            emb_host = pin((n, 512), torch.float32) if embeddings else None
+            for k, lo in enumerate(range(0, n, piece)):
+                hi = min(n, lo + piece)
+                buf = stage[k % len(stage)]
+                if sent[k % len(stage)] is not None:
+                    sent[k % len(stage)].synchronize()
+                np.copyto(buf.numpy()[:hi - lo], sq[lo:hi])
+                dev = buf[:hi - lo].to(self.device, non_blocking=True)
+                sent[k % len(stage)] = torch.cuda.Event()
+                sent[k % len(stage)].record()
+                lab_dev = torch.from_numpy(lab[lo:hi]).to(self.device) if labelled else None
+                out = eng.resnet_forward_u8_norm(dev, norm, want_embedding=embeddings)
+                logits = out[0] if embeddings else out
+                rec_host[lo:hi].copy_(eng.square_records_dev(logits, lab_dev), non_blocking=True)
+                if embeddings:
+                    emb_host[lo:hi].copy_(out[1], non_blocking=True)
+            eng.check_numerics()                             # synchronises: records and embeddings have landed
+            records = rec_host.numpy().view(SQUARE_RECORD).reshape(-1).copy()
+            emb = emb_host.numpy().copy() if embeddings else None
+        return SquaresReport(scores=SquareScores.from_records(records), embeddings=emb,
+                             aggregate=square_records_finish(records, batch_size))
+
     def _pipeline_streams(self):
         """(host->device, device->host, compute) streams of ``process_images``, created once per instance."""
         if self._streams is None:

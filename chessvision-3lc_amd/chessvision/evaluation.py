@@ -10,6 +10,11 @@ readable forms and the test checkers.  ``ChessVision.evaluate_images`` does not 
 run on the device, on the logits where the UNet left them (``HipEngine.segmentation_scores_dev``), and the per-square scores of a
 whole job come from one native call (``hip_backend.classification_scores``).
 
+The classifier's own batched caller, ``scripts/train/train_classifier.py`` (``validate()`` :90-111 and the ``tlc.collect_metrics`` pass
+:274-292 over a table of labelled 64 x 64 squares), is ``ChessVision.evaluate_squares``: ``square_records`` below is its host form and
+checker, ``SquareScores`` / ``SquaresReport`` are what it returns.  3LC's ``ClassificationMetricsCollector`` is not in the reference
+tree; loss / predicted / confidence / accuracy per sample is this library's reading of it.
+
 Two readings are stated here because the reference leaves them open:
 
 * Dice.  The reference calls ``dice_loss(..., reduction="none")`` of a vendored Pytorch-UNet whose directory is empty in its tree.
@@ -168,7 +173,109 @@ class EvaluationReport:
     aggregate: dict = field(default_factory=dict)
 
 
+@dataclass
+class SquareScores:
+    """The per-square columns of a squares table, one entry per square: the fields of ``cv_square_record_t``
+    (include/chessvision_hip.h)."""
+    predicted: NDArray[np.int32]     # first maximum of the 13 logits
+    rank: NDArray[np.int32]          # classes ranked above the true one (stable reading); 13 for a NaN row, -1 when unlabelled
+    label: NDArray[np.int32]         # true class index, -1 = unlabelled
+    flags: NDArray[np.int32]         # bit 0: the row holds a NaN
+    confidence: NDArray[np.float32]  # the largest soft-max probability
+    loss: NDArray[np.float32]        # CrossEntropyLoss(reduction="none"); NaN when unlabelled or NaN row
+    max_logit: NDArray[np.float32]
+    logsumexp: NDArray[np.float32]
+
+    @property
+    def correct(self) -> NDArray[np.bool_]:
+        """predicted == label: the reference's ``predicted.eq(target)``; False for unlabelled squares and NaN rows."""
+        return (self.label >= 0) & (self.predicted == self.label) & ((self.flags & 1) == 0)
+
+    @classmethod
+    def from_records(cls, records) -> "SquareScores":
+        """From the structured array of ``HipEngine.square_records`` (``hip_backend.SQUARE_RECORD``)."""
+        return cls(**{k: np.ascontiguousarray(records[k]) for k in ("predicted", "rank", "label", "flags", "confidence", "loss",
+                                                                     "max_logit", "logsumexp")})
+
+
+@dataclass
+class SquaresReport:
+    """What ``ChessVision.evaluate_squares`` returns: the per-square columns (also reachable as attributes of the report),
+    optionally the (N,512) classifier embeddings, and ``aggregate`` = the record of ``cv_square_records_finish`` as a dict
+    (n, n_labelled, n_correct, n_nan, hits, confusion, loss_sum, val_loss, val_acc, n_batches)."""
+    scores: SquareScores
+    embeddings: NDArray[np.float32] | None = None
+    aggregate: dict = field(default_factory=dict)
+
+    predicted = property(lambda self: self.scores.predicted)
+    confidence = property(lambda self: self.scores.confidence)
+    loss = property(lambda self: self.scores.loss)
+    correct = property(lambda self: self.scores.correct)
+    rank = property(lambda self: self.scores.rank)
+
+
 # ---- host forms of the scores ------------------------------------------------------------------------------------------------------
+def square_label_indices(labels, n: int) -> NDArray[np.int8]:
+    """Labels of a squares table -> (n,) int8 class indices, -1 = unlabelled.  Accepted: None (all unlabelled), integers -1..12,
+    label names in ``constants.LABEL_NAMES`` order ("B" .. "r", "f" = empty) and the reference's folder names (``data/squares``:
+    the black pieces' folders carry a leading underscore, "_b" .. "_r")."""
+    if labels is None:
+        return np.full(n, -1, dtype=np.int8)
+    items = list(labels.tolist() if isinstance(labels, np.ndarray) else labels)
+    if len(items) != n:
+        raise ValueError(f"labels has {len(items)} entries for {n} squares")
+    out = np.empty(n, dtype=np.int8)
+    for i, v in enumerate(items):
+        if v is None:
+            out[i] = -1
+        elif isinstance(v, str):
+            name = v[1:] if len(v) == 2 and v[0] == "_" else v
+            if name not in constants.LABEL_INDICES:
+                raise ValueError(f"square {i}: unknown label {v!r}")
+            out[i] = constants.LABEL_INDICES[name]
+        else:
+            if int(v) != v or not -1 <= int(v) < constants.NUM_CLASSES:
+                raise ValueError(f"square {i}: a label must be a class index 0..{constants.NUM_CLASSES - 1} or -1, got {v!r}")
+            out[i] = int(v)
+    return out
+
+
+def square_records(logits, labels=None) -> SquareScores:
+    """The records of ``cv_square_records`` for host arrays, in numpy and in the kernel's float32 arithmetic: (N,13) logits and N
+    labels (see ``square_label_indices``) -> ``SquareScores``.  m = first maximum by ``>``; s = sum of ``exp(x_j - m)`` added in
+    ascending j; confidence = 1 / s; loss = log(s) - (x_t - m); logsumexp = m + log(s).  The integer fields are comparisons of the
+    float32 logits and agree with the device exactly; the floats agree to the rounding of ``exp`` / ``log`` (numpy's and the
+    device's are each within an ulp).  A row holding a NaN has rank 13, flag bit 0 and NaN in all four floats."""
+    x = np.ascontiguousarray(np.asarray(logits, dtype=np.float32))
+    if x.ndim != 2 or x.shape[1] != constants.NUM_CLASSES:
+        raise ValueError(f"square_records expects (N,{constants.NUM_CLASSES}) logits")
+    n = x.shape[0]
+    t = square_label_indices(labels, n).astype(np.int32)
+    nan = np.isnan(x).any(axis=1)
+    predicted = np.zeros(n, dtype=np.int32)
+    m = x[:, 0].copy()
+    with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
+        for j in range(1, x.shape[1]):
+            up = x[:, j] > m
+            predicted[up] = j
+            m[up] = x[up, j]
+        s = np.zeros(n, dtype=np.float32)
+        for j in range(x.shape[1]):
+            s = s + np.exp(x[:, j] - m)                     # float32 throughout, ascending j
+        ls = np.log(s)
+        xt = x[np.arange(n), np.maximum(t, 0)]
+        cols = np.arange(x.shape[1])[None, :]
+        rank = ((x > xt[:, None]).sum(axis=1) + ((x == xt[:, None]) & (cols > t[:, None])).sum(axis=1)).astype(np.int32)
+        loss = (ls - (xt - m)).astype(np.float32)
+        confidence = (np.float32(1) / s).astype(np.float32)
+        logsumexp = (m + ls).astype(np.float32)
+    rank = np.where(t < 0, -1, np.where(nan, x.shape[1], rank)).astype(np.int32)
+    qnan = np.float32(np.nan)
+    return SquareScores(predicted=predicted, rank=rank, label=t, flags=nan.astype(np.int32),
+                        confidence=np.where(nan, qnan, confidence), loss=np.where(nan | (t < 0), qnan, loss),
+                        max_logit=np.where(nan, qnan, m), logsumexp=np.where(nan, qnan, logsumexp))
+
+
 def _dice(inter: float, sets_sum: float) -> float:
     if sets_sum == 0:
         sets_sum = 2 * inter

@@ -137,6 +137,9 @@ SYMBOLS = [
     ("cv_segmentation_scores_finish", _i, [_vp, _i] + [ctypes.POINTER(ctypes.c_double)] * 6),
     ("cv_fen_labels", _i, [ctypes.c_char_p, ctypes.POINTER(ctypes.c_int8)]),
     ("cv_classification_scores", _i, [_fp, ctypes.POINTER(ctypes.c_int8), _i, _vp, _vp]),
+    ("cv_resnet_forward_u8_norm", _i, [_vp, _vp, _i, _f, _f, _i, _vp, _vp, _vp]),
+    ("cv_square_records", _i, [_vp, _vp, _vp, _i, _vp, _vp]),
+    ("cv_square_records_finish", _i, [_vp, _i, _i, _vp]),
 ]
 
 # cv_score_record_t (include/chessvision_hip.h): one 64-byte record per image
@@ -152,6 +155,12 @@ SQUARE_SCORE = np.dtype({"names": ["predicted", "rank", "confidence", "reserved"
                          "formats": ["<i4", "<i4", "<f4", "<i4", "<f8"], "offsets": [0, 4, 8, 12, 16], "itemsize": 24})
 BOARD_SCORE = np.dtype({"names": ["hits", "n_nan", "mean_loss"], "formats": [("<i4", (13,)), "<i4", "<f8"],
                         "offsets": [0, 52, 56], "itemsize": 64})
+# cv_square_record_t, cv_squares_summary_t (include/chessvision_hip.h)
+SQUARE_RECORD = np.dtype({"names": ["predicted", "rank", "label", "flags", "confidence", "loss", "max_logit", "logsumexp"],
+                          "formats": ["<i4", "<i4", "<i4", "<i4", "<f4", "<f4", "<f4", "<f4"], "itemsize": 32})
+SQUARES_SUMMARY = np.dtype({"names": ["n", "n_labelled", "n_correct", "n_nan", "hits", "confusion", "loss_sum", "val_loss", "val_acc",
+                                      "n_batches"],
+                            "formats": ["<i8", "<i8", "<i8", "<i8", ("<i8", (13,)), ("<i8", (13, 13)), "<f8", "<f8", "<f8", "<i8"]})
 
 
 def trim_memory() -> int:
@@ -302,6 +311,18 @@ def segmentation_scores_finish(records: np.ndarray) -> dict:
     if r.size:
         _check(lib.cv_segmentation_scores_finish(r.ctypes.data_as(_vp), int(r.size), *(out[k].ctypes.data_as(dp) for k in names)))
     return out
+
+
+def square_records_finish(records: np.ndarray, batch_size: int = 0) -> dict:
+    """(N,) ``SQUARE_RECORD`` array -> the aggregate of the reference's ``validate()`` as a dict (``cv_square_records_finish``):
+    n, n_labelled, n_correct, n_nan, hits (13,), confusion (13,13) true x predicted, loss_sum, val_loss (mean over consecutive batches
+    of ``batch_size`` of each batch's mean loss; <= 0: one batch), val_acc (percent), n_batches."""
+    lib = load_library()
+    r = np.ascontiguousarray(records, dtype=SQUARE_RECORD).reshape(-1)
+    out = np.zeros(1, dtype=SQUARES_SUMMARY)
+    _check(lib.cv_square_records_finish(r.ctypes.data_as(_vp) if r.size else None, int(r.size), int(batch_size), out.ctypes.data_as(_vp)))
+    o = out[0]
+    return {k: (o[k].copy() if o[k].ndim else o[k].item()) for k in SQUARES_SUMMARY.names}
 
 
 def fen_labels(fen: str) -> np.ndarray:
@@ -466,6 +487,9 @@ class HipEngine:
         resnet_chunk = int(resnet_chunk or os.environ.get("CHESSVISION_HIP_RESNET_CHUNK", "0") or 0)
         if unet_chunk or resnet_chunk:
             _check(self._lib.cv_engine_set_chunk(self._h, unet_chunk, resnet_chunk))
+        self.resnet_chunk = resnet_chunk or 16384        # squares per pass of the classifier (the library's default) ...
+        while self.precision == "f32" and self.resnet_chunk > 1 and self.resnet_chunk * 34 * 34 * 64 * 4 >= 1 << 32:
+            self.resnet_chunk //= 2                      # ... which the f32 engine halves for its stem output (resnet.cpp: resnet_load)
         self.has_unet = False
         self.has_resnet = False
         self.classifier_arch: str | None = None      # "resnet18" | "resnet34" once a ResNet is loaded
@@ -628,6 +652,51 @@ class HipEngine:
             return out, emb
         _check(self._lib.cv_resnet18_forward_u8(self._h, _ptr(squares_u8), n, _ptr(out), _stream_ptr(self.device)))
         return out
+
+    def resnet_forward_u8_norm(self, squares_u8: torch.Tensor, normalize, softmax: bool = False, want_embedding: bool = False):
+        """(N,64,64) uint8 -> (N,13) float32 logits (probabilities with ``softmax``) of the loaded ResNet with the squares normalised
+        in the stem: ``normalize = (mean, std)`` is torchvision's ``ToTensor()`` + ``Normalize([mean], [std])``, bit for bit
+        (``cv_resnet_forward_u8_norm``).  With ``want_embedding`` -> (out, embedding (N,512) float32).  Like ``resnet18_forward_u8`` it
+        does not consult the numeric guard."""
+        if squares_u8.dtype != torch.uint8 or tuple(squares_u8.shape[1:]) != (64, 64):
+            raise HipBackendError("resnet_forward_u8_norm expects (N,64,64) uint8")
+        mean, std = (float(v) for v in normalize)
+        squares_u8 = squares_u8.to(self.device).contiguous()
+        n = squares_u8.shape[0]
+        out = torch.empty((n, 13), dtype=torch.float32, device=self.device)
+        emb = self._embedding_out(self.classifier_arch or "resnet18", n) if want_embedding else None
+        _check(self._lib.cv_resnet_forward_u8_norm(self._h, _ptr(squares_u8), n, mean, std, 1 if softmax else 0, _ptr(out),
+                                                   _ptr(emb) if want_embedding else None, _stream_ptr(self.device)))
+        return (out, emb) if want_embedding else out
+
+    def square_records_dev(self, logits: torch.Tensor, labels: torch.Tensor | None = None) -> torch.Tensor:
+        """The device half of ``square_records``: launches the records kernel on the current stream behind whatever produced
+        ``logits`` ((N,13) float32 on this device, contiguous); ``labels``: (N,) int8 on this device (0..12, -1 = unlabelled) or None.
+        Returns the (N,32) uint8 device tensor of records.  Nothing is synchronised or copied."""
+        if not isinstance(logits, torch.Tensor) or logits.dtype != torch.float32 or logits.device != self.device or logits.dim() != 2 \
+                or logits.shape[1] != 13 or not logits.is_contiguous():
+            raise HipBackendError("square_records expects contiguous (N,13) float32 logits on the engine's device")
+        n = int(logits.shape[0])
+        if labels is not None and (not isinstance(labels, torch.Tensor) or labels.dtype != torch.int8 or labels.device != self.device
+                                   or tuple(labels.shape) != (n,) or not labels.is_contiguous()):
+            raise HipBackendError("square_records expects (N,) int8 labels on the engine's device, or None")
+        records = torch.empty((n, 32), dtype=torch.uint8, device=self.device)
+        if n:
+            _check(self._lib.cv_square_records(self._h, _ptr(logits), _ptr(labels) if labels is not None else None, n, _ptr(records),
+                                               _stream_ptr(self.device)))
+        return records
+
+    def square_records(self, logits: torch.Tensor, labels=None) -> np.ndarray:
+        """(N,13) logits (moved to the device if need be) and N class indices (-1 = unlabelled) or None -> the (N,) ``SQUARE_RECORD``
+        array the kernel wrote: predicted, rank, label, flags, confidence, loss, max_logit, logsumexp.  Synchronises the current
+        stream.  A label outside -1..12 raises."""
+        logits = logits.to(self.device, torch.float32).contiguous()
+        if labels is not None:
+            lab = np.asarray(labels.cpu() if isinstance(labels, torch.Tensor) else labels)
+            if lab.size and (lab.min() < -1 or lab.max() > 12):
+                raise HipBackendError("square_records: labels must be class indices 0..12, or -1 for an unlabelled square")
+            labels = torch.from_numpy(np.ascontiguousarray(lab, dtype=np.int8)).to(self.device)
+        return self.square_records_dev(logits, labels).cpu().numpy().view(SQUARE_RECORD).reshape(-1)
 
     def extraction_scores_dev(self, values: torch.Tensor, transform: str = "none", want_mask: bool = False):
         """The device half of ``extraction_scores``: launches the score kernel on the current stream behind whatever produced

@@ -21,6 +21,8 @@ static_assert(sizeof(cv_score_record_t) == sizeof(cv::ScoreRecord) && offsetof(c
 static_assert(sizeof(cv_seg_record_t) == sizeof(cv::SegRecord) && offsetof(cv_seg_record_t, bce_sum) == offsetof(cv::SegRecord, bce_sum) &&
               offsetof(cv_seg_record_t, sig_label_sum) == offsetof(cv::SegRecord, sig_label_sum) &&
               offsetof(cv_seg_record_t, count) == offsetof(cv::SegRecord, count), "cv_seg_record_t is the kernel's record");
+static_assert(sizeof(cv_square_record_t) == sizeof(cv::SquareRecord) && offsetof(cv_square_record_t, confidence) == offsetof(cv::SquareRecord, confidence) &&
+              offsetof(cv_square_record_t, logsumexp) == offsetof(cv::SquareRecord, logsumexp), "cv_square_record_t is the kernel's record");
 static_assert(sizeof(cv_square_score_t) == 24 && sizeof(cv_board_score_t) == 64, "layouts the Python binding mirrors");
 
 using namespace cv;
@@ -139,13 +141,17 @@ Status unet_entry(cv_engine_t* eng, const void* x, bool x_u8, int batch, float* 
     return unet_forward(eng->impl, x, x_u8, batch, logits, mask, threshold, (hipStream_t)stream, embedding);
 }
 
-// the four cv_resnet18_forward* entry points; the u8 entries return probabilities, the float entries logits
-Status resnet_entry(cv_engine_t* eng, const void* x, bool x_u8, int n, float* out, float* embedding, void* stream) {
+// the four cv_resnet18_forward* entry points (the u8 entries return probabilities, the float entries logits) and
+// cv_resnet_forward_u8_norm, which says which it wants and has its bytes normalised in the stem
+Status resnet_entry(cv_engine_t* eng, const void* x, bool x_u8, int n, float* out, float* embedding, void* stream, bool softmax,
+                    const InputNorm* norm = nullptr) {
     CV_TRY(check_engine(eng));
     CV_TRY(check_embedding(embedding));
+    if (norm && !(std::isfinite(norm->mean) && std::isfinite(norm->std) && norm->std > 0.f))
+        return fail(CV_ERR_INVALID, "cv_resnet_forward_u8_norm: mean must be finite, std finite and > 0");
     std::lock_guard<std::mutex> lk(eng->impl.mu);
     DeviceGuard g(eng->impl.device);
-    return resnet_forward(eng->impl, x, x_u8, n, out, x_u8, (hipStream_t)stream, embedding);
+    return resnet_forward(eng->impl, x, x_u8, n, out, softmax, (hipStream_t)stream, embedding, norm);
 }
 
 // ---- single-layer entry points (parity tests) -------------------------------------------------------
@@ -599,19 +605,27 @@ int cv_unet_forward_mask(cv_engine_t* eng, const float* x, int batch, float* log
 }
 
 int cv_resnet18_forward(cv_engine_t* eng, const float* x, int n, float* logits, void* stream) {
-    return guarded("cv_resnet18_forward", [&]() -> Status { return resnet_entry(eng, x, false, n, logits, nullptr, stream); });
+    return guarded("cv_resnet18_forward", [&]() -> Status { return resnet_entry(eng, x, false, n, logits, nullptr, stream, false); });
 }
 
 int cv_resnet18_forward_u8(cv_engine_t* eng, const uint8_t* squares_u8, int n, float* probs, void* stream) {
-    return guarded("cv_resnet18_forward_u8", [&]() -> Status { return resnet_entry(eng, squares_u8, true, n, probs, nullptr, stream); });
+    return guarded("cv_resnet18_forward_u8", [&]() -> Status { return resnet_entry(eng, squares_u8, true, n, probs, nullptr, stream, true); });
 }
 
 int cv_resnet18_forward_emb(cv_engine_t* eng, const float* x, int n, float* logits, float* embedding, void* stream) {
-    return guarded("cv_resnet18_forward_emb", [&]() -> Status { return resnet_entry(eng, x, false, n, logits, embedding, stream); });
+    return guarded("cv_resnet18_forward_emb", [&]() -> Status { return resnet_entry(eng, x, false, n, logits, embedding, stream, false); });
 }
 
 int cv_resnet18_forward_u8_emb(cv_engine_t* eng, const uint8_t* squares_u8, int n, float* probs, float* embedding, void* stream) {
-    return guarded("cv_resnet18_forward_u8_emb", [&]() -> Status { return resnet_entry(eng, squares_u8, true, n, probs, embedding, stream); });
+    return guarded("cv_resnet18_forward_u8_emb", [&]() -> Status { return resnet_entry(eng, squares_u8, true, n, probs, embedding, stream, true); });
+}
+
+int cv_resnet_forward_u8_norm(cv_engine_t* eng, const uint8_t* squares_u8, int n, float mean, float std, int softmax, float* out,
+                              float* embedding, void* stream) {
+    return guarded("cv_resnet_forward_u8_norm", [&]() -> Status {
+        const InputNorm norm{mean, std};
+        return resnet_entry(eng, squares_u8, true, n, out, embedding, stream, softmax != 0, &norm);
+    });
 }
 
 int cv_embedding_dim(cv_engine_t* eng, const char* model, int* channels) {
@@ -1102,6 +1116,56 @@ int cv_classification_scores(const float* probs, const int8_t* labels, int n_boa
             if (labels[i] < 0 || labels[i] > 12)
                 return fail(CV_ERR_INVALID, "cv_classification_scores: label " + std::to_string(i) + " is not a class index (0..12)");
         classification_scores(probs, labels, n_boards, per_square, per_board);
+        return Status();
+    });
+}
+
+int cv_square_records(cv_engine_t* eng, const float* logits, const int8_t* labels, int n, cv_square_record_t* records, void* stream) {
+    return guarded("cv_square_records", [&]() -> Status {
+        CV_TRY(check_engine(eng));
+        if (!logits || !records) return fail(CV_ERR_INVALID, "cv_square_records: null tensor");
+        if (((uintptr_t)logits & 3u) || ((uintptr_t)records & 7u)) return fail(CV_ERR_INVALID, "cv_square_records: logits must be 4-byte, records 8-byte aligned");
+        if (n < 1) return fail(CV_ERR_INVALID, "cv_square_records: n must be at least 1");
+        DeviceGuard g(eng->impl.device);
+        hipError_t e = square_records(logits, labels, n, reinterpret_cast<SquareRecord*>(records), (hipStream_t)stream);
+        if (e != hipSuccess) return hip_fail(e, "square_records");
+        return Status();
+    });
+}
+
+int cv_square_records_finish(const cv_square_record_t* records, int n, int batch_size, cv_squares_summary_t* out) {
+    return guarded("cv_square_records_finish", [&]() -> Status {
+        if (!out || n < 0 || (n > 0 && !records)) return fail(CV_ERR_INVALID, "cv_square_records_finish: bad argument");
+        std::memset(out, 0, sizeof(*out));
+        out->n = n;
+        const int bs = batch_size > 0 ? batch_size : std::max(n, 1);
+        double running = 0.0;                                 // validate(): running_loss += criterion(output, target).item()
+        for (int lo = 0; lo < n; lo += bs) {
+            double batch_sum = 0.0;
+            int batch_n = 0;
+            for (int i = lo; i < std::min(n, lo + bs); ++i) {
+                const cv_square_record_t& r = records[i];
+                if (r.flags & 2) return fail(CV_ERR_INVALID, "cv_square_records_finish: record " + std::to_string(i) + " carries a label outside -1..12");
+                if (r.flags & 1) ++out->n_nan;
+                if (r.label < 0) continue;
+                if (r.label > 12 || r.predicted < 0 || r.predicted > 12)
+                    return fail(CV_ERR_INVALID, "cv_square_records_finish: record " + std::to_string(i) + " is not a record of cv_square_records");
+                ++batch_n;
+                batch_sum += (double)r.loss;
+                if (!(r.flags & 1) && r.predicted == r.label) ++out->n_correct;
+                for (int k = std::max(r.rank, 0); k < 13; ++k) ++out->hits[k];
+                ++out->confusion[r.label * 13 + r.predicted];
+            }
+            if (!batch_n) continue;
+            out->n_labelled += batch_n;
+            out->loss_sum += batch_sum;
+            running += batch_sum / (double)batch_n;
+            ++out->n_batches;
+        }
+        const double nan = std::nan("");
+        out->val_loss = out->n_batches ? running / (double)out->n_batches : nan;
+        out->val_acc = out->n_labelled ? 100.0 * (double)out->n_correct / (double)out->n_labelled : nan;
+        if (!out->n_labelled) out->loss_sum = nan;
         return Status();
     });
 }

@@ -31,6 +31,11 @@ typedef _Float16 half8 __attribute__((ext_vector_type(8)));
 typedef _Float16 half4 __attribute__((ext_vector_type(4)));
 typedef float f4 __attribute__((ext_vector_type(4)));
 
+// Normalised byte input of the two stems (the classifier's val_transforms: ToTensor + Normalize([mean], [std])): the pixel enters the
+// convolution as ((float)u8 / 255.f - mean) / std, three float32 operations in that order with true divisions -- bit for bit what
+// torch's div(255).sub_(mean).div_(std) leaves.  The zero border is not normalised (torch pads after the transform).
+struct InputNorm { float mean, std; };
+
 // Split-f16 conversion of a PAIR of f32 values in three vector instructions: hi pair = v_cvt_pk_f16_f32(v0, v1); each lo =
 // f16(v - hi) as ONE mixed-precision FMA (v_fma_mixlo / mixhi_f16: fma(f16 hi, -1, f32 v) rounded to f16 -- v - hi is exact in f32,
 // so the single rounding equals the convert-back / subtract / convert chain the compiler emits for the C expression, which costs

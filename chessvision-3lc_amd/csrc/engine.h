@@ -330,12 +330,14 @@ class Engine {
     // `graph_epoch` it was captured in and anything that re-allocates or re-folds such memory bumps the epoch (workspace growth,
     // split-K buffer growth, exponent changes, offset tables created on first use).  CV_GRAPH=0 switches the replay off.
     struct GraphKey {
-        int model = 0, n = 0, flags = 0;                  // model 0 = UNet, 1 = ResNet-18; flags: u8 entry / softmax
+        int model = 0, n = 0, flags = 0;                  // model 0 = UNet, 1 = ResNet-18; flags: u8 entry / softmax / normalised
         const void* x = nullptr; void* out = nullptr; void* mask = nullptr;
         void* emb = nullptr;                              // embedding output, or null: a forward that pools and one that does not are two graphs
         unsigned thr_bits = 0;
+        unsigned norm_bits[2] = {0, 0};                   // mean / std of a normalised byte input (flags bit 2): kernel arguments of the capture
         bool operator==(const GraphKey& o) const {
-            return model == o.model && n == o.n && flags == o.flags && x == o.x && out == o.out && mask == o.mask && emb == o.emb && thr_bits == o.thr_bits;
+            return model == o.model && n == o.n && flags == o.flags && x == o.x && out == o.out && mask == o.mask && emb == o.emb && thr_bits == o.thr_bits &&
+                   norm_bits[0] == o.norm_bits[0] && norm_bits[1] == o.norm_bits[1];
         }
     };
     struct GraphEntry {
@@ -401,7 +403,9 @@ int64_t unet_macs(Engine& e);
 
 Status resnet_load(Engine& e, const ParamMap& pm, const std::string& arch);   // arch: "resnet18" | "resnet34"
 // embedding (nullable, device, n x 512 floats): per-square channel means of layer4's output (its f32 twin under f16r) -- global_pool
-Status resnet_forward(Engine& e, const void* x, bool x_u8, int n, float* out, bool softmax, hipStream_t s, float* embedding = nullptr);
+// norm (nullable, byte input only): the squares are normalised in the stem, ((float)u8 / 255 - mean) / std (cv_kernels.h: InputNorm)
+Status resnet_forward(Engine& e, const void* x, bool x_u8, int n, float* out, bool softmax, hipStream_t s, float* embedding = nullptr,
+                      const InputNorm* norm = nullptr);
 Status resnet_activation(Engine& e, const std::string& name, TensorRef* out);
 int64_t resnet_macs(Engine& e);
 

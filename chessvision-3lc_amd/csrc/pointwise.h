@@ -37,16 +37,17 @@ hipError_t outc_1x1(int dt, const TensorRef& src, const float* w, const float* b
                     uint8_t* mask, float threshold, unsigned* flag, unsigned layer_id, hipStream_t s);
 
 // ResNet stem: conv 7x7 s2 p3 (1 -> 64, no bias) + BN affine + ReLU.  x: (n,1,64,64) f32 or (n,64,64) u8
-// (u8 is scaled by /255 first, core.py:237).  w: [64][49] f32, scale/shift [64].  dst: 64 ch @ 32x32.
+// (u8 is scaled by /255 first, core.py:237; then normalised when `norm` is given -- u8 only, cv_kernels.h: InputNorm).  w: [64][49] f32, scale/shift [64].
+// dst: 64 ch @ 32x32.
 hipError_t stem7x7(int dt, const void* x, bool x_is_u8, int n, const float* w, const float* scale,
-                   const float* shift, const TensorRef& dst, hipStream_t s);
+                   const float* shift, const TensorRef& dst, hipStream_t s, const InputNorm* norm = nullptr);
 
 // Fused stem for the f16 / split-f16 engines: conv 7x7 s2 p3 + BN + ReLU + max_pool2d(3,2,1) on the MFMA.
 // wpk: packed filter bank [hi|lo][k-step 2][fragment 4][lane 64] x half8 (packed by resnet.cpp: resnet_load).  dst: 64 ch @ 16x16.
 // in_exp: the input plane is held as x * 2^-in_exp inside the kernel (x in [0,1] -> in_exp = -7 keeps the lo halves normal)
 hipError_t stem_pool_mfma(int dt, const void* x, bool x_is_u8, int n, const void* wpk, const float* scale,
                           const float* shift, int in_exp, const TensorRef& dst, unsigned* flag, unsigned layer_id,
-                          hipStream_t s);
+                          hipStream_t s, const InputNorm* norm = nullptr);
 
 // UNet first layer for the f16 / split-f16 engines, fused with the input packing: conv 3x3 p1 (3 -> 64) + BN + ReLU straight from
 // the caller's image (x: (n,3,256,256) f32 or (n,256,256,3) u8, scaled by /255).  wpk: [hi|lo][fragment 4][lane 64] x half8
@@ -94,6 +95,17 @@ struct SegRecord {
 static_assert(sizeof(SegRecord) == 64, "one 64-byte record per image");
 hipError_t segmentation_scores(const float* logits, const uint8_t* labels, int n, int count, float threshold, SegRecord* records,
                                hipStream_t s);
+
+// Per-square records of the classifier's validation pass (train_classifier.py: validate(), the classification collector).  logits:
+// n rows of 13 float32 on the device; labels: n int8 on the device (0..12, -1 = unlabelled), or null = all unlabelled.  One thread per
+// row, everything in float32 with expf / logf, sums in ascending class order.  The fields are documented at cv_square_record_t
+// (include/chessvision_hip.h), whose layout this is.  Asynchronous on `s`; allocates nothing; one launch for any n >= 1.
+struct SquareRecord {
+    int32_t predicted, rank, label, flags;
+    float   confidence, loss, max_logit, logsumexp;
+};
+static_assert(sizeof(SquareRecord) == 32, "one 32-byte record per square");
+hipError_t square_records(const float* logits, const int8_t* labels, int n, SquareRecord* records, hipStream_t s);
 
 // MFMA lane-map probes used by cv_selftest_mfma (D = A*B^T with A:16xK, B:16xK row-major)
 hipError_t mfma_probe_f16(const half_t* a, const half_t* b, float* d, hipStream_t s);   // K = 32

@@ -605,10 +605,12 @@ __global__ void outc_1x1_kernel(TensorRef src, const float* __restrict__ w, cons
 // One workgroup per 64x64 square.  The zero-bordered plane sits in LDS; each lane owns one output pixel at
 // a time, holds its 7x7 patch in VGPRs and runs the 64x49 filter bank from the scalar cache (wave-uniform
 // weights -> s_load + v_fma with an SGPR operand), i.e. a pure VALU f32 kernel.
-template <typename T, typename XT>
+// NORM (byte input only): the stored pixel is ((float)u8 / 255 - mean) / std, ToTensor + Normalize in torch's float32 arithmetic
+// (two true divisions and a subtraction, in that order); the zero border stays zero, as torch pads after normalising.
+template <typename T, typename XT, bool NORM = false>
 __global__ __launch_bounds__(256) void stem7x7_kernel(const XT* __restrict__ x, const float* __restrict__ w,
                                                       const float* __restrict__ scale,
-                                                      const float* __restrict__ shift, TensorRef dst) {
+                                                      const float* __restrict__ shift, TensorRef dst, InputNorm norm) {
     constexpr int IN = 64, P = 3, LD = IN + 2 * P;            // 70
     constexpr int GN = Grp<T>::N;
     __shared__ float plane[LD * LD];
@@ -620,6 +622,7 @@ __global__ __launch_bounds__(256) void stem7x7_kernel(const XT* __restrict__ x, 
     for (int i = tid; i < IN * IN; i += 256) {
         float v = (float)xs[i];
         if (sizeof(XT) == 1) v = v / 255.f;
+        if (NORM) v = (v - norm.mean) / norm.std;
         plane[(i / IN + P) * LD + (i % IN) + P] = v;
     }
     __syncthreads();
@@ -668,12 +671,13 @@ __global__ __launch_bounds__(256) void stem7x7_kernel(const XT* __restrict__ x, 
 // SPLIT = split-f16 ARITHMETIC (hi + lo planes, three products); it is what a split_t tensor implies, and the f16r engine asks
 // for it with T = half_t: its stem computes at f32 grade and leaves the pooled result twice, as the f16 tensor layer1.0.conv1
 // consumes and as the f32 twin (dst.base32) the residual trunk starts from.
-template <typename T, typename XT, bool SPLIT = sizeof(T) == 4>
+// NORM: the normalised byte input of stem7x7_kernel; |value| <= 2.30 for the training constants, times 2^7 well inside f16.
+template <typename T, typename XT, bool SPLIT = sizeof(T) == 4, bool NORM = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void stem_pool_mfma_kernel(const XT* __restrict__ x, int n,
                                                              const half8* __restrict__ wpk,
                                                              const float* __restrict__ scale,
                                                              const float* __restrict__ shift, float in_mul, TensorRef dst,
-                                                             unsigned* flag, unsigned layer_id) {
+                                                             unsigned* flag, unsigned layer_id, InputNorm norm) {
     constexpr int LD = 98, ROWS = 72, PAD = 5;              // LD/2 = 49 dwords: odd rows land on the other bank half
     constexpr int NPL = SPLIT ? 2 : 1;                      // hi (+ lo) plane
     // two sets of planes: square n+1 is fetched into registers before square n is computed and written to the other set after it,
@@ -710,6 +714,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
             const int i = tid + 256 * k;
             float v = (float)pre[k];
             if (sizeof(XT) == 1) v = v / 255.f;
+            if (NORM) v = (v - norm.mean) / norm.std;    // ToTensor + Normalize, bit for bit
             v *= in_mul;                                     // power-of-two range factor of the input plane (exact)
             const half_t hi = (half_t)v;
             const int at = ((i >> 6) + PAD) * LD + (i & 63) + PAD;
@@ -1061,6 +1066,54 @@ __global__ void softmax13_kernel(const float* __restrict__ logits, int n, float*
     const float r = 1.f / s;
 #pragma unroll
     for (int j = 0; j < 13; ++j) probs[(size_t)i * 13 + j] = v[j] * r;
+}
+
+// ---- per-square records of the classifier's validation pass ------------------------------------------------------------------------
+// One thread per row of 13 logits (52 B in, 32 B out: the launch is bandwidth- and latency-bound, there is nothing to share between
+// rows).  Every comparison is of the float32 logits themselves, so the integer fields equal a host restatement bit for bit; the sums
+// run in ascending class order with expf / logf.  The grid-stride loop takes any n in one launch.
+__global__ __launch_bounds__(256) void square_records_kernel(const float* __restrict__ logits, const int8_t* __restrict__ labels, int n,
+                                                             SquareRecord* __restrict__ records) {
+    const size_t step = (size_t)gridDim.x * 256;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < (size_t)n; i += step) {
+        float x[13];
+        bool nan = false;
+#pragma unroll
+        for (int j = 0; j < 13; ++j) { x[j] = logits[i * 13 + j]; nan = nan || x[j] != x[j]; }
+        int pred = 0;
+        float m = x[0];
+#pragma unroll
+        for (int j = 1; j < 13; ++j)
+            if (x[j] > m) { m = x[j]; pred = j; }
+        float s = 0.f;
+#pragma unroll
+        for (int j = 0; j < 13; ++j) s += expf(x[j] - m);
+        const float ls = logf(s);
+        const int given = labels ? (int)labels[i] : -1;
+        const bool bad = given < -1 || given > 12;           // cannot be refused without reading device memory: flagged, scored as unlabelled
+        const int t = bad ? -1 : given;
+        int rank = -1;
+        float xt = 0.f;
+        if (t >= 0) {
+            rank = 0;
+#pragma unroll
+            for (int j = 0; j < 13; ++j)
+                if (j == t) xt = x[j];
+#pragma unroll
+            for (int j = 0; j < 13; ++j) rank += (x[j] > xt || (j > t && x[j] == xt)) ? 1 : 0;
+        }
+        const float qnan = __int_as_float(0x7fc00000);
+        SquareRecord r;
+        r.predicted = pred;
+        r.rank = t < 0 ? -1 : nan ? 13 : rank;
+        r.label = given;
+        r.flags = (nan ? 1 : 0) | (bad ? 2 : 0);
+        r.confidence = nan ? qnan : 1.f / s;
+        r.loss = (t < 0 || nan) ? qnan : ls - (xt - m);
+        r.max_logit = nan ? qnan : m;
+        r.logsumexp = nan ? qnan : m + ls;
+        records[i] = r;
+    }
 }
 
 // ---- board-extraction quality scores: per-image reductions over the UNet's logits ------------------------------------------------
@@ -1437,13 +1490,15 @@ hipError_t outc_1x1(int dt, const TensorRef& src, const float* w, const float* b
                 flag, layer_id);
 }
 hipError_t stem7x7(int dt, const void* x, bool x_is_u8, int n, const float* w, const float* scale,
-                   const float* shift, const TensorRef& dst, hipStream_t s) {
-    if (dst.C != 64 || dst.H != 32 || dst.W != 32 || dst.Coff != 0) return hipErrorInvalidValue;
+                   const float* shift, const TensorRef& dst, hipStream_t s, const InputNorm* norm) {
+    if (dst.C != 64 || dst.H != 32 || dst.W != 32 || dst.Coff != 0 || (norm && !x_is_u8)) return hipErrorInvalidValue;
     const dim3 g((unsigned)n), b(256);
+    const InputNorm nm = norm ? *norm : InputNorm{0.f, 1.f};
 #define CV_STEM(T)                                                                                                   \
     do {                                                                                                             \
-        if (x_is_u8) hipLaunchKernelGGL((stem7x7_kernel<T, uint8_t>), g, b, 0, s, (const uint8_t*)x, w, scale, shift, dst); \
-        else hipLaunchKernelGGL((stem7x7_kernel<T, float>), g, b, 0, s, (const float*)x, w, scale, shift, dst);      \
+        if (norm) hipLaunchKernelGGL((stem7x7_kernel<T, uint8_t, true>), g, b, 0, s, (const uint8_t*)x, w, scale, shift, dst, nm); \
+        else if (x_is_u8) hipLaunchKernelGGL((stem7x7_kernel<T, uint8_t>), g, b, 0, s, (const uint8_t*)x, w, scale, shift, dst, nm); \
+        else hipLaunchKernelGGL((stem7x7_kernel<T, float>), g, b, 0, s, (const float*)x, w, scale, shift, dst, nm);  \
     } while (0)
     if (dt == kF16) CV_STEM(half_t); else if (dt == kSplit) CV_STEM(split_t); else CV_STEM(float);
 #undef CV_STEM
@@ -1451,21 +1506,23 @@ hipError_t stem7x7(int dt, const void* x, bool x_is_u8, int n, const float* w, c
 }
 hipError_t stem_pool_mfma(int dt, const void* x, bool x_is_u8, int n, const void* wpk, const float* scale,
                           const float* shift, int in_exp, const TensorRef& dst, unsigned* flag, unsigned layer_id,
-                          hipStream_t s) {
-    if (dt == kF32 || dst.C != 64 || dst.Cs != 64 || dst.H != 16 || dst.W != 16 || dst.Coff != 0) return hipErrorInvalidValue;   // rows of the tensor are contiguous runs
+                          hipStream_t s, const InputNorm* norm) {
+    if (dt == kF32 || dst.C != 64 || dst.Cs != 64 || dst.H != 16 || dst.W != 16 || dst.Coff != 0 || (norm && !x_is_u8))
+        return hipErrorInvalidValue;                     // rows of the tensor are contiguous runs
     const dim3 g((unsigned)(n < 2048 ? n : 2048)), b(256);
     const half8* w = reinterpret_cast<const half8*>(wpk);
     const float im = pow2f(-in_exp);
-    if (dt == kF16 && dst.base32) {                      // f16r engine: split-f16 arithmetic, f16 tensor + f32 twin out
-        if (x_is_u8) hipLaunchKernelGGL((stem_pool_mfma_kernel<half_t, uint8_t, true>), g, b, 0, s, (const uint8_t*)x, n, w, scale, shift, im, dst, flag, layer_id);
-        else hipLaunchKernelGGL((stem_pool_mfma_kernel<half_t, float, true>), g, b, 0, s, (const float*)x, n, w, scale, shift, im, dst, flag, layer_id);
-    } else if (dt == kF16) {
-        if (x_is_u8) hipLaunchKernelGGL((stem_pool_mfma_kernel<half_t, uint8_t>), g, b, 0, s, (const uint8_t*)x, n, w, scale, shift, im, dst, flag, layer_id);
-        else hipLaunchKernelGGL((stem_pool_mfma_kernel<half_t, float>), g, b, 0, s, (const float*)x, n, w, scale, shift, im, dst, flag, layer_id);
-    } else {
-        if (x_is_u8) hipLaunchKernelGGL((stem_pool_mfma_kernel<split_t, uint8_t>), g, b, 0, s, (const uint8_t*)x, n, w, scale, shift, im, dst, flag, layer_id);
-        else hipLaunchKernelGGL((stem_pool_mfma_kernel<split_t, float>), g, b, 0, s, (const float*)x, n, w, scale, shift, im, dst, flag, layer_id);
-    }
+    const InputNorm nm = norm ? *norm : InputNorm{0.f, 1.f};
+#define CV_STEM(T, SPLIT)                                                                                                              \
+    do {                                                                                                                               \
+        if (norm) hipLaunchKernelGGL((stem_pool_mfma_kernel<T, uint8_t, SPLIT, true>), g, b, 0, s, (const uint8_t*)x, n, w, scale, shift, im, dst, flag, layer_id, nm); \
+        else if (x_is_u8) hipLaunchKernelGGL((stem_pool_mfma_kernel<T, uint8_t, SPLIT>), g, b, 0, s, (const uint8_t*)x, n, w, scale, shift, im, dst, flag, layer_id, nm); \
+        else hipLaunchKernelGGL((stem_pool_mfma_kernel<T, float, SPLIT>), g, b, 0, s, (const float*)x, n, w, scale, shift, im, dst, flag, layer_id, nm); \
+    } while (0)
+    if (dt == kF16 && dst.base32) CV_STEM(half_t, true);   // f16r engine: split-f16 arithmetic, f16 tensor + f32 twin out
+    else if (dt == kF16) CV_STEM(half_t, false);
+    else CV_STEM(split_t, true);
+#undef CV_STEM
     return hipGetLastError();
 }
 hipError_t inc0_mfma(int dt, const void* x, bool x_is_u8, int n, const void* wpk, const float* scale, const float* shift,
@@ -1511,6 +1568,12 @@ hipError_t segmentation_scores(const float* logits, const uint8_t* labels, int n
 }
 hipError_t softmax13(const float* logits, int n, float* probs, hipStream_t s) {
     hipLaunchKernelGGL(softmax13_kernel, dim3(grid_for((size_t)n)), dim3(256), 0, s, logits, n, probs);
+    return hipGetLastError();
+}
+hipError_t square_records(const float* logits, const int8_t* labels, int n, SquareRecord* records, hipStream_t s) {
+    if (!logits || !records || n < 1 || ((uintptr_t)logits & 3u) || ((uintptr_t)records & 7u)) return hipErrorInvalidValue;
+    const dim3 g_(std::min(grid_for((size_t)n), 4096u)), b_(256);
+    hipLaunchKernelGGL(square_records_kernel, g_, b_, 0, s, logits, labels, n, records);
     return hipGetLastError();
 }
 hipError_t mfma_probe_f16(const half_t* a, const half_t* b, float* d, hipStream_t s) {

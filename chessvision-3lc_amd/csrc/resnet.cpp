@@ -33,7 +33,8 @@ const ResNetArch* resnet_arch(const std::string& name) {
 
 static Status resnet_reserve(Engine& e, int n);
 static Status layer1_chain(Engine& e, int n, hipStream_t s);
-static Status resnet_chunk(Engine& e, const void* x, bool x_u8, int n, float* out, bool softmax, hipStream_t s, float* embedding = nullptr);
+static Status resnet_chunk(Engine& e, const void* x, bool x_u8, int n, float* out, bool softmax, hipStream_t s, float* embedding = nullptr,
+                           const InputNorm* norm = nullptr);
 
 // form of the chained layer1 launch (f16r): 2 (default) = two workgroups per CU, block 0's f32 output written and read back; 1 = one
 // workgroup per CU with 512 registers, the f32 trunk stays in registers -- no round trip, but nothing covers the workgroup's barriers,
@@ -362,7 +363,8 @@ Status resnet_activation(Engine& e, const std::string& name, TensorRef* out) {
     return Status();
 }
 
-static Status resnet_chunk(Engine& e, const void* x, bool x_u8, int n, float* out, bool softmax, hipStream_t s, float* embedding) {
+static Status resnet_chunk(Engine& e, const void* x, bool x_u8, int n, float* out, bool softmax, hipStream_t s, float* embedding,
+                           const InputNorm* norm) {
     Engine::ResNet& R = *e.resnet;
     R.last_n = n;
     e.ws_slot = 1;
@@ -377,7 +379,7 @@ static Status resnet_chunk(Engine& e, const void* x, bool x_u8, int n, float* ou
     if (dt == kF32) {
         begin("stem7x7", 49.0 * 64 * 1024 * n, (double)n * (4096 * in_b + 1024 * 64 * esz));
         CV_TRY(end("stem7x7", stem7x7(dt, x, x_u8, n, (const float*)R.stem_w.ptr, (const float*)R.stem_scale.ptr,
-                                       (const float*)R.stem_shift.ptr, R.stem_out.ref(n), s)));
+                                       (const float*)R.stem_shift.ptr, R.stem_out.ref(n), s, norm)));
         begin("maxpool3x3s2", 0, (double)n * (1024 + 256) * 64 * esz);
         CV_TRY(end("maxpool3x3s2", maxpool3x3s2(dt, R.stem_out.ref(n), R.pool_out.ref(n), s)));
     } else {
@@ -385,7 +387,7 @@ static Status resnet_chunk(Engine& e, const void* x, bool x_u8, int n, float* ou
         begin("stem7x7+maxpool (mfma)", 49.0 * 64 * 1024 * n, (double)n * (4096 * in_b + 256 * 64 * (esz + (R.pool_out.want32 ? 4.0 : 0.0))));
         CV_TRY(end("stem_pool_mfma", stem_pool_mfma(dt, x, x_u8, n, R.stem_wpk.ptr, (const float*)R.stem_scale.ptr,
                                                      (const float*)R.stem_shift.ptr, kInputExp, R.pool_out.ref(n),
-                                                     e.guard_ptr(), R.stem_id, s)));
+                                                     e.guard_ptr(), R.stem_id, s, norm)));
         if (e.calibrating) CV_TRY(e.measure(R.pool_out.ref(n), s));
     }
     TensorRef cur = R.pool_out.ref(n);
@@ -507,24 +509,27 @@ static Status layer1_chain(Engine& e, int n, hipStream_t s) {
     return Status();
 }
 
-Status resnet_forward(Engine& e, const void* x, bool x_u8, int n, float* out, bool softmax, hipStream_t s, float* embedding) {
+Status resnet_forward(Engine& e, const void* x, bool x_u8, int n, float* out, bool softmax, hipStream_t s, float* embedding,
+                      const InputNorm* norm) {
     if (!e.resnet) return fail(3, "ResNet weights not loaded (call cv_load_resnet or cv_load_resnet18 first)");
     if (n < 0 || (n > 0 && (!x || !out))) return fail(1, "cv_resnet18_forward: null tensor or negative batch");
+    if (norm && !x_u8) return fail(1, "resnet_forward: only a byte input can be normalised");
     if (n == 0) return Status();
     CV_TRY(e.order_forward(1, s));
     CV_TRY(resnet_reserve(e, n));
     if (n <= e.resnet->cap && n <= 512) {                // one small chunk (a board's 64 squares): the launch sequence replays as a hipGraph
         Engine::GraphKey key;
-        key.model = 1; key.n = n; key.flags = (x_u8 ? 1 : 0) | (softmax ? 2 : 0); key.x = x; key.out = out; key.emb = embedding;
+        key.model = 1; key.n = n; key.flags = (x_u8 ? 1 : 0) | (softmax ? 2 : 0) | (norm ? 4 : 0); key.x = x; key.out = out; key.emb = embedding;
+        if (norm) std::memcpy(key.norm_bits, norm, sizeof(key.norm_bits));   // baked into the captured stem launch
         e.resnet->last_n = n;                            // a graph replay skips resnet_chunk's host side (see unet_forward)
         e.ws_slot = 1;
-        return e.run_graphed(key, s, [&](hipStream_t st) { return resnet_chunk(e, x, x_u8, n, out, softmax, st, embedding); });
+        return e.run_graphed(key, s, [&](hipStream_t st) { return resnet_chunk(e, x, x_u8, n, out, softmax, st, embedding, norm); });
     }
     const size_t in_stride = (size_t)64 * 64 * (x_u8 ? 1 : 4);
     for (int off = 0; off < n; off += e.resnet->cap) {
         const int c = std::min(e.resnet->cap, n - off);
         CV_TRY(resnet_chunk(e, (const char*)x + (size_t)off * in_stride, x_u8, c, out + (size_t)off * 13, softmax, s,
-                            embedding ? embedding + (size_t)off * 512 : nullptr));
+                            embedding ? embedding + (size_t)off * 512 : nullptr, norm));
     }
     return Status();
 }

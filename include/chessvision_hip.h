@@ -453,6 +453,58 @@ typedef struct cv_board_score {
 int cv_classification_scores(const float* probs, const int8_t* labels, int n_boards, cv_square_score_t* per_square,
                              cv_board_score_t* per_board);
 
+/* ---- square-set evaluation (additions under ABI 6; detect with dlsym(handle, "cv_square_records")) ----------------------------- */
+/* The classifier's own batched caller in the reference, scripts/train/train_classifier.py: validate() (:90-111, CrossEntropyLoss and
+ * accuracy over a table of labelled 64 x 64 squares) and the tlc.collect_metrics pass (:274-292, batch 512) behind val_transforms
+ * (:45-52: ToTensor + Normalize([0.564], [0.246])).  3LC's ClassificationMetricsCollector is not in the reference tree: loss /
+ * predicted / confidence / accuracy per sample is this library's READING of it.  Out of scope: crops that are not 64 x 64 gray (PIL's
+ * Resize / Grayscale), the training transforms, normalisation inside cv_process_image (the reference does not normalise there).
+ *
+ * cv_resnet_forward_u8_norm: cv_resnet18_forward_u8 / _emb with the byte normalised in the stem: the pixel enters the first
+ * convolution as ((float)u8 / 255.f - mean) / std -- three float32 operations in that order, true divisions -- which is bit for bit
+ * torchvision's ToTensor followed by Normalize([mean], [std]); the zero padding of the convolution stays zero (torch pads after the
+ * transform).  The result equals cv_resnet18_forward on that float tensor bit for bit.  squares_u8: DEVICE (n,64,64); mean finite,
+ * std finite and > 0 (CV_ERR_INVALID otherwise); softmax != 0: `out` receives probabilities instead of logits; embedding: nullable,
+ * DEVICE (n,512), 16-byte aligned, as cv_resnet18_forward_emb.  Runs whichever ResNet is loaded, in the engine's chunks; batches up
+ * to 512 replay as a captured graph whose key includes mean and std.  The f16-family engines hold the input plane as x * 2^7 in
+ * f16: |x| <= 2.30 for the training constants; constants that push |x| beyond ~500 overflow it. */
+int cv_resnet_forward_u8_norm(cv_engine_t* eng, const uint8_t* squares_u8, int n, float mean, float std, int softmax, float* out,
+                              float* embedding, void* stream);
+/* cv_square_records: logits = n rows of 13 float32 (DEVICE, 4-byte aligned), labels = n int8 (DEVICE, nullable = all unlabelled),
+ * records = n records (DEVICE, 8-byte aligned), n >= 1.  Everything is float32 with expf / logf, sums in ascending class order.
+ * Asynchronous on `stream`; allocates nothing and synchronises nothing; one launch for any n.  A label outside -1..12 cannot be
+ * refused without reading device memory: the square is scored as unlabelled, its byte is kept in `label` and flag bit 1 is set
+ * (cv_square_records_finish then returns CV_ERR_INVALID).  Logits of +-inf are outside the contract (inf - inf). */
+typedef struct cv_square_record {   /* 32 bytes */
+    int32_t predicted;   /* first maximum of the 13 logits (scan j = 0..12, `x_j > best`) */
+    int32_t rank;        /* #{j: x_j > x_t} + #{j > t: x_j == x_t}, the stable reading documented at cv_classification_scores, on
+                            logits; 13 when the row holds a NaN; -1 when unlabelled */
+    int32_t label;       /* as given: 0..12, or -1 = unlabelled */
+    int32_t flags;       /* bit 0: the row holds a NaN; bit 1: the label byte was outside -1..12 */
+    float   confidence;  /* 1 / s, s = sum_j expf(x_j - m) added in ascending j, m = max: the largest soft-max probability */
+    float   loss;        /* logf(s) - (x_t - m): CrossEntropyLoss(reduction="none"); NaN when unlabelled or NaN row */
+    float   max_logit;   /* m */
+    float   logsumexp;   /* m + logf(s) */
+} cv_square_record_t;    /* a NaN row: confidence, loss, max_logit and logsumexp are all NaN */
+int cv_square_records(cv_engine_t* eng, const float* logits, const int8_t* labels, int n, cv_square_record_t* records, void* stream);
+/* Records (HOST) -> the aggregate of validate().  Needs no GPU and no engine.  Only labelled squares count below.
+ *   val_loss   validate()'s running_loss / len(loader): the records are cut into consecutive batches of batch_size (the last one
+ *              short; batch_size <= 0: one batch), each batch contributes the mean loss of its labelled squares (CrossEntropyLoss's
+ *              reduction="mean"; a batch without a labelled square is skipped), val_loss is the mean of those; in float64.  A
+ *              labelled NaN row makes it NaN, as it makes torch's.
+ *   val_acc    100 * n_correct / n_labelled, n_correct = squares with predicted == label (output.max(1)); NaN rows are misses
+ *   hits[k-1]  squares with rank < k;  hits[0] differs from n_correct only where the true class ties for the maximum with a later class
+ *   confusion  13 x 13, row = true class, column = predicted;  loss_sum: float64 sum of the losses
+ * CV_ERR_INVALID when a record carries flag bit 1 (a label byte outside -1..12). */
+typedef struct cv_squares_summary {
+    int64_t n, n_labelled, n_correct, n_nan;      /* n_nan: rows holding a NaN, labelled or not */
+    int64_t hits[13];
+    int64_t confusion[13 * 13];
+    double  loss_sum, val_loss, val_acc;           /* NaN when nothing is labelled */
+    int64_t n_batches;                             /* batches that held a labelled square */
+} cv_squares_summary_t;
+int cv_square_records_finish(const cv_square_record_t* records, int n, int batch_size, cv_squares_summary_t* out);
+
 /* ---- one image, host to host: the native form of ChessVision.process_image (core.py:152-195) ---------------------------------- */
 /* Everything a cgo / JNI / C++ host needs for the reference's per-image entry point in ONE call: INTER_AREA resize to 256x256
  * (core.py:212), UNet forward, sigmoid / threshold mask (core.py:273, utils.py:101-112), contours -> quadrangle (core.py:357-411),
