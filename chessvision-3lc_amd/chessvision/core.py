@@ -587,6 +587,58 @@ class ChessVision:
                                                                      resize))
         return targets.report(results)
 
+    def evaluate_thresholds(self, images: Sequence[NDArray[np.uint8]], thresholds: Sequence[float],
+                            true_fens: Sequence[str | None] | None = None,
+                            label_masks: Sequence[NDArray[np.uint8] | None] | None = None, flip: bool = False,
+                            fallback_quad: bool = False, pipeline_chunk: int = 64, timings: dict | None = None):
+        """``evaluate_images`` at every mask threshold of ``thresholds`` for ONE upload, resize and UNet pass per job: the sweep the
+        reference runs from outside (``scripts/eval/evaluate.py --threshold``, plotted by ``scripts/plot_sweep.py``).  Returns a
+        ``ThresholdSweepReport`` (``chessvision/evaluation.py``): ``thresholds`` (the caller's values in the caller's order),
+        ``reports`` (one ``EvaluationReport`` per threshold, what ``evaluate_images(..., threshold=t)`` returns), ``at(t)``,
+        ``curve`` (every key of ``aggregate`` but ``avg_time_per_prediction``, plus ``mean_pixel_accuracy``, as lists aligned with
+        ``thresholds``), ``best(key)``, ``boards_found`` and ``boards_classified``.
+
+        ``thresholds``: 1 to 32 values in [0, 1], no two equal as float32, in any order; anything else raises ``ValueError`` before
+        anything is queued.  Ground truth follows ``evaluate_images``: at least one of ``true_fens`` / ``label_masks``, checked first.
+
+        Per job one kernel behind the UNet turns the logits into a level map (one byte per pixel: the number of thresholds the
+        pixel's sigmoid exceeds, so every threshold's mask is a comparison of it) and every threshold's segmentation counts
+        (``HipEngine.threshold_levels_dev``); the host finds the quadrangles of all T masks in one native call, and the warp and
+        the classifier run once per DISTINCT quadrangle of an image (``evaluation.plan_threshold_groups``), not once per threshold
+        (``chessvision/sweep.py``).  Against ``evaluate_images`` at the same threshold: logits, mask, quadrangle, board, crops and
+        the segmentation scores are bit for bit the same; the probabilities agree to the cross-batch bar (1e-4), because a board
+        classified in a group of another size takes another launch plan.
+
+        The reports SHARE arrays: the logits always, board, crops, probabilities and per-square scores wherever two thresholds
+        found the same quadrangle.  They are views into the call's page-locked buffers: copy before writing.
+        ``self.evaluation_resize`` and ``self.evaluation_embeddings`` are honoured as in ``evaluate_images`` (the UNet embedding is
+        shared by all thresholds, the classifier embedding follows the board).  ``processing_time`` of a result is the call's
+        time divided by the number of images.  Out of scope: the single-image API, ``process_images_sharded``, ``quality=``."""
+        from .evaluation import Targets, ThresholdSweepReport, check_thresholds
+
+        if not isinstance(thresholds, (list, tuple, np.ndarray)):
+            raise ValueError(f"thresholds must be a list, tuple or array of numbers, got {type(thresholds).__name__}")
+        asked = check_thresholds(thresholds)
+        resize = self.evaluation_resize
+        self._check_resize(resize)
+        images = list(images)
+        targets = Targets(len(images), true_fens, label_masks)
+        ascending = np.sort(asked)
+        order = [int(np.searchsorted(ascending, t)) for t in asked]
+        given = [float(t) for t in thresholds]               # returned as given; compared as float32 everywhere
+        if not images:
+            return ThresholdSweepReport.from_reports(given, [targets.report([]) for _ in asked])
+        embeddings = bool(self.evaluation_embeddings)
+        report = self._recover(lambda cv: cv._evaluate_thresholds_native(images, ascending, order, targets, flip, fallback_quad,
+                                                                         pipeline_chunk, timings, embeddings, resize))
+        report.thresholds = given
+        return report
+
+    def _evaluate_thresholds_native(self, *args):
+        from . import sweep
+
+        return sweep.evaluate_thresholds(self, *args)
+
     def evaluate_squares(self, squares: NDArray[np.uint8], labels=None, normalize="train", batch_size: int = 512,
                          embeddings: bool = False):
         """The classifier's validation pass over a table of squares: one call for ``validate()`` and the ``tlc.collect_metrics`` pass

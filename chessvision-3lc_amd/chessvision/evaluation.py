@@ -302,6 +302,143 @@ def segmentation_scores(logits: NDArray[np.float32], label_mask: NDArray[np.uint
                               pixel_accuracy=(x.size - n_pred - n_label + 2 * n_both) / x.size)
 
 
+MAX_THRESHOLDS = 32
+CURVE_KEYS = tuple(k for k in AGGREGATE_KEYS if k != "avg_time_per_prediction") + ("mean_loss", "mean_dice", "mean_iou",
+                                                                                   "mean_pixel_accuracy")
+
+
+def check_thresholds(thresholds) -> NDArray[np.float32]:
+    """The thresholds of a sweep as float32, in the caller's order.  ``ValueError`` for an empty grid, more than ``MAX_THRESHOLDS``
+    values, a value that is NaN or outside [0, 1], or two values equal as float32."""
+    try:
+        t = np.asarray(list(thresholds), dtype=np.float32).reshape(-1)
+    except TypeError:
+        raise ValueError(f"thresholds must be a sequence of numbers, got {thresholds!r}") from None
+    if t.size == 0:
+        raise ValueError("thresholds is empty")
+    if t.size > MAX_THRESHOLDS:
+        raise ValueError(f"at most {MAX_THRESHOLDS} thresholds per sweep, got {t.size}")
+    if not bool(np.all((t >= 0) & (t <= 1))):                # a NaN fails both comparisons
+        raise ValueError(f"every threshold must be in [0, 1], got {[float(v) for v in t]}")
+    if np.unique(t).size != t.size:
+        raise ValueError(f"two thresholds are equal as float32: {[float(v) for v in t]}")
+    return t
+
+
+def threshold_levels(logits, thresholds, label_mask=None):
+    """The numpy form of ``cv_threshold_levels`` and its checker: (N, ...) float32 logits (the first axis counts images, as on the
+    device; a 1-D array is one image), strictly ascending thresholds in [0, 1], optional labels of the same shape ("board" iff
+    non-zero) -> (levels uint8 of the logits' shape, hist (N,2,33) int64, n_nan (N,)).  ``level = #{k: v > thresholds[k]}`` with the float32 sigmoid ``segmentation_scores`` thresholds, so
+    ``levels > k`` is its hard mask at ``thresholds[k]``; ``hist[i, b, l]`` counts image i's pixels at level l whose label is zero
+    (b = 0; every pixel without labels) or non-zero (b = 1).  A single image is treated as N = 1."""
+    x = np.asarray(logits, dtype=np.float32)
+    thr = np.asarray(thresholds, dtype=np.float32).reshape(-1)
+    if not 1 <= thr.size <= MAX_THRESHOLDS or not bool(np.all((thr >= 0) & (thr <= 1))) or not bool(np.all(thr[1:] > thr[:-1])):
+        raise ValueError(f"threshold_levels expects 1..{MAX_THRESHOLDS} strictly ascending thresholds in [0, 1]")
+    if x.size == 0:
+        raise ValueError("threshold_levels expects at least one logit")
+    flat = x.reshape(1, -1) if x.ndim < 2 else x.reshape(x.shape[0], -1)
+    with np.errstate(over="ignore", invalid="ignore"):
+        v = np.float32(1) / (np.float32(1) + np.exp(-flat))
+        levels = np.zeros(flat.shape, dtype=np.uint8)
+        for t in thr:
+            levels += v > t                                   # NaN compares false: level 0
+    if label_mask is None:
+        on = np.zeros(flat.shape, dtype=bool)
+    else:
+        on = np.asarray(label_mask).reshape(flat.shape[0], -1) != 0
+        if on.shape != flat.shape:
+            raise ValueError("threshold_levels expects one label per logit")
+    hist = np.zeros((flat.shape[0], 2, MAX_THRESHOLDS + 1), dtype=np.int64)
+    for i in range(flat.shape[0]):
+        for b in (0, 1):
+            hist[i, b] = np.bincount(levels[i][on[i] == bool(b)], minlength=MAX_THRESHOLDS + 1)
+    return levels.reshape(x.shape), hist, np.isnan(flat).sum(axis=1)
+
+
+def level_counts(hist, n_thresholds: int):
+    """``hist`` (..., 2, 33) of ``threshold_levels`` -> (n_label (...,), n_pred (..., T), n_both (..., T)): the suffix sums that give
+    every threshold's counts, ``n_pred[k] = sum_{l > k} hist[0][l] + hist[1][l]``, ``n_both[k] = sum_{l > k} hist[1][l]``."""
+    h = np.asarray(hist, dtype=np.int64)
+    above = np.flip(np.cumsum(np.flip(h, axis=-1), axis=-1), axis=-1)[..., 1:n_thresholds + 1]   # [..., b, k] = sum_{l > k}
+    return h[..., 1, :].sum(axis=-1), above[..., 0, :] + above[..., 1, :], above[..., 1, :]
+
+
+def plan_threshold_groups(quads):
+    """Which boards a threshold sweep has to warp and classify.  ``quads[k][i]``: image i's quadrangle at threshold k ((4,1,2) int32
+    or None), after the ``fallback_quad`` substitution.  Two quadrangles are the same iff their bytes are equal.  Returns
+    ``(distinct, use, groups)``: ``distinct[i]`` = image i's distinct quadrangles in order of first appearance (over k ascending);
+    ``use[k][i]`` = the index into ``distinct[i]`` that threshold k uses, or None; ``groups[g]`` = [(i, distinct[i][g]) for every image
+    that has a g-th distinct quadrangle, in image order] -- at most one board per image, so a group goes through the warp +
+    classifier stage as one ``found`` subset, and there are at most ``len(quads)`` groups."""
+    n = len(quads[0]) if quads else 0
+    distinct: list[list] = [[] for _ in range(n)]
+    keys: list[dict] = [{} for _ in range(n)]
+    use: list[list] = []
+    for row in quads:
+        if len(row) != n:
+            raise ValueError("plan_threshold_groups expects one quadrangle (or None) per image at every threshold")
+        used = []
+        for i, q in enumerate(row):
+            if q is None:
+                used.append(None)
+                continue
+            a = np.ascontiguousarray(q)
+            key = (a.dtype.str, a.shape, a.tobytes())
+            if key not in keys[i]:
+                keys[i][key] = len(distinct[i])
+                distinct[i].append(q)
+            used.append(keys[i][key])
+        use.append(used)
+    depth = max((len(d) for d in distinct), default=0)
+    groups = [[(i, distinct[i][g]) for i in range(n) if len(distinct[i]) > g] for g in range(depth)]
+    return distinct, use, groups
+
+
+@dataclass
+class ThresholdSweepReport:
+    """What ``ChessVision.evaluate_thresholds`` returns.  ``thresholds`` are the caller's values in the caller's order;
+    ``reports[j]`` is what ``evaluate_images(..., threshold=thresholds[j])`` returns; ``curve[key][j]`` is ``reports[j].aggregate[key]``
+    for every key but ``avg_time_per_prediction``, plus ``mean_pixel_accuracy``.  The reports share arrays (logits always, board,
+    crops and probabilities where the quadrangle is the same): they are views, copy before writing."""
+    thresholds: list
+    reports: list
+    curve: dict = field(default_factory=dict)
+    boards_found: int = 0          # sum over the thresholds of the boards found at each
+    boards_classified: int = 0     # distinct boards actually warped and classified
+
+    def at(self, threshold: float) -> EvaluationReport:
+        """The report of a threshold that was asked for (compared as float32)."""
+        t = np.float32(threshold)
+        for j, v in enumerate(self.thresholds):
+            if np.float32(v) == t:
+                return self.reports[j]
+        raise KeyError(f"threshold {threshold!r} is not one of {self.thresholds}")
+
+    def best(self, key: str = "top_1_accuracy") -> float:
+        """The threshold with the largest ``curve[key]``: the first one on ties, NaN ignored (``ValueError`` when all are NaN)."""
+        values = self.curve[key]
+        best = None
+        for j, v in enumerate(values):
+            if v == v and (best is None or v > values[best]):
+                best = j
+        if best is None:
+            raise ValueError(f"curve[{key!r}] holds no number")
+        return self.thresholds[best]
+
+    @classmethod
+    def from_reports(cls, thresholds, reports, boards_found: int = 0, boards_classified: int = 0) -> "ThresholdSweepReport":
+        curve = {key: [r.aggregate[key] for r in reports] for key in CURVE_KEYS if key != "mean_pixel_accuracy"}
+        curve["mean_pixel_accuracy"] = [_mean_pixel_accuracy(r.evaluations) for r in reports]
+        return cls(thresholds=list(thresholds), reports=list(reports), curve=curve, boards_found=int(boards_found),
+                   boards_classified=int(boards_classified))
+
+
+def _mean_pixel_accuracy(evaluations) -> float:
+    values = [e.segmentation.pixel_accuracy for e in evaluations if e.segmentation is not None]
+    return sum(values) / len(values) if values else math.nan
+
+
 def row_labels(true_labels, flip: bool) -> NDArray[np.int8]:
     """True class indices in a8..h1 order -> the order of the classifier's rows (``square_names``): reversed for a flipped board."""
     t = np.asarray(true_labels, dtype=np.int8)

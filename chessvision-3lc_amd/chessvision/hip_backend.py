@@ -140,6 +140,8 @@ SYMBOLS = [
     ("cv_resnet_forward_u8_norm", _i, [_vp, _vp, _i, _f, _f, _i, _vp, _vp, _vp]),
     ("cv_square_records", _i, [_vp, _vp, _vp, _i, _vp, _vp]),
     ("cv_square_records_finish", _i, [_vp, _i, _i, _vp]),
+    ("cv_threshold_levels", _i, [_vp, _vp, _vp, _i, _i, _fp, _i, _vp, _vp, _vp]),
+    ("cv_threshold_levels_finish", _i, [_vp, _i, _i] + [ctypes.POINTER(ctypes.c_double)] * 3),
 ]
 
 # cv_score_record_t (include/chessvision_hip.h): one 64-byte record per image
@@ -151,6 +153,11 @@ _TRANSFORMS = {"none": 0, "sigmoid": 1}
 SEG_RECORD = np.dtype({"names": ["n_label", "n_pred", "n_both", "n_nan", "bce_sum", "sig_sum", "sig_label_sum", "count", "reserved"],
                        "formats": ["<i4", "<i4", "<i4", "<i4", "<f8", "<f8", "<f8", "<i4", ("<i4", (5,))],
                        "offsets": [0, 4, 8, 12, 16, 24, 32, 40, 44], "itemsize": 64})
+# cv_level_record_t (include/chessvision_hip.h): one 320-byte record per image, CV_MAX_THRESHOLDS = 32
+MAX_THRESHOLDS = 32
+LEVEL_RECORD = np.dtype({"names": ["count", "n_thresholds", "n_nan", "hist", "reserved"],
+                         "formats": ["<i4", "<i4", "<i4", ("<i4", (2, MAX_THRESHOLDS + 1)), ("<i4", (11,))],
+                         "offsets": [0, 4, 8, 12, 276], "itemsize": 320})
 SQUARE_SCORE = np.dtype({"names": ["predicted", "rank", "confidence", "reserved", "loss"],
                          "formats": ["<i4", "<i4", "<f4", "<i4", "<f8"], "offsets": [0, 4, 8, 12, 16], "itemsize": 24})
 BOARD_SCORE = np.dtype({"names": ["hits", "n_nan", "mean_loss"], "formats": [("<i4", (13,)), "<i4", "<f8"],
@@ -310,6 +317,23 @@ def segmentation_scores_finish(records: np.ndarray) -> dict:
     dp = ctypes.POINTER(ctypes.c_double)
     if r.size:
         _check(lib.cv_segmentation_scores_finish(r.ctypes.data_as(_vp), int(r.size), *(out[k].ctypes.data_as(dp) for k in names)))
+    return out
+
+
+def threshold_levels_finish(records: np.ndarray, labels_present: bool = True) -> dict:
+    """(N,) ``LEVEL_RECORD`` array -> {"dice", "iou", "pixel_accuracy"}: (N,T) float64 arrays, column k = the score of
+    ``segmentation_scores_finish`` at the k-th (ascending) threshold (``cv_threshold_levels_finish``)."""
+    lib = load_library()
+    r = np.ascontiguousarray(records, dtype=LEVEL_RECORD).reshape(-1)
+    t = int(r["n_thresholds"][0]) if r.size else 0
+    names = ("dice", "iou", "pixel_accuracy")
+    out = {k: np.zeros((r.size, max(t, 0)), dtype=np.float64) for k in names}
+    dp = ctypes.POINTER(ctypes.c_double)
+    if r.size:
+        if not 1 <= t <= MAX_THRESHOLDS:
+            raise HipBackendError(f"threshold_levels_finish: a record claims {t} thresholds")
+        _check(lib.cv_threshold_levels_finish(r.ctypes.data_as(_vp), int(r.size), 1 if labels_present else 0,
+                                              *(out[k].ctypes.data_as(dp) for k in names)))
     return out
 
 
@@ -754,6 +778,36 @@ class HipEngine:
         stream."""
         rec = self.segmentation_scores_dev(logits, labels, threshold).cpu().numpy().view(SEG_RECORD).reshape(-1)
         return rec, segmentation_scores_finish(rec)
+
+    def threshold_levels_dev(self, logits: torch.Tensor, thresholds, labels: torch.Tensor | None = None):
+        """The device half of ``threshold_levels``: launches the levels kernel on the current stream behind whatever produced
+        ``logits`` ((N, ...) float32 on this device, contiguous).  ``thresholds``: 1..32 values in [0, 1], strictly ascending as
+        float32; ``labels``: uint8 on this device, one byte per logit, contiguous ("board" iff non-zero), or None.  Returns (levels
+        (N,count) uint8, records (N,320) uint8) device tensors: ``levels > k`` is the mask at ``thresholds[k]``.  Nothing is
+        synchronised or copied."""
+        if not isinstance(logits, torch.Tensor) or logits.dtype != torch.float32 or logits.device != self.device or logits.dim() < 1:
+            raise HipBackendError("threshold_levels expects an (N, ...) float32 logits tensor on the engine's device")
+        n = int(logits.shape[0])
+        count = int(logits.numel() // n) if n else 0
+        if labels is not None:
+            if not isinstance(labels, torch.Tensor) or labels.dtype != torch.uint8 or labels.device != self.device or labels.dim() < 1:
+                raise HipBackendError("threshold_levels expects an (N, ...) uint8 label tensor on the engine's device, or None")
+            if int(labels.shape[0]) != n or labels.numel() != logits.numel():
+                raise HipBackendError("threshold_levels expects one label byte per logit")
+        if n and not (logits.is_contiguous() and (labels is None or labels.is_contiguous())):
+            raise HipBackendError("threshold_levels expects contiguous images")
+        thr = np.ascontiguousarray(np.asarray(thresholds, dtype=np.float32).reshape(-1))   # checked by the C entry, before any launch
+        levels = torch.empty((n, count), dtype=torch.uint8, device=self.device)
+        records = torch.empty((n, LEVEL_RECORD.itemsize), dtype=torch.uint8, device=self.device)
+        _check(self._lib.cv_threshold_levels(self._h, _ptr(logits), _ptr(labels) if labels is not None else None, n, count,
+                                             thr.ctypes.data_as(_fp), int(thr.size), _ptr(levels), _ptr(records),
+                                             _stream_ptr(self.device)))
+        return levels, records
+
+    def threshold_levels(self, logits: torch.Tensor, thresholds, labels: torch.Tensor | None = None):
+        """-> (levels (N,count) uint8, records (N,) ``LEVEL_RECORD``) as numpy.  Synchronises the current stream."""
+        levels, records = self.threshold_levels_dev(logits, thresholds, labels)
+        return levels.cpu().numpy(), records.cpu().numpy().view(LEVEL_RECORD).reshape(-1)
 
     def softmax13(self, logits: torch.Tensor) -> torch.Tensor:
         logits = logits.to(self.device, torch.float32).contiguous()

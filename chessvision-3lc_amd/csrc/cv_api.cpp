@@ -23,6 +23,9 @@ static_assert(sizeof(cv_seg_record_t) == sizeof(cv::SegRecord) && offsetof(cv_se
               offsetof(cv_seg_record_t, count) == offsetof(cv::SegRecord, count), "cv_seg_record_t is the kernel's record");
 static_assert(sizeof(cv_square_record_t) == sizeof(cv::SquareRecord) && offsetof(cv_square_record_t, confidence) == offsetof(cv::SquareRecord, confidence) &&
               offsetof(cv_square_record_t, logsumexp) == offsetof(cv::SquareRecord, logsumexp), "cv_square_record_t is the kernel's record");
+static_assert(sizeof(cv_level_record_t) == sizeof(cv::LevelRecord) && sizeof(cv_level_record_t) % 64 == 0 && CV_MAX_THRESHOLDS == cv::kMaxLevelThresholds &&
+              offsetof(cv_level_record_t, hist) == offsetof(cv::LevelRecord, hist) && offsetof(cv_level_record_t, reserved) == offsetof(cv::LevelRecord, reserved),
+              "cv_level_record_t is the kernel's record");
 static_assert(sizeof(cv_square_score_t) == 24 && sizeof(cv_board_score_t) == 64, "layouts the Python binding mirrors");
 
 using namespace cv;
@@ -210,6 +213,15 @@ Status mask_completenesses(const uint8_t* masks, int n, int h, int w, double* sc
 double dice_of(double inter, double sets_sum) {
     if (sets_sum == 0.0) sets_sum = 2.0 * inter;
     return (2.0 * inter + 1e-6) / (sets_sum + 1e-6);
+}
+
+// Dice, IoU and pixel accuracy of a thresholded mask against a label mask, from their integer counts (the formulas documented at
+// cv_segmentation_scores_finish; cv_threshold_levels_finish applies them per threshold).  Any output may be null.
+void hard_mask_scores(long long n_label, long long n_pred, long long n_both, long long count, double* dice, double* iou, double* pixel_accuracy) {
+    const long long uni = n_pred + n_label - n_both;
+    if (dice) *dice = dice_of((double)n_both, (double)n_pred + (double)n_label);
+    if (iou) *iou = uni == 0 ? 1.0 : (double)n_both / (double)uni;
+    if (pixel_accuracy) *pixel_accuracy = (double)(count - n_pred - n_label + 2LL * n_both) / (double)count;
 }
 
 // INTER_AREA on `st` with the engine's cached tables for fractional shrinks (caller holds the engine mutex)
@@ -1084,13 +1096,60 @@ int cv_segmentation_scores_finish(const cv_seg_record_t* records, int n, double*
             if (r.count < 1) return fail(CV_ERR_INVALID, "cv_segmentation_scores_finish: record " + std::to_string(i) + " has no pixels");
             const double b = r.bce_sum / (double)r.count;
             const double dl = 1.0 - dice_of(r.sig_label_sum, r.sig_sum + (double)r.n_label);
-            const long long uni = (long long)r.n_pred + r.n_label - r.n_both;
             if (bce) bce[i] = b;
             if (dice_loss) dice_loss[i] = dl;
             if (loss) loss[i] = dl + b;
-            if (dice) dice[i] = dice_of((double)r.n_both, (double)r.n_pred + (double)r.n_label);
-            if (iou) iou[i] = uni == 0 ? 1.0 : (double)r.n_both / (double)uni;
-            if (pixel_accuracy) pixel_accuracy[i] = (double)((long long)r.count - r.n_pred - r.n_label + 2LL * r.n_both) / (double)r.count;
+            hard_mask_scores(r.n_label, r.n_pred, r.n_both, r.count, dice ? dice + i : nullptr, iou ? iou + i : nullptr,
+                             pixel_accuracy ? pixel_accuracy + i : nullptr);
+        }
+        return Status();
+    });
+}
+
+int cv_threshold_levels(cv_engine_t* eng, const float* logits, const uint8_t* labels, int n, int count, const float* thresholds,
+                        int n_thresholds, uint8_t* levels, cv_level_record_t* records, void* stream) {
+    return guarded("cv_threshold_levels", [&]() -> Status {
+        CV_TRY(check_engine(eng));
+        if (!logits || !thresholds || !levels || !records) return fail(CV_ERR_INVALID, "cv_threshold_levels: null tensor");
+        if (((uintptr_t)logits & 3u) || ((uintptr_t)records & 3u)) return fail(CV_ERR_INVALID, "cv_threshold_levels: logits and records must be 4-byte aligned");
+        if (n < 1) return fail(CV_ERR_INVALID, "cv_threshold_levels: n must be at least 1");
+        if (count < 1 || count > (1 << 24)) return fail(CV_ERR_INVALID, "cv_threshold_levels: count must be in [1, 2^24]");
+        if (n_thresholds < 1 || n_thresholds > CV_MAX_THRESHOLDS)
+            return fail(CV_ERR_INVALID, "cv_threshold_levels: n_thresholds must be in [1, " + std::to_string(CV_MAX_THRESHOLDS) + "]");
+        for (int k = 0; k < n_thresholds; ++k) {
+            if (!(thresholds[k] >= 0.f && thresholds[k] <= 1.f))
+                return fail(CV_ERR_INVALID, "cv_threshold_levels: threshold " + std::to_string(k) + " is not in [0, 1]");
+            if (k > 0 && !(thresholds[k] > thresholds[k - 1]))
+                return fail(CV_ERR_INVALID, "cv_threshold_levels: thresholds must be strictly ascending (entry " + std::to_string(k) + ")");
+        }
+        DeviceGuard g(eng->impl.device);
+        hipError_t e = threshold_levels(logits, labels, n, count, thresholds, n_thresholds, levels, reinterpret_cast<LevelRecord*>(records),
+                                        (hipStream_t)stream);
+        if (e != hipSuccess) return hip_fail(e, "threshold_levels");
+        return Status();
+    });
+}
+
+int cv_threshold_levels_finish(const cv_level_record_t* records, int n, int labels_present, double* dice, double* iou,
+                               double* pixel_accuracy) {
+    return guarded("cv_threshold_levels_finish", [&]() -> Status {
+        if (n < 0 || (n > 0 && !records)) return fail(CV_ERR_INVALID, "cv_threshold_levels_finish: bad argument");
+        for (int i = 0; i < n; ++i) {
+            const cv_level_record_t& r = records[i];
+            const int T = records[0].n_thresholds;
+            if (r.count < 1) return fail(CV_ERR_INVALID, "cv_threshold_levels_finish: record " + std::to_string(i) + " has no pixels");
+            if (T < 1 || T > CV_MAX_THRESHOLDS || r.n_thresholds != T)
+                return fail(CV_ERR_INVALID, "cv_threshold_levels_finish: record " + std::to_string(i) + " is not of the same threshold grid");
+            long long n_label = 0, n_pred = 0, n_both = 0;
+            if (labels_present)
+                for (int l = 0; l <= T; ++l) n_label += r.hist[1][l];
+            for (int k = T - 1; k >= 0; --k) {                // suffix sums: level k + 1 joins the mask at thresholds[k]
+                n_pred += (long long)r.hist[0][k + 1] + r.hist[1][k + 1];
+                if (labels_present) n_both += r.hist[1][k + 1];
+                const size_t at = (size_t)i * T + k;
+                hard_mask_scores(n_label, n_pred, n_both, r.count, dice ? dice + at : nullptr, iou ? iou + at : nullptr,
+                                 pixel_accuracy ? pixel_accuracy + at : nullptr);
+            }
         }
         return Status();
     });

@@ -96,6 +96,25 @@ static_assert(sizeof(SegRecord) == 64, "one 64-byte record per image");
 hipError_t segmentation_scores(const float* logits, const uint8_t* labels, int n, int count, float threshold, SegRecord* records,
                                hipStream_t s);
 
+// Threshold levels: every mask of a threshold grid and every grid point's segmentation counts from one sweep over the logits (the
+// reference sweeps `--threshold`, scripts/eval/evaluate.py, scripts/plot_sweep.py).  logits: n images of `count` contiguous float32
+// (4-byte aligned, 1 <= count <= 2^24); labels: n x count uint8, any alignment, "board" iff non-zero, or null = no labels;
+// thresholds: n_thresholds float32 on the HOST (read before the call returns), in [0, 1], strictly ascending, 1 <= n_thresholds <= 32.
+//   levels[i]   #{k : v > thresholds[k]}, v = 1 / (1 + __expf(-x)) (outc_1x1's mask expression): the mask at thresholds[k] is
+//               (level > k); a NaN logit gives 0.  n x count uint8, any alignment.
+//   record      hist[b][l] = pixels at level l whose label byte is zero (b = 0; all pixels without labels) / non-zero (b = 1)
+// Integer counts only: bit-identical run to run.  Asynchronous on `s`; allocates nothing.
+constexpr int kMaxLevelThresholds = 32;
+struct LevelThresholds { float t[kMaxLevelThresholds]; };
+struct LevelRecord {
+    int32_t count, n_thresholds, n_nan;
+    int32_t hist[2][kMaxLevelThresholds + 1];
+    int32_t reserved[11];
+};
+static_assert(sizeof(LevelRecord) == 320, "one 320-byte record per image");
+hipError_t threshold_levels(const float* logits, const uint8_t* labels, int n, int count, const float* thresholds, int n_thresholds,
+                            uint8_t* levels, LevelRecord* records, hipStream_t s);
+
 // Per-square records of the classifier's validation pass (train_classifier.py: validate(), the classification collector).  logits:
 // n rows of 13 float32 on the device; labels: n int8 on the device (0..12, -1 = unlabelled), or null = all unlabelled.  One thread per
 // row, everything in float32 with expf / logf, sums in ascending class order.  The fields are documented at cv_square_record_t

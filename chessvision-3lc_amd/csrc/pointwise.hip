@@ -1383,6 +1383,93 @@ __global__ __launch_bounds__(kScoreThreads) void segmentation_scores_kernel(cons
     }
 }
 
+// ---- threshold levels: every mask of an ascending threshold grid, and every grid point's counts, from one sweep -------------------
+// level = #{k : v > thr[k]} with v = score_value<1>(x), the mask expression of outc_1x1_kernel; the thresholds ascend, so the mask
+// at thr[k] is (level > k) and one byte per pixel carries all of them.  One workgroup of 16 waves per image, score_sweep's head /
+// body / tail; label bytes come in and level bytes go out four at a time where the image's byte stream is aligned at the body.  The
+// level is a data-dependent index, so the histogram [label != 0][level] lives in LDS: private to a wave, in kLevelReps copies chosen
+// by the lane's low bits (a crisp mask sends most lanes of a wave to ONE bin; an LDS add to one address serialises over its lanes),
+// rows one word longer than the bins so that the copies start in different banks.  Integer LDS adds only, copies and waves summed
+// at the end: a record is bit-identical run to run.  The thresholds are wave-uniform LDS reads (broadcast).
+constexpr int kLevelReps = 8, kLevelBins = 2 * (kMaxLevelThresholds + 1), kLevelRow = kLevelBins + 1;
+
+__global__ __launch_bounds__(kScoreThreads) void threshold_levels_kernel(const float* __restrict__ logits,
+                                                                         const uint8_t* __restrict__ labels, int count,
+                                                                         LevelThresholds thr, int nthr, uint8_t* __restrict__ levels,
+                                                                         LevelRecord* __restrict__ records) {
+    __shared__ int whist[kScoreWaves][kLevelReps][kLevelRow];
+    __shared__ int wnan[kScoreWaves];
+    __shared__ float sthr[kMaxLevelThresholds];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const float* img = logits + (size_t)blockIdx.x * count;
+    const uint8_t* lab = labels ? labels + (size_t)blockIdx.x * count : nullptr;
+    uint8_t* lev = levels + (size_t)blockIdx.x * count;
+    const int head = min(count, (int)(((16u - (unsigned)((uintptr_t)img & 15u)) & 15u) >> 2));
+    const int nvec = (count - head) >> 2;
+    const bool lab4 = lab && (((uintptr_t)(lab + head)) & 3u) == 0;
+    const bool lev4 = (((uintptr_t)(lev + head)) & 3u) == 0;
+    for (int i = tid; i < kScoreWaves * kLevelReps * kLevelRow; i += kScoreThreads) (&whist[0][0][0])[i] = 0;
+#pragma unroll
+    for (int k = 0; k < kMaxLevelThresholds; ++k)
+        if (tid == k) sthr[k] = thr.t[k];                     // constant indices: the by-value argument stays in the kernel-argument segment
+    __syncthreads();
+    int* myhist = whist[wave][lane & (kLevelReps - 1)];
+    int nan = 0;
+    score_sweep<1>(img, count, head, nvec, [&](const float* v, auto M, int at) {
+        constexpr int m = decltype(M)::value;
+        uint8_t t[m], out[m];
+        bool loaded = false;
+        if constexpr (m == 4) {
+            if (lab4) {
+                const uchar4 q = *reinterpret_cast<const uchar4*>(lab + at);
+                t[0] = q.x; t[1] = q.y; t[2] = q.z; t[3] = q.w;
+                loaded = true;
+            }
+        }
+        if (!loaded) {
+#pragma unroll
+            for (int j = 0; j < m; ++j) t[j] = lab ? lab[at + j] : (uint8_t)0;
+        }
+#pragma unroll
+        for (int j = 0; j < m; ++j) {
+            const float x = v[j];
+            int level = 0;
+            for (int k = 0; k < nthr; ++k) level += x > sthr[k];          // a NaN compares false everywhere: level 0, as the fused mask
+            nan += x != x;
+            out[j] = (uint8_t)level;
+            atomicAdd(&myhist[(t[j] != 0 ? kMaxLevelThresholds + 1 : 0) + level], 1);
+        }
+        bool stored = false;
+        if constexpr (m == 4) {
+            if (lev4) { *reinterpret_cast<uchar4*>(lev + at) = make_uchar4(out[0], out[1], out[2], out[3]); stored = true; }
+        }
+        if (!stored) {
+#pragma unroll
+            for (int j = 0; j < m; ++j) lev[at + j] = out[j];
+        }
+    });
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) nan += __shfl_down(nan, d);
+    if (lane == 0) wnan[wave] = nan;
+    __syncthreads();
+    LevelRecord* r = records + blockIdx.x;
+    if (tid < kLevelBins) {
+        int s = 0;
+        for (int w = 0; w < kScoreWaves; ++w)
+#pragma unroll
+            for (int c = 0; c < kLevelReps; ++c) s += whist[w][c][tid];
+        (&r->hist[0][0])[tid] = s;
+    } else if (tid < kLevelBins + (int)(sizeof(r->reserved) / sizeof(int32_t))) {
+        r->reserved[tid - kLevelBins] = 0;
+    } else if (tid == kScoreThreads - 1) {
+        int s = 0;
+        for (int w = 0; w < kScoreWaves; ++w) s += wnan[w];
+        r->count = count;
+        r->n_thresholds = nthr;
+        r->n_nan = s;
+    }
+}
+
 // ---- MFMA lane-map probes (same fragment addressing as conv_igemm.hip) ---------------------------
 __global__ void mfma_probe_f16_kernel(const half_t* a, const half_t* b, float* d) {
     const int lane = threadIdx.x, q = lane >> 4, r = lane & 15;
@@ -1564,6 +1651,20 @@ hipError_t segmentation_scores(const float* logits, const uint8_t* labels, int n
     if (!logits || !labels || !records || n < 1 || count < 1 || count > (1 << 24) || ((uintptr_t)logits & 3u) || !(threshold - threshold == 0.f))
         return hipErrorInvalidValue;
     hipLaunchKernelGGL(segmentation_scores_kernel, dim3((unsigned)n), dim3(kScoreThreads), 0, s, logits, labels, count, threshold, records);
+    return hipGetLastError();
+}
+hipError_t threshold_levels(const float* logits, const uint8_t* labels, int n, int count, const float* thresholds, int n_thresholds,
+                            uint8_t* levels, LevelRecord* records, hipStream_t s) {
+    if (!logits || !thresholds || !levels || !records || n < 1 || count < 1 || count > (1 << 24) || ((uintptr_t)logits & 3u) ||
+        ((uintptr_t)records & 3u) || n_thresholds < 1 || n_thresholds > kMaxLevelThresholds)
+        return hipErrorInvalidValue;
+    LevelThresholds thr;
+    for (int k = 0; k < kMaxLevelThresholds; ++k) {
+        thr.t[k] = k < n_thresholds ? thresholds[k] : 2.f;    // past the grid: above every sigmoid, never read
+        if (k < n_thresholds && (!(thr.t[k] >= 0.f && thr.t[k] <= 1.f) || (k > 0 && !(thr.t[k] > thr.t[k - 1])))) return hipErrorInvalidValue;
+    }
+    hipLaunchKernelGGL(threshold_levels_kernel, dim3((unsigned)n), dim3(kScoreThreads), 0, s, logits, labels, count, thr, n_thresholds,
+                       levels, records);
     return hipGetLastError();
 }
 hipError_t softmax13(const float* logits, int n, float* probs, hipStream_t s) {

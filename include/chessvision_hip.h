@@ -453,6 +453,37 @@ typedef struct cv_board_score {
 int cv_classification_scores(const float* probs, const int8_t* labels, int n_boards, cv_square_score_t* per_square,
                              cv_board_score_t* per_board);
 
+/* ---- threshold sweep (additions under ABI 6; detect with dlsym(handle, "cv_threshold_levels")) -------------------------------- */
+/* The mask threshold is the inference-side hyperparameter the reference sweeps (scripts/eval/evaluate.py --threshold,
+ * scripts/plot_sweep.py).  Nothing in the UNet depends on it: one pass over the logits gives every threshold's mask and counts.
+ *
+ * cv_threshold_levels: logits = n images of `count` contiguous float32 (DEVICE, 4-byte aligned; 1 <= count <= 2^24, n >= 1); labels =
+ * n x count uint8 (DEVICE, any alignment, "board" iff non-zero) or NULL = no labels; thresholds = n_thresholds float32 on the HOST
+ * (they are read and checked before the call returns and travel as a kernel argument: 1 <= n_thresholds <= CV_MAX_THRESHOLDS, every
+ * value in [0, 1], strictly ascending as float32; CV_ERR_INVALID otherwise); levels = n x count uint8 (DEVICE, any alignment);
+ * records = n records (DEVICE, 4-byte aligned).
+ *   level = #{k : v > thresholds[k]}, v = 1 / (1 + exp(-x)) in the float32 expression of the UNet's mask.  The thresholds ascend, so
+ *   (level > k) * 255 == the mask cv_unet_forward_u8 writes at thresholds[k], byte for byte; a NaN logit gives level 0.
+ * Asynchronous on `stream`; allocates nothing and synchronises nothing.  Integer counts only: bit-identical run to run. */
+#define CV_MAX_THRESHOLDS 32
+typedef struct cv_level_record {            /* 320 bytes */
+    int32_t count;
+    int32_t n_thresholds;
+    int32_t n_nan;                          /* NaN logits */
+    int32_t hist[2][CV_MAX_THRESHOLDS + 1]; /* hist[b][l]: pixels at level l whose label byte is zero (b = 0; every pixel when there
+                                               are no labels) or non-zero (b = 1).  At thresholds[k]:
+                                               n_pred = sum_{l > k} hist[0][l] + hist[1][l], n_both = sum_{l > k} hist[1][l],
+                                               n_label = sum_l hist[1][l] */
+    int32_t reserved[11];                   /* 0; pads the record to a multiple of 64 bytes */
+} cv_level_record_t;
+int cv_threshold_levels(cv_engine_t* eng, const float* logits, const uint8_t* labels, int n, int count, const float* thresholds,
+                        int n_thresholds, uint8_t* levels, cv_level_record_t* records, void* stream);
+/* Records (HOST) -> dice, iou and pixel_accuracy of cv_segmentation_scores_finish for every (image, threshold): n x T doubles each,
+ * row i = image i, T = the records' n_thresholds (all equal, CV_ERR_INVALID otherwise); any output may be NULL.  labels_present == 0:
+ * the scores are those against an empty label mask.  Needs no GPU and no engine. */
+int cv_threshold_levels_finish(const cv_level_record_t* records, int n, int labels_present, double* dice, double* iou,
+                               double* pixel_accuracy);
+
 /* ---- square-set evaluation (additions under ABI 6; detect with dlsym(handle, "cv_square_records")) ----------------------------- */
 /* The classifier's own batched caller in the reference, scripts/train/train_classifier.py: validate() (:90-111, CrossEntropyLoss and
  * accuracy over a table of labelled 64 x 64 squares) and the tlc.collect_metrics pass (:274-292, batch 512) behind val_transforms
