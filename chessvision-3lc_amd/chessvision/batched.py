@@ -14,10 +14,9 @@ hardware queue at its first use); everything else here lives for one call.
 """
 from __future__ import annotations
 
-import contextlib
 import time
 from concurrent.futures import ThreadPoolExecutor
-from dataclasses import dataclass
+from dataclasses import dataclass, field
 from typing import Sequence
 
 import numpy as np
@@ -54,17 +53,31 @@ def plan_jobs(shapes: Sequence[tuple], pipeline_chunk: int, first: int, last: in
 
 
 @dataclass(slots=True)
+class Boards:
+    """One warp + classifier launch of a job (``_Call.warp_and_classify``): ``process_images`` makes one per job, from the positions
+    that have a quadrangle; a threshold sweep one per group of distinct quadrangles."""
+    found: list[int]                            # positions within the job
+    quads: list                                 # their quadrangles in photo pixels
+    boards: torch.Tensor | None = None          # pinned (found,512,512) u8
+    probs: torch.Tensor | None = None           # pinned (found*64,13) f32
+    cls_emb: torch.Tensor | None = None         # pinned (found*64,512) f32 classifier embeddings, ``embeddings`` only (behind probs_ready)
+    probs_ready: torch.cuda.Event | None = None     # download stream: boards and probabilities have landed
+
+
+@dataclass(slots=True)
 class Job:
     """One job on its way through upload -> compute -> classify -> finish.
 
     Lifetime invariant: a device tensor written on one stream and read by a copy on ANOTHER stream stays referenced from the job
     until the event recorded behind that copy has been synchronised -- otherwise the caching allocator, which orders reuse against
     the allocating stream only, may hand its memory to a later job while the copy still reads it.  ``unet_out`` (read by the
-    download stream up to ``logits_ready``) and ``cls_out`` (up to ``probs_ready``) exist for nothing else; ``release`` drops them
-    once ``finish`` has synchronised both events.  ``batch`` is written by the upload stream and read by the compute stream: it is
-    handed over with ``record_stream`` and dropped as soon as its last kernel (the warp) is queued; ``labels`` (the label masks of
-    an evaluation call) likewise, dropped behind the segmentation-score kernel.  The embeddings of an ``embeddings=True`` call ride in
-    ``unet_out`` / ``cls_out`` like every other device tensor the download stream reads."""
+    download stream up to ``logits_ready``; set by ``_Call.send_back`` alone) and ``cls_out`` (one entry per ``Boards`` record of
+    ``boards``, each read up to that record's ``probs_ready``; appended by ``_Call.warp_and_classify`` alone) exist for nothing else;
+    ``release`` drops them once ``finish`` has synchronised ``logits_ready`` and every record's ``probs_ready``.  ``batch`` is written
+    by the upload stream and read by the compute stream: it is handed over with ``record_stream`` and dropped as soon as its last
+    kernel (the last warp) is queued; ``labels`` (the label masks of an evaluation call) likewise, dropped behind the
+    segmentation-score kernel.  The embeddings of an ``embeddings=True`` call and the level map and records of a threshold sweep ride
+    in ``unet_out`` / ``cls_out`` like every other device tensor the download stream reads."""
     ids: list[int]
     # upload
     staged: torch.Tensor | None = None          # pinned source of the upload
@@ -74,27 +87,24 @@ class Job:
     arrived: torch.cuda.Event | None = None     # upload stream: the batch (and the label masks) are there
     # compute
     unet_done: torch.cuda.Event | None = None   # compute stream: UNet (and scores) queued up to here; gates the upload two jobs on
-    unet_out: tuple | None = None               # device: logits, masks, score records, segmentation records -- held for the download stream
-    masks: torch.Tensor | None = None           # pinned (n,256,256) u8
+    unet_out: tuple | None = None               # device: logits, masks (or level map), every record -- held for the download stream
+    masks: torch.Tensor | None = None           # pinned (n,256,256) u8: the masks, or the level map of a threshold sweep
     logits: torch.Tensor | None = None          # pinned (n,256,256) f32
     records: torch.Tensor | None = None         # pinned (n,64) u8 score records, ``quality`` only
     half: torch.Tensor | None = None            # pinned (n,256,256) u8 ``v > 0.5`` masks, ``quality`` only
+    level_records: torch.Tensor | None = None   # pinned (n,320) u8 level records, threshold sweep only
     seg_records: torch.Tensor | None = None     # pinned (n,64) u8 segmentation-score records, evaluation only
     unet_emb: torch.Tensor | None = None        # pinned (n,C) f32 bottleneck embeddings, ``embeddings`` only (behind logits_ready)
     masks_ready: torch.cuda.Event | None = None     # download stream: masks have landed
-    logits_ready: torch.cuda.Event | None = None    # download stream: logits (and records, half) have landed
+    logits_ready: torch.cuda.Event | None = None    # download stream: logits (and every record, half) have landed
     # classify
-    quads: list | None = None                   # per image: quadrangle in photo pixels or None
-    found: list[int] | None = None              # positions within the job that have one
     quality: list[ExtractionQuality] | None = None
-    cls_out: tuple | None = None                # device: probabilities, boards, squares -- held for the download stream
-    boards: torch.Tensor | None = None          # pinned (found,512,512) u8
-    probs: torch.Tensor | None = None           # pinned (found*64,13) f32
-    cls_emb: torch.Tensor | None = None         # pinned (found*64,512) f32 classifier embeddings, ``embeddings`` only (behind probs_ready)
-    probs_ready: torch.cuda.Event | None = None     # download stream: boards and probabilities have landed
+    cls_out: list | None = None                 # device, per ``Boards`` record: probabilities, boards, squares -- held for the download stream
+    boards: list[Boards] = field(default_factory=list)
+    sweep: object | None = None                 # what a threshold sweep keeps between classify and finish (sweep.py); host arrays only
 
     def release(self) -> None:
-        self.batch = self.labels = self.unet_out = self.cls_out = None
+        self.batch = self.labels = self.unet_out = self.cls_out = self.sweep = None
 
 
 @dataclass(slots=True)
@@ -114,11 +124,41 @@ def _pinned(shape, dtype):
     return torch.empty(shape, dtype=dtype, pin_memory=True)
 
 
+def score_positions(ids, found, probs, validated, fix_lists, true, flip) -> list:
+    """The probabilities of one ``Boards`` record against the true placements (one native call): board j shows image
+    ``ids[found[j]]``, ``true[i]`` holds image i's class indices in a8..h1 order or None, and row i of a board is compared with the
+    true piece on ``square_names[i]``.  Returns one ``PositionScores`` per board, None for a board without a true placement."""
+    from .evaluation import PositionScores, row_labels
+
+    out: list = [None] * len(found)
+    sel = [j for j, k in enumerate(found) if true[ids[k]] is not None]
+    if not sel:
+        return out
+    rows = np.stack([row_labels(true[ids[found[j]]], flip) for j in sel])
+    per_square, per_board = classification_scores(probs[sel], rows)
+    # once per record: the columns as arrays of their own (the scores below hold rows of them), the accuracies as lists
+    predicted, valid = per_square["predicted"].astype(np.int8), validated[sel]
+    rank, conf, loss = (np.ascontiguousarray(per_square[name]) for name in ("rank", "confidence", "loss"))
+    top = (per_board["hits"][:, :3] / 64).tolist()
+    acc_o = (np.count_nonzero(predicted == rows, axis=1) / 64).tolist()
+    acc_v = (np.count_nonzero(valid == rows, axis=1) / 64).tolist()
+    mean_loss = per_board["mean_loss"].tolist()
+    for m, j in enumerate(sel):
+        out[j] = PositionScores(
+            top_k=tuple(top[m]), accuracy_original=acc_o[m], accuracy_validated=acc_v[m], mean_loss=mean_loss[m],
+            num_fixes=len(fix_lists[j]), true_labels=rows[m], predicted_labels=predicted[m], validated_labels=valid[m],
+            rank=rank[m], confidence=conf[m], loss=loss[m])
+    return out
+
+
 class _Call:
-    """The state one ``process_images`` call shares between its stages.  The compute stream is the CURRENT stream."""
+    """The state one ``process_images`` call shares between its stages.  ``run`` makes the compute stream ``main`` the current one."""
 
     def __init__(self, cv, images, threshold, flip, fallback_quad, return_crops, timings, quality, started, targets=None,
                  embeddings=False, resize="area"):
+        for image in images:
+            assert isinstance(image, np.ndarray) and image.dtype == np.uint8 and image.ndim == 3
+        _ = cv.board_extractor, cv.classifier
         self.cv, self.images, self.started = cv, images, started
         self.resize = resize                             # "area" | "antialias": how a photo becomes the UNet's input (forward)
         self.targets = targets                           # evaluation.Targets of an evaluate_images call, else None
@@ -127,8 +167,13 @@ class _Call:
         self.eng, self.eng_cls, self.dev = cv._get_engine("unet"), cv._get_engine("resnet18"), cv.device
         self.names = constants.SQUARE_NAMES_FLIPPED if flip else constants.SQUARE_NAMES_NORMAL
         self.n_host = host_threads()
-        self.main = torch.cuda.current_stream(self.dev)
-        self.up, self.down = cv._pipeline_streams()[:2]
+        # A caller that chose no stream gets the instance's own compute stream, not the NULL stream: kernels queued on the legacy
+        # stream from one thread while other threads load models / run request slots was one of the two ingredients of the device
+        # faults of the round-6 soak (profiles/r06_tuning.md section 8).  Everything the call returns has been waited for through
+        # events when it ends, so nothing is left to order against the caller's stream.
+        self.up, self.down, own = cv._pipeline_streams()
+        current = torch.cuda.current_stream(self.dev)
+        self.main = own if current == torch.cuda.default_stream(self.dev) else current
         if cv._copy_pool is None:
             cv._copy_pool = ThreadPoolExecutor(max_workers=min(16, self.n_host), thread_name_prefix="cv-stage")
         self.pool = cv._copy_pool
@@ -203,27 +248,62 @@ class _Call:
             job.arrived.record()
         return job
 
-    def forward(self, batch):
-        """The photos of one job -> (logits, mask, embedding | None) in the call's resize mode: "area" is INTER_AREA to bytes and the
-        u8 UNet entry (``process_image``'s arithmetic, reference core.py:212); "antialias" is the antialiased bilinear resize to
+    def forward(self, batch, want_mask=True):
+        """The photos of one job -> (logits, mask | None, embedding | None) in the call's resize mode: "area" is INTER_AREA to bytes and
+        the u8 UNet entry (``process_image``'s arithmetic, reference core.py:212); "antialias" is the antialiased bilinear resize to
         float32 NCHW and the float UNet entry (the enrichment job's arithmetic, process_pipeline.py:340-344).  Two engine calls either
-        way, under the same two timing keys."""
+        way, under the same two timing keys.  ``want_mask=False`` (a threshold sweep) leaves the fused mask out."""
         eng, size = self.eng, (constants.INPUT_SIZE[1], constants.INPUT_SIZE[0])
         if self.resize == "antialias":
             small, unet = self.gpu_timed("resize_ms", eng.resize_antialias_f32, batch, size), eng.unet_forward_mask
         else:
             small, unet = self.gpu_timed("resize_ms", eng.resize_area_u8, batch, size), eng.unet_forward_u8
-        if self.embeddings:                              # the same forward plus one pooling launch per chunk, inside unet_ms
-            return self.gpu_timed("unet_ms", unet, small, threshold=self.threshold, want_mask=True, want_embedding=True)
-        lg, mk = self.gpu_timed("unet_ms", unet, small, threshold=self.threshold, want_mask=True)
-        return lg, mk, None
+        # with embeddings: the same forward plus one pooling launch per chunk, inside unet_ms.  The keywords are pinned by
+        # tests/test_resize_antialias_cpu.py: a masked forward names want_embedding only when it is on
+        kw = {} if want_mask and not self.embeddings else {"want_embedding": self.embeddings}
+        out = self.gpu_timed("unet_ms", unet, small, threshold=self.threshold, want_mask=want_mask, **kw)
+        return out[0], out[1], (out[2] if self.embeddings else None)
 
-    def compute(self, job: Job) -> None:
-        """resize + UNet (+ the score reductions, on the logits where the UNet left them) on the compute stream; masks start back."""
-        n, eng, down = len(job.ids), self.eng, self.down
+    def begin_compute(self, job: Job) -> None:
+        """The compute stream takes the job's photos over from the upload stream."""
         self.main.wait_event(job.arrived)
         job.batch.record_stream(self.main)
         self.tm.setdefault("first_enqueue_s", time.time() - self.started)   # host time until the first kernel of the call is queued
+
+    def send_back(self, job: Job, contour_input, lg, scored=None, level=None, seg=None, emb=None) -> None:
+        """The UNet's outputs start back on the download stream: ``contour_input`` ((n,256,256) u8: the masks, or a sweep's level map)
+        first, then the logits and whichever records the call made -- ``scored`` (quality: records, half masks), ``level`` (sweep),
+        ``seg`` (evaluation) and the embedding.  Everything that stream reads is held in ``job.unet_out`` (``Job``'s docstring)."""
+        n, down = len(job.ids), self.down
+        job.unet_done = torch.cuda.Event()
+        job.unet_done.record()
+        job.unet_out = (lg, contour_input, scored, level, seg, emb)
+        job.logits, job.masks = _pinned((n, 256, 256), torch.float32), _pinned((n, 256, 256), torch.uint8)
+        job.masks_ready, job.logits_ready = torch.cuda.Event(), torch.cuda.Event()
+        with torch.cuda.stream(down):
+            down.wait_event(job.unet_done)
+            job.masks.copy_(contour_input, non_blocking=True)    # first: the contour stage waits for them only
+            job.masks_ready.record()
+            job.logits.copy_(lg[:, 0], non_blocking=True)
+            if scored is not None:
+                job.records, job.half = _pinned((n, 64), torch.uint8), _pinned((n, 256, 256), torch.uint8)
+                job.records.copy_(scored[0], non_blocking=True)
+                job.half.copy_(scored[1].view(n, 256, 256), non_blocking=True)
+            if level is not None:
+                job.level_records = _pinned(tuple(level.shape), torch.uint8)
+                job.level_records.copy_(level, non_blocking=True)
+            if seg is not None:
+                job.seg_records = _pinned((n, 64), torch.uint8)
+                job.seg_records.copy_(seg, non_blocking=True)
+            if emb is not None:
+                job.unet_emb = _pinned(tuple(emb.shape), torch.float32)
+                job.unet_emb.copy_(emb, non_blocking=True)
+            job.logits_ready.record()
+
+    def compute(self, job: Job) -> None:
+        """resize + UNet (+ the score reductions, on the logits where the UNet left them) on the compute stream; masks start back."""
+        eng = self.eng
+        self.begin_compute(job)
         lg, mk, emb = self.forward(job.batch)
         scored = None
         if self.quality:
@@ -234,74 +314,57 @@ class _Call:
             job.labels.record_stream(self.main)
             seg = self.gpu_timed("seg_ms", eng.segmentation_scores_dev, lg, job.labels, self.threshold)
             job.labels = None
-        job.unet_done = torch.cuda.Event()
-        job.unet_done.record()
-        job.unet_out = (lg, mk, scored, seg, emb)
-        job.logits, job.masks = _pinned((n, 256, 256), torch.float32), _pinned((n, 256, 256), torch.uint8)
-        job.masks_ready, job.logits_ready = torch.cuda.Event(), torch.cuda.Event()
+        self.send_back(job, mk, lg, scored, seg=seg, emb=emb)
+
+    def warp_and_classify(self, job: Job, found: list[int], quads: list) -> Boards:
+        """One ``Boards`` record of the job: ``quads`` are the quadrangles, in mask pixels, of the photos at positions ``found``.
+        Homographies (host) -> warp + split -> classifier (device); boards and probabilities start back."""
+        t0 = time.perf_counter()
+        ids, down = job.ids, self.down
+        rec = Boards(found, [self.cv._scale_quadrangle(q, self.images[ids[k]].shape[:2]) for k, q in zip(found, quads)])
+        inv = board_homographies(np.stack([q.reshape(4, 2) for q in rec.quads]), constants.BOARD_SIZE)
+        self.clock("homography_s", t0)
+        src = job.batch if len(found) == len(ids) else job.batch[torch.as_tensor(found, device=self.dev)]
+        squares_dev, boards_dev = self.gpu_timed("warp_ms", self.eng.extract_squares_u8, src, inv)
+        warped = torch.cuda.Event()
+        warped.record()
+        rec.boards = _pinned((len(found), constants.BOARD_SIZE[1], constants.BOARD_SIZE[0]), torch.uint8)
+        with torch.cuda.stream(down):                    # the rectified boards travel back while the classifier runs
+            down.wait_event(warped)
+            rec.boards.copy_(boards_dev, non_blocking=True)
+        cls_emb = None
+        if self.embeddings:                              # the pooled layer4 output of every square, inside resnet_ms
+            probs_dev, cls_emb = self.gpu_timed("resnet_ms", self.eng_cls.resnet18_forward_u8, squares_dev, want_embedding=True)
+        else:
+            probs_dev = self.gpu_timed("resnet_ms", self.eng_cls.resnet18_forward_u8, squares_dev)
+        done = torch.cuda.Event()
+        done.record()
+        rec.probs = _pinned((len(found) * 64, constants.NUM_CLASSES), torch.float32)
+        job.cls_out.append((probs_dev, boards_dev, squares_dev, cls_emb))
+        rec.probs_ready = torch.cuda.Event()
         with torch.cuda.stream(down):
-            down.wait_event(job.unet_done)
-            job.masks.copy_(mk, non_blocking=True)       # masks first: the contour stage waits for them only
-            job.masks_ready.record()
-            job.logits.copy_(lg[:, 0], non_blocking=True)
-            if scored is not None:
-                job.records, job.half = _pinned((n, 64), torch.uint8), _pinned((n, 256, 256), torch.uint8)
-                job.records.copy_(scored[0], non_blocking=True)
-                job.half.copy_(scored[1].view(n, 256, 256), non_blocking=True)
-            if seg is not None:
-                job.seg_records = _pinned((n, 64), torch.uint8)
-                job.seg_records.copy_(seg, non_blocking=True)
-            if emb is not None:
-                job.unet_emb = _pinned(tuple(emb.shape), torch.float32)
-                job.unet_emb.copy_(emb, non_blocking=True)
-            job.logits_ready.record()
+            down.wait_event(done)
+            rec.probs.copy_(probs_dev, non_blocking=True)
+            if cls_emb is not None:
+                rec.cls_emb = _pinned(tuple(cls_emb.shape), torch.float32)
+                rec.cls_emb.copy_(cls_emb, non_blocking=True)
+            rec.probs_ready.record()
+        return rec
 
     def classify(self, job: Job) -> None:
         """masks -> quadrangles (host) -> warp + split + classifier (device); boards and probabilities start back."""
         t0 = time.perf_counter()
         job.masks_ready.synchronize()
         self.clock("wait_masks_s", t0)
-        ids, down = job.ids, self.down
+        ids = job.ids
         t0 = time.perf_counter()
         found_quads = find_quadrangles(job.masks.numpy(), n_threads=self.n_host)
         self.clock("contours_s", t0)
-        t0 = time.perf_counter()
-        job.quads = []
-        for k, q in enumerate(found_quads):
-            if q is None and self.fallback_quad:
-                q = constants.WHOLE_MASK_QUADRANGLE
-            shape = self.images[ids[k]].shape
-            job.quads.append(None if q is None else self.cv._scale_quadrangle(q, (shape[0], shape[1])))
-        found = job.found = [k for k in range(len(ids)) if job.quads[k] is not None]
+        quads = [constants.WHOLE_MASK_QUADRANGLE if q is None and self.fallback_quad else q for q in found_quads]
+        found = [k for k, q in enumerate(quads) if q is not None]
+        job.cls_out = []
         if found:
-            inv = board_homographies(np.stack([job.quads[k].reshape(4, 2) for k in found]), constants.BOARD_SIZE)
-        self.clock("homography_s", t0)
-        if found:
-            src = job.batch if len(found) == len(ids) else job.batch[torch.as_tensor(found, device=self.dev)]
-            squares_dev, boards_dev = self.gpu_timed("warp_ms", self.eng.extract_squares_u8, src, inv)
-            warped = torch.cuda.Event()
-            warped.record()
-            job.boards = _pinned((len(found), constants.BOARD_SIZE[1], constants.BOARD_SIZE[0]), torch.uint8)
-            with torch.cuda.stream(down):                # the rectified boards travel back while the classifier runs
-                down.wait_event(warped)
-                job.boards.copy_(boards_dev, non_blocking=True)
-            cls_emb = None
-            if self.embeddings:                          # the pooled layer4 output of every square, inside resnet_ms
-                probs_dev, cls_emb = self.gpu_timed("resnet_ms", self.eng_cls.resnet18_forward_u8, squares_dev, want_embedding=True)
-            else:
-                probs_dev = self.gpu_timed("resnet_ms", self.eng_cls.resnet18_forward_u8, squares_dev)
-            done = torch.cuda.Event()
-            done.record()
-            job.probs = _pinned((len(found) * 64, constants.NUM_CLASSES), torch.float32)
-            job.cls_out = (probs_dev, boards_dev, squares_dev, cls_emb)
-            job.probs_ready = torch.cuda.Event()
-            with torch.cuda.stream(down):
-                down.wait_event(done)
-                job.probs.copy_(probs_dev, non_blocking=True)
-                if cls_emb is not None:
-                    job.cls_emb = _pinned(tuple(cls_emb.shape), torch.float32)
-                    job.cls_emb.copy_(cls_emb, non_blocking=True)
-                job.probs_ready.record()
+            job.boards.append(self.warp_and_classify(job, found, [quads[k] for k in found]))
         job.batch = None
         if self.quality:                                 # the device has this job's classifier queued: finish its scores meanwhile
             t0 = time.perf_counter()
@@ -324,68 +387,50 @@ class _Call:
 
     def finish(self, job: Job) -> None:
         """probabilities -> labels, FEN, pawn rule (one native call per job); the job's arrays go to its images' slots."""
-        ids, names, slots = job.ids, self.names, self.slots
+        ids, slots = job.ids, self.slots
         t0 = time.perf_counter()
         job.logits_ready.synchronize()
         lg, mk = job.logits.numpy(), job.masks.numpy()
         for k, i in enumerate(ids):
-            slots[i] = _ImageSlot(lg[k], mk[k], job.quads[k], job.quality[k] if job.quality else None)
+            slots[i] = _ImageSlot(lg[k], mk[k], None, job.quality[k] if job.quality else None)
         if job.unet_emb is not None:
             ue = job.unet_emb.numpy()
             for k, i in enumerate(ids):
                 slots[i].unet_emb = ue[k]
-        if job.found:
-            job.probs_ready.synchronize()
+        for rec in job.boards:
+            rec.probs_ready.synchronize()
         self.clock("wait_probs_s", t0)
-        if not job.found:
-            return
+        for rec in job.boards:
+            for k, (quad, board, position, cls_emb, scores) in zip(rec.found, self.decode(job, rec)):
+                slot = slots[ids[k]]
+                slot.quad, slot.board, slot.position, slot.cls_emb = quad, board, position, cls_emb
+                if scores is not None:
+                    self.targets.position[ids[k]] = scores
+
+    def decode(self, job: Job, rec: Boards) -> list[tuple]:
+        """A landed ``Boards`` record -> per board (quadrangle, board image, ``PositionResult``, classifier-embedding rows | None,
+        ``PositionScores`` | None): labels, FEN and pawn rule of all its boards by one native call, their scores against the true
+        placements (an evaluation call) by another."""
         t0 = time.perf_counter()
-        m = len(job.found)
-        probs = job.probs.numpy().reshape(m, 64, constants.NUM_CLASSES)
-        brd = job.boards.numpy()
+        m, names = len(rec.found), self.names
+        probs = rec.probs.numpy().reshape(m, 64, constants.NUM_CLASSES)
+        brd = rec.boards.numpy()
         fens, origs, validated, fixes = decode_positions(probs, self.flip)
-        if job.cls_emb is not None:                      # rows follow square_names, as the probabilities do
-            ce = job.cls_emb.numpy().reshape(m, 64, -1)
-            for j, k in enumerate(job.found):
-                slots[ids[k]].cls_emb = ce[j]
         fix_lists: list[list] = [[] for _ in range(m)]
         for b, sq, old, new in fixes:
             fix_lists[b].append(pawn_rule_fix(names, sq, old, new))
-        for j, k in enumerate(job.found):
-            slot = slots[ids[k]]
-            slot.board = brd[j]
-            crops = self.cv.extract_squares(brd[j]) if self.return_crops else None
-            slot.position = PositionResult(fen=fens[j], original_fen=origs[j], model_probabilities=probs[j], squares=crops,
-                                           square_names=names, validation_fixes=fix_lists[j])
+        positions = [PositionResult(fen=fens[j], original_fen=origs[j], model_probabilities=probs[j],
+                                    squares=self.cv.extract_squares(brd[j]) if self.return_crops else None, square_names=names,
+                                    validation_fixes=fix_lists[j]) for j in range(m)]
+        # the embedding rows follow square_names, as the probabilities do
+        cls_emb = [None] * m if rec.cls_emb is None else rec.cls_emb.numpy().reshape(m, 64, -1)
         self.clock("decode_s", t0)
+        scores = [None] * m
         if self.targets is not None:
             t0 = time.perf_counter()
-            self.score_positions(job, probs, validated, fix_lists)
+            scores = score_positions(job.ids, rec.found, probs, validated, fix_lists, self.targets.labels, self.flip)
             self.clock("evaluation", t0)
-
-    def score_positions(self, job: Job, probs, validated, fix_lists) -> None:
-        """The job's probabilities against the true placements (one native call): row i of a board is compared with the true piece
-        on ``square_names[i]``."""
-        from .evaluation import PositionScores, row_labels
-
-        true = self.targets.labels
-        sel = [j for j, k in enumerate(job.found) if true[job.ids[k]] is not None]
-        if not sel:
-            return
-        rows = np.stack([row_labels(true[job.ids[job.found[j]]], self.flip) for j in sel])
-        per_square, per_board = classification_scores(probs[sel], rows)
-        # once per job: the columns as arrays of their own (the records below hold rows of them), the accuracies as lists
-        predicted, valid = per_square["predicted"].astype(np.int8), validated[sel]
-        rank, conf, loss = (np.ascontiguousarray(per_square[name]) for name in ("rank", "confidence", "loss"))
-        top = (per_board["hits"][:, :3] / 64).tolist()
-        acc_o = (np.count_nonzero(predicted == rows, axis=1) / 64).tolist()
-        acc_v = (np.count_nonzero(valid == rows, axis=1) / 64).tolist()
-        mean_loss = per_board["mean_loss"].tolist()
-        for m, j in enumerate(sel):
-            self.targets.position[job.ids[job.found[j]]] = PositionScores(
-                top_k=tuple(top[m]), accuracy_original=acc_o[m], accuracy_validated=acc_v[m], mean_loss=mean_loss[m],
-                num_fixes=len(fix_lists[j]), true_labels=rows[m], predicted_labels=predicted[m], validated_labels=valid[m],
-                rank=rank[m], confidence=conf[m], loss=loss[m])
+        return list(zip(rec.quads, brd, positions, cls_emb, scores))
 
     # ---- the software pipeline --------------------------------------------------------------------------------------------------
     def issue(self, jobs: list[list[int]]) -> float:
@@ -415,11 +460,15 @@ class _Call:
         retire(classified)
         return t_last
 
-    def assemble(self) -> list[ChessVisionResult]:
+    def collect(self):
+        """What the call returns, once every job is finished (``run``)."""
+        return self.assemble(self.slots)
+
+    def assemble(self, slots) -> list[ChessVisionResult]:
         t0 = time.perf_counter()
-        per_image = (time.time() - self.started) / len(self.slots)
+        per_image = (time.time() - self.started) / len(slots)
         results = []
-        for s in self.slots:
+        for s in slots:
             extraction = BoardExtractionResult(board_image=s.board, binary_mask=s.mask, quadrangle=s.quad, probabilities=s.logits)
             emb = Embeddings(board_extractor=s.unet_emb, classifier=s.cls_emb) if self.embeddings else None
             results.append(ChessVisionResult(board_extraction=extraction, position=s.position, processing_time=per_image,
@@ -439,29 +488,25 @@ def process_images(cv, images, threshold, flip, fallback_quad, pipeline_chunk, r
     started = time.time()
     if resize not in RESIZE_MODES:
         raise ValueError(f"resize must be one of {RESIZE_MODES}, got {resize!r}")
-    for image in images:
-        assert isinstance(image, np.ndarray) and image.dtype == np.uint8 and image.ndim == 3
     if not images:
         return []
-    _ = cv.board_extractor, cv.classifier
-    jobs = plan_jobs([im.shape for im in images], pipeline_chunk, first=int(first_job), last=int(last_job))
-    # A caller that chose no stream gets the instance's own compute stream, not the NULL stream: kernels queued on the legacy stream
-    # from one thread while other threads load models / run request slots was one of the two ingredients of the device faults of
-    # the round-6 soak (profiles/r06_tuning.md section 8).  Everything the call returns has been waited for through events when it
-    # ends, so nothing is left to order against the caller's stream.
-    own = torch.cuda.current_stream(cv.device) == torch.cuda.default_stream(cv.device)
-    with torch.cuda.stream(cv._pipeline_streams()[2]) if own else contextlib.nullcontext():
-        call = _Call(cv, images, threshold, flip, fallback_quad, return_crops, timings, quality, started, targets, embeddings,
-                     resize)
+    call = _Call(cv, images, threshold, flip, fallback_quad, return_crops, timings, quality, started, targets, embeddings, resize)
+    return run(call, plan_jobs([im.shape for im in images], pipeline_chunk, first=int(first_job), last=int(last_job)))
+
+
+def run(call: _Call, jobs: list[list[int]]):
+    """The driver of a call: all jobs on the call's compute stream, one look at the numeric guard, the call's results
+    (``call.collect()``) and its timings."""
+    with torch.cuda.stream(call.main):
         t_last = call.issue(jobs)
         call.eng.check_numerics()                        # one look at the numeric guard for the whole call
         if call.eng_cls is not call.eng:
             call.eng_cls.check_numerics()
         call.tm["drain_s"] = time.perf_counter() - t_last    # last job: wait for its classifier, copies back, decode
-        results = call.assemble()
-        if timings is not None:
+        out = call.collect()
+        if call.timed:
             for name, a, b in call.gpu_events:
-                timings[name] = timings.get(name, 0.0) + a.elapsed_time(b)
-            timings["jobs"] = len(jobs)
-            timings["total_s"] = time.time() - started
-    return results
+                call.tm[name] = call.tm.get(name, 0.0) + a.elapsed_time(b)
+            call.tm["jobs"] = len(jobs)
+            call.tm["total_s"] = time.time() - call.started
+    return out

@@ -530,8 +530,14 @@ class Targets:
         self.position: list = [None] * n_images
 
     def report(self, results: list[ChessVisionResult]) -> EvaluationReport:
-        evaluations = [ImageEvaluation(segmentation=self.segmentation[i], position=self.position[i],
-                                       extraction_failed=self.labels[i] is not None and r.position is None)
-                       for i, r in enumerate(results)]
-        return EvaluationReport(results=results, evaluations=evaluations,
-                                aggregate=aggregate(evaluations, [r.processing_time for r in results]))
+        return build_report(results, self.labels, self.segmentation, self.position)
+
+
+def build_report(results: list[ChessVisionResult], labels, segmentation, position) -> EvaluationReport:
+    """The report of one call (one threshold of a sweep) from its results and, per image, the true class indices (or None), the
+    ``SegmentationScores`` (or None) and the ``PositionScores`` (or None)."""
+    evaluations = [ImageEvaluation(segmentation=segmentation[i], position=position[i],
+                                   extraction_failed=labels[i] is not None and r.position is None)
+                   for i, r in enumerate(results)]
+    return EvaluationReport(results=results, evaluations=evaluations,
+                            aggregate=aggregate(evaluations, [r.processing_time for r in results]))

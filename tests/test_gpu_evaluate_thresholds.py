@@ -208,3 +208,29 @@ def test_options_follow_evaluate_images(cv_model, data, option):
         assert all(r.position is not None for r in sweep.at(0.6).results) and sweep.boards_found == 10
     if option == "flip":
         assert all(r.position.square_names[0] == "h1" for r in sweep.at(0.6).results if r.position is not None)
+
+
+def test_three_jobs_with_embeddings_follow_evaluate_images(cv_model, data):
+    """Five photos in jobs of two: the third upload is gated and the first job retires behind the second one's classifier, with the
+    embeddings of both networks riding in the holds of the shared steps."""
+    images, fens, masks = (seq[:5] for seq in data)
+    timings, single_timings = {}, {}
+    try:
+        cv_model.evaluation_embeddings = True
+        sweep = cv_model.evaluate_thresholds(images, THRESHOLDS, true_fens=fens, label_masks=masks, pipeline_chunk=2, timings=timings)
+        singles = {t: cv_model.evaluate_images(images, true_fens=fens, label_masks=masks, threshold=t, pipeline_chunk=2,
+                                               timings=single_timings if t == 0.5 else None) for t in THRESHOLDS}
+    finally:
+        del cv_model.evaluation_embeddings                   # back to the class default
+    assert cv_model.evaluation_embeddings is False
+    for t in THRESHOLDS:
+        _check_contract(sweep.at(t), singles[t])
+        for g, w in zip(sweep.at(t).results, singles[t].results):
+            assert g.embeddings.board_extractor is not None
+            assert _same_array(g.embeddings.board_extractor, w.embeddings.board_extractor)       # bit for bit
+            assert (g.embeddings.classifier is None) == (w.embeddings.classifier is None) == (g.position is None)
+    for i in range(5):                                       # one UNet embedding per image, shared by its thresholds
+        a, b, c = (sweep.at(t).results[i].embeddings.board_extractor for t in THRESHOLDS)
+        assert a is b is c
+    assert timings["jobs"] == 3 == single_timings["jobs"]
+    assert set(timings) == set(single_timings) | {"levels_ms"}

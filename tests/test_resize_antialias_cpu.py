@@ -166,6 +166,19 @@ def test_antialias_issues_the_float_resize_then_the_float_entry(embeddings):
     assert out == ("logits", "mask", "embedding" if embeddings else None)
 
 
+@pytest.mark.parametrize("embeddings", [False, True])
+@pytest.mark.parametrize("resize, calls", [("area", ("resize_area_u8", "bytes 256", "unet_forward_u8")),
+                                           ("antialias", ("resize_antialias_f32", "floats 256", "unet_forward_mask"))])
+def test_a_maskless_forward_is_the_threshold_sweeps_call_sequence(resize, calls, embeddings):
+    """``forward(batch, want_mask=False)``: the same two engine calls; the UNet entry is told to leave the mask out and is always
+    told whether to pool the embedding."""
+    call = _ForwardOnly(resize, embeddings)
+    out = call.forward("photos", want_mask=False)
+    kw = dict(threshold=0.4, want_mask=False, want_embedding=embeddings)
+    assert call.eng.log == [(calls[0], "photos", (SIZE,), {}), (calls[2], calls[1], (), kw)]
+    assert out[0] == "logits" and out[2] == ("embedding" if embeddings else None) and len(out) == 3
+
+
 def test_the_mode_reaches_the_call_from_both_public_methods():
     """``process_images`` and ``evaluate_images`` hand the mode to ``_process_images_native`` as the last positional argument, where
     the repeat on the exact-f32 instance (``_recover``) finds it too: the lambda is the same for both runs."""

@@ -220,3 +220,23 @@ def test_level_record_mirrors_the_header():
     assert {"cv_threshold_levels", "cv_threshold_levels_finish"} <= declared
     assert {"cv_threshold_levels", "cv_threshold_levels_finish"} <= {name for name, _, _ in hip_backend.SYMBOLS}
     assert hasattr(hip_backend.HipEngine, "threshold_levels_dev") and hasattr(hip_backend.HipEngine, "threshold_levels")
+
+
+# ---- one threshold's report from explicit lists ------------------------------------------------------------------------------------
+def test_build_report_reads_its_lists_and_leaves_the_targets_alone():
+    from chessvision.cv_types import BoardExtractionResult, ChessVisionResult
+
+    fen = "8/8/8/8/8/8/8/8"
+    targets = evaluation.Targets(3, true_fens=[fen, fen, None], label_masks=[np.zeros((256, 256), np.uint8), None, None])
+    own_seg, own_pos = targets.segmentation, targets.position
+    blank = BoardExtractionResult(board_image=None, binary_mask=None, quadrangle=None, probabilities=None)
+    results = [ChessVisionResult(board_extraction=blank, position=None, processing_time=0.5) for _ in range(3)]
+    seg = [evaluation.SegmentationScores(bce=0.1, dice_loss=0.2, loss=0.3, dice=0.5, iou=0.4, pixel_accuracy=0.9), None, None]
+    rep = evaluation.build_report(results, targets.labels, seg, [None] * 3)
+    assert rep.results is results and [e.segmentation for e in rep.evaluations] == seg
+    assert [e.extraction_failed for e in rep.evaluations] == [True, True, False]      # a FEN but no board; no FEN: not a failure
+    assert rep.aggregate["extraction_failures"] == 2 and rep.aggregate["mean_dice"] == 0.5
+    assert targets.segmentation is own_seg and targets.position is own_pos
+    assert own_seg == [None] * 3 and own_pos == [None] * 3
+    same = targets.report(results)                            # Targets.report is the same function on the instance's own lists
+    assert [e.segmentation for e in same.evaluations] == [None] * 3 and same.aggregate["extraction_failures"] == 2
