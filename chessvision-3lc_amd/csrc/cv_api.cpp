@@ -228,7 +228,7 @@ void hard_mask_scores(long long n_label, long long n_pred, long long n_both, lon
 Status resize_on_stream(Engine& en, const uint8_t* src, int n, int h, int w_, int channels, uint8_t* dst, int out_h, int out_w, hipStream_t st) {
     hipError_t e;
     const bool integer = h % out_h == 0 && w_ % out_w == 0;
-    if (!integer && out_h <= h && out_w <= w_ && channels <= 4) {
+    if (!integer && out_h <= h && out_w <= w_) {
         // fractional shrink: OpenCV's float32 table form; the two tables are built once per geometry and stay on the device
         ResizeTables& tabs = en.area_tabs;
         const int geom[4] = {h, w_, out_h, out_w};

@@ -71,7 +71,7 @@ __global__ __launch_bounds__(256) void resize_area_2x2c3_kernel(const uint8_t* _
 // horizontal pass buf = buf + S * alpha over the column table's entries in order, then sum = beta * buf for the first source row of
 // a destination row and sum = sum + beta * buf for the others; saturate_cast<uchar>(sum) rounds half to even.  The tables
 // (computeResizeAreaTab: weights computed in double, stored as float) come from the host (resize_area_tables below).
-// One lane = one destination pixel, all channels (<= 4).
+// One lane = one destination pixel, all channels (any count, four at a time).
 struct AreaTabs { const int* xofs; const int* xsi; const float* xa; const int* yofs; const int* ysi; const float* ya; };
 
 __global__ __launch_bounds__(256) void resize_area_tab_kernel(const uint8_t* __restrict__ src, int n, int h, int w, int c,
@@ -85,22 +85,25 @@ __global__ __launch_bounds__(256) void resize_area_tab_kernel(const uint8_t* __r
     const size_t img = idx / ((size_t)ow * oh);
     const uint8_t* s = src + img * (size_t)h * w * c;
     const int k0 = t.xofs[dx], k1 = t.xofs[dx + 1], j0 = t.yofs[dy], j1 = t.yofs[dy + 1];
-    float sum[4] = {0.f, 0.f, 0.f, 0.f};
-    for (int j = j0; j < j1; ++j) {
-        const uint8_t* row = s + (size_t)t.ysi[j] * w * c;
-        const float beta = t.ya[j];
-        float buf[4] = {0.f, 0.f, 0.f, 0.f};
-        for (int k = k0; k < k1; ++k) {
-            const float alpha = t.xa[k];
-            const uint8_t* px = row + (size_t)t.xsi[k] * c;
-            for (int ch = 0; ch < c; ++ch) buf[ch] = buf[ch] + (float)px[ch] * alpha;
+    for (int c0 = 0; c0 < c; c0 += 4) {                     // channels in groups of 4 (one group for the usual c <= 4): a channel's
+        const int cn = min(4, c - c0);                      // operations and their order do not depend on the group it falls into
+        float sum[4] = {0.f, 0.f, 0.f, 0.f};
+        for (int j = j0; j < j1; ++j) {
+            const uint8_t* row = s + (size_t)t.ysi[j] * w * c + c0;
+            const float beta = t.ya[j];
+            float buf[4] = {0.f, 0.f, 0.f, 0.f};
+            for (int k = k0; k < k1; ++k) {
+                const float alpha = t.xa[k];
+                const uint8_t* px = row + (size_t)t.xsi[k] * c;
+                for (int ch = 0; ch < cn; ++ch) buf[ch] = buf[ch] + (float)px[ch] * alpha;
+            }
+            for (int ch = 0; ch < cn; ++ch) sum[ch] = j == j0 ? beta * buf[ch] : sum[ch] + beta * buf[ch];
         }
-        for (int ch = 0; ch < c; ++ch) sum[ch] = j == j0 ? beta * buf[ch] : sum[ch] + beta * buf[ch];
-    }
-    uint8_t* d = dst + idx * c;
-    for (int ch = 0; ch < c; ++ch) {
-        const float v = rintf(sum[ch]);
-        d[ch] = (uint8_t)(v < 0.f ? 0.f : v > 255.f ? 255.f : v);
+        uint8_t* d = dst + idx * c + c0;
+        for (int ch = 0; ch < cn; ++ch) {
+            const float v = rintf(sum[ch]);
+            d[ch] = (uint8_t)(v < 0.f ? 0.f : v > 255.f ? 255.f : v);
+        }
     }
 }
 
@@ -125,46 +128,25 @@ __global__ void resize_area_u8_kernel(const uint8_t* __restrict__ src, int n, in
         dst[idx] = (uint8_t)((acc + (fy * fx) / 2) / (fy * fx));
         return;
     }
-    // (a fractional SHRINK never reaches this kernel: resize_area_tab_kernel reproduces OpenCV's float32 table form; the branch below
-    // stays for callers without tables)
-    const double sy = (double)h / oh, sx = (double)w / ow;
-    double acc = 0.0;
-    if (oh <= h && ow <= w) {
-        const double y_lo = oy * sy, y_hi = (oy + 1) * sy, x_lo = ox * sx, x_hi = (ox + 1) * sx;
-        const int y0 = (int)floor(y_lo), y1 = min(h, (int)ceil(y_hi));
-        const int x0 = (int)floor(x_lo), x1 = min(w, (int)ceil(x_hi));
-        for (int y = y0; y < y1; ++y) {
-            const double wy = fmax(0.0, fmin(y_hi, (double)(y + 1)) - fmax(y_lo, (double)y)) / sy;
-            double row = 0.0;
-            for (int x = x0; x < x1; ++x) {
-                const double wx = fmax(0.0, fmin(x_hi, (double)(x + 1)) - fmax(x_lo, (double)x)) / sx;
-                row += wx * (double)s[((size_t)y * w + x) * c + ch];
-            }
-            acc += wy * row;
-        }
-    } else {
-        // Enlarging in either direction: OpenCV has no area algorithm there and runs its 8-bit bilinear resizer with the AREA
-        // coefficient rule (resize.cpp): s = floor(d * scale), f = (float)((d + 1) - (s + 1) * inv_scale) reduced to [0, 1), both
-        // clamped at the last source pixel, 11-bit coefficients round((1 - f) * 2048), round(f * 2048); horizontal pass in int32,
-        // vertical pass (((b0 * (r0 >> 4)) >> 16) + ((b1 * (r1 >> 4)) >> 16) + 2) >> 2 (VResizeLinear<uchar>).  Integers: exact.
-        auto axis = [](int d, double scale, double inv_scale, int ssize, int& s0, int& s1, int& c0, int& c1) {
-            int sx = (int)floor(d * scale);
-            float f = (float)((double)(d + 1) - (double)(sx + 1) * inv_scale);
-            f = f <= 0.f ? 0.f : f - floorf(f);
-            if (sx >= ssize - 1) { f = 0.f; sx = ssize - 1; }
-            s0 = sx; s1 = sx + 1 < ssize ? sx + 1 : ssize - 1;
-            c0 = (int)rintf((1.f - f) * 2048.f); c1 = (int)rintf(f * 2048.f);
-        };
-        int x0, x1, a0, a1, y0, y1, b0, b1;
-        axis(ox, inv_x.x, inv_x.y, w, x0, x1, a0, a1);
-        axis(oy, inv_y.x, inv_y.y, h, y0, y1, b0, b1);
-        const int r0 = (int)s[((size_t)y0 * w + x0) * c + ch] * a0 + (int)s[((size_t)y0 * w + x1) * c + ch] * a1;
-        const int r1 = (int)s[((size_t)y1 * w + x0) * c + ch] * a0 + (int)s[((size_t)y1 * w + x1) * c + ch] * a1;
-        dst[idx] = (uint8_t)((((b0 * (r0 >> 4)) >> 16) + ((b1 * (r1 >> 4)) >> 16) + 2) >> 2);
-        return;
-    }
-    const double v = rint(acc);
-    dst[idx] = (uint8_t)(v < 0.0 ? 0.0 : v > 255.0 ? 255.0 : v);
+    // (a fractional SHRINK never reaches this kernel: resize_area_tab_kernel is OpenCV's float32 table form, and resize_area_u8 below
+    // refuses one.)  Enlarging in either direction: OpenCV has no area algorithm there and runs its 8-bit bilinear resizer with the AREA
+    // coefficient rule (resize.cpp): s = floor(d * scale), f = (float)((d + 1) - (s + 1) * inv_scale) reduced to [0, 1), both
+    // clamped at the last source pixel, 11-bit coefficients round((1 - f) * 2048), round(f * 2048); horizontal pass in int32,
+    // vertical pass (((b0 * (r0 >> 4)) >> 16) + ((b1 * (r1 >> 4)) >> 16) + 2) >> 2 (VResizeLinear<uchar>).  Integers: exact.
+    auto axis = [](int d, double scale, double inv_scale, int ssize, int& s0, int& s1, int& c0, int& c1) {
+        int sx = (int)floor(d * scale);
+        float f = (float)((double)(d + 1) - (double)(sx + 1) * inv_scale);
+        f = f <= 0.f ? 0.f : f - floorf(f);
+        if (sx >= ssize - 1) { f = 0.f; sx = ssize - 1; }
+        s0 = sx; s1 = sx + 1 < ssize ? sx + 1 : ssize - 1;
+        c0 = (int)rintf((1.f - f) * 2048.f); c1 = (int)rintf(f * 2048.f);
+    };
+    int x0, x1, a0, a1, y0, y1, b0, b1;
+    axis(ox, inv_x.x, inv_x.y, w, x0, x1, a0, a1);
+    axis(oy, inv_y.x, inv_y.y, h, y0, y1, b0, b1);
+    const int r0 = (int)s[((size_t)y0 * w + x0) * c + ch] * a0 + (int)s[((size_t)y0 * w + x1) * c + ch] * a1;
+    const int r1 = (int)s[((size_t)y1 * w + x0) * c + ch] * a0 + (int)s[((size_t)y1 * w + x1) * c + ch] * a1;
+    dst[idx] = (uint8_t)((((b0 * (r0 >> 4)) >> 16) + ((b1 * (r1 >> 4)) >> 16) + 2) >> 2);
 }
 
 // ---- antialiased bilinear resize (what the reference's enrichment job feeds its UNet) ----------------------------------------
@@ -326,6 +308,10 @@ __global__ __launch_bounds__(256) void extract_squares_u8_kernel(const uint8_t* 
     const double W0 = (m6 * blk + m7 * ys) + m8;
     const uint8_t* s = images + (size_t)img * h * w * 3;
     const unsigned row_bytes = (unsigned)w * 3u;
+    // interior pixels x0 < x_in, y0 < y_in: both taps of both rows inside the image and nothing the CV_16SC2 map saturates.  Never below
+    // 0 (w == 1: w - 2 would wrap as unsigned and send every pixel down the 64-bit loads), never above 32767 (a pixel the map saturates
+    // takes the border path, which clamps).  Uniform: once per wave, nothing per pixel.
+    const unsigned x_in = (unsigned)min(max(w - 2, 0), 32767), y_in = (unsigned)min(max(h - 1, 0), 32767);
     uint32_t packed = 0;
 #pragma unroll
     for (int j = 0; j < 4; ++j) {                                       // flipped pixel bx0 + j  <->  column xs3 + 3 - j
@@ -336,12 +322,12 @@ __global__ __launch_bounds__(256) void extract_squares_u8_kernel(const uint8_t* 
         const double fys = (Y0 + m3 * x1) * W;
         // saturate_cast<int>(clamp(f, INT_MIN, INT_MAX)): nearest-even, then the conversion itself saturates at both ends
         const int xi = (int)rint(fxs), yi = (int)rint(fys);
-        const int x0 = xi >> 5, y0 = yi >> 5;                           // (the CV_16SC2 map saturates to int16: only far outside any image)
+        const int x0 = xi >> 5, y0 = yi >> 5;                           // (the CV_16SC2 map saturates to int16: in the border path)
         const unsigned wx1 = (unsigned)(xi & 31), wy1 = (unsigned)(yi & 31), wx0 = 32u - wx1, wy0 = 32u - wy1;
         // Separable form of OpenCV's integer blend: with h_r = wx0 * p(r, x0) + wx1 * p(r, x0 + 1),
         //   (w00 p00 + w01 p01 + w10 p10 + w11 p11 + 2^14) >> 15  ==  (wy0 h_0 + wy1 h_1 + 512) >> 10     (w_ij = 32 wy_i wx_j: exact)
         unsigned bb, gg, rr;
-        if ((unsigned)x0 < (unsigned)(w - 2) && (unsigned)y0 < (unsigned)(h - 1)) {
+        if ((unsigned)x0 < x_in && (unsigned)y0 < y_in) {
             // interior: both taps of a row are 6 consecutive bytes B0 G0 R0 B1 G1 R1; one unaligned 64-bit load per row (stays inside
             // the row), the horizontal blends as byte dot products (v_dot4_u32_u8) straight on the loaded words
             const unsigned off = (unsigned)(y0 * w + x0) * 3u;
@@ -456,14 +442,16 @@ void resize_area_table(int ssize, int dsize, std::vector<int>& ofs, std::vector<
 // tabs: device pointers of the two tables (built by the caller with resize_area_table and uploaded once per geometry)
 hipError_t resize_area_u8_tab(const uint8_t* src, int n, int h, int w, int c, uint8_t* dst, int oh, int ow, const int* xofs,
                               const int* xsi, const float* xa, const int* yofs, const int* ysi, const float* ya, hipStream_t s) {
-    if (c < 1 || c > 4) return hipErrorInvalidValue;
+    if (c < 1) return hipErrorInvalidValue;
     const size_t total = (size_t)n * oh * ow;
     const AreaTabs t{xofs, xsi, xa, yofs, ysi, ya};
     hipLaunchKernelGGL(resize_area_tab_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, src, n, h, w, c, dst, oh, ow, t);
     return hipGetLastError();
 }
 
+// integer shrink factors in both directions (1 included) and enlarging; a fractional shrink is resize_area_u8_tab's
 hipError_t resize_area_u8(const uint8_t* src, int n, int h, int w, int c, uint8_t* dst, int oh, int ow, hipStream_t s) {
+    if ((h % oh != 0 || w % ow != 0) && oh <= h && ow <= w) return hipErrorInvalidValue;
     if (c == 3 && h == 2 * oh && w == 2 * ow && ow % 4 == 0 && ((uintptr_t)src & 7) == 0 && ((uintptr_t)dst & 3) == 0) {
         const size_t total = (size_t)n * oh * (ow / 4);
         hipLaunchKernelGGL(resize_area_2x2c3_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, src, n, h, w, dst);

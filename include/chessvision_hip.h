@@ -298,8 +298,11 @@ int cv_find_quadrangles(const uint8_t* masks, int n, int h, int w, int32_t* quad
 int cv_find_contours(const uint8_t* mask, int h, int w, int method, int32_t* xy, int64_t cap_points, int32_t* counts,
                      int32_t* holes, int64_t cap_contours, int64_t* n_contours);
 
-/* (n,h,w,channels) uint8 -> (n,out_h,out_w,channels) uint8, INTER_AREA semantics (cv2.resize at core.py:212): exact
- * box mean with round-half-up for integer shrink factors, coverage-weighted mean otherwise.  DEVICE pointers. */
+/* (n,h,w,channels) uint8 -> (n,out_h,out_w,channels) uint8, INTER_AREA semantics (cv2.resize at core.py:212), any channel
+ * count and any h, w, out_h, out_w >= 1: exact box mean with round-half-up for integer shrink factors in both directions; any
+ * other shrink is OpenCV's ResizeArea_Invoker in float32 (computeResizeAreaTab weights, horizontal pass first, round half to
+ * even); enlarging in either direction is OpenCV's 8-bit bilinear resizer with the AREA coefficient rule.  Byte-exact against
+ * chessvision/classical.py: resize_area and oracle/classical_ref.py.  DEVICE pointers, no alignment required. */
 int cv_resize_area_u8(cv_engine_t* eng, const uint8_t* src, int n, int h, int w, int channels, uint8_t* dst,
                       int out_h, int out_w, void* stream);
 
