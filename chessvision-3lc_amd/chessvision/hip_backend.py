@@ -142,6 +142,10 @@ SYMBOLS = [
     ("cv_square_records_finish", _i, [_vp, _i, _i, _vp]),
     ("cv_threshold_levels", _i, [_vp, _vp, _vp, _i, _i, _fp, _i, _vp, _vp, _vp]),
     ("cv_threshold_levels_finish", _i, [_vp, _i, _i] + [ctypes.POINTER(ctypes.c_double)] * 3),
+    ("cv_jpeg_info", _i, [_vp, ctypes.c_size_t, _vp]),
+    ("cv_jpeg_entropy_decode", _i, [_vp, ctypes.c_size_t, _vp, ctypes.c_size_t, _vp]),
+    ("cv_jpeg_reconstruct_u8", _i, [_vp, _vp, _vp, _i, _vp, _i, _vp, ctypes.c_size_t, _vp, _vp]),
+    ("cv_process_jpeg", _i, [_vp, _vp, _vp, ctypes.c_size_t, _f, _i, _i, ctypes.c_void_p, ctypes.c_size_t, _vp]),
 ]
 
 # cv_score_record_t (include/chessvision_hip.h): one 64-byte record per image
@@ -442,6 +446,28 @@ def process_image_native(unet_engine: "HipEngine", classifier_engine: "HipEngine
     img = np.ascontiguousarray(image, dtype=np.uint8)
     if img.ndim != 3 or img.shape[2] != 3:
         raise HipBackendError("process_image_native expects an (H,W,3) uint8 image")
+    res, arrays = _image_result_buffers()
+    _check(lib.cv_process_image_v2(unet_engine._h, classifier_engine._h, img.ctypes.data, img.shape[0], img.shape[1],
+                                   float(threshold), int(bool(flip)), int(bool(fallback_quad)), ctypes.byref(res), ctypes.sizeof(res),
+                                   _stream_ptr(unet_engine.device) if stream is None else stream))    # stream: a request slot's own HIP stream
+    return _image_result_dict(res, arrays)
+
+
+def process_jpeg_native(unet_engine: "HipEngine", classifier_engine: "HipEngine", blob, threshold: float = 0.5, flip: bool = False,
+                        fallback_quad: bool = False, stream: int | None = None) -> dict:
+    """One JPEG stream through ``cv_process_jpeg``: ``process_image_native`` with the decode behind the C ABI as well (Huffman stage on
+    this thread into the engine's page-locked block, reconstruction on the device).  Same dict."""
+    lib = load_library()
+    blob = bytes(blob)
+    res, arrays = _image_result_buffers()
+    status = lib.cv_process_jpeg(unet_engine._h, classifier_engine._h, blob, len(blob), float(threshold), int(bool(flip)),
+                                 int(bool(fallback_quad)), ctypes.byref(res), ctypes.sizeof(res),
+                                 _stream_ptr(unet_engine.device) if stream is None else stream)
+    _check(status)
+    return _image_result_dict(res, arrays)
+
+
+def _image_result_buffers():
     logits = np.empty((256, 256), np.float32)
     mask = np.empty((256, 256), np.uint8)
     board = np.empty((512, 512), np.uint8)
@@ -450,9 +476,11 @@ def process_image_native(unet_engine: "HipEngine", classifier_engine: "HipEngine
     res = _ImageResult()
     res.logits, res.mask, res.board = logits.ctypes.data, mask.ctypes.data, board.ctypes.data
     res.probabilities, res.squares, res.labels = probs.ctypes.data, squares.ctypes.data, None
-    _check(lib.cv_process_image_v2(unet_engine._h, classifier_engine._h, img.ctypes.data, img.shape[0], img.shape[1],
-                                   float(threshold), int(bool(flip)), int(bool(fallback_quad)), ctypes.byref(res), ctypes.sizeof(res),
-                                   _stream_ptr(unet_engine.device) if stream is None else stream))    # stream: a request slot's own HIP stream
+    return res, (logits, mask, board, probs, squares)
+
+
+def _image_result_dict(res, arrays) -> dict:
+    logits, mask, board, probs, squares = arrays
     out = {"logits": logits, "mask": mask, "found": bool(res.found)}
     if res.found:
         out.update(quadrangle=np.frombuffer(res.quadrangle, dtype=np.float32).reshape(4, 1, 2).copy(), board=board, probabilities=probs, squares=squares,
@@ -862,6 +890,61 @@ class HipEngine:
         _check(self._lib.cv_extract_squares_u8_dev(self._h, _ptr(images), n, h, w, _ptr(inv_dev), _ptr(squares),
                                                    _ptr(boards) if want_boards else None, _stream_ptr(self.device)))
         return squares, boards
+
+    # -- JPEG decode: host entropy stage (chessvision/jpeg.py), device reconstruction (csrc/jpeg.hip) ----------------------
+    def jpeg_reconstruct_dev(self, coeffs: torch.Tensor, qtables: torch.Tensor, info, channel_order: str = "bgr",
+                             out: torch.Tensor | None = None) -> torch.Tensor:
+        """Device form: ``coeffs`` int16 ``(n, 64 * info.blocks)`` and ``qtables`` ``(n, components, 64)`` (uint16 values in an int16
+        tensor), both on the device and 16-byte aligned, as ``jpeg.entropy_decode`` wrote them for n images of the one geometry
+        ``info`` -> ``(n, h, w, 3)`` uint8, or ``(n, h, w)`` for ``"gray"`` (written into ``out`` when given).  Two launches on the
+        current stream; nothing waits."""
+        from .jpeg import ORDERS
+        if channel_order not in ORDERS:
+            raise HipBackendError(f"channel_order must be one of {sorted(ORDERS)}")
+        if coeffs.dtype != torch.int16 or qtables.dtype != torch.int16 or coeffs.dim() != 2 or not coeffs.is_contiguous() \
+                or not qtables.is_contiguous() or coeffs.device != self.device or qtables.device != self.device:
+            raise HipBackendError("jpeg_reconstruct_dev expects contiguous int16 device tensors")
+        n = coeffs.shape[0]
+        if coeffs.shape[1] != 64 * info.blocks or qtables.numel() != n * info.components * 64:
+            raise HipBackendError("jpeg_reconstruct_dev: tensors do not match the geometry")
+        shape = (n, info.height, info.width) if channel_order == "gray" else (n, info.height, info.width, 3)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.uint8, device=self.device)
+        elif out.dtype != torch.uint8 or tuple(out.shape) != shape or not out.is_contiguous() or out.device != self.device:
+            raise HipBackendError(f"jpeg_reconstruct_dev: out must be a contiguous uint8 device tensor of shape {shape}")
+        if n == 0:
+            return out
+        planes = torch.empty(n * 64 * info.blocks, dtype=torch.uint8, device=self.device)
+        c_info = info.to_c()
+        _check(self._lib.cv_jpeg_reconstruct_u8(self._h, _ptr(coeffs), _ptr(qtables), n, ctypes.addressof(c_info), ORDERS[channel_order],
+                                                _ptr(planes), planes.numel(), _ptr(out), _stream_ptr(self.device)))
+        return out
+
+    def jpeg_decode(self, blobs, channel_order: str = "bgr") -> torch.Tensor:
+        """JPEG streams of ONE geometry (size, components, sampling) -> device tensor ``(n, h, w, 3)`` uint8 in ``"bgr"`` (default) or
+        ``"rgb"`` order, or ``(n, h, w)`` for ``"gray"`` (1-component streams only).  The Huffman stage runs on host threads into one
+        page-locked buffer, one copy takes it to the device, two launches reconstruct the pixels: libjpeg's, byte for byte.
+        Raises ``jpeg.UnsupportedJpeg`` (a ``ValueError``) naming the refused blobs."""
+        from . import jpeg as _jpeg
+        blobs = list(blobs)
+        if not blobs:
+            raise HipBackendError("jpeg_decode needs at least one stream")
+        infos = [_jpeg.jpeg_info(b) for b in blobs]
+        bad = {i: f.reason for i, f in enumerate(infos) if not f.supported}
+        if bad:
+            raise _jpeg.UnsupportedJpeg(bad)
+        info = infos[0]
+        if any(f.geometry != info.geometry for f in infos):
+            raise HipBackendError("jpeg_decode: all streams of one call must share one geometry (ChessVision.decode_jpegs groups them)")
+        n, count, tables = len(blobs), 64 * info.blocks, 64 * info.components
+        staging = torch.empty(n * (count + tables), dtype=torch.int16).pin_memory()
+        host = staging.numpy()
+        co, qt = host[:n * count].reshape(n, count), host[n * count:].view(np.uint16).reshape(n, info.components, 64)
+        _jpeg.entropy_decode_many(blobs, infos, co, qt)
+        dev = staging.to(self.device, non_blocking=True)
+        out = self.jpeg_reconstruct_dev(dev[:n * count].view(n, count), dev[n * count:].view(n, info.components, 64), info, channel_order)
+        torch.cuda.current_stream(self.device).synchronize()          # the page-locked buffer is released on return
+        return out
 
     # -- introspection ----------------------------------------------------------------------------
     def activation(self, model: str, name: str) -> np.ndarray:

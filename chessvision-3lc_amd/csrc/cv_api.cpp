@@ -12,6 +12,8 @@
 
 #include "engine.h"
 #include "host_stages.h"
+#include "jpeg.h"
+#include "jpeg_device.h"
 #include "models.h"
 #include "pipeline.h"
 #include "pointwise.h"
@@ -26,6 +28,11 @@ static_assert(sizeof(cv_square_record_t) == sizeof(cv::SquareRecord) && offsetof
 static_assert(sizeof(cv_level_record_t) == sizeof(cv::LevelRecord) && sizeof(cv_level_record_t) % 64 == 0 && CV_MAX_THRESHOLDS == cv::kMaxLevelThresholds &&
               offsetof(cv_level_record_t, hist) == offsetof(cv::LevelRecord, hist) && offsetof(cv_level_record_t, reserved) == offsetof(cv::LevelRecord, reserved),
               "cv_level_record_t is the kernel's record");
+static_assert(sizeof(cv_jpeg_info_t) == sizeof(cvjpeg::Info) && offsetof(cv_jpeg_info_t, luma_h) == offsetof(cvjpeg::Info, luma_h) &&
+              offsetof(cv_jpeg_info_t, orientation) == offsetof(cvjpeg::Info, orientation) && offsetof(cv_jpeg_info_t, supported) == offsetof(cvjpeg::Info, supported) &&
+              offsetof(cv_jpeg_info_t, reason) == offsetof(cvjpeg::Info, reason) && (int)CV_ERR_INVALID == (int)cvjpeg::kInvalid &&
+              (int)CV_JPEG_BGR == (int)cv::kJpegBGR && (int)CV_JPEG_RGB == (int)cv::kJpegRGB && (int)CV_JPEG_GRAY == (int)cv::kJpegGray,
+              "cv_jpeg_info_t is the parser's record");
 static_assert(sizeof(cv_square_score_t) == 24 && sizeof(cv_board_score_t) == 64, "layouts the Python binding mirrors");
 
 using namespace cv;
@@ -329,15 +336,35 @@ struct SideStreamJoin {
     ~SideStreamJoin() { if (side) (void)hipStreamSynchronize(side); }
 };
 
-Status process_image(cv_engine_t* ue, cv_engine_t* ce, const uint8_t* image, int h, int w_, float threshold, int flip, int fallback_quad,
+// the geometry a device launch may rely on: what parse_info accepts, restated on the caller's copy of the record
+Status check_jpeg_info(const cvjpeg::Info& info) {
+    if (!info.supported) return fail(CV_ERR_INVALID, std::string("unsupported JPEG stream: ") + std::string(info.reason, strnlen(info.reason, sizeof info.reason)));
+    const bool luma_ok = (info.luma_h == 1 && info.luma_v == 1) || (info.luma_h == 2 && info.luma_v == 1) || (info.luma_h == 2 && info.luma_v == 2);
+    if (info.width < 1 || info.height < 1 || info.width > 65535 || info.height > 65535 || (size_t)info.width * info.height > ((size_t)1 << 28) ||
+        (info.components != 1 && info.components != 3) || !luma_ok || (info.components == 1 && info.luma_h != 1))
+        return fail(CV_ERR_INVALID, "malformed cv_jpeg_info_t");
+    return Status();
+}
+
+// The two fronts of the one-image pipeline: the caller's pixels (cv_process_image, cv_process_image_v2) or a JPEG stream
+// (cv_process_jpeg), which the entropy stage decodes into the page-locked block and the device reconstructs into the image's place.
+struct ImageFront {
+    const uint8_t* image = nullptr;        // (h, w, 3) uint8, or
+    const uint8_t* jpeg = nullptr;         // an encoded stream of jpeg_len bytes whose header is `info`
+    size_t jpeg_len = 0;
+    cvjpeg::Info info;
+};
+
+Status process_image(cv_engine_t* ue, cv_engine_t* ce, const ImageFront& front, int h, int w_, float threshold, int flip, int fallback_quad,
                      cv_image_result_t* out, size_t out_size, void* stream) {
+    const uint8_t* const image = front.image;
     // the caller's struct may be the shorter one of an earlier ABI: nothing at or beyond out_size is touched
     if (out && out_size < offsetof(cv_image_result_t, n_fixes) + sizeof(int32_t))
         return fail(CV_ERR_INVALID, "cv_process_image: result struct smaller than the ABI 3 layout");
     uint8_t* const out_squares = (out && out_size >= offsetof(cv_image_result_t, squares) + sizeof(uint8_t*)) ? out->squares : nullptr;
     CV_TRY(check_engine(ue));
     CV_TRY(check_engine(ce));
-    if (!image || !out || h <= 0 || w_ <= 0 || (size_t)h * w_ > ((size_t)1 << 28)) return fail(CV_ERR_INVALID, "cv_process_image: bad argument");
+    if ((!image && !front.jpeg) || !out || h <= 0 || w_ <= 0 || (size_t)h * w_ > ((size_t)1 << 28)) return fail(CV_ERR_INVALID, "cv_process_image: bad argument");
     if (!(threshold >= 0.f && threshold <= 1.f)) return fail(CV_ERR_INVALID, "threshold must be between 0 and 1");
     if (ue->impl.device != ce->impl.device) return fail(CV_ERR_STATE, "cv_process_image: both engines must live on one device");
     Engine& U = ue->impl;
@@ -354,11 +381,15 @@ Status process_image(cv_engine_t* ue, cv_engine_t* ce, const uint8_t* image, int
         for (size_t b : sizes) { *off++ = at; at += (b + 255) & ~(size_t)255; }
         return at;
     };
-    size_t h_off[7], d_off[6];
-    // host block: image | mask | logits | board | probs | inv | two guard words (extractor, classifier)
-    const size_t h_need = carve({img_b, mk_b, lg_b, bd_b, pr_b, inv_b, gd_b}, h_off);
-    // device block: image | small | logits | squares | board | inv
-    const size_t d_need = carve({img_b, small_b, lg_b, sq_b, bd_b, inv_b}, d_off);
+    // the JPEG front's pieces: coefficients and tables on both sides, component planes on the device; empty for the pixel front, whose
+    // blocks and offsets are what they always were
+    const size_t jpeg_blocks = front.jpeg ? cvjpeg::layout_of(front.info).blocks : 0;
+    const size_t co_b = jpeg_blocks * 64 * sizeof(int16_t), qt_b = front.jpeg ? 3 * 64 * sizeof(uint16_t) : 0, pl_b = jpeg_blocks * 64;
+    size_t h_off[9], d_off[9];
+    // host block: image | mask | logits | board | probs | inv | two guard words (extractor, classifier) | coefficients | tables
+    const size_t h_need = carve({front.jpeg ? (size_t)0 : img_b, mk_b, lg_b, bd_b, pr_b, inv_b, gd_b, co_b, qt_b}, h_off);
+    // device block: image | small | logits | squares | board | inv | coefficients | tables | planes
+    const size_t d_need = carve({img_b, small_b, lg_b, sq_b, bd_b, inv_b, co_b, qt_b, pl_b}, d_off);
     std::lock_guard<std::mutex> pipe_lock(U.pipe_mu);   // one request at a time per extractor engine: the staging blocks are shared
     {
         std::unique_lock<std::mutex> lk(U.mu);
@@ -386,8 +417,20 @@ Status process_image(cv_engine_t* ue, cv_engine_t* ce, const uint8_t* image, int
     uint8_t* h_bd = (uint8_t*)(hb + h_off[3]); float* h_pr = (float*)(hb + h_off[4]); double* h_inv = (double*)(hb + h_off[5]);
     unsigned* h_gd = (unsigned*)(hb + h_off[6]);
 
-    std::memcpy(h_img, image, img_b);
-    hipError_t e = hipMemcpyAsync(d_img, h_img, img_b, hipMemcpyHostToDevice, st);
+    hipError_t e;
+    if (front.jpeg) {
+        int16_t* h_co = (int16_t*)(hb + h_off[7]); uint16_t* h_qt = (uint16_t*)(hb + h_off[8]);
+        int16_t* d_co = (int16_t*)(db + d_off[6]); uint16_t* d_qt = (uint16_t*)(db + d_off[7]); uint8_t* d_pl = (uint8_t*)(db + d_off[8]);
+        char why[200];
+        if (cvjpeg::entropy_decode(front.jpeg, front.jpeg_len, h_co, jpeg_blocks * 64, h_qt, nullptr, why, sizeof why) != cvjpeg::kOk)
+            return fail(CV_ERR_INVALID, std::string("cv_process_jpeg: ") + why);
+        e = hipMemcpyAsync(d_co, h_co, co_b, hipMemcpyHostToDevice, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(d_qt, h_qt, qt_b, hipMemcpyHostToDevice, st);
+        if (e == hipSuccess) e = jpeg_reconstruct_u8(d_co, d_qt, 1, front.info, kJpegBGR, d_pl, d_img, st);
+    } else {
+        std::memcpy(h_img, image, img_b);
+        e = hipMemcpyAsync(d_img, h_img, img_b, hipMemcpyHostToDevice, st);
+    }
     if (e != hipSuccess) return hip_fail(e, "cv_process_image: upload");
     Status s;
     {
@@ -1314,16 +1357,81 @@ int cv_extract_squares_u8_dev(cv_engine_t* eng, const uint8_t* images, int n, in
 int cv_process_image_v2(cv_engine_t* unet_engine, cv_engine_t* classifier_engine, const uint8_t* image, int h, int w, float threshold,
                         int flip, int fallback_quad, cv_image_result_t* out, size_t out_size, void* stream) {
     return guarded("cv_process_image_v2", [&]() -> Status {
-        return process_image(unet_engine, classifier_engine, image, h, w, threshold, flip, fallback_quad, out, out_size, stream);
+        ImageFront front;
+        front.image = image;
+        return process_image(unet_engine, classifier_engine, front, h, w, threshold, flip, fallback_quad, out, out_size, stream);
     });
 }
 
 int cv_process_image(cv_engine_t* unet_engine, cv_engine_t* classifier_engine, const uint8_t* image, int h, int w, float threshold,
                      int flip, int fallback_quad, cv_image_result_t* out, void* stream) {
     return guarded("cv_process_image", [&]() -> Status {      // the struct of ABI 3 / 4: `squares` did not exist
-        return process_image(unet_engine, classifier_engine, image, h, w, threshold, flip, fallback_quad, out,
+        ImageFront front;
+        front.image = image;
+        return process_image(unet_engine, classifier_engine, front, h, w, threshold, flip, fallback_quad, out,
                              offsetof(cv_image_result_t, squares), stream);
     });
 }
 
+// ---- JPEG decode: host entropy stage (jpeg.cpp), device reconstruction (jpeg.hip) ------------------------------------------
+int cv_jpeg_info(const uint8_t* bytes, size_t len, cv_jpeg_info_t* info) {
+    return guarded("cv_jpeg_info", [&]() -> Status {
+        if (!bytes || !info) return fail(CV_ERR_INVALID, "cv_jpeg_info: null argument");
+        cvjpeg::parse_info(bytes, len, reinterpret_cast<cvjpeg::Info*>(info));
+        return Status();
+    });
+}
+
+int cv_jpeg_entropy_decode(const uint8_t* bytes, size_t len, int16_t* coeffs, size_t capacity, uint16_t* qtables) {
+    return guarded("cv_jpeg_entropy_decode", [&]() -> Status {
+        if (!bytes || !coeffs || !qtables) return fail(CV_ERR_INVALID, "cv_jpeg_entropy_decode: null argument");
+        char why[200];
+        if (cvjpeg::entropy_decode(bytes, len, coeffs, capacity, qtables, nullptr, why, sizeof why) != cvjpeg::kOk)
+            return fail(CV_ERR_INVALID, std::string("cv_jpeg_entropy_decode: ") + why);
+        return Status();
+    });
+}
+
+int cv_jpeg_reconstruct_u8(cv_engine_t* eng, const int16_t* coeffs, const uint16_t* qtables, int n, const cv_jpeg_info_t* info,
+                           int channel_order, uint8_t* planes, size_t planes_bytes, uint8_t* dst, void* stream) {
+    return guarded("cv_jpeg_reconstruct_u8", [&]() -> Status {
+        CV_TRY(check_engine(eng));
+        if (!coeffs || !qtables || !info || !planes || !dst || n <= 0) return fail(CV_ERR_INVALID, "cv_jpeg_reconstruct_u8: bad argument");
+        const cvjpeg::Info& in = *reinterpret_cast<const cvjpeg::Info*>(info);
+        CV_TRY(check_jpeg_info(in));
+        if (channel_order != CV_JPEG_BGR && channel_order != CV_JPEG_RGB && channel_order != CV_JPEG_GRAY)
+            return fail(CV_ERR_INVALID, "cv_jpeg_reconstruct_u8: unknown channel order");
+        if (channel_order == CV_JPEG_GRAY && in.components != 1)
+            return fail(CV_ERR_INVALID, "cv_jpeg_reconstruct_u8: gray output is for 1-component streams only");
+        if (((uintptr_t)coeffs & 15u) || ((uintptr_t)qtables & 15u) || ((uintptr_t)planes & 7u))
+            return fail(CV_ERR_INVALID, "cv_jpeg_reconstruct_u8: coeffs and qtables must be 16-byte aligned, planes 8-byte aligned");
+        if ((size_t)n > ((size_t)1 << 31) / cvjpeg::layout_of(in).blocks) return fail(CV_ERR_INVALID, "cv_jpeg_reconstruct_u8: batch too large");
+        if (planes_bytes < jpeg_planes_bytes(in, n)) return fail(CV_ERR_INVALID, "cv_jpeg_reconstruct_u8: planes buffer too small");
+        DeviceGuard g(eng->impl.device);
+        const hipError_t e = jpeg_reconstruct_u8(coeffs, qtables, n, in, channel_order, planes, dst, (hipStream_t)stream);
+        if (e != hipSuccess) return hip_fail(e, "jpeg_reconstruct_u8");
+        return Status();
+    });
+}
+
+int cv_process_jpeg(cv_engine_t* unet_engine, cv_engine_t* classifier_engine, const uint8_t* bytes, size_t len, float threshold, int flip,
+                    int fallback_quad, cv_image_result_t* out, size_t out_size, void* stream) {
+    return guarded("cv_process_jpeg", [&]() -> Status {
+        if (!bytes) return fail(CV_ERR_INVALID, "cv_process_jpeg: null stream");
+        ImageFront front;
+        front.jpeg = bytes;
+        front.jpeg_len = len;
+        cvjpeg::parse_info(bytes, len, &front.info);
+        CV_TRY(check_jpeg_info(front.info));
+        return process_image(unet_engine, classifier_engine, front, front.info.height, front.info.width, threshold, flip, fallback_quad, out,
+                             out_size, stream);
+    });
+}
+
 }  // extern "C"
+
+// ---- the JPEG decoder's two halves are part of this translation unit -------------------------------------------------------
+// The library's list of units is fixed (every build of it, the host-only sanitizer builds included, compiles and links exactly
+// that list).  jpeg.cpp stays a plain C++17 file that g++ compiles on its own; jpeg.hip holds the two kernels and their launch wrapper.
+#include "jpeg.cpp"
+#include "jpeg.hip"

@@ -580,6 +580,55 @@ int cv_process_image_v2(cv_engine_t* unet_engine, cv_engine_t* classifier_engine
 int cv_process_image(cv_engine_t* unet_engine, cv_engine_t* classifier_engine, const uint8_t* image, int h, int w,
                      float threshold, int flip, int fallback_quad, cv_image_result_t* out, void* stream);
 
+/* ---- JPEG decode (additions under ABI 6: look the symbols up with dlsym; the version stays 6) ------------------------------------ */
+/* Baseline / extended sequential Huffman JPEG, 8 bit, one interleaved scan; 1 component, or 3 components (YCbCr) with luma sampling
+ * 1x1, 2x1 or 2x2 and chroma 1x1.  The decode is split where the hardware splits it: the serial Huffman stage on the host
+ * (cv_jpeg_entropy_decode, one image per host thread), everything after it on the device (cv_jpeg_reconstruct_u8).  The pixels are
+ * those of libjpeg with its defaults (JDCT_ISLOW, fancy up-sampling, fixed-point YCbCr tables), i.e. of cv2.imdecode without
+ * EXIF rotation and of Pillow, byte for byte, on every stream an encoder writes.  Progressive, arithmetic, lossless, hierarchical and
+ * 12-bit streams, 4 components, Adobe RGB, other sampling factors, several scans and truncated or corrupt data are refused with
+ * CV_ERR_INVALID and a message naming the reason and the byte offset; no partial image is ever returned. */
+typedef struct cv_jpeg_info {
+    int32_t width, height;
+    int32_t components;          /* 1 or 3 */
+    int32_t luma_h, luma_v;      /* luma sampling factors; 1 x 1 for a 1-component stream */
+    int32_t restart_interval;    /* MCUs between restart markers, 0: none */
+    int32_t orientation;         /* EXIF orientation tag (1..8), 0: absent.  Reported, never applied. */
+    int32_t supported;           /* 0: this library does not decode the stream; `reason` says why */
+    char    reason[160];         /* empty when supported */
+} cv_jpeg_info_t;
+enum { CV_JPEG_BGR = 0, CV_JPEG_RGB = 1, CV_JPEG_GRAY = 2 };
+
+/* Parse the markers up to the first scan.  HOST only, no engine, no HIP call.  CV_OK whenever *info was filled: an unsupported,
+ * truncated or corrupt header comes back as supported = 0 with its reason, not as an error code. */
+int cv_jpeg_info(const uint8_t* bytes, size_t len, cv_jpeg_info_t* info);
+/* The Huffman stage of one image.  HOST only, no engine, no HIP call; thread-safe; `coeffs` may be page-locked memory.
+ *   coeffs: `capacity` int16 elements, at least 64 x the blocks of the stream: one plane of 8 x 8 blocks per component,
+ *   [component][block_row][block_col][64], natural (de-zigzagged) order, padded to whole MCUs (MCU = 8 luma_h x 8 luma_v pixels;
+ *   component 0 has luma_h x luma_v blocks per MCU, the others one; a 1-component stream has MCUs of one block).
+ *   qtables: components x 64 uint16, natural order, the table of each component.
+ * CV_ERR_INVALID with the reason and byte offset for every stream cv_jpeg_info reports as unsupported, for a capacity too small, and
+ * for entropy data that is truncated or corrupt (a code that is not in its table, a coefficient index past 63, a wrong restart
+ * marker, no EOI behind the scan); `coeffs` holds nothing of use then. */
+int cv_jpeg_entropy_decode(const uint8_t* bytes, size_t len, int16_t* coeffs, size_t capacity, uint16_t* qtables);
+/* Dequantise + inverse DCT, chroma up-sampling and colour conversion of n images of ONE geometry, asynchronously on `stream`: two
+ * launches, no allocation, no synchronisation.
+ *   coeffs: DEVICE, n x (64 x blocks) int16 as cv_jpeg_entropy_decode writes them, 16-BYTE ALIGNED; qtables: DEVICE, n x components
+ *   x 64 uint16, 16-byte aligned (each image has its own tables); info: HOST, the geometry all n images share;
+ *   planes: DEVICE scratch between the two launches, at least n x 64 x blocks bytes (planes_bytes says how many there are), 8-byte
+ *   aligned; dst: DEVICE, (n, height, width, 3) uint8 in channel_order CV_JPEG_BGR / CV_JPEG_RGB (a 1-component stream is replicated
+ *   into the three channels), or (n, height, width) for CV_JPEG_GRAY (1-component streams only), any alignment.
+ * CV_ERR_INVALID for a misaligned pointer, a short planes buffer or an info record that is not supported. */
+int cv_jpeg_reconstruct_u8(cv_engine_t* eng, const int16_t* coeffs, const uint16_t* qtables, int n, const cv_jpeg_info_t* info,
+                           int channel_order, uint8_t* planes, size_t planes_bytes, uint8_t* dst, void* stream);
+/* cv_process_image_v2 with a different front: `bytes` is a JPEG stream instead of decoded pixels.  The entropy stage writes into the
+ * extractor engine's page-locked block, the coefficients are uploaded and reconstructed (BGR) into the device image where
+ * cv_process_image_v2 copies the caller's pixels; everything after that is the same code.  The quadrangle is in the stream's pixel
+ * coordinates; EXIF orientation is not applied.  The engine's staging blocks grow by the coefficient pieces at the first call.
+ * CV_ERR_INVALID with the parser's reason for a stream that is not supported. */
+int cv_process_jpeg(cv_engine_t* unet_engine, cv_engine_t* classifier_engine, const uint8_t* bytes, size_t len, float threshold,
+                    int flip, int fallback_quad, cv_image_result_t* out, size_t out_size, void* stream);
+
 /* MFMA lane-map self test: computes D = A(16xK) * B(Kx16) with the kernels' fragment loaders for both
  * precisions and returns the max abs error against a host reference (used by tests; 0 expected). */
 int cv_selftest_mfma(cv_engine_t* eng, float* max_err_f16, float* max_err_f32);
