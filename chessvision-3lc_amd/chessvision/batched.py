@@ -62,6 +62,13 @@ class Boards:
     probs: torch.Tensor | None = None           # pinned (found*64,13) f32
     cls_emb: torch.Tensor | None = None         # pinned (found*64,512) f32 classifier embeddings, ``embeddings`` only (behind probs_ready)
     probs_ready: torch.cuda.Event | None = None     # download stream: boards and probabilities have landed
+    # ``board_jpeg`` only: the encoder's device tensors (out, offsets, lengths), their pinned offsets / lengths and the event behind those
+    jpeg_dev: tuple | None = None
+    jpeg_offsets: torch.Tensor | None = None    # pinned (found + 1,) int64
+    jpeg_lengths: torch.Tensor | None = None    # pinned (found,) int32
+    jpeg_sized: torch.cuda.Event | None = None  # download stream: offsets and lengths have landed
+    jpeg_bytes: torch.Tensor | None = None      # pinned: exactly the bytes the files occupy (``_Call.fetch_jpegs``)
+    jpegs: list | None = None                   # the files, one ``bytes`` per board
 
 
 @dataclass(slots=True)
@@ -118,6 +125,7 @@ class _ImageSlot:
     position: PositionResult | None = None
     unet_emb: np.ndarray | None = None
     cls_emb: np.ndarray | None = None
+    jpeg: bytes | None = None
 
 
 def _pinned(shape, dtype):
@@ -154,8 +162,10 @@ def score_positions(ids, found, probs, validated, fix_lists, true, flip) -> list
 class _Call:
     """The state one ``process_images`` call shares between its stages.  ``run`` makes the compute stream ``main`` the current one."""
 
+    board_jpeg = None                                    # the class default: a call built without __init__ (the recorders) encodes nothing
+
     def __init__(self, cv, images, threshold, flip, fallback_quad, return_crops, timings, quality, started, targets=None,
-                 embeddings=False, resize="area"):
+                 embeddings=False, resize="area", board_jpeg=None):
         for image in images:
             assert isinstance(image, np.ndarray) and image.dtype == np.uint8 and image.ndim == 3
         _ = cv.board_extractor, cv.classifier
@@ -163,6 +173,7 @@ class _Call:
         self.resize = resize                             # "area" | "antialias": how a photo becomes the UNet's input (forward)
         self.targets = targets                           # evaluation.Targets of an evaluate_images call, else None
         self.embeddings = bool(embeddings)               # both forwards also pool their hook tensor (HipEngine: want_embedding)
+        self.board_jpeg = None if board_jpeg is None else int(board_jpeg)   # a quality: every found board also comes back as a JPEG file
         self.threshold, self.flip, self.fallback_quad, self.return_crops, self.quality = threshold, flip, fallback_quad, return_crops, quality
         self.eng, self.eng_cls, self.dev = cv._get_engine("unet"), cv._get_engine("resnet18"), cv.device
         self.names = constants.SQUARE_NAMES_FLIPPED if flip else constants.SQUARE_NAMES_NORMAL
@@ -185,6 +196,8 @@ class _Call:
             self.tm.setdefault("quality", 0.0)           # host seconds of the score stage (its kernel: quality_ms)
         if targets is not None:
             self.tm.setdefault("evaluation", 0.0)        # host seconds of the ground-truth scores (the kernel: seg_ms)
+        if self.board_jpeg is not None:
+            self.tm.setdefault("fetch_jpeg_s", 0.0)      # host seconds waiting for the files (the kernels: encode_ms)
         self.gpu_events: list[tuple[str, torch.cuda.Event, torch.cuda.Event]] = []
         self.slots: list[_ImageSlot | None] = [None] * len(images)
 
@@ -349,7 +362,45 @@ class _Call:
                 rec.cls_emb = _pinned(tuple(cls_emb.shape), torch.float32)
                 rec.cls_emb.copy_(cls_emb, non_blocking=True)
             rec.probs_ready.record()
+        if self.board_jpeg is not None:
+            self.encode_boards(job, rec, boards_dev)
         return rec
+
+    def encode_boards(self, job: Job, rec: Boards, boards_dev) -> None:
+        """``board_jpeg``: the encoder is queued on the boards where the warp left them, behind the classifier (the probabilities are
+        not held back); the offsets and lengths start back on the download stream.  The device tensors ride in ``job.cls_out``."""
+        m = len(rec.found)
+        rec.jpeg_dev = self.gpu_timed("encode_ms", self.eng.jpeg_encode_gray_dev, boards_dev, self.board_jpeg)
+        encoded = torch.cuda.Event()
+        encoded.record()
+        job.cls_out.append(rec.jpeg_dev)
+        rec.jpeg_offsets, rec.jpeg_lengths = _pinned((m + 1,), torch.int64), _pinned((m,), torch.int32)
+        rec.jpeg_sized = torch.cuda.Event()
+        with torch.cuda.stream(self.down):
+            self.down.wait_event(encoded)
+            rec.jpeg_offsets.copy_(rec.jpeg_dev[1], non_blocking=True)
+            rec.jpeg_lengths.copy_(rec.jpeg_dev[2], non_blocking=True)
+            rec.jpeg_sized.record()
+
+    def fetch_jpegs(self, recs: list) -> None:
+        """The files of the landed records: once the sizes are known, exactly the bytes the files occupy (each rounded up to 16)
+        travel back on the download stream -- never the worst-case capacity of the device buffer."""
+        t0 = time.perf_counter()
+        landed = []
+        for rec in recs:
+            rec.jpeg_sized.synchronize()
+            total = int(rec.jpeg_offsets[-1])
+            rec.jpeg_bytes = _pinned((total,), torch.uint8)
+            landed.append(torch.cuda.Event())
+            with torch.cuda.stream(self.down):
+                rec.jpeg_bytes.copy_(rec.jpeg_dev[0][:total], non_blocking=True)
+                landed[-1].record()
+        for rec, event in zip(recs, landed):
+            event.synchronize()
+            host, off, ln = rec.jpeg_bytes.numpy(), rec.jpeg_offsets.numpy(), rec.jpeg_lengths.numpy()
+            rec.jpegs = [host[int(o):int(o) + int(n)].tobytes() for o, n in zip(off[:-1], ln)]
+            rec.jpeg_dev = None
+        self.clock("fetch_jpeg_s", t0)
 
     def classify(self, job: Job) -> None:
         """masks -> quadrangles (host) -> warp + split + classifier (device); boards and probabilities start back."""
@@ -400,12 +451,17 @@ class _Call:
         for rec in job.boards:
             rec.probs_ready.synchronize()
         self.clock("wait_probs_s", t0)
+        if self.board_jpeg is not None and job.boards:
+            self.fetch_jpegs(job.boards)
         for rec in job.boards:
             for k, (quad, board, position, cls_emb, scores) in zip(rec.found, self.decode(job, rec)):
                 slot = slots[ids[k]]
                 slot.quad, slot.board, slot.position, slot.cls_emb = quad, board, position, cls_emb
                 if scores is not None:
                     self.targets.position[ids[k]] = scores
+            if rec.jpegs is not None:
+                for k, blob in zip(rec.found, rec.jpegs):
+                    slots[ids[k]].jpeg = blob
 
     def decode(self, job: Job, rec: Boards) -> list[tuple]:
         """A landed ``Boards`` record -> per board (quadrangle, board image, ``PositionResult``, classifier-embedding rows | None,
@@ -475,22 +531,25 @@ class _Call:
                                              quality=s.quality))
             if emb is not None:
                 results[-1].embeddings = emb             # an attribute, not a constructor argument (cv_types.ChessVisionResult)
+            if self.board_jpeg is not None:
+                results[-1].board_jpeg = s.jpeg          # likewise; None where no board was found
         self.clock("assemble_s", t0)
         return results
 
 
 def process_images(cv, images, threshold, flip, fallback_quad, pipeline_chunk, return_crops, timings, first_job, last_job,
-                   quality, targets=None, embeddings=False, resize="area") -> list[ChessVisionResult]:
+                   quality, targets=None, embeddings=False, resize="area", board_jpeg=None) -> list[ChessVisionResult]:
     """``ChessVision.process_images`` on the instance's native engines (arguments: see there).  ``targets`` (``evaluation.Targets``,
     from ``ChessVision.evaluate_images``) additionally scores every job against its ground truth and leaves the records there;
     ``embeddings`` attaches an ``Embeddings`` record to every result; ``resize`` ("area" | "antialias") chooses how a photo becomes
-    the UNet's input (``_Call.forward``)."""
+    the UNet's input (``_Call.forward``); ``board_jpeg`` (an int quality, None = off) also returns every found board as a JPEG file,
+    encoded on the device (``_Call.encode_boards``)."""
     started = time.time()
     if resize not in RESIZE_MODES:
         raise ValueError(f"resize must be one of {RESIZE_MODES}, got {resize!r}")
     if not images:
         return []
-    call = _Call(cv, images, threshold, flip, fallback_quad, return_crops, timings, quality, started, targets, embeddings, resize)
+    call = _Call(cv, images, threshold, flip, fallback_quad, return_crops, timings, quality, started, targets, embeddings, resize, board_jpeg)
     return run(call, plan_jobs([im.shape for im in images], pipeline_chunk, first=int(first_job), last=int(last_job)))
 
 

@@ -496,7 +496,8 @@ class ChessVision:
     def process_images(self, images: Sequence[NDArray[np.uint8]], threshold: float = 0.5, flip: bool = False,
                        fallback_quad: bool = False, pipeline_chunk: int = 64, return_crops: bool = True,
                        timings: dict | None = None, first_job: int = 16, last_job: int = 0, resize: str = "area",
-                       embeddings: bool = False, quality: str | None = None) -> list[ChessVisionResult]:
+                       embeddings: bool = False, board_jpeg: int | None = None,
+                       quality: str | None = None) -> list[ChessVisionResult]:
         """Batched pipeline (``chessvision/batched.py``): the native stages of ``process_image``, cut into jobs of up to
         ``pipeline_chunk`` equally sized images and software-pipelined; the first job of a call is cut to ``first_job`` images and
         the last one to ``last_job`` (0: no split).  A call whose f16-based engine reports a non-finite value is repeated as a whole
@@ -538,12 +539,56 @@ class ChessVision:
         ``ValueError`` before anything is launched; a call repeated on the exact-f32 instance keeps its mode.  Out of scope: the
         single-image ``process_image`` / ``extract_board`` / ``cv_process_image_v2`` (the core.py:212 path: they stay INTER_AREA),
         ``distributed.process_images_sharded``, torchvision's uint8 path (fixed-point weights), PIL's resize (train_unet.py:52), and
-        float-tensor inputs, including the job's ``(x * 255).astype(uint8)`` round trip of the photo."""
+        float-tensor inputs, including the job's ``(x * 255).astype(uint8)`` round trip of the photo.
+
+        ``board_jpeg`` (an int quality, clamped to 1..100 as libjpeg clamps it; None = off: nothing extra is launched, allocated,
+        copied or returned) attaches ``result.board_jpeg``: the rectified board as a complete baseline JPEG file (``bytes``), what the
+        reference's endpoint writes to ``boards/<uuid>.jpg`` -- byte for byte the file libjpeg (Pillow) writes for
+        ``board_extraction.board_image`` at that quality; None where no board was found.  The encoder (``csrc/jpeg_enc.hip``) is queued
+        on the boards where the warp left them, behind the classifier; the file sizes and then exactly the files' bytes travel back
+        on the download stream behind events.  ``board_image`` still comes back; ``timings`` gains ``encode_ms`` (device) and
+        ``fetch_jpeg_s`` (host).  A call repeated on the exact-f32 instance keeps the keyword.  Out of scope: colour, optimised
+        Huffman tables, progressive, restart markers, EXIF, PNG, the single-image API, ``process_images_sharded``, ``evaluate_*`` and
+        per-square files (``encode_gray`` takes the crops)."""
         if quality not in (None, "logits", "sigmoid"):
             raise ValueError(f"quality must be None, 'logits' or 'sigmoid', got {quality!r}")
         self._check_resize(resize)
+        extra = self._board_jpeg_keyword(board_jpeg)
         return self._recover(lambda cv: cv._process_images_native(images, threshold, flip, fallback_quad, pipeline_chunk, return_crops,
-                                                                  timings, first_job, last_job, quality, None, bool(embeddings), resize))
+                                                                  timings, first_job, last_job, quality, None, bool(embeddings), resize,
+                                                                  **extra))
+
+    @staticmethod
+    def _board_jpeg_keyword(board_jpeg) -> dict:
+        """The keyword the native calls take for ``board_jpeg``: named only when it is on, so an off call is the call it always was."""
+        if board_jpeg is None:
+            return {}
+        if isinstance(board_jpeg, bool) or not isinstance(board_jpeg, (int, np.integer)):
+            raise ValueError(f"board_jpeg must be None or an int quality, got {board_jpeg!r}")
+        return {"board_jpeg": int(board_jpeg)}
+
+    def encode_gray(self, images: Sequence[NDArray[np.uint8]], quality: int = 95) -> list[bytes]:
+        """Gray host arrays ``(h, w)`` uint8 of any mix of sizes (1..4096 each way) -> complete baseline JPEG files in input order:
+        byte for byte what ``PIL.Image.fromarray(a, "L").save(f, "JPEG", quality=quality)`` writes.  Images are grouped by shape
+        (as ``decode_jpegs`` groups by geometry); each group is one ``HipEngine.jpeg_encode_gray``.  The 64 x 64 crops of
+        ``extract_squares`` (``(64, 64, 1)`` arrays are taken too), the training-folder format, go through this."""
+        arrays = [np.asarray(a) for a in images]
+        for a in arrays:
+            if a.dtype != np.uint8 or not (a.ndim == 2 or (a.ndim == 3 and a.shape[2] == 1)) or a.size == 0:
+                raise ValueError("encode_gray expects non-empty (h, w) or (h, w, 1) uint8 arrays")
+        groups: dict[tuple, list[int]] = {}
+        for i, a in enumerate(arrays):
+            groups.setdefault(a.shape[:2], []).append(i)
+        out: list = [None] * len(arrays)
+        eng = self._get_engine("unet")
+        for shape, ids in groups.items():
+            step = max(1, (64 << 20) // (shape[0] * shape[1]))       # 64 MB of pixels per upload
+            for k0 in range(0, len(ids), step):
+                part = ids[k0:k0 + step]
+                files = eng.jpeg_encode_gray(np.stack([arrays[i].reshape(shape) for i in part]), quality)
+                for i, blob in zip(part, files):
+                    out[i] = blob
+        return out
 
     # ---- encoded input: JPEG streams in, the decode inside the library (chessvision/jpeg.py, csrc/jpeg.cpp, csrc/jpeg.hip) ----------
     def process_jpeg(self, blob, threshold: float = 0.5, flip: bool = False) -> ChessVisionResult:
@@ -584,7 +629,7 @@ class ChessVision:
 
     def process_encoded(self, blobs: Sequence[bytes], threshold: float = 0.5, flip: bool = False, fallback_quad: bool = False,
                         pipeline_chunk: int = 64, return_crops: bool = True, timings: dict | None = None, first_job: int = 16,
-                        last_job: int = 0, resize: str = "area", embeddings: bool = False,
+                        last_job: int = 0, resize: str = "area", embeddings: bool = False, board_jpeg: int | None = None,
                         quality: str | None = None) -> list[ChessVisionResult]:
         """``process_images`` for JPEG streams: every keyword and the result type are ``process_images``'s, and so are the results,
         bit for bit, of the photos the streams decode to (libjpeg's pixels, BGR; EXIF orientation not applied).
@@ -594,21 +639,22 @@ class ChessVision:
         are planned by ``plan_jobs`` on the geometry (size, components, sampling).  In the upload stage the copy threads run the Huffman
         stage straight into the pinned staging buffer, the coefficients travel where the pixels did, and two launches at the head of
         the job's compute reconstruct its photos on the device (``chessvision/encoded.py``).  ``timings`` gains ``entropy_s`` (host
-        seconds in the Huffman stage) and ``jpeg_ms`` (device)."""
+        seconds in the Huffman stage) and ``jpeg_ms`` (device).  ``board_jpeg`` as in ``process_images``."""
         from . import jpeg
 
         if quality not in (None, "logits", "sigmoid"):
             raise ValueError(f"quality must be None, 'logits' or 'sigmoid', got {quality!r}")
         self._check_resize(resize)
+        extra = self._board_jpeg_keyword(board_jpeg)
         blobs = [bytes(b) for b in blobs]
         infos = jpeg.parse_all(blobs)
         return self._recover(lambda cv: cv._process_encoded_native(blobs, infos, threshold, flip, fallback_quad, pipeline_chunk, return_crops,
-                                                                   timings, first_job, last_job, quality, bool(embeddings), resize))
+                                                                   timings, first_job, last_job, quality, bool(embeddings), resize, **extra))
 
-    def _process_encoded_native(self, *args) -> list[ChessVisionResult]:
+    def _process_encoded_native(self, *args, **kw) -> list[ChessVisionResult]:
         from . import encoded
 
-        return encoded.process_encoded(self, *args)
+        return encoded.process_encoded(self, *args, **kw)
 
     @staticmethod
     def _check_resize(resize) -> None:
@@ -617,10 +663,10 @@ class ChessVision:
         if resize not in RESIZE_MODES:
             raise ValueError(f"resize must be one of {RESIZE_MODES}, got {resize!r}")
 
-    def _process_images_native(self, *args) -> list[ChessVisionResult]:
+    def _process_images_native(self, *args, **kw) -> list[ChessVisionResult]:
         from . import batched
 
-        return batched.process_images(self, *args)
+        return batched.process_images(self, *args, **kw)
 
     def evaluate_images(self, images: Sequence[NDArray[np.uint8]], true_fens: Sequence[str | None] | None = None,
                         label_masks: Sequence[NDArray[np.uint8] | None] | None = None, threshold: float = 0.5, flip: bool = False,

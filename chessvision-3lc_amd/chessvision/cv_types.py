@@ -89,6 +89,10 @@ class ChessVisionResult:
     # batched pipeline after construction: the dataclass fields (the constructor's arguments and their order) end with ``quality``, as
     # tests/test_quality_cpu.py and tests/test_evaluation_cpu.py pin them.
     embeddings = None
+    # process_images(board_jpeg=q) / process_encoded(board_jpeg=q) only; NOT a reference field: the rectified board as the complete
+    # baseline JPEG file libjpeg writes for ``board_extraction.board_image`` at that quality (``bytes``; None where no board was found).
+    # An attribute set after construction, like ``embeddings``.
+    board_jpeg = None
 
 
 @dataclass

@@ -80,10 +80,10 @@ class _EncodedCall(_Call):
 
 
 def process_encoded(cv, blobs, infos, threshold, flip, fallback_quad, pipeline_chunk, return_crops, timings, first_job, last_job,
-                    quality, embeddings=False, resize="area"):
+                    quality, embeddings=False, resize="area", board_jpeg=None):
     """``ChessVision.process_encoded`` on the instance's native engines; ``infos`` are the parsed, supported headers of ``blobs``."""
     started = time.time()
     if not blobs:
         return []
-    call = _EncodedCall(cv, blobs, infos, threshold, flip, fallback_quad, return_crops, timings, quality, started, None, embeddings, resize)
+    call = _EncodedCall(cv, blobs, infos, threshold, flip, fallback_quad, return_crops, timings, quality, started, None, embeddings, resize, board_jpeg)
     return run(call, plan_jobs([f.geometry for f in infos], pipeline_chunk, first=int(first_job), last=int(last_job)))

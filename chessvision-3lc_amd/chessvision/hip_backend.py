@@ -146,6 +146,9 @@ SYMBOLS = [
     ("cv_jpeg_entropy_decode", _i, [_vp, ctypes.c_size_t, _vp, ctypes.c_size_t, _vp]),
     ("cv_jpeg_reconstruct_u8", _i, [_vp, _vp, _vp, _i, _vp, _i, _vp, ctypes.c_size_t, _vp, _vp]),
     ("cv_process_jpeg", _i, [_vp, _vp, _vp, ctypes.c_size_t, _f, _i, _i, ctypes.c_void_p, ctypes.c_size_t, _vp]),
+    ("cv_jpeg_gray_header", _i, [_i, _i, _i, _vp, _vp]),
+    ("cv_jpeg_gray_max_bytes", _i, [_i, _i, ctypes.POINTER(ctypes.c_size_t)]),
+    ("cv_jpeg_encode_gray_u8", _i, [_vp, _vp, _i, _i, _i, _i, _vp, ctypes.c_size_t, _vp, _vp, _vp]),
 ]
 
 # cv_score_record_t (include/chessvision_hip.h): one 64-byte record per image
@@ -487,6 +490,21 @@ def _image_result_dict(res, arrays) -> dict:
                    fen=res.fen.decode(), original_fen=res.original_fen.decode(),
                    fixes=[(int(res.fixes[4 * i + 1]), int(res.fixes[4 * i + 2]), int(res.fixes[4 * i + 3])) for i in range(res.n_fixes)])
     return out
+
+
+def jpeg_gray_max_bytes(h: int, w: int) -> int:
+    """The largest file ``HipEngine.jpeg_encode_gray`` can write for an h x w image (``cv_jpeg_gray_max_bytes``)."""
+    v = ctypes.c_size_t(0)
+    _check(load_library().cv_jpeg_gray_max_bytes(int(h), int(w), ctypes.byref(v)))
+    return int(v.value)
+
+
+def jpeg_gray_header(h: int, w: int, quality: int = 95):
+    """``(header, qtable)``: the 328 bytes libjpeg writes in front of a gray image's entropy-coded segment and the (64,) uint16
+    quantisation table in natural order (``cv_jpeg_gray_header``; host only)."""
+    header, qt = np.zeros(328, np.uint8), np.zeros(64, np.uint16)
+    _check(load_library().cv_jpeg_gray_header(int(h), int(w), int(quality), header.ctypes.data, qt.ctypes.data))
+    return header.tobytes(), qt
 
 
 def decode_positions(probabilities: np.ndarray, flip: bool = False):
@@ -945,6 +963,51 @@ class HipEngine:
         out = self.jpeg_reconstruct_dev(dev[:n * count].view(n, count), dev[n * count:].view(n, info.components, 64), info, channel_order)
         torch.cuda.current_stream(self.device).synchronize()          # the page-locked buffer is released on return
         return out
+
+    # -- JPEG encode: tables and header on the host (csrc/jpeg.cpp), everything else on the device (csrc/jpeg_enc.hip) -----------
+    def jpeg_encode_gray_dev(self, images: torch.Tensor, quality: int = 95):
+        """Device form: ``images`` (n, h, w) uint8 on the device, n >= 1, h and w 1..4096 -> ``(out, offsets, lengths)`` device tensors:
+        file i is ``out[offsets[i] : offsets[i] + lengths[i]]`` (uint8; int64 offsets in 16-byte steps, n + 1 of them: the last is the
+        end of the last file; int32 lengths).  ``out`` is sized for the worst case (``jpeg_gray_max_bytes`` per image) and is never
+        meant to be downloaded whole.  Launches on the current stream; nothing waits."""
+        if not isinstance(images, torch.Tensor) or images.dtype != torch.uint8 or images.dim() != 3 or images.device != self.device \
+                or not images.is_contiguous():
+            raise HipBackendError("jpeg_encode_gray_dev expects a contiguous (n, h, w) uint8 tensor on the engine's device")
+        n, h, w = (int(v) for v in images.shape)
+        if n < 1 or not (1 <= h <= 4096 and 1 <= w <= 4096):
+            raise HipBackendError("jpeg_encode_gray_dev: n >= 1 images of 1..4096 x 1..4096 pixels")
+        each = jpeg_gray_max_bytes(h, w)
+        out = torch.empty(n * each, dtype=torch.uint8, device=self.device)
+        offsets = torch.empty(n + 1, dtype=torch.int64, device=self.device)
+        lengths = torch.empty(n, dtype=torch.int32, device=self.device)
+        _check(self._lib.cv_jpeg_encode_gray_u8(self._h, _ptr(images), n, h, w, int(quality), _ptr(out), out.numel(), _ptr(offsets),
+                                                _ptr(lengths), _stream_ptr(self.device)))
+        return out, offsets, lengths
+
+    def jpeg_encode_gray(self, images, quality: int = 95) -> list:
+        """Gray images of ONE size, (n, h, w) uint8 as a device tensor or a numpy array -> n complete baseline JPEG files (``bytes``):
+        libjpeg's with its defaults, byte for byte (``jpeg.encode_gray`` is the numpy form).  The offsets and lengths come back first,
+        then exactly the bytes the files occupy; both waits are on events of the current stream, never device-wide."""
+        if isinstance(images, np.ndarray):
+            a = np.ascontiguousarray(images, dtype=np.uint8)
+            if a.ndim != 3:
+                raise HipBackendError("jpeg_encode_gray expects (n, h, w) uint8 images")
+            images = torch.from_numpy(a).to(self.device)
+        out, offsets, lengths = self.jpeg_encode_gray_dev(images.contiguous(), quality)
+        n = lengths.numel()
+        table = torch.empty(2 * n + 1, dtype=torch.int64, pin_memory=True)
+        table[:n + 1].copy_(offsets, non_blocking=True)
+        table[n + 1:].copy_(lengths, non_blocking=True)          # widened on the device, one more small launch
+        landed = torch.cuda.Event()
+        landed.record()
+        landed.synchronize()
+        t = table.numpy()
+        host = torch.empty(int(t[n]), dtype=torch.uint8, pin_memory=True)
+        host.copy_(out[:int(t[n])], non_blocking=True)
+        landed.record()
+        landed.synchronize()
+        h = host.numpy()
+        return [h[int(t[i]):int(t[i]) + int(t[n + 1 + i])].tobytes() for i in range(n)]
 
     # -- introspection ----------------------------------------------------------------------------
     def activation(self, model: str, name: str) -> np.ndarray:

@@ -251,3 +251,154 @@ def decode(blob, channel_order: str = "bgr") -> np.ndarray:
     ``HipEngine.jpeg_decode``)."""
     coeffs, qtables, info = entropy_decode(blob)
     return reconstruct(coeffs, qtables, info, channel_order)
+
+
+# ---- JPEG encode: the numpy host form of csrc/jpeg_enc.hip -----------------------------------------------------------------
+# What libjpeg writes for a one-component image with its defaults (``PIL.Image.fromarray(a, "L").save(f, "JPEG", quality=q)``):
+# baseline, the Annex K luminance table scaled by jpeg_set_quality(q, force_baseline), the "islow" integer forward DCT, the Annex K
+# DC0 / AC0 Huffman tables, a JFIF 1.1 header.  The tables below are those of ITU-T T.81 Annex K.
+ZIGZAG = np.array([0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6, 7, 14, 21, 28,
+                   35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55,
+                   62, 63])
+LUMA_QUANT = np.array([16, 11, 10, 16, 24, 40, 51, 61, 12, 12, 14, 19, 26, 58, 60, 55, 14, 13, 16, 24, 40, 57, 69, 56, 14, 17, 22, 29, 51,
+                       87, 80, 62, 18, 22, 37, 56, 68, 109, 103, 77, 24, 35, 55, 64, 81, 104, 113, 92, 49, 64, 78, 87, 103, 121, 120, 101,
+                       72, 92, 95, 98, 112, 100, 103, 99])
+DC_BITS = (0, 1, 5, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0)
+DC_VALS = tuple(range(12))
+AC_BITS = (0, 2, 1, 3, 3, 2, 4, 3, 5, 5, 4, 4, 0, 0, 1, 0x7d)
+AC_VALS = (0x01, 0x02, 0x03, 0x00, 0x04, 0x11, 0x05, 0x12, 0x21, 0x31, 0x41, 0x06, 0x13, 0x51, 0x61, 0x07, 0x22, 0x71, 0x14, 0x32, 0x81,
+           0x91, 0xa1, 0x08, 0x23, 0x42, 0xb1, 0xc1, 0x15, 0x52, 0xd1, 0xf0, 0x24, 0x33, 0x62, 0x72, 0x82, 0x09, 0x0a, 0x16, 0x17, 0x18,
+           0x19, 0x1a, 0x25, 0x26, 0x27, 0x28, 0x29, 0x2a, 0x34, 0x35, 0x36, 0x37, 0x38, 0x39, 0x3a, 0x43, 0x44, 0x45, 0x46, 0x47, 0x48,
+           0x49, 0x4a, 0x53, 0x54, 0x55, 0x56, 0x57, 0x58, 0x59, 0x5a, 0x63, 0x64, 0x65, 0x66, 0x67, 0x68, 0x69, 0x6a, 0x73, 0x74, 0x75,
+           0x76, 0x77, 0x78, 0x79, 0x7a, 0x83, 0x84, 0x85, 0x86, 0x87, 0x88, 0x89, 0x8a, 0x92, 0x93, 0x94, 0x95, 0x96, 0x97, 0x98, 0x99,
+           0x9a, 0xa2, 0xa3, 0xa4, 0xa5, 0xa6, 0xa7, 0xa8, 0xa9, 0xaa, 0xb2, 0xb3, 0xb4, 0xb5, 0xb6, 0xb7, 0xb8, 0xb9, 0xba, 0xc2, 0xc3,
+           0xc4, 0xc5, 0xc6, 0xc7, 0xc8, 0xc9, 0xca, 0xd2, 0xd3, 0xd4, 0xd5, 0xd6, 0xd7, 0xd8, 0xd9, 0xda, 0xe1, 0xe2, 0xe3, 0xe4, 0xe5,
+           0xe6, 0xe7, 0xe8, 0xe9, 0xea, 0xf1, 0xf2, 0xf3, 0xf4, 0xf5, 0xf6, 0xf7, 0xf8, 0xf9, 0xfa)
+GRAY_HEADER_BYTES = 328
+
+
+def encode_quant_table(quality: int) -> np.ndarray:
+    """``jpeg_set_quality(quality, force_baseline=TRUE)`` on the Annex K luminance table: (64,) int64 in natural order."""
+    q = min(100, max(1, int(quality)))
+    scale = 5000 // q if q < 50 else 200 - 2 * q
+    return np.clip((LUMA_QUANT.astype(np.int64) * scale + 50) // 100, 1, 255)
+
+
+def _huffman_codes(bits, vals):
+    """Annex C: ``{symbol: (code, length)}`` of a table given as its sixteen counts and its symbols."""
+    out, code, at = {}, 0, 0
+    for length in range(1, 17):
+        for _ in range(bits[length - 1]):
+            out[vals[at]] = (code, length)
+            code, at = code + 1, at + 1
+        code <<= 1
+    return out
+
+
+def gray_header(width: int, height: int, quality: int) -> bytes:
+    """The 328 bytes in front of the entropy-coded segment: SOI, APP0 (JFIF 1.1, no units, density 1 x 1), DQT, SOF0, DHT DC0, DHT AC0,
+    SOS."""
+    qt = encode_quant_table(quality)
+    out = bytearray(b"\xff\xd8\xff\xe0\x00\x10JFIF\x00\x01\x01\x00\x00\x01\x00\x01\x00\x00")
+    out += b"\xff\xdb\x00\x43\x00" + bytes(int(qt[k]) for k in ZIGZAG)
+    out += b"\xff\xc0\x00\x0b\x08" + int(height).to_bytes(2, "big") + int(width).to_bytes(2, "big") + b"\x01\x01\x11\x00"
+    out += b"\xff\xc4\x00\x1f\x00" + bytes(DC_BITS) + bytes(DC_VALS)
+    out += b"\xff\xc4\x00\xb5\x10" + bytes(AC_BITS) + bytes(AC_VALS)
+    out += b"\xff\xda\x00\x08\x01\x01\x00\x00\x3f\x00"
+    assert len(out) == GRAY_HEADER_BYTES
+    return bytes(out)
+
+
+def _fdct_pass(d, first):
+    """jfdctint.c's 8-point pass along axis 0 of an int64 array (8, ...): the row pass (``first``) leaves two extra bits, the column
+    pass takes them out again together with the three of the 8 x 8 scaling it keeps."""
+    tmp0, tmp7, tmp1, tmp6 = d[0] + d[7], d[0] - d[7], d[1] + d[6], d[1] - d[6]
+    tmp2, tmp5, tmp3, tmp4 = d[2] + d[5], d[2] - d[5], d[3] + d[4], d[3] - d[4]
+    tmp10, tmp13, tmp11, tmp12 = tmp0 + tmp3, tmp0 - tmp3, tmp1 + tmp2, tmp1 - tmp2
+    shift = 11 if first else 15
+    desc = lambda x, n: (x + (1 << (n - 1))) >> n                          # noqa: E731
+    o0 = (tmp10 + tmp11) << 2 if first else desc(tmp10 + tmp11, 2)
+    o4 = (tmp10 - tmp11) << 2 if first else desc(tmp10 - tmp11, 2)
+    z1 = (tmp12 + tmp13) * 4433
+    o2, o6 = desc(z1 + tmp13 * 6270, shift), desc(z1 - tmp12 * 15137, shift)
+    z1, z2, z3, z4 = tmp4 + tmp7, tmp5 + tmp6, tmp4 + tmp6, tmp5 + tmp7
+    z5 = (z3 + z4) * 9633
+    tmp4, tmp5, tmp6, tmp7 = tmp4 * 2446, tmp5 * 16819, tmp6 * 25172, tmp7 * 12299
+    z1, z2, z3, z4 = z1 * -7373, z2 * -20995, z3 * -16069 + z5, z4 * -3196 + z5
+    o7, o5, o3, o1 = desc(tmp4 + z1 + z3, shift), desc(tmp5 + z2 + z4, shift), desc(tmp6 + z2 + z3, shift), desc(tmp7 + z1 + z4, shift)
+    return np.stack([o0, o1, o2, o3, o4, o5, o6, o7])
+
+
+def encode_coefficients(image, quality: int = 95) -> np.ndarray:
+    """(h, w) uint8 -> (blocks, 64) int64 quantised coefficients in zigzag order, blocks in raster order: edge replication to whole
+    blocks, level shift, the islow forward DCT, division with rounding by ``q << 3``."""
+    a = np.ascontiguousarray(image, dtype=np.uint8)
+    if a.ndim != 2 or a.size == 0:
+        raise ValueError("encode_gray expects a non-empty (h, w) uint8 image")
+    h, w = a.shape
+    rows, cols = (h + 7) // 8, (w + 7) // 8
+    a = np.pad(a, ((0, rows * 8 - h), (0, cols * 8 - w)), mode="edge").astype(np.int64) - 128
+    blk = a.reshape(rows, 8, cols, 8).transpose(0, 2, 1, 3).reshape(rows * cols, 8, 8)            # [block, row, col]
+    ws = _fdct_pass(np.moveaxis(blk, 2, 0), True)                                                 # rows: ws[u, block, row]
+    out = _fdct_pass(np.moveaxis(ws, 2, 0), False)                                                # columns: out[v, u, block]
+    nat = np.transpose(out, (2, 0, 1)).reshape(rows * cols, 64)
+    d = encode_quant_table(quality) << 3
+    mag = (np.abs(nat) + (d >> 1)) // d
+    return np.where(nat < 0, -mag, mag)[:, ZIGZAG]
+
+
+def encode_gray(image, quality: int = 95) -> bytes:
+    """One gray image (h, w) uint8 -> the complete baseline JPEG file libjpeg writes for it at ``quality`` (clamped to 1..100), byte
+    for byte ``PIL.Image.fromarray(image, "L").save(f, "JPEG", quality=quality)``.  The numpy form of ``HipEngine.jpeg_encode_gray``
+    and its checker; it shares no code with the kernels."""
+    zz = encode_coefficients(image, quality)
+    h, w = np.asarray(image).shape
+    nb = zz.shape[0]
+    dc, ac = _huffman_codes(DC_BITS, DC_VALS), _huffman_codes(AC_BITS, AC_VALS)
+    dc_code, dc_len = np.array([dc[s][0] for s in range(12)], np.uint64), np.array([dc[s][1] for s in range(12)], np.int64)
+    ac_code, ac_len = np.zeros(256, np.uint64), np.zeros(256, np.int64)
+    for sym, (code, length) in ac.items():
+        ac_code[sym], ac_len[sym] = code, length
+
+    def size_and_extra(v):                                                  # category and the bits that follow its code
+        mag = np.abs(v)
+        size = np.where(mag > 0, np.floor(np.log2(np.maximum(mag, 1))).astype(np.int64) + 1, 0)
+        extra = np.where(v < 0, v - 1, v) & ((1 << size) - 1)
+        return size, extra.astype(np.uint64)
+
+    # one item per block for the DC difference, one per non-zero AC coefficient (its ZRLs in front), one per end-of-block
+    diff = zz[:, 0] - np.concatenate([[0], zz[:-1, 0]])
+    s, e = size_and_extra(diff)
+    items = [(np.arange(nb) * 65, (dc_code[s] << s.astype(np.uint64)) | e, dc_len[s] + s)]
+    pos = np.where(zz != 0, np.arange(64), -1)
+    pos[:, 0] = 0
+    prev = np.maximum.accumulate(pos, axis=1)
+    b, k = np.nonzero(zz[:, 1:])
+    k = k + 1
+    run = k - 1 - prev[b, k - 1]
+    s, e = size_and_extra(zz[b, k])
+    sym = ((run & 15) << 4) | s
+    zrl = run >> 4
+    val = (ac_code[sym] << s.astype(np.uint64)) | e
+    length = ac_len[sym] + s
+    zc, zl = int(ac_code[0xF0]), int(ac_len[0xF0])
+    for r in (1, 2, 3):
+        pre = np.uint64(sum(zc << (zl * i) for i in range(r)))
+        val = np.where(zrl == r, (pre << length.astype(np.uint64)) | val, val)
+    length = length + zrl * zl
+    items.append((b * 65 + k, val, length))
+    eob = np.nonzero(zz[:, 63] == 0)[0]
+    items.append((eob * 65 + 64, np.full(eob.size, ac_code[0], np.uint64), np.full(eob.size, ac_len[0], np.int64)))
+    key = np.concatenate([i[0] for i in items])
+    order = np.argsort(key, kind="stable")
+    val, length = np.concatenate([i[1] for i in items])[order], np.concatenate([i[2] for i in items])[order]
+    start = np.cumsum(length) - length
+    total = int(length.sum())
+    bits = np.ones((total + 7) // 8 * 8, np.uint8)                          # the last byte is filled with 1-bits
+    for j in range(int(length.max())):
+        m = length > j
+        bits[start[m] + j] = ((val[m] >> (length[m] - 1 - j).astype(np.uint64)) & np.uint64(1)).astype(np.uint8)
+    payload = np.packbits(bits)
+    ff = np.nonzero(payload == 0xFF)[0]
+    payload = np.insert(payload, ff + 1, 0)                                 # FF is followed by a stuffed 00
+    return gray_header(w, h, quality) + payload.tobytes() + b"\xff\xd9"

@@ -14,6 +14,7 @@
 #include "host_stages.h"
 #include "jpeg.h"
 #include "jpeg_device.h"
+#include "jpeg_enc_device.h"
 #include "models.h"
 #include "pipeline.h"
 #include "pointwise.h"
@@ -1430,8 +1431,63 @@ int cv_process_jpeg(cv_engine_t* unet_engine, cv_engine_t* classifier_engine, co
 
 }  // extern "C"
 
+// ---- JPEG encode: tables and header on the host (jpeg.cpp), everything else on the device (jpeg_enc.hip) ---------------------------
+int cv_jpeg_gray_max_bytes(int h, int w, size_t* bytes) {
+    return guarded("cv_jpeg_gray_max_bytes", [&]() -> Status {
+        if (!bytes || h < 1 || w < 1 || h > kJpegEncMaxSide || w > kJpegEncMaxSide)
+            return fail(CV_ERR_INVALID, "cv_jpeg_gray_max_bytes: height and width must be 1..4096");
+        *bytes = cvjpeg::gray_max_bytes(w, h);
+        return Status();
+    });
+}
+
+int cv_jpeg_gray_header(int h, int w, int quality, uint8_t* header, uint16_t* qtable) {
+    return guarded("cv_jpeg_gray_header", [&]() -> Status {
+        cvjpeg::EncTables t;
+        if (!header || cvjpeg::encoder_tables(w, h, quality, &t) != cvjpeg::kOk)
+            return fail(CV_ERR_INVALID, "cv_jpeg_gray_header: null header or a size outside 1..65535");
+        std::memcpy(header, t.header, CV_JPEG_GRAY_HEADER_BYTES);
+        if (qtable) cvjpeg::quant_table(quality, qtable);
+        return Status();
+    });
+}
+
+int cv_jpeg_encode_gray_u8(cv_engine_t* eng, const uint8_t* src, int n, int h, int w, int quality, uint8_t* out, size_t out_capacity,
+                           int64_t* offsets, int32_t* lengths, void* stream) {
+    return guarded("cv_jpeg_encode_gray_u8", [&]() -> Status {
+        CV_TRY(check_engine(eng));
+        if (!src || !out || !offsets || !lengths || n < 1) return fail(CV_ERR_INVALID, "cv_jpeg_encode_gray_u8: bad argument");
+        if (h < 1 || w < 1 || h > kJpegEncMaxSide || w > kJpegEncMaxSide)
+            return fail(CV_ERR_INVALID, "cv_jpeg_encode_gray_u8: height and width must be 1..4096");
+        const size_t each = cvjpeg::gray_max_bytes(w, h);
+        if (out_capacity / each < (size_t)n) return fail(CV_ERR_INVALID, "cv_jpeg_encode_gray_u8: out holds less than n x cv_jpeg_gray_max_bytes");
+        cvjpeg::EncTables tables;
+        if (cvjpeg::encoder_tables(w, h, quality, &tables) != cvjpeg::kOk) return fail(CV_ERR_INVALID, "cv_jpeg_encode_gray_u8: bad size");
+        Engine& E = eng->impl;
+        hipStream_t st = (hipStream_t)stream;
+        DeviceGuard g(E.device);
+        std::lock_guard<std::mutex> lk(E.mu);
+        hipError_t e = hipSuccess;
+        // the scratch has one user at a time ON THE DEVICE: this encode starts behind the previous one, whatever stream that ran on
+        if (!E.jpeg_enc_done) e = hipEventCreateWithFlags(&E.jpeg_enc_done, hipEventDisableTiming);
+        else e = hipStreamWaitEvent(st, E.jpeg_enc_done, 0);
+        if (e != hipSuccess) return hip_fail(e, "cv_jpeg_encode_gray_u8");
+        const size_t need = jpeg_encode_scratch_bytes(n, h, w);
+        if (E.jpeg_enc_scratch.bytes < need) {                   // grown for a larger geometry only: the previous encode must have left it
+            e = hipEventSynchronize(E.jpeg_enc_done);
+            if (e != hipSuccess) return hip_fail(e, "cv_jpeg_encode_gray_u8");
+            CV_TRY(E.jpeg_enc_scratch.alloc(need, false));
+        }
+        e = jpeg_encode_gray_u8(src, n, h, w, tables, E.jpeg_enc_scratch.ptr, out, offsets, lengths, st);
+        if (e == hipSuccess) e = hipEventRecord(E.jpeg_enc_done, st);
+        if (e != hipSuccess) return hip_fail(e, "jpeg_encode_gray_u8");
+        return Status();
+    });
+}
+
 // ---- the JPEG decoder's two halves are part of this translation unit -------------------------------------------------------
 // The library's list of units is fixed (every build of it, the host-only sanitizer builds included, compiles and links exactly
 // that list).  jpeg.cpp stays a plain C++17 file that g++ compiles on its own; jpeg.hip holds the two kernels and their launch wrapper.
 #include "jpeg.cpp"
 #include "jpeg.hip"
+#include "jpeg_enc.hip"

@@ -723,6 +723,7 @@ Engine::~Engine() {
     if (pipe_event) (void)hipEventDestroy(pipe_event);
     if (pipe_event2) (void)hipEventDestroy(pipe_event2);
     if (pipe_event3) (void)hipEventDestroy(pipe_event3);
+    if (jpeg_enc_done) (void)hipEventDestroy(jpeg_enc_done);
     if (pipe_side) (void)hipStreamDestroy(pipe_side);
 }
 

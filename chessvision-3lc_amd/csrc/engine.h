@@ -298,6 +298,9 @@ class Engine {
     hipEvent_t pipe_event2 = nullptr;               // cv_process_image: "the rectified board exists" -> its download on pipe_side beside the classifier
     hipStream_t pipe_side = nullptr;
     hipEvent_t pipe_event3 = nullptr;               // cv_process_image: "the board is home" (side stream) -> joined into the caller's stream on the device
+    // cv_jpeg_encode_gray_u8: one pass's worth of scratch (grown on demand, out of the block cache), and "the last encode has left it"
+    DeviceBuffer jpeg_enc_scratch;
+    hipEvent_t jpeg_enc_done = nullptr;
     ResizeTables area_tabs;                             // INTER_AREA tables of the last fractional resize geometry (cv_resize_area_u8)
     ResizeTables aa_tabs;                               // tap tables of the last antialiased resize geometry (cv_resize_antialias_f32)
 

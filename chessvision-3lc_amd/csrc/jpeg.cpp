@@ -415,4 +415,82 @@ int entropy_decode(const uint8_t* data, size_t len, int16_t* coeffs, size_t capa
     return rc;
 }
 
+// ---- encoder: quality scaling, Annex K tables, derived codes, header ---------------------------------------------------------------
+namespace {
+
+const uint8_t kLumaQuant[64] = {16, 11, 10, 16, 24,  40,  51,  61,  12, 12, 14, 19, 26,  58,  60,  55,  14, 13, 16, 24, 40,  57,
+                                69, 56, 14, 17, 22,  29,  51,  87,  80, 62, 18, 22, 37,  56,  68,  109, 103, 77, 24, 35, 55, 64,
+                                81, 104, 113, 92, 49, 64, 78,  87,  103, 121, 120, 101, 72, 92, 95, 98,  112, 100, 103, 99};
+const uint8_t kDcBits[16] = {0, 1, 5, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0};
+const uint8_t kDcVals[12] = {0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11};
+const uint8_t kAcBits[16] = {0, 2, 1, 3, 3, 2, 4, 3, 5, 5, 4, 4, 0, 0, 1, 0x7d};
+const uint8_t kAcVals[162] = {
+    0x01, 0x02, 0x03, 0x00, 0x04, 0x11, 0x05, 0x12, 0x21, 0x31, 0x41, 0x06, 0x13, 0x51, 0x61, 0x07, 0x22, 0x71, 0x14, 0x32, 0x81, 0x91, 0xa1,
+    0x08, 0x23, 0x42, 0xb1, 0xc1, 0x15, 0x52, 0xd1, 0xf0, 0x24, 0x33, 0x62, 0x72, 0x82, 0x09, 0x0a, 0x16, 0x17, 0x18, 0x19, 0x1a, 0x25, 0x26,
+    0x27, 0x28, 0x29, 0x2a, 0x34, 0x35, 0x36, 0x37, 0x38, 0x39, 0x3a, 0x43, 0x44, 0x45, 0x46, 0x47, 0x48, 0x49, 0x4a, 0x53, 0x54, 0x55, 0x56,
+    0x57, 0x58, 0x59, 0x5a, 0x63, 0x64, 0x65, 0x66, 0x67, 0x68, 0x69, 0x6a, 0x73, 0x74, 0x75, 0x76, 0x77, 0x78, 0x79, 0x7a, 0x83, 0x84, 0x85,
+    0x86, 0x87, 0x88, 0x89, 0x8a, 0x92, 0x93, 0x94, 0x95, 0x96, 0x97, 0x98, 0x99, 0x9a, 0xa2, 0xa3, 0xa4, 0xa5, 0xa6, 0xa7, 0xa8, 0xa9, 0xaa,
+    0xb2, 0xb3, 0xb4, 0xb5, 0xb6, 0xb7, 0xb8, 0xb9, 0xba, 0xc2, 0xc3, 0xc4, 0xc5, 0xc6, 0xc7, 0xc8, 0xc9, 0xca, 0xd2, 0xd3, 0xd4, 0xd5, 0xd6,
+    0xd7, 0xd8, 0xd9, 0xda, 0xe1, 0xe2, 0xe3, 0xe4, 0xe5, 0xe6, 0xe7, 0xe8, 0xe9, 0xea, 0xf1, 0xf2, 0xf3, 0xf4, 0xf5, 0xf6, 0xf7, 0xf8, 0xf9,
+    0xfa};
+
+// Annex C: the codes of a table given as its sixteen counts and its symbols, as (code << 8) | length at out[symbol]
+void derive_codes(const uint8_t bits[16], const uint8_t* vals, int nvals, uint32_t* out, int nout) {
+    uint32_t code = 0;
+    int at = 0;
+    for (int len = 1; len <= 16; ++len) {
+        for (int k = 0; k < bits[len - 1] && at < nvals; ++k, ++at, ++code)
+            if (vals[at] < nout) out[vals[at]] = (code << 8) | (uint32_t)len;
+        code <<= 1;
+    }
+}
+
+}  // namespace
+
+int clamp_quality(int quality) { return quality < 1 ? 1 : quality > 100 ? 100 : quality; }
+
+void quant_table(int quality, uint16_t out[64]) {
+    const int q = clamp_quality(quality);
+    const int scale = q < 50 ? 5000 / q : 200 - 2 * q;
+    for (int i = 0; i < 64; ++i) {
+        const int v = (kLumaQuant[i] * scale + 50) / 100;
+        out[i] = (uint16_t)(v < 1 ? 1 : v > 255 ? 255 : v);
+    }
+}
+
+size_t gray_max_bytes(int width, int height) {
+    const size_t blocks = (size_t)((width + 7) / 8) * (size_t)((height + 7) / 8);
+    const size_t payload = (blocks * kEncMaxBlockBits + 7) / 8;
+    return (kGrayHeaderBytes + 2 * payload + 2 + 15) & ~(size_t)15;
+}
+
+int encoder_tables(int width, int height, int quality, EncTables* t) {
+    if (!t || width < 1 || height < 1 || width > 65535 || height > 65535) return kInvalid;
+    std::memset(t, 0, sizeof *t);
+    uint16_t qt[64];
+    quant_table(quality, qt);
+    for (int k = 0; k < 64; ++k) t->divisor[k] = (uint16_t)(qt[kNatural[k]] << 3);
+    derive_codes(kDcBits, kDcVals, 12, t->dc, 12);
+    derive_codes(kAcBits, kAcVals, 162, t->ac, 256);
+    uint8_t* p = t->header;
+    const uint8_t app0[20] = {0xff, 0xd8, 0xff, 0xe0, 0, 16, 'J', 'F', 'I', 'F', 0, 1, 1, 0, 0, 1, 0, 1, 0, 0};
+    std::memcpy(p, app0, 20); p += 20;
+    const uint8_t dqt[5] = {0xff, 0xdb, 0, 67, 0};
+    std::memcpy(p, dqt, 5); p += 5;
+    for (int k = 0; k < 64; ++k) *p++ = (uint8_t)qt[kNatural[k]];
+    const uint8_t sof[13] = {0xff, 0xc0, 0, 11, 8, (uint8_t)(height >> 8), (uint8_t)height, (uint8_t)(width >> 8), (uint8_t)width, 1, 1, 0x11, 0};
+    std::memcpy(p, sof, 13); p += 13;
+    const uint8_t dht_dc[5] = {0xff, 0xc4, 0, 31, 0x00};
+    std::memcpy(p, dht_dc, 5); p += 5;
+    std::memcpy(p, kDcBits, 16); p += 16;
+    std::memcpy(p, kDcVals, 12); p += 12;
+    const uint8_t dht_ac[5] = {0xff, 0xc4, 0, 181, 0x10};
+    std::memcpy(p, dht_ac, 5); p += 5;
+    std::memcpy(p, kAcBits, 16); p += 16;
+    std::memcpy(p, kAcVals, 162); p += 162;
+    const uint8_t sos[10] = {0xff, 0xda, 0, 8, 1, 1, 0x00, 0, 63, 0};
+    std::memcpy(p, sos, 10); p += 10;
+    return (p - t->header) == kGrayHeaderBytes ? kOk : kInvalid;
+}
+
 }  // namespace cvjpeg

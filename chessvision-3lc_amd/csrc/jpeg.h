@@ -39,4 +39,24 @@ int parse_info(const uint8_t* data, size_t len, Info* info);
 int entropy_decode(const uint8_t* data, size_t len, int16_t* coeffs, size_t capacity, uint16_t* qtables, Info* info_out, char* err,
                    size_t err_len);
 
+// ---- the host half of the gray ENCODER (jpeg_enc.hip holds the kernels) ------------------------------------------------------------
+// What libjpeg writes for a one-component image with its defaults: baseline, the Annex K luminance table scaled by
+// jpeg_set_quality(quality, force_baseline = TRUE), the Annex K DC0 / AC0 Huffman tables, a JFIF 1.1 header.
+enum { kGrayHeaderBytes = 328, kEncMaxBlockBits = 20 + 63 * 26 };
+
+// everything the kernels read besides the pixels; handed to them by value, so nothing is uploaded or cached
+struct EncTables {
+    uint16_t divisor[64];                  // quantiser steps << 3 in ZIGZAG order (the forward DCT leaves its output scaled by 8)
+    uint32_t dc[12];                       // (code << 8) | length of each DC category
+    uint32_t ac[256];                      // (code << 8) | length of each (run << 4 | size) symbol, 0 where Annex K has none
+    uint8_t header[kGrayHeaderBytes];      // SOI, APP0 (JFIF 1.1, no units, density 1 x 1), DQT, SOF0, DHT DC0, DHT AC0, SOS
+};
+
+int clamp_quality(int quality);                            // libjpeg's: below 1 is 1, above 100 is 100
+void quant_table(int quality, uint16_t out[64]);           // natural order, every entry 1..255
+// width, height 1..65535.  Fills every field of *t; returns kInvalid for a null pointer or a size outside that range.
+int encoder_tables(int width, int height, int quality, EncTables* t);
+// bytes a file of that size can reach at most: header, every block at kEncMaxBlockBits with every byte stuffed, EOI; a multiple of 16
+size_t gray_max_bytes(int width, int height);
+
 }  // namespace cvjpeg

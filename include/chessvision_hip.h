@@ -629,6 +629,27 @@ int cv_jpeg_reconstruct_u8(cv_engine_t* eng, const int16_t* coeffs, const uint16
 int cv_process_jpeg(cv_engine_t* unet_engine, cv_engine_t* classifier_engine, const uint8_t* bytes, size_t len, float threshold,
                     int flip, int fallback_quad, cv_image_result_t* out, size_t out_size, void* stream);
 
+/* ---- JPEG encode (additions under ABI 6: look the symbols up with dlsym; the version stays 6) ------------------------------------ */
+/* Gray images to complete baseline JPEG files, byte for byte what libjpeg writes for a one-component image with its defaults
+ * (PIL.Image.fromarray(a, "L").save(f, "JPEG", quality=q)): Annex K luminance table scaled by jpeg_set_quality(q, TRUE), JDCT_ISLOW,
+ * Annex K Huffman tables DC0 / AC0, JFIF 1.1 header, no restart markers.  quality is clamped to 1..100.  Colour, optimised tables,
+ * progressive and EXIF are not written. */
+#define CV_JPEG_GRAY_HEADER_BYTES 328
+/* The bytes in front of the entropy-coded segment: SOI, APP0, DQT, SOF0, DHT, DHT, SOS.  header: CV_JPEG_GRAY_HEADER_BYTES bytes;
+ * qtable: 64 uint16 in natural order, or NULL.  Host only, no engine.  h, w: 1..65535. */
+int cv_jpeg_gray_header(int h, int w, int quality, uint8_t* header, uint16_t* qtable);
+/* The largest file an h x w image (1..4096 each) can give: header + every 8x8 block at 20 + 63 * 26 bits with every byte stuffed
+ * + EOI, a multiple of 16. */
+int cv_jpeg_gray_max_bytes(int h, int w, size_t* bytes);
+/* src: DEVICE, (n, h, w) uint8, n >= 1, h and w 1..4096.  out: DEVICE, out_capacity >= n * cv_jpeg_gray_max_bytes(h, w) bytes; offsets:
+ * DEVICE, n + 1 int64; lengths: DEVICE, n int32.  File i is the lengths[i] bytes at out + offsets[i]; offsets are multiples of 16 in
+ * input order and offsets[n] is the end of the last file rounded up, so a caller downloads out[0 .. offsets[n]) and never the capacity.
+ * Launches only, on `stream`; images are worked through in fixed chunks over scratch of the engine (at most ~90 MB whatever n, grown
+ * once per larger geometry), so n is unbounded.  The output is a pure function of pixels and quality.  Two encodes on one engine
+ * are ordered on the device, whatever their streams. */
+int cv_jpeg_encode_gray_u8(cv_engine_t* eng, const uint8_t* src, int n, int h, int w, int quality, uint8_t* out, size_t out_capacity,
+                           int64_t* offsets, int32_t* lengths, void* stream);
+
 /* MFMA lane-map self test: computes D = A(16xK) * B(Kx16) with the kernels' fragment loaders for both
  * precisions and returns the max abs error against a host reference (used by tests; 0 expected). */
 int cv_selftest_mfma(cv_engine_t* eng, float* max_err_f16, float* max_err_f32);
