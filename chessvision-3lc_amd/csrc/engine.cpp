@@ -10,8 +10,6 @@
 
 namespace cv {
 
-static int env_int(const char* name, int dflt);       // experiment switches, defined below
-
 // ---- error plumbing: thread-local message, never abort (SURVEY.md section 8b "Errors") -------------
 static thread_local std::string g_err;
 static thread_local bool g_capturing = false;
@@ -311,8 +309,21 @@ Status Activation::reserve_all(const std::vector<Activation*>& acts, int cap_) {
 // 4q..4q+3 of fragments f = 0..3 ends up with 16 consecutive channels (conv_igemm.hip epilogue).
 static inline int conv_row_to_channel(int R) {
     const int slab = R / 64, within = R % 64;
-    const int f = within / 16, i = within % 16, q = i / 4, r = i % 4;
-    return slab * 64 + q * (4 * kConvFC) + f * 4 + r;
+    return slab * 64 + frag_row_channel(kConvFC, within / 16, within % 16);
+}
+
+int row_exponent(const float* row, int n) {
+    float m = 0.f;
+    for (int k = 0; k < n; ++k) m = std::max(m, std::fabs(row[k]));
+    int e = 0;
+    if (m > 0.f) (void)std::frexp(m, &e);
+    return e;
+}
+int normalise_row(float* row, int n) {
+    const int e = row_exponent(row, n);
+    if (e != 0)
+        for (int k = 0; k < n; ++k) row[k] = std::ldexp(row[k], -e);
+    return e;
 }
 
 // A K row is a sequence of 16-byte chunks.  chunk_k0 / chunk_is_lo describe what chunk kc of the row holds:
@@ -339,10 +350,7 @@ static void pack_rows(int dt, std::vector<char>& out, int CT, int nCt, int nStag
                         const int kk = k0 + e;
                         const float v = (row < rows && kk < K) ? Wk[(size_t)row * K + kk] : 0.f;
                         if (dt == kF32) reinterpret_cast<float*>(d)[e] = v;
-                        else {
-                            const _Float16 hi = (_Float16)v;
-                            reinterpret_cast<_Float16*>(d)[e] = lo ? (_Float16)(v - (float)hi) : hi;
-                        }
+                        else reinterpret_cast<_Float16*>(d)[e] = f16_half(v, lo);
                     }
                 }
             }
@@ -366,21 +374,11 @@ static Status finish_layer(ConvLayer& L, std::vector<float>& Wk, int K, const st
         if (!std::isfinite(scale[r]) || !std::isfinite(shift[r]))
             return fail(1, L.name + ": non-finite BatchNorm scale/shift for output channel " + std::to_string(r) +
                            " (running_var + eps <= 0, or non-finite statistics)");
-    // Row normalisation (f16 / split-f16): row r is stored as w * 2^-e_r with max |w| in [0.5, 1) and 2^e_r goes into the
-    // f32 epilogue scale -- exact, and it keeps the lo halves of small trained weights out of the f16 subnormals
-    // (|w| ~ 1e-2 would otherwise keep 17 of its 22 bits, |w| ~ 1e-3 only 14).
+    // Row normalisation (models.h: normalise_row; |w| ~ 1e-2 would otherwise keep 17 of its 22 bits, |w| ~ 1e-3 only 14)
     L.h_scale.assign(L.rowsPad, 0.f);
     L.h_shift.assign(L.rowsPad, 0.f);
     for (int r = 0; r < L.rows; ++r) {
-        int e = 0;
-        if (L.dt != kF32) {
-            float m = 0.f;
-            for (int k = 0; k < K; ++k) m = std::max(m, std::fabs(Wk[(size_t)r * K + k]));
-            if (m > 0.f) {
-                (void)std::frexp(m, &e);
-                for (int k = 0; k < K; ++k) Wk[(size_t)r * K + k] = std::ldexp(Wk[(size_t)r * K + k], -e);
-            }
-        }
+        const int e = L.dt != kF32 ? normalise_row(&Wk[(size_t)r * K], K) : 0;
         L.h_scale[r] = std::ldexp(scale[r], e);
         L.h_shift[r] = shift[r];
         if (!std::isfinite(L.h_scale[r])) return fail(1, L.name + ": weight magnitude x BatchNorm scale leaves the f32 range");
@@ -618,9 +616,13 @@ Status ConvLayer::get_pos(const TensorRef& x, int Ho, int Wo, const int** tab, c
 }
 
 // experiment switches (documented in DESIGN.md / r01_tuning.md); each is read from the environment once per process
-static int env_int(const char* name, int dflt) {
+int env_int(const char* name, int dflt) {
     const char* v = std::getenv(name);
     return v && *v ? std::atoi(v) : dflt;
+}
+bool env_switch(const char* name, bool dflt) {
+    const char* v = std::getenv(name);
+    return v && (v[0] == '0' || v[0] == '1') ? v[0] == '1' : dflt;
 }
 struct Knobs {
     int halo = env_int("CV_HALO", 1), ct256 = env_int("CV_CT256", 1), ct256_min_blocks = env_int("CV_CT256_MIN_BLOCKS", 256);
@@ -786,14 +788,7 @@ Status Engine::guard_check(hipStream_t s) {
     if (!guard.ptr) return Status();
     unsigned v = 0xffffffffu;
     CV_HIP(copy_to_host_sync(&v, guard.ptr, sizeof(v), s));
-    if (v == 0xffffffffu) return Status();
-    CV_HIP(sync_memset(guard.ptr, 0xff, sizeof(unsigned)));
-    const std::string who = v < layer_names.size() ? layer_names[v] : ("layer #" + std::to_string(v));
-    if (v == 0) return fail(5, "non-finite value (NaN / inf) in the input tensor");
-    return fail(5, "non-finite value produced by '" + who + "': an activation left the range the " +
-                       (dt == kF32 ? std::string("f32") : std::string("f16-based")) +
-                       " engine can hold (|x| > 65504 * 2^exp after calibration) or a NaN reached it; results of this "
-                       "call are invalid -- use precision f32 for this checkpoint");
+    return guard_eval(v);
 }
 
 // calibration: real-valued absolute maximum of the tensor just produced
@@ -841,9 +836,84 @@ Status Engine::measure_tap_sums(ConvLayer& L, const TensorRef& x, int Ho, int Wo
 
 size_t Engine::workspace_bytes() const {
     size_t total = 0;
-    if (unet) for (const Activation* a : unet->acts) total += a->buf.bytes + a->buf32.bytes;
-    if (resnet) for (const Activation* a : resnet->acts) total += a->buf.bytes + a->buf32.bytes;
+    for (const ModelBase* M : {(const ModelBase*)unet.get(), (const ModelBase*)resnet.get()})
+        if (M) for (const Activation* a : M->acts) total += a->buf.bytes + a->buf32.bytes;
     return total;
+}
+
+// ---- what the model plans share (models.h) ---------------------------------------------------------------------------------------
+Status need(const ParamMap& pm, const std::string& key, std::vector<int64_t> shape, const float** out) {
+    auto it = pm.find(key);
+    if (it == pm.end()) return fail(1, "state dict is missing key '" + key + "'");
+    if (it->second.shape != shape) {
+        std::string got, want;
+        for (auto d : it->second.shape) got += std::to_string(d) + ",";
+        for (auto d : shape) want += std::to_string(d) + ",";
+        return fail(1, "state dict key '" + key + "' has shape (" + got + ") expected (" + want + ")");
+    }
+    *out = it->second.data;
+    return Status();
+}
+
+Status bn_fold(const ParamMap& pm, const std::string& prefix, int c, std::vector<float>& scale, std::vector<float>& shift) {
+    const float *g, *b, *m, *v;
+    CV_TRY(need(pm, prefix + ".weight", {c}, &g));
+    CV_TRY(need(pm, prefix + ".bias", {c}, &b));
+    CV_TRY(need(pm, prefix + ".running_mean", {c}, &m));
+    CV_TRY(need(pm, prefix + ".running_var", {c}, &v));
+    scale.resize(c); shift.resize(c);
+    for (int i = 0; i < c; ++i) {
+        const float s = g[i] / std::sqrt(v[i] + 1e-5f);
+        scale[i] = s;
+        shift[i] = b[i] - m[i] * s;
+    }
+    return Status();
+}
+
+Status build_conv_bn(Engine& e, ConvLayer& L, const ParamMap& pm, const std::string& conv_key, const std::string& bn_key, int cout,
+                     int cin, int k, int stride, int cinPad, int64_t pixels, int out_hw, int layer_dt) {
+    const float* w;
+    CV_TRY(need(pm, conv_key + ".weight", {cout, cin, k, k}, &w));
+    std::vector<float> sc, sh;
+    CV_TRY(bn_fold(pm, bn_key, cout, sc, sh));
+    CV_TRY(L.build_conv(conv_key, layer_dt < 0 ? e.dt : layer_dt, w, cout, cin, k, stride, sc.data(), sh.data(), cinPad, pixels, out_hw));
+    L.layer_id = e.register_layer(conv_key);
+    return Status();
+}
+
+void bn_keys(std::vector<std::string>& out, const std::string& p) {
+    for (const char* leaf : {".weight", ".bias", ".running_mean", ".running_var"}) out.push_back(p + leaf);
+}
+
+Status reject_unknown_keys(const ParamMap& pm, const std::vector<std::string>& known, const char* model) {
+    for (const auto& kv : pm) {
+        bool ok = false;
+        for (const auto& k : known)
+            if (kv.first == k) { ok = true; break; }
+        if (!ok) return fail(1, std::string("state dict has key '") + kv.first + "' that " + model + " does not define");
+    }
+    return Status();
+}
+
+Status model_reserve(Engine& e, ModelBase& M, int n) {
+    const int want = std::min(M.max_cap, std::max(n, 1));
+    if (want <= M.cap) return Status();
+    CV_HIP(device_synchronize());                    // nothing may still read the buffers about to be replaced
+    e.graph_invalidate();                            // captured launches hold the old buffers
+    CV_TRY(Activation::reserve_all(M.acts, want));
+    M.cap = want;
+    M.taps.clear();
+    M.build_taps(e, want);
+    return Status();
+}
+
+bool ModelBase::tap(const std::string& name, TensorRef* out) const {
+    auto it = taps.find(name);
+    if (it == taps.end()) return false;
+    *out = it->second;
+    out->exp = static_cast<Activation*>(out->owner)->exp_of(out->Coff);   // per half of a concatenation; `exp` of any other tensor
+    out->N = last_n;
+    return true;
 }
 
 static bool halo_th8_for(const ConvLayer& L, const ConvParams& p, int ct, int Ho, bool fused) {

@@ -310,7 +310,7 @@ class Engine {
     unsigned register_layer(const std::string& name);
     unsigned* guard_ptr() const { return reinterpret_cast<unsigned*>(guard.ptr); }
     Status guard_init();
-    Status guard_check(hipStream_t s);                  // synchronises; fails with the layer name and re-arms
+    Status guard_check(hipStream_t s);                  // downloads the word, synchronises, then guard_eval
     Status guard_read_async(unsigned* pinned, hipStream_t s);   // ... in two halves: enqueue the download into page-locked memory,
     Status guard_eval(unsigned v);                      // ... and judge the word after the caller's own synchronisation
 
@@ -385,10 +385,21 @@ class Engine {
     Status flush_pending(PendingConv& a, PendingConv& b, hipStream_t s);
     void prof_begin(const std::string& name, bool is_conv, double macs, hipStream_t s, double bytes = 0);
     void prof_end(hipStream_t s);
+    // the bracket around a launch outside run_conv: timed_begin before it (records the start event when profiling), timed_end with its
+    // result (records the end event; a failed launch becomes hip_fail(err, what))
+    void timed_begin(const char* name, hipStream_t s, double bytes = 0, double macs = 0) { if (profiling) prof_begin(name, false, macs, s, bytes); }
+    Status timed_end(const char* what, hipError_t err, hipStream_t s) {
+        if (profiling) prof_end(s);
+        return err != hipSuccess ? hip_fail(err, what) : Status();
+    }
     Status prof_collect();
     void prof_clear();
 };
 
+// experiment switches from the environment (DESIGN.md / profiles/*_tuning.md).  env_int: unset or empty gives dflt, else atoi.
+// env_switch: unset or empty gives dflt, a first character '0' off, '1' on, anything else dflt.
+int env_int(const char* name, int dflt);
+bool env_switch(const char* name, bool dflt);
 bool calibration_enabled();                         // CV_CALIBRATE=0 switches the activation exponents off (tests of the guard)
 bool bias_correction_enabled();                     // CV_BIAS_CORR=0 switches the rounding-bias correction of the f16 layers off
 int choose_ct(int rows, int64_t pixels_hint, bool halo_ok);

@@ -7,7 +7,6 @@
 // BasicBlock = conv1-bn1-ReLU-conv2-bn2-(+shortcut)-ReLU: both BNs, the residual add and both ReLUs are conv
 // epilogues here; the squares of many boards are batched so the 2x2 / 4x4 stages still form large GEMMs.
 #include <cmath>
-#include <cstdlib>
 #include <cstring>
 
 #include "engine.h"
@@ -15,13 +14,6 @@
 #include "pointwise.h"
 
 namespace cv {
-
-Status build_conv_bn_public(Engine& e, ConvLayer& L, const ParamMap& pm, const std::string& conv_key,
-                            const std::string& bn_key, int cout, int cin, int k, int stride, int cinPad,
-                            int64_t pixels, int out_hw, int layer_dt = -1);
-Status need_public(const ParamMap& pm, const std::string& key, std::vector<int64_t> shape, const float** out);
-Status bn_fold_public(const ParamMap& pm, const std::string& prefix, int c, std::vector<float>& scale, std::vector<float>& shift);
-Status reject_unknown_keys_public(const ParamMap& pm, const std::vector<std::string>& known, const char* model);
 
 static const ResNetArch kResNetArchs[] = {{"resnet18", {2, 2, 2, 2}}, {"resnet34", {3, 4, 6, 3}}};
 
@@ -31,7 +23,6 @@ const ResNetArch* resnet_arch(const std::string& name) {
     return nullptr;
 }
 
-static Status resnet_reserve(Engine& e, int n);
 static Status layer1_chain(Engine& e, int n, hipStream_t s);
 static Status resnet_chunk(Engine& e, const void* x, bool x_u8, int n, float* out, bool softmax, hipStream_t s, float* embedding = nullptr,
                            const InputNorm* norm = nullptr);
@@ -40,31 +31,21 @@ static Status resnet_chunk(Engine& e, const void* x, bool x_u8, int n, float* ou
 // workgroup per CU with 512 registers, the f32 trunk stays in registers -- no round trip, but nothing covers the workgroup's barriers,
 // prologue and epilogues: 1.81 against 1.62 ms per 16384 squares (CV_CHAIN_WG=1; r05_tuning.md step 6)
 static int chain_form() {
-    static const int form = [] { const char* v = std::getenv("CV_CHAIN_WG"); return v && v[0] == '1' ? 1 : 2; }();
+    static const int form = env_switch("CV_CHAIN_WG", false) ? 1 : 2;
     return form;
 }
 
 // split-f16 engine: squares from which the dedicated shortcut kernel replaces the generic launch (CV_SHORTCUT_SPLIT_MIN; below it the
 // generic launch shares conv1's launch, Engine::PendingConv)
 static int fast_sc_min_squares() {
-    static const int v = [] { const char* e = std::getenv("CV_SHORTCUT_SPLIT_MIN"); return e && *e ? std::atoi(e) : 1024; }();
+    static const int v = env_int("CV_SHORTCUT_SPLIT_MIN", 1024);
     return v;
-}
-
-static void bn_keys(std::vector<std::string>& out, const std::string& p) {
-    for (const char* leaf : {".weight", ".bias", ".running_mean", ".running_var"}) out.push_back(p + leaf);
 }
 
 // fold the stem's output exponent into the device copies of its epilogue constants (ConvLayer::set_exps for the stem)
 static Status stem_set_exp(Engine::ResNet& R, int dt, int out_exp, hipStream_t s) {
-    if (R.stem_scale.ptr && out_exp == R.stem_out_exp) return Status();
-    if (capture_flag()) return fail(1, "stem constants re-folded during graph capture");
-    if (R.stem_scale.ptr) CV_HIP(hipStreamSynchronize(s));
-    std::vector<float> sc(64), sh(64);
-    const int in_exp = dt == kF32 ? 0 : kInputExp;
-    for (int i = 0; i < 64; ++i) { sc[i] = std::ldexp(R.h_stem_scale[i], in_exp - out_exp); sh[i] = std::ldexp(R.h_stem_shift[i], -out_exp); }
-    CV_TRY(R.stem_scale.upload(sc.data(), 64 * sizeof(float)));
-    CV_TRY(R.stem_shift.upload(sh.data(), 64 * sizeof(float)));
+    if (out_exp == R.stem_out_exp) return Status();
+    CV_TRY(fold_exps("conv1", R.h_stem_scale, R.h_stem_shift, R.stem_scale.ptr, R.stem_shift.ptr, dt == kF32 ? 0 : kInputExp, out_exp, s));
     R.stem_out_exp = out_exp;
     return Status();
 }
@@ -90,24 +71,17 @@ Status resnet_load(Engine& e, const ParamMap& pm, const std::string& arch) {
 
     {   // stem: conv1 (64,1,7,7) + bn1
         const float* w;
-        CV_TRY(need_public(pm, "conv1.weight", {64, 1, 7, 7}, &w));
+        CV_TRY(need(pm, "conv1.weight", {64, 1, 7, 7}, &w));
         std::vector<float> sc, sh;
-        CV_TRY(bn_fold_public(pm, "bn1", 64, sc, sh));
+        CV_TRY(bn_fold(pm, "bn1", 64, sc, sh));
         known.push_back("conv1.weight"); bn_keys(known, "bn1");
         std::vector<float> wn(w, w + 64 * 49);
         R.h_stem_scale.assign(64, 0.f); R.h_stem_shift.assign(64, 0.f);
         for (int ch = 0; ch < 64; ++ch) {
-            int ex = 0;
-            float mx = 0.f;
-            for (int k = 0; k < 49; ++k) {
+            for (int k = 0; k < 49; ++k)
                 if (!std::isfinite(w[ch * 49 + k])) return fail(1, "conv1: non-finite weight in the state dict");
-                mx = std::max(mx, std::fabs(w[ch * 49 + k]));
-            }
             if (!std::isfinite(sc[ch]) || !std::isfinite(sh[ch])) return fail(1, "bn1: non-finite BatchNorm scale/shift (running_var + eps <= 0?)");
-            if (dt != kF32 && mx > 0.f) {                   // filter normalisation, as ConvLayer rows (engine.cpp: finish_layer)
-                (void)std::frexp(mx, &ex);
-                for (int k = 0; k < 49; ++k) wn[ch * 49 + k] = std::ldexp(wn[ch * 49 + k], -ex);
-            }
+            const int ex = dt != kF32 ? normalise_row(&wn[ch * 49], 49) : 0;      // filter normalisation, as ConvLayer rows
             R.h_stem_scale[ch] = std::ldexp(sc[ch], ex);
             R.h_stem_shift[ch] = sh[ch];
         }
@@ -120,17 +94,15 @@ Status resnet_load(Engine& e, const ParamMap& pm, const std::string& arch) {
                 for (int ks = 0; ks < 2; ++ks)
                     for (int f = 0; f < 4; ++f)
                         for (int lane = 0; lane < 64; ++lane) {
-                            const int i = lane & 15, q = lane >> 4, ky = ks * 4 + q;
-                            const int ch = 16 * (i / 4) + 4 * f + (i % 4);
-                            for (int j = 0; j < 8; ++j) {
-                                const float v = (ky < 7 && j < 7) ? wn[ch * 49 + ky * 7 + j] : 0.f;
-                                const _Float16 hi = (_Float16)v;
-                                pk[((((size_t)hl * 2 + ks) * 4 + f) * 64 + lane) * 8 + j] = hl ? (_Float16)(v - (float)hi) : hi;
-                            }
+                            const int ch = frag_row_channel(4, f, lane & 15), ky = ks * 4 + (lane >> 4);
+                            for (int j = 0; j < 8; ++j)
+                                pk[((((size_t)hl * 2 + ks) * 4 + f) * 64 + lane) * 8 + j] = f16_half((ky < 7 && j < 7) ? wn[ch * 49 + ky * 7 + j] : 0.f, hl);
                         }
             CV_TRY(R.stem_wpk.upload(pk.data(), pk.size() * sizeof(_Float16)));
         }
         R.stem_id = e.register_layer("conv1");
+        CV_TRY(R.stem_scale.alloc(64 * sizeof(float), false));
+        CV_TRY(R.stem_shift.alloc(64 * sizeof(float), false));
         CV_TRY(stem_set_exp(R, dt, 0, nullptr));
     }
     if (dt == kF32) { R.stem_out.shape(32, 32, 64, dt); R.acts.push_back(&R.stem_out); }   // other engines fuse stem + pool
@@ -151,8 +123,8 @@ Status resnet_load(Engine& e, const ParamMap& pm, const std::string& arch) {
             const int64_t px = (int64_t)S * res[l] * res[l];
             known.push_back(p + ".conv1.weight"); bn_keys(known, p + ".bn1");
             known.push_back(p + ".conv2.weight"); bn_keys(known, p + ".bn2");
-            CV_TRY(build_conv_bn_public(e, B.conv1, pm, p + ".conv1", p + ".bn1", w, cin, 3, stride, cin, px, res[l]));
-            CV_TRY(build_conv_bn_public(e, B.conv2, pm, p + ".conv2", p + ".bn2", w, w, 3, 1, w, px, res[l]));
+            CV_TRY(build_conv_bn(e, B.conv1, pm, p + ".conv1", p + ".bn1", w, cin, 3, stride, cin, px, res[l]));
+            CV_TRY(build_conv_bn(e, B.conv2, pm, p + ".conv2", p + ".bn2", w, w, 3, 1, w, px, res[l]));
             B.has_down = (stride != 1 || cin != w);
             if (B.has_down) {
                 known.push_back(p + ".downsample.0.weight"); bn_keys(known, p + ".downsample.1");
@@ -160,8 +132,8 @@ Status resnet_load(Engine& e, const ParamMap& pm, const std::string& arch) {
                 // straight onto the skip path (CPU emulation of the arithmetic, 4096 squares: worst soft-max error 9.7e-4 with f16
                 // shortcuts, 6.5e-4 with exact ones).  It holds 1.1 % of the network's MACs: run it on the f32 MFMA, f32 twin in,
                 // f32 twin out; no f16 copy of the shortcut tensor exists.
-                CV_TRY(build_conv_bn_public(e, B.down, pm, p + ".downsample.0", p + ".downsample.1", w, cin, 1, stride, cin, px, res[l],
-                                            e.trunk32 ? (int)kF32 : -1));
+                CV_TRY(build_conv_bn(e, B.down, pm, p + ".downsample.0", p + ".downsample.1", w, cin, 1, stride, cin, px, res[l],
+                                     e.trunk32 ? (int)kF32 : -1));
                 B.sc.shape(res[l], res[l], w, dt);
                 B.sc.want32 = B.sc.only32 = e.trunk32;
                 R.acts.push_back(&B.sc);
@@ -169,15 +141,15 @@ Status resnet_load(Engine& e, const ParamMap& pm, const std::string& arch) {
                 // every wave) 0.31 / 0.21 / 0.15 ms per 16384 squares against 0.27 / 0.19 / 0.16 for `down` on the f32-input MFMA; the second
                 // form (weights resident in LDS, persistent waves, full-line stores) 0.145 / 0.085 / 0.084 -- ON by default;
                 // CV_SHORTCUT_FAST=0 switches it off (the generic launch then rides with conv1 at single-board sizes, Engine::PendingConv)
-                static const bool fast_on = [] { const char* v = std::getenv("CV_SHORTCUT_FAST"); return !(v && v[0] == '0'); }();
+                static const bool fast_on = env_switch("CV_SHORTCUT_FAST", true);
                 // round 6: the headline engine (split-f16 tensors) takes the same kernel in its SPLIT form at throughput batch sizes -- there it
                 // computes exactly what the generic launch computes (same products, same order: bit-identical), so the choice may follow the batch
                 // (layer4's shortcut, 256 -> 512 on 2 x 2 maps, stays on the generic tile there: 0.071 against 0.090 ms per 16384 squares)
                 if (((e.trunk32 && dt == kF16) || dt == kSplit) && fast_on && w == 2 * cin && (cin == 64 || cin == 128 || (cin == 256 && dt != kSplit))) {
                     const float* wd;
-                    CV_TRY(need_public(pm, p + ".downsample.0.weight", {w, cin, 1, 1}, &wd));
+                    CV_TRY(need(pm, p + ".downsample.0.weight", {w, cin, 1, 1}, &wd));
                     std::vector<float> sc, sh;
-                    CV_TRY(bn_fold_public(pm, p + ".downsample.1", w, sc, sh));
+                    CV_TRY(bn_fold(pm, p + ".downsample.1", w, sc, sh));
                     CV_TRY(B.fast_sc.pack(w, cin, [&](int ch, int k) { return wd[(size_t)ch * cin + k]; }, [&](int ch) { return sc[ch]; },
                                           [&](int ch) { return sh[ch]; }, B.down.name));
                     B.fast_sc.layer_id = B.down.layer_id;
@@ -194,8 +166,8 @@ Status resnet_load(Engine& e, const ParamMap& pm, const std::string& arch) {
     }
     {
         const float *w, *b;
-        CV_TRY(need_public(pm, "fc.weight", {13, 512}, &w));
-        CV_TRY(need_public(pm, "fc.bias", {13}, &b));
+        CV_TRY(need(pm, "fc.weight", {13, 512}, &w));
+        CV_TRY(need(pm, "fc.bias", {13}, &b));
         known.push_back("fc.weight"); known.push_back("fc.bias");
         for (int i = 0; i < 13 * 512; ++i)
             if (!std::isfinite(w[i])) return fail(1, "fc: non-finite weight in the state dict");
@@ -206,12 +178,12 @@ Status resnet_load(Engine& e, const ParamMap& pm, const std::string& arch) {
         R.head_id = e.register_layer("fc");
         macs += 13 * 512;
     }
-    CV_TRY(reject_unknown_keys_public(pm, known, (std::string(A->name) + "(in_chans=1, num_classes=13)").c_str()));
+    CV_TRY(reject_unknown_keys(pm, known, (std::string(A->name) + "(in_chans=1, num_classes=13)").c_str()));
     R.macs = macs;
     {   // f16r: layer1 as one chained launch -- the chained layers' weight stages (9 taps x 64 rows x 128 B each) back to back.
         // A three-block layer1 (resnet34) chains all three blocks by default; CV_RESNET_CHAIN_BLOCKS=2 chains the first two.
-        static const bool on = [] { const char* v = std::getenv("CV_RESNET_CHAIN"); return !(v && v[0] == '0'); }();
-        static const int max_nb = [] { const char* v = std::getenv("CV_RESNET_CHAIN_BLOCKS"); return v && *v ? std::atoi(v) : 3; }();
+        static const bool on = env_switch("CV_RESNET_CHAIN", true);
+        static const int max_nb = env_int("CV_RESNET_CHAIN_BLOCKS", 3);
         const int nb = std::min(A->depth[0], max_nb);
         std::vector<ConvLayer*> L;
         for (int b = 0; b < nb; ++b) { L.push_back(&R.blocks[b].conv1); L.push_back(&R.blocks[b].conv2); }
@@ -231,7 +203,7 @@ Status resnet_load(Engine& e, const ParamMap& pm, const std::string& arch) {
     // (the rounding-bias pass of the fp16 layers, ConvLayer::want_round_err, reads 128 more: 64 of noise and 64 smooth ones --
     // bilinear blow-ups of a random 4 x 4 grid, what a board crop looks like away from piece edges -- so that the channel means it
     // measures are not those of one texture)
-    Status st = resnet_reserve(e, 128);
+    Status st = model_reserve(e, R, 128);
     if (st.ok() && dt != kF32 && calibration_enabled()) {
         constexpr int kCal = 128, kBias = 256;
         std::vector<float> host((size_t)kBias * 4096);
@@ -263,51 +235,24 @@ Status resnet_load(Engine& e, const ParamMap& pm, const std::string& arch) {
                     host[((size_t)q * 64 + y) * 64 + x] = v / 255.f;
                 }
         }
-        DeviceBuffer xin, lout;
+        DeviceBuffer xin;
         st = xin.upload(host.data(), host.size() * sizeof(float));
-        if (st.ok()) st = lout.alloc((size_t)kBias * 13 * sizeof(float), false);
+        std::vector<ConvLayer*> layers;                                         // the f16 layers of the rounding-bias pass
+        for (int b = 0; b < R.nblocks; ++b) {
+            Engine::ResNet::Block& B = R.blocks[b];
+            layers.push_back(&B.conv1); layers.push_back(&B.conv2);
+            if (B.has_down) layers.push_back(&B.down);
+        }
         if (st.ok())
-            st = e.calibrate(e.resnet->acts, [&]() -> Status {                 // the statistics accumulate over the chunks
-                for (int off = 0; off < 128; off += e.resnet->cap) {
-                    const int c = std::min(e.resnet->cap, 128 - off);
-                    CV_TRY(resnet_chunk(e, (const float*)xin.ptr + (size_t)off * 4096, false, c, (float*)lout.ptr + (size_t)off * 13, false, nullptr));
-                }
-                return Status();
-            }, nullptr, A->name);
-        if (st.ok()) {                                                          // exponents are final: rounding-bias pass of the f16 layers
-            std::vector<ConvLayer*> layers;
-            for (int b = 0; b < e.resnet->nblocks; ++b) {
-                Engine::ResNet::Block& B = e.resnet->blocks[b];
-                layers.push_back(&B.conv1); layers.push_back(&B.conv2);
-                if (B.has_down) layers.push_back(&B.down);
-            }
-            st = e.calibrate_rounding_bias(layers, [&]() -> Status {
-                for (int off = 0; off < kBias; off += e.resnet->cap) {
-                    const int c = std::min(e.resnet->cap, kBias - off);
-                    CV_TRY(resnet_chunk(e, (const float*)xin.ptr + (size_t)off * 4096, false, c, (float*)lout.ptr + (size_t)off * 13, false, nullptr));
-                }
-                return Status();
-            }, nullptr);
-        }
-        if (st.ok()) {
-            hipError_t he = device_synchronize();
-            if (he != hipSuccess) st = hip_fail(he, (std::string(A->name) + " calibration").c_str());
-        }
+            st = calibrate_model(e, R, layers, (const float*)xin.ptr, 4096, kCal, kBias, 13, A->name,
+                                 [&](const float* x, int n, float* out) { return resnet_chunk(e, x, false, n, out, false, nullptr); });
     }
     if (!st.ok()) e.resnet.reset();
     return st;
 }
 
-static Status resnet_reserve(Engine& e, int n) {
-    Engine::ResNet& R = *e.resnet;
-    const int want = std::min(R.max_cap, std::max(n, 1));
-    if (want <= R.cap) return Status();
-    CV_HIP(device_synchronize());
-    e.graph_invalidate();                            // captured launches hold the old buffers
-    CV_TRY(Activation::reserve_all(R.acts, want));
-    R.cap = want;
-    const int S = want;
-    R.taps.clear();
+void Engine::ResNet::build_taps(const Engine& e, int S) {
+    Engine::ResNet& R = *this;
     // f16r: a trunk tensor (pool output, block outputs) IS its unrounded f32 twin -- what the residual adds and the head read; the f16
     // copy beside it is that tensor rounded once for the next convolution.  The taps report the twin: a tap of the copy is 2^-12 off
     // the head's input, more than the head kernel's own error
@@ -329,7 +274,6 @@ static Status resnet_reserve(Engine& e, int n) {
         }
         R.taps["layer" + std::to_string(l + 1)] = trunk(R.blocks[R.first[l + 1] - 1].out);
     }
-    return Status();
 }
 
 int64_t resnet_macs(Engine& e) { return e.resnet ? e.resnet->macs : 0; }
@@ -337,8 +281,7 @@ int64_t resnet_macs(Engine& e) { return e.resnet ? e.resnet->macs : 0; }
 Status resnet_activation(Engine& e, const std::string& name, TensorRef* out) {
     if (!e.resnet) return fail(3, "ResNet not loaded");
     const Engine::ResNet& R = *e.resnet;
-    auto it = R.taps.find(name);
-    if (it == R.taps.end()) {
+    if (!R.tap(name, out)) {
         // the fp16 classifier runs the first chain_nb blocks of layer1 as ONE launch: their conv1 outputs (and, in the one-workgroup form,
         // the outputs of every chained block but the last) exist in LDS / registers only
         if (R.chain_ok) {
@@ -357,37 +300,26 @@ Status resnet_activation(Engine& e, const std::string& name, TensorRef* out) {
         }
         return fail(1, "unknown " + std::string(R.arch->name) + " activation '" + name + "'");
     }
-    *out = it->second;
-    out->exp = static_cast<Activation*>(out->owner)->exp;
-    out->N = e.resnet->last_n;
     return Status();
 }
 
 static Status resnet_chunk(Engine& e, const void* x, bool x_u8, int n, float* out, bool softmax, hipStream_t s, float* embedding,
                            const InputNorm* norm) {
     Engine::ResNet& R = *e.resnet;
-    R.last_n = n;
-    e.ws_slot = 1;
     const int dt = e.dt;
     const double esz = dtype_size(dt), in_b = x_u8 ? 1.0 : 4.0;
-    auto begin = [&](const char* name, double macs, double bytes) { if (e.profiling) e.prof_begin(name, false, macs, s, bytes); };
-    auto end = [&](const char* name, hipError_t err) -> Status {
-        if (e.profiling) e.prof_end(s);
-        if (err != hipSuccess) return hip_fail(err, name);
-        return Status();
-    };
     if (dt == kF32) {
-        begin("stem7x7", 49.0 * 64 * 1024 * n, (double)n * (4096 * in_b + 1024 * 64 * esz));
-        CV_TRY(end("stem7x7", stem7x7(dt, x, x_u8, n, (const float*)R.stem_w.ptr, (const float*)R.stem_scale.ptr,
-                                       (const float*)R.stem_shift.ptr, R.stem_out.ref(n), s, norm)));
-        begin("maxpool3x3s2", 0, (double)n * (1024 + 256) * 64 * esz);
-        CV_TRY(end("maxpool3x3s2", maxpool3x3s2(dt, R.stem_out.ref(n), R.pool_out.ref(n), s)));
+        e.timed_begin("stem7x7", s, (double)n * (4096 * in_b + 1024 * 64 * esz), 49.0 * 64 * 1024 * n);
+        CV_TRY(e.timed_end("stem7x7", stem7x7(dt, x, x_u8, n, (const float*)R.stem_w.ptr, (const float*)R.stem_scale.ptr,
+                                              (const float*)R.stem_shift.ptr, R.stem_out.ref(n), s, norm), s));
+        e.timed_begin("maxpool3x3s2", s, (double)n * (1024 + 256) * 64 * esz);
+        CV_TRY(e.timed_end("maxpool3x3s2", maxpool3x3s2(dt, R.stem_out.ref(n), R.pool_out.ref(n), s), s));
     } else {
         CV_TRY(stem_set_exp(R, dt, R.pool_out.exp, s));
-        begin("stem7x7+maxpool (mfma)", 49.0 * 64 * 1024 * n, (double)n * (4096 * in_b + 256 * 64 * (esz + (R.pool_out.want32 ? 4.0 : 0.0))));
-        CV_TRY(end("stem_pool_mfma", stem_pool_mfma(dt, x, x_u8, n, R.stem_wpk.ptr, (const float*)R.stem_scale.ptr,
-                                                     (const float*)R.stem_shift.ptr, kInputExp, R.pool_out.ref(n),
-                                                     e.guard_ptr(), R.stem_id, s, norm)));
+        e.timed_begin("stem7x7+maxpool (mfma)", s, (double)n * (4096 * in_b + 256 * 64 * (esz + (R.pool_out.want32 ? 4.0 : 0.0))), 49.0 * 64 * 1024 * n);
+        CV_TRY(e.timed_end("stem_pool_mfma", stem_pool_mfma(dt, x, x_u8, n, R.stem_wpk.ptr, (const float*)R.stem_scale.ptr,
+                                                            (const float*)R.stem_shift.ptr, kInputExp, R.pool_out.ref(n),
+                                                            e.guard_ptr(), R.stem_id, s, norm), s));
         if (e.calibrating) CV_TRY(e.measure(R.pool_out.ref(n), s));
     }
     TensorRef cur = R.pool_out.ref(n);
@@ -439,13 +371,12 @@ static Status resnet_chunk(Engine& e, const void* x, bool x_u8, int n, float* ou
     if (cur.base32) { cur.base = cur.base32; head_dt = kF32; }   // f16r: pool the trunk's f32 twin
     if (embedding && !e.calibrating) {
         // the embedding of the reference's hook (named_modules()[90] = global_pool): channel means of the tensor the head pools
-        begin("embedding (channel means)", 0, (double)n * 512 * (cur.H * cur.W * dtype_size(head_dt) + 4));
-        CV_TRY(end("channel_means", channel_means(head_dt, cur, embedding, s)));
+        e.timed_begin("embedding (channel means)", s, (double)n * 512 * (cur.H * cur.W * dtype_size(head_dt) + 4));
+        CV_TRY(e.timed_end("channel_means", channel_means(head_dt, cur, embedding, s), s));
     }
-    begin("head_avgpool_fc", 13.0 * 512 * n, (double)n * (cur.H * cur.W * 512 * dtype_size(head_dt) + 13 * 4));
-    CV_TRY(end("head_avgpool_fc", head_avgpool_fc(head_dt, cur, (const float*)R.fc_w.ptr, (const float*)R.fc_b.ptr, out,
-                                                   softmax ? 1 : 0, e.guard_ptr(), R.head_id, s)));
-    return Status();
+    e.timed_begin("head_avgpool_fc", s, (double)n * (cur.H * cur.W * 512 * dtype_size(head_dt) + 13 * 4), 13.0 * 512 * n);
+    return e.timed_end("head_avgpool_fc", head_avgpool_fc(head_dt, cur, (const float*)R.fc_w.ptr, (const float*)R.fc_b.ptr, out,
+                                                          softmax ? 1 : 0, e.guard_ptr(), R.head_id, s), s);
 }
 
 // the first chain_nb blocks of layer1 in one launch (f16r engine): pool_out (f16 copy + f32 twin) -> blocks[nb-1].out (f16 copy + f32 twin),
@@ -503,35 +434,21 @@ static Status layer1_chain(Engine& e, int n, hipStream_t s) {
                      px * (2 + 4 + 8 * (nb - 1) + 4 + 2) + 2.0 * nb * 9 * 64 * 64 * 2);
         e.prof.back().kernel = "conv3x3_halo_kernel<half_t,64,16x16,CHAIN" + std::to_string(2 * nb) + ">";
     }
-    const hipError_t err = conv_halo_chain_launch(p, n, s);
-    if (e.profiling) e.prof_end(s);
-    if (err != hipSuccess) return hip_fail(err, "layer1 chain launch");
-    return Status();
+    return e.timed_end("layer1 chain launch", conv_halo_chain_launch(p, n, s), s);
 }
 
 Status resnet_forward(Engine& e, const void* x, bool x_u8, int n, float* out, bool softmax, hipStream_t s, float* embedding,
                       const InputNorm* norm) {
     if (!e.resnet) return fail(3, "ResNet weights not loaded (call cv_load_resnet or cv_load_resnet18 first)");
-    if (n < 0 || (n > 0 && (!x || !out))) return fail(1, "cv_resnet18_forward: null tensor or negative batch");
     if (norm && !x_u8) return fail(1, "resnet_forward: only a byte input can be normalised");
-    if (n == 0) return Status();
-    CV_TRY(e.order_forward(1, s));
-    CV_TRY(resnet_reserve(e, n));
-    if (n <= e.resnet->cap && n <= 512) {                // one small chunk (a board's 64 squares): the launch sequence replays as a hipGraph
-        Engine::GraphKey key;
-        key.model = 1; key.n = n; key.flags = (x_u8 ? 1 : 0) | (softmax ? 2 : 0) | (norm ? 4 : 0); key.x = x; key.out = out; key.emb = embedding;
-        if (norm) std::memcpy(key.norm_bits, norm, sizeof(key.norm_bits));   // baked into the captured stem launch
-        e.resnet->last_n = n;                            // a graph replay skips resnet_chunk's host side (see unet_forward)
-        e.ws_slot = 1;
-        return e.run_graphed(key, s, [&](hipStream_t st) { return resnet_chunk(e, x, x_u8, n, out, softmax, st, embedding, norm); });
-    }
-    const size_t in_stride = (size_t)64 * 64 * (x_u8 ? 1 : 4);
-    for (int off = 0; off < n; off += e.resnet->cap) {
-        const int c = std::min(e.resnet->cap, n - off);
-        CV_TRY(resnet_chunk(e, (const char*)x + (size_t)off * in_stride, x_u8, c, out + (size_t)off * 13, softmax, s,
-                            embedding ? embedding + (size_t)off * 512 : nullptr, norm));
-    }
-    return Status();
+    Engine::GraphKey key;
+    key.flags = (x_u8 ? 1 : 0) | (softmax ? 2 : 0) | (norm ? 4 : 0);
+    if (norm) std::memcpy(key.norm_bits, norm, sizeof(key.norm_bits));   // baked into the captured stem launch
+    const ForwardShape shape{512, (size_t)64 * 64 * (x_u8 ? 1 : 4), 13, 512};   // one small chunk: a board's 64 squares
+    return forward_chunked(e, *e.resnet, shape, key, "cv_resnet18_forward", x, n, out, nullptr, embedding, s,
+                           [&](const void* xc, int c, float* o, uint8_t*, float* emb, hipStream_t st) {
+                               return resnet_chunk(e, xc, x_u8, c, o, softmax, st, emb, norm);
+                           });
 }
 
 }  // namespace cv

@@ -101,7 +101,7 @@ def is_unet(sd) -> bool:
 
 
 def unet_ops(sd) -> list:
-    """Every module output of UNet(3, 1[, bilinear]) by its tap name (cv_get_activation; unet.cpp: unet_reserve) + "logits"."""
+    """Every module output of UNet(3, 1[, bilinear]) by its tap name (cv_get_activation; unet.cpp: Engine::UNet::build_taps) + "logits"."""
     bilinear = "up1.up.weight" not in sd
     ops = [Op("input", [INPUT], lambda sd, x: F.pad(x, (0, 0, 0, 0, 0, 5)), "copy")]      # the 8-channel packed copy (f32 engine)
 
@@ -135,7 +135,7 @@ def resnet_depths(sd) -> tuple:
 
 
 def resnet_ops(sd, entry: str = "float") -> list:
-    """Every module output of the timm ResNet (18 or 34, by the keys of ``sd``) by its tap name (resnet.cpp: resnet_reserve) + "logits";
+    """Every module output of the timm ResNet (18 or 34, by the keys of ``sd``) by its tap name (resnet.cpp: Engine::ResNet::build_taps) + "logits";
     ``entry="u8"`` adds "probs", the soft-max the u8 classifier entry returns."""
     ops = [Op("act1", [INPUT], lambda sd, x: conv_bn(sd, "conv1", "bn1", x, stride=2), "conv"),
            Op("maxpool", ["act1"], lambda sd, x: maxpool3s2(x), "pool")]
