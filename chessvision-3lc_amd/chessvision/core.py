@@ -826,6 +826,21 @@ class ChessVision:
         return SquaresReport(scores=SquareScores.from_records(records), embeddings=emb,
                              aggregate=square_records_finish(records, batch_size))
 
+    def embedding_neighbours(self, queries, corpus=None, k: int = 10, exclude_self=None):
+        """The exact k nearest neighbours of every row of an embedding table (``chessvision/embeddings.py``: ``neighbours`` is the
+        definition) -- the graph the reference's PaCMAP reduction starts from, and the direct answer to "which earlier uploads look
+        like this one".  ``queries`` / ``corpus``: (rows, channels) host arrays or device tensors, e.g. ``embeddings.stack(results)``;
+        ``corpus=None``: the table against itself without each row's own entry.  Returns a ``Neighbours`` of numpy arrays.  With a HIP
+        model plugged in the search runs on its engine, on the caller's current stream, and equals the numpy form bit for bit;
+        otherwise the numpy form itself runs."""
+        from . import embeddings as emb
+
+        model = next((m for m in (self._classifier, self._board_extractor) if m is not None and self._native(m)), None)
+        if model is None:                                    # nothing loaded yet counts as "no HIP model": no checkpoint is read for this
+            return emb.neighbours(queries, corpus, k, exclude_self)
+        with torch.cuda.device(self.device):
+            return model.engine.embedding_neighbours(queries, corpus, k, exclude_self)
+
     def _pipeline_streams(self):
         """(host->device, device->host, compute) streams of ``process_images``, created once per instance."""
         if self._streams is None:

@@ -14,11 +14,19 @@ embeddings=True)``), and for any other stored layer on request (``HipEngine.acti
 "flatten" index 90 gives the same vector (global_pool's output is (B, 512)); at index 52 it needs the whole tensor, for which
 ``HipEngine.activation`` remains the way.
 
-This module holds what needs no device: the reference's integer layer indices as tap names, and the host form of the reduction for
-model objects that are not HIP models.  The PaCMAP reduction itself is out of scope, and the HIP model objects are not ``nn.Module``s
-that take forward hooks.
+This module holds what needs no device: the reference's integer layer indices as tap names, the host form of the reduction for
+model objects that are not HIP models, and the host form of the neighbour search.  The HIP model objects are not ``nn.Module``s that
+take forward hooks.
+
+What the table is collected for: the reference reduces it with ``run.reduce_embeddings_by_foreign_table_url(..., method="pacmap")``
+(``process_pipeline.py:351``, ``train_classifier.py:312``).  The PaCMAP reduction itself stays out of scope; the exact k-nearest-
+neighbour graph it (and UMAP) starts from is served: ``neighbours`` here is the definition and the checker in numpy,
+``HipEngine.embedding_neighbours`` / ``ChessVision.embedding_neighbours`` the device form, equal to it bit for bit.  ``stack`` turns
+``process_images(..., embeddings=True)`` results into the table, ``duplicate_groups`` answers "which uploads are near-duplicates".
 """
 from __future__ import annotations
+
+import dataclasses
 
 import numpy as np
 
@@ -144,3 +152,133 @@ def channel_mean(nchw) -> np.ndarray:
     if a.ndim == 2:
         return a.astype(np.float32)
     return a.astype(np.float64).mean(axis=tuple(range(2, a.ndim))).astype(np.float32)
+
+
+# ---- exact nearest neighbours: the definition (include/chessvision_hip.h: cv_embedding_neighbours) -----------------------------------
+MAX_NEIGHBOURS = 64
+
+
+@dataclasses.dataclass
+class Neighbours:
+    """``indices`` (Q, k) int32, -1 where fewer than k corpus rows were eligible or the query row is not finite; ``sq_distances``
+    (Q, k) float64 squared Euclidean distances (+inf / NaN in those slots); ``stats``: the record of ``cv_neighbour_stats_t`` as a
+    dict (the numpy form certifies nothing: every finite row counts as an exact-path row)."""
+    indices: np.ndarray
+    sq_distances: np.ndarray
+    stats: dict
+
+
+def _table(a, name: str) -> np.ndarray:
+    a = np.asarray(a.detach().cpu() if hasattr(a, "detach") else a)
+    if a.ndim != 2 or a.shape[0] < 1 or a.shape[1] < 1:
+        raise ValueError(f"{name} must be a (rows, channels) table with at least one row and one channel, got shape {a.shape}")
+    return np.ascontiguousarray(a, dtype=np.float32)
+
+
+def check_neighbour_arguments(q: int, n: int, c_q: int, c_n: int, k: int, corpus_given: bool, exclude_self) -> bool:
+    """The argument rules both forms share; returns the effective ``exclude_self``."""
+    if c_q != c_n:
+        raise ValueError(f"queries have {c_q} channels, the corpus {c_n}")
+    if not 1 <= int(k) <= MAX_NEIGHBOURS:
+        raise ValueError(f"k must be in [1, {MAX_NEIGHBOURS}], got {k}")
+    if exclude_self is None:
+        exclude_self = not corpus_given
+    if exclude_self and q != n:
+        raise ValueError(f"exclude_self drops corpus row i for query row i and needs as many queries as corpus rows, got {q} and {n}")
+    return bool(exclude_self)
+
+
+def neighbours(queries, corpus=None, k: int = 10, exclude_self=None) -> Neighbours:
+    """The k nearest corpus rows of every query row, exactly, in numpy -- the definition the device form is held to bit for bit.
+
+    ``D(a, b)``: ``s = 0.0``; for ascending channel c: ``t = float64(a[c]) - float64(b[c])``; ``s = s + t * t`` (product rounded,
+    then sum rounded: an explicit loop, because numpy's pairwise ``sum`` adds in another order).  Row i of the result holds the k
+    eligible corpus rows with the smallest ``(D, j)``, ascending: distance first, corpus index second.  ``corpus=None``: the graph of
+    the table against itself, ``exclude_self`` then defaults to True.  ``exclude_self`` drops corpus row ``j == i`` by index (an
+    exact duplicate elsewhere stays, at distance 0.0).  A corpus row with a NaN or an infinity is never returned; a query row with
+    one gets indices -1 and distances NaN; slots beyond the eligible rows are index -1, distance +inf."""
+    a = _table(queries, "queries")
+    b = a if corpus is None else _table(corpus, "corpus")
+    exclude_self = check_neighbour_arguments(a.shape[0], b.shape[0], a.shape[1], b.shape[1], k, corpus is not None, exclude_self)
+    q, n, c = a.shape[0], b.shape[0], a.shape[1]
+    k = int(k)
+    q_bad = ~np.isfinite(a).all(axis=1)
+    b_bad = ~np.isfinite(b).all(axis=1)
+    indices = np.full((q, k), -1, np.int32)
+    dist = np.full((q, k), np.inf, np.float64)
+    b64 = np.where(b_bad[:, None], 0.0, b.astype(np.float64))
+    a64 = np.where(q_bad[:, None], 0.0, a.astype(np.float64))
+    step = max(1, (1 << 24) // n)                            # query rows per piece: 128 MB of float64 distances
+    for lo in range(0, q, step):
+        hi = min(q, lo + step)
+        d = np.zeros((hi - lo, n), np.float64)
+        for ch in range(c):                                   # strictly ascending c, one rounding per product and per sum
+            t = a64[lo:hi, ch, None] - b64[None, :, ch]
+            d += t * t
+        d[:, b_bad] = np.inf
+        if exclude_self:
+            d[np.arange(hi - lo), np.arange(lo, hi)] = np.inf
+        eligible = np.isfinite(d)                             # D of two finite float32 rows never overflows float64
+        order = np.argsort(d, axis=1, kind="stable")[:, :k]   # stable: equal distances stay in index order
+        picked = np.take_along_axis(d, order, axis=1)
+        ok = np.take_along_axis(eligible, order, axis=1)
+        kk = order.shape[1]
+        indices[lo:hi, :kk] = np.where(ok, order, -1)
+        dist[lo:hi, :kk] = np.where(ok, picked, np.inf)
+    indices[q_bad] = -1
+    dist[q_bad] = np.nan
+    finite_rows = int(q - q_bad.sum())
+    stats = {"query_rows": q, "certified_rows": 0, "exact_rows": finite_rows, "nonfinite_query_rows": int(q_bad.sum()),
+             "nonfinite_corpus_rows": int(b_bad.sum())}
+    return Neighbours(indices, dist, stats)
+
+
+def duplicate_groups(neigh: Neighbours, radius: float) -> list[list[int]]:
+    """Rows of a table's own neighbour graph (``neighbours(table)``) joined wherever ``sq_distance <= radius ** 2``: the connected
+    groups with more than one member, each ascending, ordered by their first row -- "which uploads are near-duplicates".  Host
+    union-find.  Only pairs inside the graph's k are seen: a group of more than k + 1 mutual duplicates may come back in pieces."""
+    idx, dist = np.asarray(neigh.indices), np.asarray(neigh.sq_distances)
+    parent = list(range(idx.shape[0]))
+
+    def find(i: int) -> int:
+        while parent[i] != i:
+            parent[i] = parent[parent[i]]
+            i = parent[i]
+        return i
+
+    limit = float(radius) ** 2
+    for i, j in zip(*np.nonzero((idx >= 0) & (dist <= limit))):
+        other = int(idx[i, j])
+        if other >= len(parent):
+            raise ValueError("duplicate_groups needs the graph of a table against itself")
+        ra, rb = find(int(i)), find(other)
+        if ra != rb:
+            parent[max(ra, rb)] = min(ra, rb)
+    groups: dict[int, list[int]] = {}
+    for i in range(len(parent)):
+        groups.setdefault(find(i), []).append(i)
+    return [g for _, g in sorted(groups.items()) if len(g) > 1]
+
+
+def stack(results, which: str = "board_extractor"):
+    """``process_images(..., embeddings=True)`` results -> ``(table, keys)``: the (N, C) float32 table of ``which`` ("board_extractor":
+    one row per image, "classifier": 64 rows per image with a board) and the (N, 2) int32 ``(image, square)`` key of each row (square
+    -1 for the extractor's rows).  Images without embeddings -- for "classifier": without a board -- are skipped."""
+    if which not in ("board_extractor", "classifier"):
+        raise ValueError(f"which must be 'board_extractor' or 'classifier', got {which!r}")
+    rows, keys = [], []
+    for i, res in enumerate(results):
+        emb = getattr(res, "embeddings", None)
+        part = getattr(emb, which, None) if emb is not None else None
+        if part is None:
+            continue
+        part = np.asarray(part, dtype=np.float32)
+        if which == "board_extractor":
+            rows.append(part.reshape(1, -1))
+            keys.append([(i, -1)])
+        else:
+            rows.append(part.reshape(part.shape[0], -1))
+            keys.append([(i, s) for s in range(part.shape[0])])
+    if not rows:
+        return np.zeros((0, 0), np.float32), np.zeros((0, 2), np.int32)
+    return np.concatenate(rows, axis=0), np.asarray([k for ks in keys for k in ks], dtype=np.int32).reshape(-1, 2)

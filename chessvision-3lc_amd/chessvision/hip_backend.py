@@ -149,7 +149,12 @@ SYMBOLS = [
     ("cv_jpeg_gray_header", _i, [_i, _i, _i, _vp, _vp]),
     ("cv_jpeg_gray_max_bytes", _i, [_i, _i, ctypes.POINTER(ctypes.c_size_t)]),
     ("cv_jpeg_encode_gray_u8", _i, [_vp, _vp, _i, _i, _i, _i, _vp, ctypes.c_size_t, _vp, _vp, _vp]),
+    ("cv_embedding_neighbours_scratch_bytes", ctypes.c_size_t, [_i, _i, _i, _i]),
+    ("cv_embedding_neighbours", _i, [_vp, _vp, _i, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, ctypes.c_size_t, _vp]),
 ]
+NEIGHBOURS_EXCLUDE_SELF, NEIGHBOURS_EXACT_ONLY = 1, 2
+# cv_neighbour_stats_t (include/chessvision_hip.h): eight int32
+NEIGHBOUR_STATS = ("query_rows", "certified_rows", "exact_rows", "nonfinite_query_rows", "nonfinite_corpus_rows")
 
 # cv_score_record_t (include/chessvision_hip.h): one 64-byte record per image
 SCORE_RECORD = np.dtype({"names": ["hist", "above_half", "n_nan", "top_sum", "top_count", "reserved"],
@@ -767,6 +772,51 @@ class HipEngine:
                 raise HipBackendError("square_records: labels must be class indices 0..12, or -1 for an unlabelled square")
             labels = torch.from_numpy(np.ascontiguousarray(lab, dtype=np.int8)).to(self.device)
         return self.square_records_dev(logits, labels).cpu().numpy().view(SQUARE_RECORD).reshape(-1)
+
+    def embedding_neighbours_dev(self, queries: torch.Tensor, corpus: torch.Tensor, k: int, exclude_self: bool = False,
+                                 exact_only: bool = False):
+        """The device half of ``embedding_neighbours`` (``cv_embedding_neighbours``): ``queries`` (Q, C) and ``corpus`` (N, C), dense
+        float32 tensors on this device (the same tensor for a table against itself), -> ``(indices (Q, k) int32, sq_distances (Q, k)
+        float64, stats (8,) int32)`` device tensors.  Launched on the current stream behind whatever produced the tables; the scratch
+        comes from the caching allocator on that stream.  Nothing is synchronised or copied.  ``exact_only`` sends every row through
+        the exact path (the device's own reference)."""
+        for name, t in (("queries", queries), ("corpus", corpus)):
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.device != self.device or t.dim() != 2 \
+                    or not t.is_contiguous() or t.shape[0] < 1 or t.shape[1] < 1:
+                raise HipBackendError(f"embedding_neighbours expects {name} as a dense (rows, channels) float32 tensor on the engine's device")
+        q, c = (int(v) for v in queries.shape)
+        n = int(corpus.shape[0])
+        if int(corpus.shape[1]) != c:
+            raise HipBackendError(f"embedding_neighbours: queries have {c} channels, the corpus {int(corpus.shape[1])}")
+        flags = (NEIGHBOURS_EXCLUDE_SELF if exclude_self else 0) | (NEIGHBOURS_EXACT_ONLY if exact_only else 0)
+        need = int(self._lib.cv_embedding_neighbours_scratch_bytes(q, n, c, int(k)))
+        with torch.cuda.device(self.device):
+            scratch = torch.empty(max(need, 16), dtype=torch.uint8, device=self.device)
+            indices = torch.empty((q, max(int(k), 0)), dtype=torch.int32, device=self.device)
+            dist = torch.empty((q, max(int(k), 0)), dtype=torch.float64, device=self.device)
+            stats = torch.empty(8, dtype=torch.int32, device=self.device)
+            _check(self._lib.cv_embedding_neighbours(self._h, _ptr(queries), q, _ptr(corpus), n, c, int(k), flags, _ptr(indices), _ptr(dist),
+                                                     _ptr(stats), _ptr(scratch), need, _stream_ptr(self.device)))
+        return indices, dist, stats
+
+    def embedding_neighbours(self, queries, corpus=None, k: int = 10, exclude_self=None, exact_only: bool = False):
+        """``chessvision.embeddings.neighbours`` on the device, bit for bit: host arrays or tensors in (moved to the device if need
+        be), a ``Neighbours`` of numpy arrays out, ``stats`` telling how many rows the filter certified and how many went through the
+        exact path.  ``corpus=None``: the table against itself without each row's own entry.  Synchronises the current stream."""
+        from .embeddings import Neighbours, check_neighbour_arguments
+
+        def dev(t):
+            t = t if isinstance(t, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(t, dtype=np.float32))
+            return t.to(self.device, torch.float32).contiguous()
+
+        a = dev(queries)
+        b = a if corpus is None else dev(corpus)
+        if a.dim() != 2 or b.dim() != 2 or a.shape[0] < 1 or b.shape[0] < 1 or a.shape[1] < 1:
+            raise ValueError(f"embedding_neighbours expects (rows, channels) tables, got {tuple(a.shape)} and {tuple(b.shape)}")
+        exclude_self = check_neighbour_arguments(a.shape[0], b.shape[0], a.shape[1], b.shape[1], k, corpus is not None, exclude_self)
+        indices, dist, stats = self.embedding_neighbours_dev(a, b, int(k), exclude_self, exact_only)
+        record = stats.cpu().numpy()
+        return Neighbours(indices.cpu().numpy(), dist.cpu().numpy(), {name: int(record[i]) for i, name in enumerate(NEIGHBOUR_STATS)})
 
     def extraction_scores_dev(self, values: torch.Tensor, transform: str = "none", want_mask: bool = False):
         """The device half of ``extraction_scores``: launches the score kernel on the current stream behind whatever produced

@@ -16,6 +16,7 @@
 #include "jpeg_device.h"
 #include "jpeg_enc_device.h"
 #include "models.h"
+#include "neighbours.h"
 #include "pipeline.h"
 #include "pointwise.h"
 
@@ -34,6 +35,10 @@ static_assert(sizeof(cv_jpeg_info_t) == sizeof(cvjpeg::Info) && offsetof(cv_jpeg
               offsetof(cv_jpeg_info_t, reason) == offsetof(cvjpeg::Info, reason) && (int)CV_ERR_INVALID == (int)cvjpeg::kInvalid &&
               (int)CV_JPEG_BGR == (int)cv::kJpegBGR && (int)CV_JPEG_RGB == (int)cv::kJpegRGB && (int)CV_JPEG_GRAY == (int)cv::kJpegGray,
               "cv_jpeg_info_t is the parser's record");
+static_assert(sizeof(cv_neighbour_stats_t) == sizeof(cv::NeighbourStats) && sizeof(cv_neighbour_stats_t) == 32 &&
+              offsetof(cv_neighbour_stats_t, nonfinite_corpus_rows) == offsetof(cv::NeighbourStats, nonfinite_corpus_rows) &&
+              (int)CV_NEIGHBOURS_EXCLUDE_SELF == (int)cv::kNeighbourExcludeSelf && (int)CV_NEIGHBOURS_EXACT_ONLY == (int)cv::kNeighbourExactOnly,
+              "cv_neighbour_stats_t is the kernels' record");
 static_assert(sizeof(cv_square_score_t) == 24 && sizeof(cv_board_score_t) == 64, "layouts the Python binding mirrors");
 
 using namespace cv;
@@ -1485,9 +1490,48 @@ int cv_jpeg_encode_gray_u8(cv_engine_t* eng, const uint8_t* src, int n, int h, i
     });
 }
 
+// ---- embedding neighbours (neighbours.hip) ----------------------------------------------------------------------------------------
+static bool neighbours_in_limits(int q, int n, int c, int k) {
+    return q >= 1 && q <= kNeighbourMaxRows && n >= 1 && n <= kNeighbourMaxRows && c >= 1 && c <= kNeighbourMaxC && k >= 1 && k <= kNeighbourMaxK;
+}
+
+size_t cv_embedding_neighbours_scratch_bytes(int q, int n, int c, int k) {
+    return neighbours_in_limits(q, n, c, k) ? neighbour_plan(q, n, c, k).bytes : 0;
+}
+
+int cv_embedding_neighbours(cv_engine_t* eng, const float* queries, int q, const float* corpus, int n, int c, int k, int flags,
+                            int32_t* indices, double* sq_distances, cv_neighbour_stats_t* stats, void* scratch, size_t scratch_bytes,
+                            void* stream) {
+    return guarded("cv_embedding_neighbours", [&]() -> Status {
+        CV_TRY(check_engine(eng));
+        const std::string me = "cv_embedding_neighbours: ";
+        if (k < 1 || k > kNeighbourMaxK) return fail(CV_ERR_INVALID, me + "k must be in [1, 64], got " + std::to_string(k));
+        if (c < 1 || c > kNeighbourMaxC) return fail(CV_ERR_INVALID, me + "c must be in [1, 4096], got " + std::to_string(c));
+        if (q < 1 || q > kNeighbourMaxRows) return fail(CV_ERR_INVALID, me + "q must be in [1, 2^22], got " + std::to_string(q));
+        if (n < 1 || n > kNeighbourMaxRows) return fail(CV_ERR_INVALID, me + "n must be in [1, 2^22], got " + std::to_string(n));
+        if (flags & ~(CV_NEIGHBOURS_EXCLUDE_SELF | CV_NEIGHBOURS_EXACT_ONLY)) return fail(CV_ERR_INVALID, me + "flags holds an unknown bit");
+        if ((flags & CV_NEIGHBOURS_EXCLUDE_SELF) && q != n) return fail(CV_ERR_INVALID, me + "flags: exclude-self needs q == n");
+        if (!queries || ((uintptr_t)queries & 3u)) return fail(CV_ERR_INVALID, me + "queries must be a 4-byte aligned device pointer");
+        if (!corpus || ((uintptr_t)corpus & 3u)) return fail(CV_ERR_INVALID, me + "corpus must be a 4-byte aligned device pointer");
+        if (!indices || ((uintptr_t)indices & 3u)) return fail(CV_ERR_INVALID, me + "indices must be a 4-byte aligned device pointer");
+        if (!sq_distances || ((uintptr_t)sq_distances & 7u)) return fail(CV_ERR_INVALID, me + "sq_distances must be an 8-byte aligned device pointer");
+        if ((uintptr_t)stats & 3u) return fail(CV_ERR_INVALID, me + "stats must be 4-byte aligned");
+        const size_t need = neighbour_plan(q, n, c, k).bytes;
+        if (!scratch || ((uintptr_t)scratch & 15u)) return fail(CV_ERR_INVALID, me + "scratch must be a 16-byte aligned device pointer");
+        if (scratch_bytes < need)
+            return fail(CV_ERR_INVALID, me + "scratch_bytes is " + std::to_string(scratch_bytes) + ", " + std::to_string(need) + " needed");
+        DeviceGuard g(eng->impl.device);
+        hipError_t e = embedding_neighbours(queries, q, corpus, n, c, k, flags, indices, sq_distances, reinterpret_cast<NeighbourStats*>(stats),
+                                            scratch, (hipStream_t)stream);
+        if (e != hipSuccess) return hip_fail(e, "embedding_neighbours");
+        return Status();
+    });
+}
+
 // ---- the JPEG decoder's two halves are part of this translation unit -------------------------------------------------------
 // The library's list of units is fixed (every build of it, the host-only sanitizer builds included, compiles and links exactly
 // that list).  jpeg.cpp stays a plain C++17 file that g++ compiles on its own; jpeg.hip holds the two kernels and their launch wrapper.
 #include "jpeg.cpp"
 #include "jpeg.hip"
 #include "jpeg_enc.hip"
+#include "neighbours.hip"

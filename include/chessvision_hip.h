@@ -539,6 +539,47 @@ typedef struct cv_squares_summary {
 } cv_squares_summary_t;
 int cv_square_records_finish(const cv_square_record_t* records, int n, int batch_size, cv_squares_summary_t* out);
 
+/* ---- embedding neighbours (additions under ABI 6; detect with dlsym(handle, "cv_embedding_neighbours")) ------------------------- */
+/* The one thing the embeddings are collected for: the reference reduces the table with run.reduce_embeddings_by_foreign_table_url(...,
+ * method="pacmap") (scripts/process_new_raw/process_pipeline.py:351, scripts/train/train_classifier.py:312) so that uploads and squares
+ * can be browsed by similarity.  PaCMAP and UMAP both start from the k-nearest-neighbour graph of the table; this is that graph, exact.
+ * The reduction itself, PaCMAP's scaled-distance neighbour choice, other metrics (normalise the rows for cosine), approximate indices
+ * and corpora that do not fit the device are out of scope.
+ *
+ * Definition, for float32 rows a (query) and b (corpus) of length c:
+ *     D(a, b):  s = 0.0 (double);  for ch = 0 .. c-1 ascending:  t = (double)a[ch] - (double)b[ch];  p = t * t;  s = s + p;  return s
+ *   the product rounded to double, then the sum rounded to double, never contracted into a fused multiply-add.
+ * Order: the result of query row i is the k eligible corpus rows with the smallest (D, j) pairs, ascending -- distance first, corpus
+ *   index second: the order of a stable sort of float64 brute force.  sq_distances holds D itself (squared, float64).
+ * Eligibility: with flag bit 0 (exclude self; needs q == n) corpus row j == i is dropped BY INDEX, so an exact duplicate stored
+ *   elsewhere stays visible at distance 0.0.  A corpus row holding a NaN or an infinity is never returned.  A query row holding one
+ *   gets indices -1 and distances NaN.  When fewer than k rows are eligible the remaining slots are index -1, distance +inf.
+ * How: a float32 MFMA filter on mean-centred rows keeps k + 16 candidates per row and the smallest approximate distance T it did not
+ *   keep; the candidates are re-computed with D and sorted; the row is CERTIFIED when D_k < T - E, E a proven bound on |approximate - D|
+ *   (DESIGN.md section 4 "Embedding neighbours") -- then no row outside the candidates can belong to the answer, tie order included.
+ *   Every other row is recomputed against the whole corpus with D alone (the exact path; flag bit 1 sends every row there).  Either
+ *   way the output is the definition's, bit for bit, and the same run to run.
+ *
+ * queries: DEVICE (q, c) float32, dense, 4-byte aligned; corpus: DEVICE (n, c) likewise; queries == corpus is allowed.
+ * Limits: 1 <= k <= 64, 1 <= c <= 4096, 1 <= q, n <= 1 << 22.  flags: CV_NEIGHBOURS_EXCLUDE_SELF | CV_NEIGHBOURS_EXACT_ONLY.
+ * indices: DEVICE (q, k) int32; sq_distances: DEVICE (q, k) double, 8-byte aligned; stats: DEVICE, nullable, 4-byte aligned;
+ * scratch: DEVICE, 16-byte aligned, scratch_bytes >= cv_embedding_neighbours_scratch_bytes(q, n, c, k) (0 for arguments outside the
+ * limits); the caller owns it and may reuse it once `stream` has passed the call.
+ * Asynchronous on `stream`; allocates nothing and synchronises nothing.  CV_ERR_INVALID names the offending argument. */
+enum { CV_NEIGHBOURS_EXCLUDE_SELF = 1, CV_NEIGHBOURS_EXACT_ONLY = 2 };
+typedef struct cv_neighbour_stats {   /* 32 bytes, written with integer atomics and plain stores */
+    int32_t query_rows;               /* q */
+    int32_t certified_rows;           /* rows whose filter result was proven exact */
+    int32_t exact_rows;               /* rows recomputed against the whole corpus */
+    int32_t nonfinite_query_rows;     /* query_rows == certified_rows + exact_rows + nonfinite_query_rows */
+    int32_t nonfinite_corpus_rows;
+    int32_t reserved[3];              /* 0 */
+} cv_neighbour_stats_t;
+size_t cv_embedding_neighbours_scratch_bytes(int q, int n, int c, int k);
+int cv_embedding_neighbours(cv_engine_t* eng, const float* queries, int q, const float* corpus, int n, int c, int k, int flags,
+                            int32_t* indices, double* sq_distances, cv_neighbour_stats_t* stats, void* scratch, size_t scratch_bytes,
+                            void* stream);
+
 /* ---- one image, host to host: the native form of ChessVision.process_image (core.py:152-195) ---------------------------------- */
 /* Everything a cgo / JNI / C++ host needs for the reference's per-image entry point in ONE call: INTER_AREA resize to 256x256
  * (core.py:212), UNet forward, sigmoid / threshold mask (core.py:273, utils.py:101-112), contours -> quadrangle (core.py:357-411),
