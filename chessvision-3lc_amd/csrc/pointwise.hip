@@ -10,10 +10,11 @@
 // adaptive_avg_pool2d(1) + linear 512->13 (+ softmax, core.py:242), and the u8 HWC -> /255 -> NCHW input
 // packing of core.py:215-216 / 236-237.
 #include "pointwise.h"
-#include "conv_device.h"   // OutVec (split-f16 store units)
+#include "engine.h"        // env_switch
 
 #include <algorithm>
 #include <cmath>
+#include <type_traits>
 
 namespace cv {
 
@@ -100,19 +101,26 @@ static inline unsigned grid_for(size_t work, int block = 256) {
     return (unsigned)(g < 1 ? 1 : g);
 }
 
-// decode a flat (pixel, group) work index of tensor `t`
-struct PG { int n, y, x, g; bool live; };
-template <typename T> __device__ __forceinline__ PG decode_pg(const TensorRef& t) {
-    const int groups = t.C / Grp<T>::N;
-    const size_t total = (size_t)t.N * t.H * t.W * groups;
-    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    PG r;
-    r.live = idx < total;
-    r.g = (int)(idx % groups);
-    size_t pix = idx / groups;
+// The one flat-index decode of this file.  A flat interior-pixel index of `t` (x fastest, then y, then the image) -> (n, y, x); the
+// index is 64-bit, as every kernel's flat work index is.  What is left above the rows lands in n: the image, or image * C + channel
+// for a walk over planes (unpack_nchw_f32_kernel).
+struct Pix { int n, y, x; };
+__device__ __forceinline__ Pix decode_pix(const TensorRef& t, size_t pix) {
+    Pix r;
     r.x = (int)(pix % t.W); pix /= t.W;
     r.y = (int)(pix % t.H);
     r.n = (int)(pix / t.H);
+    return r;
+}
+// a flat (pixel, group) work index of `t`, group fastest: the thread's own unless the kernel strides over several
+struct PG : Pix { int g; bool live; };
+template <typename T>
+__device__ __forceinline__ PG decode_pg(const TensorRef& t, size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x) {
+    const int groups = t.C / Grp<T>::N;
+    PG r;
+    r.live = idx < (size_t)t.N * t.H * t.W * groups;
+    r.g = (int)(idx % groups);
+    static_cast<Pix&>(r) = decode_pix(t, idx / groups);
     return r;
 }
 
@@ -141,17 +149,14 @@ __global__ void pack_hwc3_u8_kernel(const uint8_t* __restrict__ src, TensorRef d
     const size_t total = (size_t)dst.N * dst.H * dst.W;
     const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= total) return;
-    size_t pix = idx;
-    const int x = (int)(pix % dst.W); pix /= dst.W;
-    const int y = (int)(pix % dst.H);
-    const int n = (int)(pix / dst.H);
+    const Pix p = decode_pix(dst, idx);
     const uint8_t* s = src + idx * 3;
     // /255 first (the reference's arithmetic, core.py:215), then the power-of-two range factor (exact)
     const float f[8] = {(float)s[0] / 255.f * mul, (float)s[1] / 255.f * mul, (float)s[2] / 255.f * mul, 0.f, 0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int g = 0; g < 8 / GN; ++g) {
         int par;
-        char* d = grp_ptr<T>(dst, pix_index(dst, n, y, x), g, &par);
+        char* d = grp_ptr<T>(dst, pix_index(dst, p.n, p.y, p.x), g, &par);
         Grp<T>::store(d, par, f + g * GN);
     }
 }
@@ -162,13 +167,10 @@ __global__ void unpack_nchw_f32_kernel(TensorRef src, float* __restrict__ dst, f
     const size_t total = (size_t)src.N * src.C * src.H * src.W;
     const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= total) return;
-    size_t r = idx;
-    const int x = (int)(r % src.W); r /= src.W;
-    const int y = (int)(r % src.H); r /= src.H;
-    const int c = (int)(r % src.C);
-    const int n = (int)(r / src.C);
+    const Pix q = decode_pix(src, idx);                      // q.n: the plane, image * C + channel (< 2^31 as N * C is)
+    const int c = q.n % src.C, n = q.n / src.C;
     int par;
-    const char* p = grp_ptr<T>(src, pix_index(src, n, y, x), c / GN, &par);
+    const char* p = grp_ptr<T>(src, pix_index(src, n, q.y, q.x), c / GN, &par);
     float v[GN];
     Grp<T>::load(p, par, v);
     float out = v[0];
@@ -182,18 +184,13 @@ __global__ void unpack_nchw_f32_kernel(TensorRef src, float* __restrict__ dst, f
 template <typename T>
 __global__ void absmax_kernel(TensorRef src, unsigned* __restrict__ out) {
     constexpr int GN = Grp<T>::N;
-    const int groups = src.C / GN;
-    const size_t total = (size_t)src.N * src.H * src.W * groups;
     unsigned m = 0;
-    for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (size_t)gridDim.x * blockDim.x) {
-        const int g = (int)(idx % groups);
-        size_t pix = idx / groups;
-        const int x = (int)(pix % src.W); pix /= src.W;
-        const int y = (int)(pix % src.H);
-        const int n = (int)(pix / src.H);
+    for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;; idx += (size_t)gridDim.x * blockDim.x) {
+        const PG p = decode_pg<T>(src, idx);
+        if (!p.live) break;
         int par;
         float v[GN];
-        Grp<T>::load(grp_ptr<T>(src, pix_index(src, n, y, x), g, &par), par, v);
+        Grp<T>::load(grp_ptr<T>(src, pix_index(src, p.n, p.y, p.x), p.g, &par), par, v);
 #pragma unroll
         for (int j = 0; j < GN; ++j) {
             const unsigned b = __float_as_uint(v[j]) & 0x7fffffffu;
@@ -370,6 +367,64 @@ __device__ __forceinline__ void bilinear_axis(float scale, int index, int in_siz
     l1 = f - (float)i0;
 }
 
+// ---- the split-f16 up-sample, shared by the two kernels below: one tap loader, one blend-and-store tail, hence the same bits ----------
+// (round 5) With every tap converted to f32 (hi + lo) before the blend the kernel was bound by vector issue, not by HBM: ~200
+// instructions per 32 stored bytes.  The taps stay f16: each of the eight products per value is one mixed-precision FMA that reads the
+// f16 half directly (v_fma_mix_f32), the four weights ly * lx * mul are formed once per output and rounded once (the nested form of the
+// other storage types rounds its partial sums: a last-bit difference; the parity bars are 1e-5 on the op, 1e-3 end to end), and the
+// numeric guard runs on the packed hi pairs.
+// The four taps (y0 | y1, x0 | x1) of group g, t[tap][0..3] the first 16-byte half of the group and t[tap][4..7] the second.  32-bit
+// byte offsets from the (wave-uniform) tensor base: tensors stay below 4 GiB (checked by the engine), and the per-tap 64-bit address
+// arithmetic was a third of the vector instructions.
+__device__ __forceinline__ void upsample_split_load4(const TensorRef& src, int n, int y0, int y1, int x0, int x1, unsigned g, unsigned (&t)[4][8]) {
+    const char* const sbase = reinterpret_cast<const char*>(src.base);
+    const unsigned spix = (unsigned)src.Cs * 4u, goff = (unsigned)src.Coff * 4u + g * 32u;
+    const unsigned r0 = (unsigned)pix_index(src, n, y0, 0), r1 = (unsigned)pix_index(src, n, y1, 0);
+    const unsigned o00 = (r0 + (unsigned)x0) * spix + goff, o10 = (r1 + (unsigned)x0) * spix + goff, dxb = (unsigned)(x1 - x0) * spix;
+    const unsigned off[4] = {o00, o00 + dxb, o10, o10 + dxb};
+    typedef unsigned u4t __attribute__((ext_vector_type(4)));
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const u4t a = *reinterpret_cast<const u4t*>(sbase + off[q]), b = *reinterpret_cast<const u4t*>(sbase + off[q] + 16);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) { t[q][i] = a[i]; t[q][4 + i] = b[i]; }
+    }
+}
+// one output pixel's group from its four taps: blend (taps 00, 01, 10, 11; of each the first half, then the second -- which of them
+// holds hi and which lo does not matter to the sum), split, guard, store by the output group's parity
+__device__ __forceinline__ void upsample_split_emit(const TensorRef& dst, size_t opix, unsigned g, const unsigned (&t)[4][8], float w00, float w01,
+                                                    float w10, float w11, float& bad) {
+    const float wt[4] = {w00, w01, w10, w11};
+    float o[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) o[j] = 0.f;
+    // tap-major: the eight accumulators are independent, so no FMA waits for the one before it (value-major, the compiler padded every
+    // dependent pair of these asm instructions with an s_nop)
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) o[j] = fma_mix_f16(t[k][j >> 1], j & 1, wt[k], o[j]);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) o[j] = fma_mix_f16(t[k][4 + (j >> 1)], j & 1, wt[k], o[j]);
+    }
+    const int opar = (dst.Coff / 8 + (int)g) & 1;
+    char* const dp = reinterpret_cast<char*>(dst.base) + ((unsigned)opix * ((unsigned)dst.Cs * 4u) + (unsigned)dst.Coff * 4u + g * 32u);
+    typedef unsigned u4 __attribute__((ext_vector_type(4)));
+    typedef _Float16 h2 __attribute__((ext_vector_type(2)));
+    u4 hi, lo;
+    h2 g2 = {(half_t)0.f, (half_t)0.f};
+#pragma unroll
+    for (int j = 0; j < 8; j += 2) {
+        unsigned hp, lp;
+        split_pair(o[j], o[j + 1], hp, lp);                   // behind the FMAs that consume nothing else: no MFMA in these kernels
+        g2 = __builtin_elementwise_fma(__builtin_bit_cast(h2, hp), h2{(half_t)0.f, (half_t)0.f}, g2);
+        hi[j / 2] = hp; lo[j / 2] = lp;
+    }
+    bad = __builtin_fmaf((float)g2[0] + (float)g2[1], 0.f, bad);
+    *reinterpret_cast<u4*>(dp + (opar ? 16 : 0)) = hi;
+    *reinterpret_cast<u4*>(dp + (opar ? 0 : 16)) = lo;
+}
+
 // torch upsample_bilinear2d, align_corners=True: src = dst * (in-1)/(out-1); weights (1-l, l) in f32.
 // Grid = (row segments, output rows, images): the row's source lines and vertical weights are wave-uniform and a thread finds its
 // (column, channel group) with one 32-bit division (r03: the flat one-thread-per-element form decoded its index with three 64-bit
@@ -395,58 +450,9 @@ __global__ __launch_bounds__(256) void upsample_bilinear2x_kernel(TensorRef src,
         bilinear_axis(sx, (int)x, src.W, x0, x1, lx1);
         const float lx0 = 1.f - lx1;
         if constexpr (__is_same(T, split_t)) {
-            // split-f16 (round 5): the kernel is bound by vector issue, not by HBM (~200 instructions per 32 stored bytes: every tap
-            // converted hi and lo to f32 and added them before the blend).  The taps stay f16: each of the eight products per value is one
-            // mixed-precision FMA that reads the f16 half directly (v_fma_mix_f32), the four weights are formed once per lane, and the
-            // numeric guard runs on the packed hi pairs.  Rounding: the weights ly*lx are rounded once instead of the nested form's
-            // partial sums -- a last-bit difference (the parity bars are 1e-5 on the op, 1e-3 end to end).
-            // 32-bit byte offsets from the (wave-uniform) tensor bases: tensors stay below 4 GiB (checked by the engine), and the per-tap
-            // 64-bit address arithmetic was a third of this kernel's vector instructions
-            const char* const sbase = reinterpret_cast<const char*>(src.base);
-            const unsigned spix = (unsigned)src.Cs * 4u, goff = (unsigned)src.Coff * 4u + g * 32u;
-            const unsigned o00 = ((unsigned)row0 + (unsigned)x0) * spix + goff, o10 = ((unsigned)row1 + (unsigned)x0) * spix + goff;
-            const unsigned dxb = (unsigned)(x1 - x0) * spix;
-            const char* const p00 = sbase + o00;
-            const char* const p01 = sbase + (o00 + dxb);
-            const char* const p10 = sbase + o10;
-            const char* const p11 = sbase + (o10 + dxb);
-            const half8 a00 = *reinterpret_cast<const half8*>(p00), b00 = *reinterpret_cast<const half8*>(p00 + 16);
-            const half8 a01 = *reinterpret_cast<const half8*>(p01), b01 = *reinterpret_cast<const half8*>(p01 + 16);
-            const half8 a10 = *reinterpret_cast<const half8*>(p10), b10 = *reinterpret_cast<const half8*>(p10 + 16);
-            const half8 a11 = *reinterpret_cast<const half8*>(p11), b11 = *reinterpret_cast<const half8*>(p11 + 16);
-            const float w00 = ly0 * lx0 * mul, w01 = ly0 * lx1 * mul, w10 = ly1 * lx0 * mul, w11 = ly1 * lx1 * mul;   // mul = 2^k: exact
-            float o[8];
-            typedef unsigned u4t __attribute__((ext_vector_type(4)));
-            const u4t ta[4] = {__builtin_bit_cast(u4t, a00), __builtin_bit_cast(u4t, a01), __builtin_bit_cast(u4t, a10), __builtin_bit_cast(u4t, a11)};
-            const u4t tb[4] = {__builtin_bit_cast(u4t, b00), __builtin_bit_cast(u4t, b01), __builtin_bit_cast(u4t, b10), __builtin_bit_cast(u4t, b11)};
-            const float wt[4] = {w00, w01, w10, w11};
-#pragma unroll
-            for (int j = 0; j < 8; ++j) o[j] = 0.f;
-            // tap-major: the eight accumulators are independent, so no FMA waits for the one before it (value-major, the compiler padded
-            // every dependent pair of these asm instructions with an s_nop)
-#pragma unroll
-            for (int t = 0; t < 4; ++t) {
-#pragma unroll
-                for (int j = 0; j < 8; ++j) o[j] = fma_mix_f16(ta[t][j >> 1], j & 1, wt[t], o[j]);   // hi + lo of a tap: the chunk order
-#pragma unroll
-                for (int j = 0; j < 8; ++j) o[j] = fma_mix_f16(tb[t][j >> 1], j & 1, wt[t], o[j]);   // inside the group does not matter
-            }
-            const int opar = (dst.Coff / 8 + (int)g) & 1;
-            char* const dp = reinterpret_cast<char*>(dst.base) + (((unsigned)orow + x) * ((unsigned)dst.Cs * 4u) + (unsigned)dst.Coff * 4u + g * 32u);
-            typedef unsigned u4 __attribute__((ext_vector_type(4)));
-            typedef _Float16 h2 __attribute__((ext_vector_type(2)));
-            u4 hi, lo;
-            h2 g2 = {(half_t)0.f, (half_t)0.f};
-#pragma unroll
-            for (int j = 0; j < 8; j += 2) {
-                unsigned hp, lp;
-                split_pair(o[j], o[j + 1], hp, lp);                   // behind the FMAs that consume nothing else: no MFMA in this kernel
-                g2 = __builtin_elementwise_fma(__builtin_bit_cast(h2, hp), h2{(half_t)0.f, (half_t)0.f}, g2);
-                hi[j / 2] = hp; lo[j / 2] = lp;
-            }
-            bad = __builtin_fmaf((float)g2[0] + (float)g2[1], 0.f, bad);
-            *reinterpret_cast<u4*>(dp + (opar ? 16 : 0)) = hi;
-            *reinterpret_cast<u4*>(dp + (opar ? 0 : 16)) = lo;
+            unsigned t[4][8];
+            upsample_split_load4(src, n, y0, y1, x0, x1, g, t);
+            upsample_split_emit(dst, orow + x, g, t, ly0 * lx0 * mul, ly0 * lx1 * mul, ly1 * lx0 * mul, ly1 * lx1 * mul, bad);   // mul = 2^k: exact
         } else {
         float v00[GN], v01[GN], v10[GN], v11[GN], o[GN];
         int par;
@@ -466,41 +472,10 @@ __global__ __launch_bounds__(256) void upsample_bilinear2x_kernel(TensorRef src,
 // split-f16, 2 x 2 OUTPUT pixels per lane (round 5).  With align_corners=True and an exact factor of two the output rows 2k - 1 and 2k
 // blend the SAME two source rows (k - 1, k) -- likewise the columns -- so a lane that owns the block {2k - 1, 2k} x {2j - 1, 2j} loads
 // four source pixels (8 x 16 bytes) for four outputs instead of 32 x 16 bytes: the one-output-per-lane kernel above moved its bytes
-// at 0.44 of the HBM rate on tap loads through L1, not on arithmetic.  Each output keeps the exact operation order of that kernel
-// (weights ly * lx * mul rounded once, taps accumulated 00, 01, 10, 11), so both kernels produce the same bits; a block whose rows or
+// at 0.44 of the HBM rate on tap loads through L1, not on arithmetic.  Each output leaves through that kernel's own tail
+// (upsample_split_emit, with weights formed by the same expression), so both kernels produce the same bits; a block whose rows or
 // columns do NOT share their source pair (never for a factor of two; checked, not assumed: the indices come from the same float
 // products torch forms) falls back to that order with its own loads.  Grid = (segments of (W_in + 1) x groups, H_in + 1, images).
-__device__ __forceinline__ void upsample_split_emit(const TensorRef& dst, size_t opix, unsigned g, const unsigned (&t)[4][8], float w00, float w01,
-                                                    float w10, float w11, float& bad) {
-    const float wt[4] = {w00, w01, w10, w11};
-    float o[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) o[j] = 0.f;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) o[j] = fma_mix_f16(t[k][j >> 1], j & 1, wt[k], o[j]);          // first 16-byte half of the group
-#pragma unroll
-        for (int j = 0; j < 8; ++j) o[j] = fma_mix_f16(t[k][4 + (j >> 1)], j & 1, wt[k], o[j]);    // second half
-    }
-    const int opar = (dst.Coff / 8 + (int)g) & 1;
-    char* const dp = reinterpret_cast<char*>(dst.base) + ((unsigned)opix * ((unsigned)dst.Cs * 4u) + (unsigned)dst.Coff * 4u + g * 32u);
-    typedef unsigned u4 __attribute__((ext_vector_type(4)));
-    typedef _Float16 h2 __attribute__((ext_vector_type(2)));
-    u4 hi, lo;
-    h2 g2 = {(half_t)0.f, (half_t)0.f};
-#pragma unroll
-    for (int j = 0; j < 8; j += 2) {
-        unsigned hp, lp;
-        split_pair(o[j], o[j + 1], hp, lp);
-        g2 = __builtin_elementwise_fma(__builtin_bit_cast(h2, hp), h2{(half_t)0.f, (half_t)0.f}, g2);
-        hi[j / 2] = hp; lo[j / 2] = lp;
-    }
-    bad = __builtin_fmaf((float)g2[0] + (float)g2[1], 0.f, bad);
-    *reinterpret_cast<u4*>(dp + (opar ? 16 : 0)) = hi;
-    *reinterpret_cast<u4*>(dp + (opar ? 0 : 16)) = lo;
-}
-
 __global__ __launch_bounds__(256) void upsample_bilinear2x_split2x2_kernel(TensorRef src, TensorRef dst, float mul, float sy, float sx,
                                                                            unsigned* flag, unsigned layer_id) {
     const int k = blockIdx.y, n = blockIdx.z;
@@ -528,22 +503,8 @@ __global__ __launch_bounds__(256) void upsample_bilinear2x_split2x2_kernel(Tenso
             bilinear_axis(sx, cv_[c] ? cx[c] : 0, src.W, x0[c], x1[c], lx1[c]);
         }
         const int cbase = cv_[0] ? 0 : 1;
-        const char* const sbase = reinterpret_cast<const char*>(src.base);
-        const unsigned spix = (unsigned)src.Cs * 4u, goff = (unsigned)src.Coff * 4u + g * 32u;
-        auto load4 = [&](int yy0, int yy1, int xx0, int xx1, unsigned (&t)[4][8]) {
-            const unsigned r0 = (unsigned)pix_index(src, n, yy0, 0), r1 = (unsigned)pix_index(src, n, yy1, 0);
-            const unsigned off[4] = {(r0 + (unsigned)xx0) * spix + goff, (r0 + (unsigned)xx1) * spix + goff, (r1 + (unsigned)xx0) * spix + goff,
-                                     (r1 + (unsigned)xx1) * spix + goff};
-            typedef unsigned u4t __attribute__((ext_vector_type(4)));
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const u4t a = *reinterpret_cast<const u4t*>(sbase + off[q]), b = *reinterpret_cast<const u4t*>(sbase + off[q] + 16);
-#pragma unroll
-                for (int i = 0; i < 4; ++i) { t[q][i] = a[i]; t[q][4 + i] = b[i]; }
-            }
-        };
         unsigned t[4][8];
-        load4(y0[rbase], y1[rbase], x0[cbase], x1[cbase], t);
+        upsample_split_load4(src, n, y0[rbase], y1[rbase], x0[cbase], x1[cbase], g, t);
 #pragma unroll
         for (int r = 0; r < 2; ++r) {
             if (!rv[r]) continue;
@@ -559,7 +520,7 @@ __global__ __launch_bounds__(256) void upsample_bilinear2x_split2x2_kernel(Tenso
                     upsample_split_emit(dst, opix, g, t, w00, w01, w10, w11, bad);
                 } else {                                      // not reached for a factor of two; kept so that the kernel is exact for any geometry
                     unsigned u[4][8];
-                    load4(y0[r], y1[r], x0[c], x1[c], u);
+                    upsample_split_load4(src, n, y0[r], y1[r], x0[c], x1[c], g, u);
                     upsample_split_emit(dst, opix, g, u, w00, w01, w10, w11, bad);
                 }
             }
@@ -582,13 +543,10 @@ __global__ void outc_1x1_kernel(TensorRef src, const float* __restrict__ w, cons
     size_t pix = idx / lpp;
     const bool live = pix < npix;
     if (!live) pix = npix - 1;
-    size_t r = pix;
-    const int x = (int)(r % src.W); r /= src.W;
-    const int y = (int)(r % src.H);
-    const int n = (int)(r / src.H);
+    const Pix p = decode_pix(src, pix);
     float v[GN];
     int par;
-    Grp<T>::load(grp_ptr<T>(src, pix_index(src, n, y, x), part, &par), par, v);
+    Grp<T>::load(grp_ptr<T>(src, pix_index(src, p.n, p.y, p.x), part, &par), par, v);
     float acc = 0.f;
 #pragma unroll
     for (int j = 0; j < GN; ++j) acc += v[j] * w[part * GN + j];
@@ -1140,21 +1098,71 @@ __device__ __forceinline__ float score_unkey(unsigned k) {
     return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
 }
 
+// The frame the three score kernels share.  A workgroup's image: `count` float32 of which `head` (< 4) come before the first 16-byte
+// boundary, then `nvec` 16-byte pieces (the body), then the rest.  A byte stream that runs beside the image (labels, masks, levels: one
+// byte per element, any alignment) moves four bytes at a time over the body where it is 4-aligned there.
+struct ScoreSpan {
+    const float* img;
+    int count, head, nvec;
+    __device__ ScoreSpan(const float* images, int count_) : img(images + (size_t)blockIdx.x * count_), count(count_) {
+        head = min(count, (int)(((16u - (unsigned)((uintptr_t)img & 15u)) & 15u) >> 2));
+        nvec = (count - head) >> 2;
+    }
+    __device__ bool aligned4(const uint8_t* bytes) const { return (((uintptr_t)(bytes + head)) & 3u) == 0; }
+};
+// m bytes at bytes[at]: one 4-byte access for a body piece (m == 4) of an aligned4 stream, single bytes otherwise
+template <int m> __device__ __forceinline__ void load_bytes(const uint8_t* bytes, int at, bool aligned, uint8_t (&v)[m]) {
+    if constexpr (m == 4) {
+        if (aligned) {
+            const uchar4 q = *reinterpret_cast<const uchar4*>(bytes + at);
+            v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
+            return;
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < m; ++j) v[j] = bytes[at + j];
+}
+template <int m> __device__ __forceinline__ void store_bytes(uint8_t* bytes, int at, bool aligned, const uint8_t (&v)[m]) {
+    if constexpr (m == 4) {
+        if (aligned) { *reinterpret_cast<uchar4*>(bytes + at) = make_uchar4(v[0], v[1], v[2], v[3]); return; }
+    }
+#pragma unroll
+    for (int j = 0; j < m; ++j) bytes[at + j] = v[j];
+}
+
 // f(values, ScoreInt<m>, index of values[0]): m = 4 for the 16-byte aligned body, 1 for the elements before and after it
 template <int TR, class F>
-__device__ __forceinline__ void score_sweep(const float* __restrict__ img, int count, int head, int nvec, F&& f) {
-    const float4* body = reinterpret_cast<const float4*>(img + head);
-    for (int i = threadIdx.x; i < nvec; i += kScoreThreads) {
+__device__ __forceinline__ void score_sweep(const ScoreSpan& sp, F&& f) {
+    const float4* body = reinterpret_cast<const float4*>(sp.img + sp.head);
+    for (int i = threadIdx.x; i < sp.nvec; i += kScoreThreads) {
         const float4 q = body[i];
         const float v[4] = {score_value<TR>(q.x), score_value<TR>(q.y), score_value<TR>(q.z), score_value<TR>(q.w)};
-        f(v, ScoreInt<4>(), head + 4 * i);
+        f(v, ScoreInt<4>(), sp.head + 4 * i);
     }
-    const int tail = head + 4 * nvec;
-    for (int i = threadIdx.x; i < count - 4 * nvec; i += kScoreThreads) {
-        const int at = i < head ? i : tail + (i - head);
-        const float v[1] = {score_value<TR>(img[at])};
+    const int tail = sp.head + 4 * sp.nvec;
+    for (int i = threadIdx.x; i < sp.count - 4 * sp.nvec; i += kScoreThreads) {
+        const int at = i < sp.head ? i : tail + (i - sp.head);
+        const float v[1] = {score_value<TR>(sp.img[at])};
         f(v, ScoreInt<1>(), at);
     }
+}
+
+// Per-lane values -> workgroup totals in a fixed order, so that float64 sums are the same bits run to run: score_wave_totals adds the
+// lanes of each wave by __shfl_down with d = 32 .. 1 and leaves lane 0's result in part[wave]; after a barrier, score_block_total adds
+// the waves' column j in index order (one thread per total).
+template <typename V, int K> __device__ __forceinline__ void score_wave_totals(V (&v)[K], V (*part)[K]) {
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1)
+#pragma unroll
+        for (int j = 0; j < K; ++j) v[j] += __shfl_down(v[j], d);
+    if ((threadIdx.x & 63) == 0)
+#pragma unroll
+        for (int j = 0; j < K; ++j) part[threadIdx.x >> 6][j] = v[j];
+}
+template <typename V, int K> __device__ __forceinline__ V score_block_total(const V (*part)[K], int j) {
+    V s = 0;
+    for (int w = 0; w < kScoreWaves; ++w) s += part[w][j];
+    return s;
 }
 
 // One radix step (every thread of the block calls it): merge the per-wave histograms, let wave 0 find the bin that holds the
@@ -1203,14 +1211,12 @@ __global__ __launch_bounds__(kScoreThreads) void extraction_scores_kernel(const 
     __shared__ int tot[256];
     __shared__ int wstat[kScoreWaves][12];
     __shared__ int stat[12];
-    __shared__ double wsum[kScoreWaves];
+    __shared__ double wsum[kScoreWaves][1];
     __shared__ int sel[2];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const float* img = values + (size_t)blockIdx.x * count;
+    const int tid = threadIdx.x, wave = tid >> 6;
+    const ScoreSpan sp(values, count);
     uint8_t* mk = half_mask ? half_mask + (size_t)blockIdx.x * count : nullptr;
-    const int head = min(count, (int)(((16u - (unsigned)((uintptr_t)img & 15u)) & 15u) >> 2));
-    const int nvec = (count - head) >> 2;
-    const bool mk4 = mk && (((uintptr_t)(mk + head)) & 3u) == 0;       // the body's mask bytes go out four at a time
+    const bool mk4 = mk && sp.aligned4(mk);
     int* myhist = whist[wave];
     for (int i = tid; i < kScoreWaves * 256; i += kScoreThreads) (&whist[0][0])[i] = 0;
     __syncthreads();
@@ -1220,7 +1226,7 @@ __global__ __launch_bounds__(kScoreThreads) void extraction_scores_kernel(const 
     int c[12];
 #pragma unroll
     for (int j = 0; j < 12; ++j) c[j] = 0;
-    score_sweep<TR>(img, count, head, nvec, [&](const float* v, auto M, int at) {
+    score_sweep<TR>(sp, [&](const float* v, auto M, int at) {
         constexpr int m = decltype(M)::value;
         constexpr float edge[10] = {0.f, 0.1f, 0.2f, 0.3f, 0.4f, 0.5f, 0.6f, 0.7f, 0.8f, 0.9f};
         uint8_t bits[m];
@@ -1236,37 +1242,18 @@ __global__ __launch_bounds__(kScoreThreads) void extraction_scores_kernel(const 
             bits[j] = x > 0.5f ? 255 : 0;
             atomicAdd(&myhist[score_key(x) >> 24], 1);
         }
-        if (mk) {
-            bool stored = false;
-            if constexpr (m == 4) {
-                if (mk4) { *reinterpret_cast<uchar4*>(mk + at) = make_uchar4(bits[0], bits[1], bits[2], bits[3]); stored = true; }
-            }
-            if (!stored) {
-#pragma unroll
-                for (int j = 0; j < m; ++j) mk[at + j] = bits[j];
-            }
-        }
+        if (mk) store_bytes<m>(mk, at, mk4, bits);
     });
-#pragma unroll
-    for (int j = 0; j < 12; ++j) {
-        int s = c[j];
-#pragma unroll
-        for (int d = 32; d > 0; d >>= 1) s += __shfl_down(s, d);
-        if (lane == 0) wstat[wave][j] = s;
-    }
+    score_wave_totals(c, wstat);
     int krem = count >> 2;                                    // k: how many of the largest values are averaged
     const int k = krem;
     unsigned prefix = (unsigned)score_select(whist, tot, sel, krem);      // (its first barrier publishes wstat too)
-    if (tid < 12) {
-        int s = 0;
-        for (int w = 0; w < kScoreWaves; ++w) s += wstat[w][tid];
-        stat[tid] = s;
-    }
+    if (tid < 12) stat[tid] = score_block_total(wstat, tid);
 
     // sweeps 1..3: among the values whose key starts with `prefix`, histogram the next eight key bits
 #pragma unroll 1
     for (int shift = 16; shift >= 0; shift -= 8) {
-        score_sweep<TR>(img, count, head, nvec, [&](const float* v, auto M, int) {
+        score_sweep<TR>(sp, [&](const float* v, auto M, int) {
 #pragma unroll
             for (int j = 0; j < decltype(M)::value; ++j) {
                 const unsigned key = score_key(v[j]);
@@ -1278,15 +1265,13 @@ __global__ __launch_bounds__(kScoreThreads) void extraction_scores_kernel(const 
 
     // sweep 4: prefix is the key of the k-th largest value t; sum |v - 0.5| over the values above it.  The krem values equal to t
     // that complete the k are added once at the end (ties at t contribute (k - number strictly greater) * |t - 0.5|).
-    double sum = 0.0;
-    score_sweep<TR>(img, count, head, nvec, [&](const float* v, auto M, int) {
+    double sum[1] = {0.0};
+    score_sweep<TR>(sp, [&](const float* v, auto M, int) {
 #pragma unroll
         for (int j = 0; j < decltype(M)::value; ++j)
-            if (score_key(v[j]) > prefix) sum += (double)fabsf(v[j] - 0.5f);
+            if (score_key(v[j]) > prefix) sum[0] += (double)fabsf(v[j] - 0.5f);
     });
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) sum += __shfl_down(sum, d);
-    if (lane == 0) wsum[wave] = sum;
+    score_wave_totals(sum, wsum);
     __syncthreads();
     if (tid == 0) {
         ScoreRecord r;
@@ -1294,9 +1279,7 @@ __global__ __launch_bounds__(kScoreThreads) void extraction_scores_kernel(const 
         r.hist[9] = stat[9];
         r.above_half = stat[10];
         r.n_nan = stat[11];
-        double total = 0.0;
-        for (int w = 0; w < kScoreWaves; ++w) total += wsum[w];
-        r.top_sum = total + (double)krem * (double)fabsf(score_unkey(prefix) - 0.5f);
+        r.top_sum = score_block_total(wsum, 0) + (double)krem * (double)fabsf(score_unkey(prefix) - 0.5f);
         r.top_count = k;
         r.reserved = 0;
         records[blockIdx.x] = r;
@@ -1313,29 +1296,15 @@ __global__ __launch_bounds__(kScoreThreads) void segmentation_scores_kernel(cons
                                                                             SegRecord* __restrict__ records) {
     __shared__ double wsum[kScoreWaves][3];
     __shared__ int wcnt[kScoreWaves][4];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const float* img = logits + (size_t)blockIdx.x * count;
+    const ScoreSpan sp(logits, count);
     const uint8_t* lab = labels + (size_t)blockIdx.x * count;
-    const int head = min(count, (int)(((16u - (unsigned)((uintptr_t)img & 15u)) & 15u) >> 2));
-    const int nvec = (count - head) >> 2;
-    const bool lab4 = (((uintptr_t)(lab + head)) & 3u) == 0;            // the body's label bytes come in four at a time
+    const bool lab4 = sp.aligned4(lab);
     int c[4] = {0, 0, 0, 0};                                            // n_label, n_pred, n_both, n_nan
-    double bce = 0.0, sig = 0.0, sigl = 0.0;
-    score_sweep<0>(img, count, head, nvec, [&](const float* x, auto M, int at) {
+    double s[3] = {0.0, 0.0, 0.0};                                      // bce_sum, sig_sum, sig_label_sum
+    score_sweep<0>(sp, [&](const float* x, auto M, int at) {
         constexpr int m = decltype(M)::value;
         uint8_t t[m];
-        bool loaded = false;
-        if constexpr (m == 4) {
-            if (lab4) {
-                const uchar4 q = *reinterpret_cast<const uchar4*>(lab + at);
-                t[0] = q.x; t[1] = q.y; t[2] = q.z; t[3] = q.w;
-                loaded = true;
-            }
-        }
-        if (!loaded) {
-#pragma unroll
-            for (int j = 0; j < m; ++j) t[j] = lab[at + j];
-        }
+        load_bytes<m>(lab, at, lab4, t);
 #pragma unroll
         for (int j = 0; j < m; ++j) {
             const float xv = x[j];
@@ -1348,35 +1317,19 @@ __global__ __launch_bounds__(kScoreThreads) void segmentation_scores_kernel(cons
             c[2] += on && pred;
             c[3] += xv != xv;
             const float term = (xv > 0.f ? xv : 0.f) - xv * tf + log1pf(expf(-fabsf(xv)));
-            bce += (double)term;
-            sig += (double)v;
-            sigl += (double)(v * tf);
+            s[0] += (double)term;
+            s[1] += (double)v;
+            s[2] += (double)(v * tf);
         }
     });
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) {
-        bce += __shfl_down(bce, d);
-        sig += __shfl_down(sig, d);
-        sigl += __shfl_down(sigl, d);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) c[j] += __shfl_down(c[j], d);
-    }
-    if (lane == 0) {
-        wsum[wave][0] = bce; wsum[wave][1] = sig; wsum[wave][2] = sigl;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) wcnt[wave][j] = c[j];
-    }
+    score_wave_totals(s, wsum);
+    score_wave_totals(c, wcnt);
     __syncthreads();
-    if (tid == 0) {
+    if (threadIdx.x == 0) {
         SegRecord r;
-        double s[3] = {0.0, 0.0, 0.0};
-        int k[4] = {0, 0, 0, 0};
-        for (int w = 0; w < kScoreWaves; ++w) {
-            for (int j = 0; j < 3; ++j) s[j] += wsum[w][j];
-            for (int j = 0; j < 4; ++j) k[j] += wcnt[w][j];
-        }
-        r.n_label = k[0]; r.n_pred = k[1]; r.n_both = k[2]; r.n_nan = k[3];
-        r.bce_sum = s[0]; r.sig_sum = s[1]; r.sig_label_sum = s[2];
+        r.n_label = score_block_total(wcnt, 0); r.n_pred = score_block_total(wcnt, 1);
+        r.n_both = score_block_total(wcnt, 2); r.n_nan = score_block_total(wcnt, 3);
+        r.bce_sum = score_block_total(wsum, 0); r.sig_sum = score_block_total(wsum, 1); r.sig_label_sum = score_block_total(wsum, 2);
         r.count = count;
         for (int j = 0; j < 5; ++j) r.reserved[j] = 0;
         records[blockIdx.x] = r;
@@ -1398,25 +1351,24 @@ __global__ __launch_bounds__(kScoreThreads) void threshold_levels_kernel(const f
                                                                          LevelThresholds thr, int nthr, uint8_t* __restrict__ levels,
                                                                          LevelRecord* __restrict__ records) {
     __shared__ int whist[kScoreWaves][kLevelReps][kLevelRow];
-    __shared__ int wnan[kScoreWaves];
+    __shared__ int wnan[kScoreWaves][1];
     __shared__ float sthr[kMaxLevelThresholds];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const float* img = logits + (size_t)blockIdx.x * count;
+    const ScoreSpan sp(logits, count);
     const uint8_t* lab = labels ? labels + (size_t)blockIdx.x * count : nullptr;
     uint8_t* lev = levels + (size_t)blockIdx.x * count;
-    const int head = min(count, (int)(((16u - (unsigned)((uintptr_t)img & 15u)) & 15u) >> 2));
-    const int nvec = (count - head) >> 2;
-    const bool lab4 = lab && (((uintptr_t)(lab + head)) & 3u) == 0;
-    const bool lev4 = (((uintptr_t)(lev + head)) & 3u) == 0;
+    const bool lab4 = lab && sp.aligned4(lab), lev4 = sp.aligned4(lev);
     for (int i = tid; i < kScoreWaves * kLevelReps * kLevelRow; i += kScoreThreads) (&whist[0][0][0])[i] = 0;
 #pragma unroll
     for (int k = 0; k < kMaxLevelThresholds; ++k)
         if (tid == k) sthr[k] = thr.t[k];                     // constant indices: the by-value argument stays in the kernel-argument segment
     __syncthreads();
     int* myhist = whist[wave][lane & (kLevelReps - 1)];
-    int nan = 0;
-    score_sweep<1>(img, count, head, nvec, [&](const float* v, auto M, int at) {
+    int nan[1] = {0};
+    score_sweep<1>(sp, [&](const float* v, auto M, int at) {
         constexpr int m = decltype(M)::value;
+        // the label bytes are load_bytes written out, with "no labels" read as zeros: through the helper (behind `if (lab)`, or with the
+        // null test inside it) this kernel measured 2 % slower, twice (profiles/pointwise_one_scaffold.md)
         uint8_t t[m], out[m];
         bool loaded = false;
         if constexpr (m == 4) {
@@ -1435,22 +1387,13 @@ __global__ __launch_bounds__(kScoreThreads) void threshold_levels_kernel(const f
             const float x = v[j];
             int level = 0;
             for (int k = 0; k < nthr; ++k) level += x > sthr[k];          // a NaN compares false everywhere: level 0, as the fused mask
-            nan += x != x;
+            nan[0] += x != x;
             out[j] = (uint8_t)level;
             atomicAdd(&myhist[(t[j] != 0 ? kMaxLevelThresholds + 1 : 0) + level], 1);
         }
-        bool stored = false;
-        if constexpr (m == 4) {
-            if (lev4) { *reinterpret_cast<uchar4*>(lev + at) = make_uchar4(out[0], out[1], out[2], out[3]); stored = true; }
-        }
-        if (!stored) {
-#pragma unroll
-            for (int j = 0; j < m; ++j) lev[at + j] = out[j];
-        }
+        store_bytes<m>(lev, at, lev4, out);
     });
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) nan += __shfl_down(nan, d);
-    if (lane == 0) wnan[wave] = nan;
+    score_wave_totals(nan, wnan);
     __syncthreads();
     LevelRecord* r = records + blockIdx.x;
     if (tid < kLevelBins) {
@@ -1462,11 +1405,9 @@ __global__ __launch_bounds__(kScoreThreads) void threshold_levels_kernel(const f
     } else if (tid < kLevelBins + (int)(sizeof(r->reserved) / sizeof(int32_t))) {
         r->reserved[tid - kLevelBins] = 0;
     } else if (tid == kScoreThreads - 1) {
-        int s = 0;
-        for (int w = 0; w < kScoreWaves; ++w) s += wnan[w];
         r->count = count;
         r->n_thresholds = nthr;
-        r->n_nan = s;
+        r->n_nan = score_block_total(wnan, 0);
     }
 }
 
@@ -1492,36 +1433,49 @@ __global__ void mfma_probe_f32_kernel(const float* a, const float* b, float* d) 
 }
 
 // ---- host wrappers ----------------------------------------------------------------------------------
-#define CV_DISPATCH(KERN, WORK, ...)                                                                         \
-    do {                                                                                                     \
-        const dim3 g_(grid_for(WORK)), b_(256);                                                              \
-        if (dt == kF16) hipLaunchKernelGGL(KERN<half_t>, g_, b_, 0, s, __VA_ARGS__);                         \
-        else if (dt == kSplit) hipLaunchKernelGGL(KERN<split_t>, g_, b_, 0, s, __VA_ARGS__);                 \
-        else hipLaunchKernelGGL(KERN<float>, g_, b_, 0, s, __VA_ARGS__);                                     \
-        return hipGetLastError();                                                                            \
-    } while (0)
+// The one storage-type switch: f(Tag<T>()) with T = half_t (kF16), split_t (kSplit) or float (kF32 and anything else); the lambda
+// names its kernel with T.  A wrapper whose kernel does not exist for float refuses kF32 first and leaves that case empty
+// (`if constexpr`), so nothing is instantiated for it.
+template <typename T> struct Tag { using type = T; };
+template <class G> using tag_t = typename G::type;
+template <class F> static inline void with_dtype(int dt, F&& f) {
+    if (dt == kF16) f(Tag<half_t>());
+    else if (dt == kSplit) f(Tag<split_t>());
+    else f(Tag<float>());
+}
+// The caller's image beside it: f(typed pointer, NORM) -- float, u8 (/255 in the kernel), or u8 that is normalised as well.
+template <class P> using pointee_t = std::remove_const_t<std::remove_pointer_t<P>>;
+template <class F> static inline void with_input(const void* x, bool x_is_u8, bool norm, F&& f) {
+    if (norm) f((const uint8_t*)x, std::true_type());
+    else if (x_is_u8) f((const uint8_t*)x, std::false_type());
+    else f((const float*)x, std::false_type());
+}
 
 static inline float pow2f(int e) { return ldexpf(1.f, e); }
 
 hipError_t pack_nchw_f32(int dt, const float* src, int c, const TensorRef& dst, unsigned* flag, hipStream_t s) {
     if (dst.C % dtype_group(dt) || dst.Coff % dtype_group(dt)) return hipErrorInvalidValue;
-    CV_DISPATCH(pack_nchw_f32_kernel, (size_t)dst.N * dst.H * dst.W * (dst.C / dtype_group(dt)), src, c, dst, pow2f(-dst.exp), flag);
+    const dim3 g(grid_for((size_t)dst.N * dst.H * dst.W * (dst.C / dtype_group(dt)))), b(256);
+    with_dtype(dt, [&](auto t) { hipLaunchKernelGGL(pack_nchw_f32_kernel<tag_t<decltype(t)>>, g, b, 0, s, src, c, dst, pow2f(-dst.exp), flag); });
+    return hipGetLastError();
 }
 hipError_t pack_hwc3_u8(int dt, const uint8_t* src, const TensorRef& dst, hipStream_t s) {
     if (dst.C != 8 || dst.Coff % 8) return hipErrorInvalidValue;
-    CV_DISPATCH(pack_hwc3_u8_kernel, (size_t)dst.N * dst.H * dst.W, src, dst, pow2f(-dst.exp));
+    const dim3 g(grid_for((size_t)dst.N * dst.H * dst.W)), b(256);
+    with_dtype(dt, [&](auto t) { hipLaunchKernelGGL(pack_hwc3_u8_kernel<tag_t<decltype(t)>>, g, b, 0, s, src, dst, pow2f(-dst.exp)); });
+    return hipGetLastError();
 }
 hipError_t unpack_nchw_f32(int dt, const TensorRef& src, float* dst, hipStream_t s) {
     if (src.Coff % dtype_group(dt)) return hipErrorInvalidValue;
-    CV_DISPATCH(unpack_nchw_f32_kernel, (size_t)src.N * src.C * src.H * src.W, src, dst, pow2f(src.exp));
+    const dim3 g(grid_for((size_t)src.N * src.C * src.H * src.W)), b(256);
+    with_dtype(dt, [&](auto t) { hipLaunchKernelGGL(unpack_nchw_f32_kernel<tag_t<decltype(t)>>, g, b, 0, s, src, dst, pow2f(src.exp)); });
+    return hipGetLastError();
 }
 hipError_t absmax(int dt, const TensorRef& src, unsigned* out, hipStream_t s) {
     if (src.C % dtype_group(dt) || src.Coff % dtype_group(dt)) return hipErrorInvalidValue;
     const size_t work = (size_t)src.N * src.H * src.W * (src.C / dtype_group(dt));
-    const dim3 g_((unsigned)std::min<size_t>(grid_for(work), 4096)), b_(256);
-    if (dt == kF16) hipLaunchKernelGGL(absmax_kernel<half_t>, g_, b_, 0, s, src, out);
-    else if (dt == kSplit) hipLaunchKernelGGL(absmax_kernel<split_t>, g_, b_, 0, s, src, out);
-    else hipLaunchKernelGGL(absmax_kernel<float>, g_, b_, 0, s, src, out);
+    const dim3 g((unsigned)std::min<size_t>(grid_for(work), 4096)), b(256);
+    with_dtype(dt, [&](auto t) { hipLaunchKernelGGL(absmax_kernel<tag_t<decltype(t)>>, g, b, 0, s, src, out); });
     return hipGetLastError();
 }
 hipError_t channel_means(int dt, const TensorRef& src, float* out, hipStream_t s) {
@@ -1531,11 +1485,8 @@ hipError_t channel_means(int dt, const TensorRef& src, float* out, hipStream_t s
         return hipErrorInvalidValue;
     const int slices = channel_means_slices(src.H * src.W);
     const size_t units = (size_t)src.N * (src.C / 8);
-    const dim3 g_(grid_for(units, 256 / slices)), b_(256);
-    const float mul = pow2f(src.exp);
-    if (dt == kF16) hipLaunchKernelGGL(channel_means_kernel<half_t>, g_, b_, 0, s, src, slices, mul, out);
-    else if (dt == kSplit) hipLaunchKernelGGL(channel_means_kernel<split_t>, g_, b_, 0, s, src, slices, mul, out);
-    else hipLaunchKernelGGL(channel_means_kernel<float>, g_, b_, 0, s, src, slices, mul, out);
+    const dim3 g(grid_for(units, 256 / slices)), b(256);
+    with_dtype(dt, [&](auto t) { hipLaunchKernelGGL(channel_means_kernel<tag_t<decltype(t)>>, g, b, 0, s, src, slices, pow2f(src.exp), out); });
     return hipGetLastError();
 }
 hipError_t tap_sums_f16(const TensorRef& src, int Ho, int Wo, int stride, int k, int slices, double* out, hipStream_t s) {
@@ -1547,48 +1498,50 @@ hipError_t tap_sums_f16(const TensorRef& src, int Ho, int Wo, int stride, int k,
     return hipGetLastError();
 }
 hipError_t maxpool2x2(int dt, const TensorRef& src, const TensorRef& dst, hipStream_t s) {
-    CV_DISPATCH(maxpool2x2_kernel, (size_t)dst.N * dst.H * dst.W * (dst.C / dtype_group(dt)), src, dst);
+    const dim3 g(grid_for((size_t)dst.N * dst.H * dst.W * (dst.C / dtype_group(dt)))), b(256);
+    with_dtype(dt, [&](auto t) { hipLaunchKernelGGL(maxpool2x2_kernel<tag_t<decltype(t)>>, g, b, 0, s, src, dst); });
+    return hipGetLastError();
 }
 hipError_t maxpool3x3s2(int dt, const TensorRef& src, const TensorRef& dst, hipStream_t s) {
-    CV_DISPATCH(maxpool3x3s2_kernel, (size_t)dst.N * dst.H * dst.W * (dst.C / dtype_group(dt)), src, dst);
+    const dim3 g(grid_for((size_t)dst.N * dst.H * dst.W * (dst.C / dtype_group(dt)))), b(256);
+    with_dtype(dt, [&](auto t) { hipLaunchKernelGGL(maxpool3x3s2_kernel<tag_t<decltype(t)>>, g, b, 0, s, src, dst); });
+    return hipGetLastError();
 }
 hipError_t upsample_bilinear2x(int dt, const TensorRef& src, const TensorRef& dst, unsigned* flag, unsigned layer_id,
                                hipStream_t s) {
-    const dim3 g_((unsigned)((dst.W * (dst.C / dtype_group(dt)) + 255) / 256), (unsigned)dst.H, (unsigned)dst.N), b_(256);
+    const dim3 g((unsigned)((dst.W * (dst.C / dtype_group(dt)) + 255) / 256), (unsigned)dst.H, (unsigned)dst.N), b(256);
     const float mul = pow2f(src.exp - dst.exp);
     const float sy = dst.H > 1 ? (float)(src.H - 1) / (float)(dst.H - 1) : 0.f;
     const float sx = dst.W > 1 ? (float)(src.W - 1) / (float)(dst.W - 1) : 0.f;
-    if (dt == kF16) hipLaunchKernelGGL(upsample_bilinear2x_kernel<half_t>, g_, b_, 0, s, src, dst, mul, sy, sx, flag, layer_id);
-    else if (dt == kSplit) {
-        static const bool block2x2 = [] { const char* v = std::getenv("CV_UPSAMPLE_2X2"); return !(v && v[0] == '0'); }();
-        if (block2x2 && dst.H == 2 * src.H && dst.W == 2 * src.W) {
-            const dim3 g2((unsigned)(((src.W + 1) * (dst.C / 8) + 255) / 256), (unsigned)(src.H + 1), (unsigned)dst.N);
-            hipLaunchKernelGGL(upsample_bilinear2x_split2x2_kernel, g2, b_, 0, s, src, dst, mul, sy, sx, flag, layer_id);
-        } else hipLaunchKernelGGL(upsample_bilinear2x_kernel<split_t>, g_, b_, 0, s, src, dst, mul, sy, sx, flag, layer_id);
+    static const bool block2x2 = env_switch("CV_UPSAMPLE_2X2", true);    // read once per process
+    if (dt == kSplit && block2x2 && dst.H == 2 * src.H && dst.W == 2 * src.W) {
+        const dim3 g2((unsigned)(((src.W + 1) * (dst.C / 8) + 255) / 256), (unsigned)(src.H + 1), (unsigned)dst.N);
+        hipLaunchKernelGGL(upsample_bilinear2x_split2x2_kernel, g2, b, 0, s, src, dst, mul, sy, sx, flag, layer_id);
+    } else {
+        with_dtype(dt, [&](auto t) { hipLaunchKernelGGL(upsample_bilinear2x_kernel<tag_t<decltype(t)>>, g, b, 0, s, src, dst, mul, sy, sx, flag, layer_id); });
     }
-    else hipLaunchKernelGGL(upsample_bilinear2x_kernel<float>, g_, b_, 0, s, src, dst, mul, sy, sx, flag, layer_id);
     return hipGetLastError();
 }
 hipError_t outc_1x1(int dt, const TensorRef& src, const float* w, const float* bias, float* logits,
                     uint8_t* mask, float threshold, unsigned* flag, unsigned layer_id, hipStream_t s) {
     const int lpp = src.C / dtype_group(dt);
     if (lpp < 1 || lpp > 64 || (lpp & (lpp - 1))) return hipErrorInvalidValue;
-    CV_DISPATCH(outc_1x1_kernel, (size_t)src.N * src.H * src.W * lpp, src, w, bias, pow2f(src.exp), logits, mask, threshold,
-                flag, layer_id);
+    const dim3 g(grid_for((size_t)src.N * src.H * src.W * lpp)), b(256);
+    with_dtype(dt, [&](auto t) {
+        hipLaunchKernelGGL(outc_1x1_kernel<tag_t<decltype(t)>>, g, b, 0, s, src, w, bias, pow2f(src.exp), logits, mask, threshold, flag, layer_id);
+    });
+    return hipGetLastError();
 }
 hipError_t stem7x7(int dt, const void* x, bool x_is_u8, int n, const float* w, const float* scale,
                    const float* shift, const TensorRef& dst, hipStream_t s, const InputNorm* norm) {
     if (dst.C != 64 || dst.H != 32 || dst.W != 32 || dst.Coff != 0 || (norm && !x_is_u8)) return hipErrorInvalidValue;
     const dim3 g((unsigned)n), b(256);
     const InputNorm nm = norm ? *norm : InputNorm{0.f, 1.f};
-#define CV_STEM(T)                                                                                                   \
-    do {                                                                                                             \
-        if (norm) hipLaunchKernelGGL((stem7x7_kernel<T, uint8_t, true>), g, b, 0, s, (const uint8_t*)x, w, scale, shift, dst, nm); \
-        else if (x_is_u8) hipLaunchKernelGGL((stem7x7_kernel<T, uint8_t>), g, b, 0, s, (const uint8_t*)x, w, scale, shift, dst, nm); \
-        else hipLaunchKernelGGL((stem7x7_kernel<T, float>), g, b, 0, s, (const float*)x, w, scale, shift, dst, nm);  \
-    } while (0)
-    if (dt == kF16) CV_STEM(half_t); else if (dt == kSplit) CV_STEM(split_t); else CV_STEM(float);
-#undef CV_STEM
+    with_dtype(dt, [&](auto t) {
+        with_input(x, x_is_u8, norm != nullptr, [&](auto* px, auto NORM) {
+            hipLaunchKernelGGL((stem7x7_kernel<tag_t<decltype(t)>, pointee_t<decltype(px)>, decltype(NORM)::value>), g, b, 0, s, px, w, scale, shift, dst, nm);
+        });
+    });
     return hipGetLastError();
 }
 hipError_t stem_pool_mfma(int dt, const void* x, bool x_is_u8, int n, const void* wpk, const float* scale,
@@ -1600,16 +1553,18 @@ hipError_t stem_pool_mfma(int dt, const void* x, bool x_is_u8, int n, const void
     const half8* w = reinterpret_cast<const half8*>(wpk);
     const float im = pow2f(-in_exp);
     const InputNorm nm = norm ? *norm : InputNorm{0.f, 1.f};
-#define CV_STEM(T, SPLIT)                                                                                                              \
-    do {                                                                                                                               \
-        if (norm) hipLaunchKernelGGL((stem_pool_mfma_kernel<T, uint8_t, SPLIT, true>), g, b, 0, s, (const uint8_t*)x, n, w, scale, shift, im, dst, flag, layer_id, nm); \
-        else if (x_is_u8) hipLaunchKernelGGL((stem_pool_mfma_kernel<T, uint8_t, SPLIT>), g, b, 0, s, (const uint8_t*)x, n, w, scale, shift, im, dst, flag, layer_id, nm); \
-        else hipLaunchKernelGGL((stem_pool_mfma_kernel<T, float, SPLIT>), g, b, 0, s, (const float*)x, n, w, scale, shift, im, dst, flag, layer_id, nm); \
-    } while (0)
-    if (dt == kF16 && dst.base32) CV_STEM(half_t, true);   // f16r engine: split-f16 arithmetic, f16 tensor + f32 twin out
-    else if (dt == kF16) CV_STEM(half_t, false);
-    else CV_STEM(split_t, true);
-#undef CV_STEM
+    with_dtype(dt, [&](auto t) {
+        using T = tag_t<decltype(t)>;
+        if constexpr (!std::is_same_v<T, float>) with_input(x, x_is_u8, norm != nullptr, [&](auto* px, auto NORM) {
+            auto launch = [&](auto SPLIT) {
+                hipLaunchKernelGGL((stem_pool_mfma_kernel<T, pointee_t<decltype(px)>, decltype(SPLIT)::value, decltype(NORM)::value>), g, b, 0, s, px, n, w,
+                                   scale, shift, im, dst, flag, layer_id, nm);
+            };
+            if constexpr (std::is_same_v<T, split_t>) launch(std::true_type());
+            else if (dst.base32) launch(std::true_type());    // f16r engine: split-f16 arithmetic, f16 tensor + f32 twin out
+            else launch(std::false_type());
+        });
+    });
     return hipGetLastError();
 }
 hipError_t inc0_mfma(int dt, const void* x, bool x_is_u8, int n, const void* wpk, const float* scale, const float* shift,
@@ -1618,13 +1573,12 @@ hipError_t inc0_mfma(int dt, const void* x, bool x_is_u8, int n, const void* wpk
     const dim3 g((unsigned)(n * 32)), b(256);
     const half8* w = reinterpret_cast<const half8*>(wpk);
     const float im = pow2f(-in_exp);
-    if (dt == kF16) {
-        if (x_is_u8) hipLaunchKernelGGL((inc0_mfma_kernel<half_t, uint8_t>), g, b, 0, s, (const uint8_t*)x, w, scale, shift, im, dst, flag, layer_id);
-        else hipLaunchKernelGGL((inc0_mfma_kernel<half_t, float>), g, b, 0, s, (const float*)x, w, scale, shift, im, dst, flag, layer_id);
-    } else {
-        if (x_is_u8) hipLaunchKernelGGL((inc0_mfma_kernel<split_t, uint8_t>), g, b, 0, s, (const uint8_t*)x, w, scale, shift, im, dst, flag, layer_id);
-        else hipLaunchKernelGGL((inc0_mfma_kernel<split_t, float>), g, b, 0, s, (const float*)x, w, scale, shift, im, dst, flag, layer_id);
-    }
+    with_dtype(dt, [&](auto t) {
+        using T = tag_t<decltype(t)>;
+        if constexpr (!std::is_same_v<T, float>) with_input(x, x_is_u8, false, [&](auto* px, auto) {
+            hipLaunchKernelGGL((inc0_mfma_kernel<T, pointee_t<decltype(px)>>), g, b, 0, s, px, w, scale, shift, im, dst, flag, layer_id);
+        });
+    });
     return hipGetLastError();
 }
 hipError_t head_avgpool_fc(int dt, const TensorRef& src, const float* w, const float* b, float* out,
@@ -1632,10 +1586,7 @@ hipError_t head_avgpool_fc(int dt, const TensorRef& src, const float* w, const f
     if (src.C != 512 || src.Coff != 0 || src.Cs != 512) return hipErrorInvalidValue;      // the kernel keeps lane l on channels 8l..8l+7
     const int blocks = (src.N + 3) / 4;
     const dim3 g((unsigned)(blocks < 1 ? 1 : blocks > 2048 ? 2048 : blocks)), blk(256);
-    const float mul = pow2f(src.exp);
-    if (dt == kF16) hipLaunchKernelGGL(head_kernel<half_t>, g, blk, 0, s, src, w, b, mul, out, softmax, flag, layer_id);
-    else if (dt == kSplit) hipLaunchKernelGGL(head_kernel<split_t>, g, blk, 0, s, src, w, b, mul, out, softmax, flag, layer_id);
-    else hipLaunchKernelGGL(head_kernel<float>, g, blk, 0, s, src, w, b, mul, out, softmax, flag, layer_id);
+    with_dtype(dt, [&](auto t) { hipLaunchKernelGGL(head_kernel<tag_t<decltype(t)>>, g, blk, 0, s, src, w, b, pow2f(src.exp), out, softmax, flag, layer_id); });
     return hipGetLastError();
 }
 hipError_t extraction_scores(const float* values, int n, int count, int transform, ScoreRecord* records, uint8_t* half_mask,
