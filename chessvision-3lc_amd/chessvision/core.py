@@ -264,16 +264,19 @@ class ChessVision:
                                                    square_crops=squares)
 
     # ---- the native single-image path -----------------------------------------------------------------
-    def _process_image_native(self, image, threshold, flip, started, fallback_quad: bool = False, encoded: bool = False) -> ChessVisionResult:
+    def _process_image_native(self, image, threshold, flip, started, fallback_quad: bool = False, encoded: bool = False,
+                              apply_orientation: bool = False) -> ChessVisionResult:
         """``process_image`` as ONE native call (``cv_process_image``): upload, resize, UNet, mask, contours, homography, warp, split,
         classifier, soft-max, FEN and the pawn rule all happen behind the C ABI; Python only wraps the arrays into the result records.
-        ``encoded``: ``image`` is a JPEG stream and the call is ``cv_process_jpeg``, which decodes it behind the C ABI as well."""
+        ``encoded``: ``image`` is a JPEG stream and the call is ``cv_process_jpeg``, which decodes it behind the C ABI as well
+        (``apply_orientation``: ``cv_process_jpeg_oriented``, which also turns the photo as its EXIF orientation says)."""
         from .hip_backend import process_image_native, process_jpeg_native
 
+        extra = {"apply_orientation": True} if encoded and apply_orientation else {}
         slot = self._acquire_slot()
         try:
             r = (process_jpeg_native if encoded else process_image_native)(
-                slot.extractor_engine, slot.classifier_engine, image, threshold, flip, fallback_quad, stream=slot.stream.cuda_stream)
+                slot.extractor_engine, slot.classifier_engine, image, threshold, flip, fallback_quad, stream=slot.stream.cuda_stream, **extra)
         finally:
             self._release_slot(slot)
         if not r["found"]:
@@ -591,48 +594,56 @@ class ChessVision:
         return out
 
     # ---- encoded input: JPEG streams in, the decode inside the library (chessvision/jpeg.py, csrc/jpeg.cpp, csrc/jpeg.hip) ----------
-    def process_jpeg(self, blob, threshold: float = 0.5, flip: bool = False) -> ChessVisionResult:
+    def process_jpeg(self, blob, threshold: float = 0.5, flip: bool = False, orientation: str = "ignore") -> ChessVisionResult:
         """``process_image`` for a JPEG stream (``bytes``): one native call, ``cv_process_jpeg``, over the request slots.  The Huffman
         stage runs on the calling thread into the slot engine's page-locked block, the device reconstructs the BGR photo where
         ``process_image`` uploads one, and everything after is the same code: the result equals ``process_image`` of the decoded
-        photo bit for bit.  EXIF orientation is not applied (``jpeg.jpeg_info(blob).orientation`` reports it).  Raises
-        ``jpeg.UnsupportedJpeg`` (a ``ValueError``) for a stream the decoder refuses, before any GPU work."""
+        photo bit for bit.  EXIF orientation is not applied by default (``jpeg.jpeg_info(blob).orientation`` reports it);
+        ``orientation="exif"`` applies it in the reconstruction (``cv_process_jpeg_oriented``): the result is ``process_image`` of
+        ``jpeg.apply_orientation(photo, tag)``, quadrangle included -- what the reference computes for an upload, if ``cv2.imdecode``
+        turns the photo as OpenCV's source reads (not run here).  Raises ``jpeg.UnsupportedJpeg`` (a ``ValueError``) for a stream the
+        decoder refuses, before any GPU work."""
         from . import jpeg
 
+        extra = {"apply_orientation": True} if jpeg.check_orientation(orientation) else {}
         blob = bytes(blob)
         jpeg.parse_all([blob])
         started = time.time()
         _ = self.board_extractor, self.classifier
-        return self._recover(lambda cv: cv._process_image_native(blob, threshold, flip, started, encoded=True))
+        return self._recover(lambda cv: cv._process_image_native(blob, threshold, flip, started, encoded=True, **extra))
 
-    def decode_jpegs(self, blobs: Sequence[bytes], channel_order: str = "bgr") -> list[NDArray[np.uint8]]:
+    def decode_jpegs(self, blobs: Sequence[bytes], channel_order: str = "bgr", orientation: str = "ignore") -> list[NDArray[np.uint8]]:
         """JPEG streams -> host arrays ``(h, w, 3)`` uint8 (BGR by default, as ``cv2.imread`` hands them over), in input order: what
         the callers that take decoded arrays (``evaluate_images``, ``evaluate_thresholds``, ``process_images_sharded``) are fed with.
         Streams are grouped by geometry; each group is one ``HipEngine.jpeg_decode`` (Huffman stage on host threads, reconstruction
-        on the device).  Pixels are libjpeg's, byte for byte; EXIF orientation is not applied."""
+        on the device).  Pixels are libjpeg's, byte for byte.  EXIF orientation is not applied unless ``orientation="exif"``: the
+        groups are then (geometry, effective tag) and every array comes back upright, ``(w, h, 3)`` for the transposing tags 5..8."""
         from . import jpeg
 
+        jpeg.check_orientation(orientation)
         blobs = [bytes(b) for b in blobs]
         infos = jpeg.parse_all(blobs)
         groups: dict[tuple, list[int]] = {}
         for i, info in enumerate(infos):
-            groups.setdefault(info.geometry, []).append(i)
+            groups.setdefault(jpeg.job_key(info, orientation), []).append(i)
         out: list = [None] * len(blobs)
         eng = self._get_engine("unet")
         for ids in groups.values():
             for k0 in range(0, len(ids), 64):
                 part = ids[k0:k0 + 64]
-                pixels = eng.jpeg_decode([blobs[i] for i in part], channel_order).cpu().numpy()
+                pixels = eng.jpeg_decode([blobs[i] for i in part], channel_order, orientation).cpu().numpy()
                 for k, i in enumerate(part):
                     out[i] = pixels[k]
         return out
 
     def process_encoded(self, blobs: Sequence[bytes], threshold: float = 0.5, flip: bool = False, fallback_quad: bool = False,
                         pipeline_chunk: int = 64, return_crops: bool = True, timings: dict | None = None, first_job: int = 16,
-                        last_job: int = 0, resize: str = "area", embeddings: bool = False, board_jpeg: int | None = None,
-                        quality: str | None = None) -> list[ChessVisionResult]:
+                        last_job: int = 0, resize: str = "area", embeddings: bool = False, orientation: str = "ignore",
+                        board_jpeg: int | None = None, quality: str | None = None) -> list[ChessVisionResult]:
         """``process_images`` for JPEG streams: every keyword and the result type are ``process_images``'s, and so are the results,
-        bit for bit, of the photos the streams decode to (libjpeg's pixels, BGR; EXIF orientation not applied).
+        bit for bit, of the photos the streams decode to (libjpeg's pixels, BGR; EXIF orientation not applied by default).
+        ``orientation="exif"``: each photo is reconstructed as its EXIF orientation tag turns it (``jpeg.apply_orientation``), jobs
+        are planned on (geometry, effective tag), and resize, quadrangle and warp work on the upright photo the device holds.
 
         All headers are parsed first: if any stream is unsupported (progressive, arithmetic, 12-bit, CMYK, other sampling factors,
         several scans, truncated) ``jpeg.UnsupportedJpeg`` (a ``ValueError``) lists the indices and reasons before any GPU work.  Jobs
@@ -646,6 +657,8 @@ class ChessVision:
             raise ValueError(f"quality must be None, 'logits' or 'sigmoid', got {quality!r}")
         self._check_resize(resize)
         extra = self._board_jpeg_keyword(board_jpeg)
+        if jpeg.check_orientation(orientation):
+            extra["orientation"] = orientation               # named only when it is on, as board_jpeg is
         blobs = [bytes(b) for b in blobs]
         infos = jpeg.parse_all(blobs)
         return self._recover(lambda cv: cv._process_encoded_native(blobs, infos, threshold, flip, fallback_quad, pipeline_chunk, return_crops,

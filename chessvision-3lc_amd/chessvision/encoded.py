@@ -6,6 +6,11 @@ quantised coefficients (3 bytes per pixel at 4:2:0, what the BGR upload weighs).
 stream reconstruct the job's BGR photos into ``job.batch`` (``HipEngine.jpeg_reconstruct_dev``: libjpeg's pixels, byte for byte), and
 from there on every stage is ``_Call``'s own: the resize reads ``job.batch``, the warp later reads full-resolution BGR from it.
 ``issue`` is inherited and still uses nothing but the four stages.
+
+``orientation="exif"``: the reconstruction's second launch stores each photo as its EXIF orientation tag turns it
+(``jpeg.apply_orientation``), so ``job.batch`` holds upright photos and nothing behind it knows.  A launch turns all its photos alike:
+jobs are planned on (geometry, effective tag), and the stand-in images carry the oriented shape, which is the one the quadrangle
+scaling and the warp must use.
 """
 from __future__ import annotations
 
@@ -25,15 +30,17 @@ class EncodedJob(Job):
     ``coeffs`` its copy on the device until ``begin_compute`` has queued the reconstruction behind it."""
     coeffs: torch.Tensor | None = None
     info: jpeg.JpegInfo | None = None
+    tag: int = 0                                 # the EXIF orientation the reconstruction applies (0: none)
 
 
 _ZERO = np.zeros((), np.uint8)
 
 
 class _EncodedCall(_Call):
-    def __init__(self, cv, blobs, infos, *args, **kw):
+    def __init__(self, cv, blobs, infos, *args, orientation="ignore", **kw):
         # the stages ask the call's images for nothing but their shape: a zero-stride array per stream stands in for the pixels
-        super().__init__(cv, [np.broadcast_to(_ZERO, (f.height, f.width, 3)) for f in infos], *args, **kw)
+        self.tags = [jpeg.effective_tag(f, orientation) for f in infos]
+        super().__init__(cv, [np.broadcast_to(_ZERO, jpeg.oriented_shape(f, t) + (3,)) for f, t in zip(infos, self.tags)], *args, **kw)
         self.blobs, self.infos = blobs, infos
         self.tm.setdefault("entropy_s", 0.0)             # host seconds inside the Huffman stage (wall clock of the copy threads' maps)
 
@@ -43,7 +50,7 @@ class _EncodedCall(_Call):
         t0 = time.perf_counter()
         up, n, info = self.up, len(ids), self.infos[ids[0]]
         count, tables = 64 * info.blocks, 64 * info.components
-        job = EncodedJob(ids, staged=_pinned((n * (count + tables),), torch.int16), info=info)
+        job = EncodedJob(ids, staged=_pinned((n * (count + tables),), torch.int16), info=info, tag=self.tags[ids[0]])
         host = job.staged.numpy()
         co = host[:n * count].reshape(n, count)
         qt = host[n * count:].view(np.uint16).reshape(n, info.components, 64)
@@ -73,17 +80,20 @@ class _EncodedCall(_Call):
         job.coeffs.record_stream(self.main)
         n, info = len(job.ids), job.info
         count = 64 * info.blocks
+        turned = {"orientation": job.tag} if job.tag else {}                # named only when there is something to turn
         job.batch = self.gpu_timed("jpeg_ms", self.eng.jpeg_reconstruct_dev, job.coeffs[:n * count].view(n, count),
-                                   job.coeffs[n * count:].view(n, info.components, 64), info, "bgr")
+                                   job.coeffs[n * count:].view(n, info.components, 64), info, "bgr", **turned)
         job.coeffs = None
         self.tm.setdefault("first_enqueue_s", time.time() - self.started)
 
 
 def process_encoded(cv, blobs, infos, threshold, flip, fallback_quad, pipeline_chunk, return_crops, timings, first_job, last_job,
-                    quality, embeddings=False, resize="area", board_jpeg=None):
+                    quality, embeddings=False, resize="area", orientation="ignore", board_jpeg=None):
     """``ChessVision.process_encoded`` on the instance's native engines; ``infos`` are the parsed, supported headers of ``blobs``."""
     started = time.time()
+    jpeg.check_orientation(orientation)
     if not blobs:
         return []
-    call = _EncodedCall(cv, blobs, infos, threshold, flip, fallback_quad, return_crops, timings, quality, started, None, embeddings, resize, board_jpeg)
-    return run(call, plan_jobs([f.geometry for f in infos], pipeline_chunk, first=int(first_job), last=int(last_job)))
+    call = _EncodedCall(cv, blobs, infos, threshold, flip, fallback_quad, return_crops, timings, quality, started, None, embeddings, resize, board_jpeg,
+                        orientation=orientation)
+    return run(call, plan_jobs([jpeg.job_key(f, orientation) for f in infos], pipeline_chunk, first=int(first_job), last=int(last_job)))

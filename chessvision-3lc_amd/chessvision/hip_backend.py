@@ -146,6 +146,8 @@ SYMBOLS = [
     ("cv_jpeg_entropy_decode", _i, [_vp, ctypes.c_size_t, _vp, ctypes.c_size_t, _vp]),
     ("cv_jpeg_reconstruct_u8", _i, [_vp, _vp, _vp, _i, _vp, _i, _vp, ctypes.c_size_t, _vp, _vp]),
     ("cv_process_jpeg", _i, [_vp, _vp, _vp, ctypes.c_size_t, _f, _i, _i, ctypes.c_void_p, ctypes.c_size_t, _vp]),
+    ("cv_jpeg_reconstruct_oriented_u8", _i, [_vp, _vp, _vp, _i, _vp, _i, _i, _vp, ctypes.c_size_t, _vp, _vp]),
+    ("cv_process_jpeg_oriented", _i, [_vp, _vp, _vp, ctypes.c_size_t, _f, _i, _i, _i, ctypes.c_void_p, ctypes.c_size_t, _vp]),
     ("cv_jpeg_gray_header", _i, [_i, _i, _i, _vp, _vp]),
     ("cv_jpeg_gray_max_bytes", _i, [_i, _i, ctypes.POINTER(ctypes.c_size_t)]),
     ("cv_jpeg_encode_gray_u8", _i, [_vp, _vp, _i, _i, _i, _i, _vp, ctypes.c_size_t, _vp, _vp, _vp]),
@@ -462,15 +464,16 @@ def process_image_native(unet_engine: "HipEngine", classifier_engine: "HipEngine
 
 
 def process_jpeg_native(unet_engine: "HipEngine", classifier_engine: "HipEngine", blob, threshold: float = 0.5, flip: bool = False,
-                        fallback_quad: bool = False, stream: int | None = None) -> dict:
+                        fallback_quad: bool = False, stream: int | None = None, apply_orientation: bool = False) -> dict:
     """One JPEG stream through ``cv_process_jpeg``: ``process_image_native`` with the decode behind the C ABI as well (Huffman stage on
-    this thread into the engine's page-locked block, reconstruction on the device).  Same dict."""
+    this thread into the engine's page-locked block, reconstruction on the device).  Same dict.  ``apply_orientation``: the call is
+    ``cv_process_jpeg_oriented``, which reconstructs the photo as its EXIF orientation tag turns it."""
     lib = load_library()
     blob = bytes(blob)
     res, arrays = _image_result_buffers()
-    status = lib.cv_process_jpeg(unet_engine._h, classifier_engine._h, blob, len(blob), float(threshold), int(bool(flip)),
-                                 int(bool(fallback_quad)), ctypes.byref(res), ctypes.sizeof(res),
-                                 _stream_ptr(unet_engine.device) if stream is None else stream)
+    head = (unet_engine._h, classifier_engine._h, blob, len(blob), float(threshold), int(bool(flip)), int(bool(fallback_quad)))
+    tail = (ctypes.byref(res), ctypes.sizeof(res), _stream_ptr(unet_engine.device) if stream is None else stream)
+    status = lib.cv_process_jpeg_oriented(*head, 1, *tail) if apply_orientation else lib.cv_process_jpeg(*head, *tail)
     _check(status)
     return _image_result_dict(res, arrays)
 
@@ -961,12 +964,15 @@ class HipEngine:
 
     # -- JPEG decode: host entropy stage (chessvision/jpeg.py), device reconstruction (csrc/jpeg.hip) ----------------------
     def jpeg_reconstruct_dev(self, coeffs: torch.Tensor, qtables: torch.Tensor, info, channel_order: str = "bgr",
-                             out: torch.Tensor | None = None) -> torch.Tensor:
+                             out: torch.Tensor | None = None, orientation: int = 0) -> torch.Tensor:
         """Device form: ``coeffs`` int16 ``(n, 64 * info.blocks)`` and ``qtables`` ``(n, components, 64)`` (uint16 values in an int16
         tensor), both on the device and 16-byte aligned, as ``jpeg.entropy_decode`` wrote them for n images of the one geometry
         ``info`` -> ``(n, h, w, 3)`` uint8, or ``(n, h, w)`` for ``"gray"`` (written into ``out`` when given).  Two launches on the
-        current stream; nothing waits."""
-        from .jpeg import ORDERS
+        current stream; nothing waits.  ``orientation``: an EXIF tag 0..8 all n images are turned by in the colour stage's store
+        (``cv_jpeg_reconstruct_oriented_u8``; ``info.orientation`` is not read); ``h`` and ``w`` are then ``jpeg.oriented_shape``'s.
+        0 is the call it always was."""
+        from .jpeg import ORDERS, check_tag, oriented_shape
+        orientation = check_tag(orientation)
         if channel_order not in ORDERS:
             raise HipBackendError(f"channel_order must be one of {sorted(ORDERS)}")
         if coeffs.dtype != torch.int16 or qtables.dtype != torch.int16 or coeffs.dim() != 2 or not coeffs.is_contiguous() \
@@ -975,7 +981,7 @@ class HipEngine:
         n = coeffs.shape[0]
         if coeffs.shape[1] != 64 * info.blocks or qtables.numel() != n * info.components * 64:
             raise HipBackendError("jpeg_reconstruct_dev: tensors do not match the geometry")
-        shape = (n, info.height, info.width) if channel_order == "gray" else (n, info.height, info.width, 3)
+        shape = (n,) + oriented_shape(info, orientation) + (() if channel_order == "gray" else (3,))
         if out is None:
             out = torch.empty(shape, dtype=torch.uint8, device=self.device)
         elif out.dtype != torch.uint8 or tuple(out.shape) != shape or not out.is_contiguous() or out.device != self.device:
@@ -984,16 +990,25 @@ class HipEngine:
             return out
         planes = torch.empty(n * 64 * info.blocks, dtype=torch.uint8, device=self.device)
         c_info = info.to_c()
+        if orientation:
+            _check(self._lib.cv_jpeg_reconstruct_oriented_u8(self._h, _ptr(coeffs), _ptr(qtables), n, ctypes.addressof(c_info),
+                                                             ORDERS[channel_order], orientation, _ptr(planes), planes.numel(), _ptr(out),
+                                                             _stream_ptr(self.device)))
+            return out
         _check(self._lib.cv_jpeg_reconstruct_u8(self._h, _ptr(coeffs), _ptr(qtables), n, ctypes.addressof(c_info), ORDERS[channel_order],
                                                 _ptr(planes), planes.numel(), _ptr(out), _stream_ptr(self.device)))
         return out
 
-    def jpeg_decode(self, blobs, channel_order: str = "bgr") -> torch.Tensor:
+    def jpeg_decode(self, blobs, channel_order: str = "bgr", orientation: str = "ignore") -> torch.Tensor:
         """JPEG streams of ONE geometry (size, components, sampling) -> device tensor ``(n, h, w, 3)`` uint8 in ``"bgr"`` (default) or
         ``"rgb"`` order, or ``(n, h, w)`` for ``"gray"`` (1-component streams only).  The Huffman stage runs on host threads into one
         page-locked buffer, one copy takes it to the device, two launches reconstruct the pixels: libjpeg's, byte for byte.
-        Raises ``jpeg.UnsupportedJpeg`` (a ``ValueError``) naming the refused blobs."""
+        ``orientation="exif"`` turns the pictures as their EXIF orientation tag says, in the second launch's store (the table in
+        ``chessvision/jpeg.py``); the streams must then share the effective tag as well (absent and 1 count as one), and ``h``, ``w``
+        are the turned picture's.  Raises ``jpeg.UnsupportedJpeg`` (a ``ValueError``) naming the refused blobs, and ``ValueError``
+        naming the streams whose tag differs from the first one's."""
         from . import jpeg as _jpeg
+        _jpeg.check_orientation(orientation)
         blobs = list(blobs)
         if not blobs:
             raise HipBackendError("jpeg_decode needs at least one stream")
@@ -1004,13 +1019,19 @@ class HipEngine:
         info = infos[0]
         if any(f.geometry != info.geometry for f in infos):
             raise HipBackendError("jpeg_decode: all streams of one call must share one geometry (ChessVision.decode_jpegs groups them)")
+        tag = _jpeg.effective_tag(info, orientation)                  # 0 for every stream under "ignore"
+        odd = [i for i, f in enumerate(infos) if _jpeg.effective_tag(f, orientation) != tag]
+        if odd:
+            raise ValueError(f"jpeg_decode: streams {odd} do not carry the EXIF orientation of stream 0 ({tag or 1}); one call turns "
+                             "all its pictures alike (ChessVision.decode_jpegs groups them)")
         n, count, tables = len(blobs), 64 * info.blocks, 64 * info.components
         staging = torch.empty(n * (count + tables), dtype=torch.int16).pin_memory()
         host = staging.numpy()
         co, qt = host[:n * count].reshape(n, count), host[n * count:].view(np.uint16).reshape(n, info.components, 64)
         _jpeg.entropy_decode_many(blobs, infos, co, qt)
         dev = staging.to(self.device, non_blocking=True)
-        out = self.jpeg_reconstruct_dev(dev[:n * count].view(n, count), dev[n * count:].view(n, info.components, 64), info, channel_order)
+        extra = {"orientation": tag} if tag else {}
+        out = self.jpeg_reconstruct_dev(dev[:n * count].view(n, count), dev[n * count:].view(n, info.components, 64), info, channel_order, **extra)
         torch.cuda.current_stream(self.device).synchronize()          # the page-locked buffer is released on return
         return out
 

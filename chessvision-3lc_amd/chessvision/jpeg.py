@@ -6,6 +6,8 @@ numpy, what ``csrc/jpeg.hip`` does with those coefficients on the device: dequan
 fancy chroma up-sampling and its fixed-point YCbCr -> RGB conversion.  As everywhere in this package the numpy form is the readable
 checker: it shares no code with the kernel, and both are held to the bytes libjpeg itself produces (Pillow and ``cv2.imdecode``
 decode with libjpeg's defaults).  All arithmetic wraps in 32 bits, so the two forms agree on any coefficients.
+``apply_orientation`` is the numpy form of the EXIF orientation the oriented colour kernel applies in its store
+(``orientation="exif"`` on the JPEG entries; the default ``"ignore"`` leaves the tag reported and unused).
 """
 from __future__ import annotations
 
@@ -39,7 +41,7 @@ class JpegInfo(NamedTuple):
     luma_h: int
     luma_v: int
     restart_interval: int
-    orientation: int          # EXIF tag 0x0112 as found (1..8), 0 when absent: reported, never applied
+    orientation: int          # EXIF tag 0x0112 as found (1..8), 0 when absent; applied only under orientation="exif"
     supported: bool
     reason: str
 
@@ -251,6 +253,65 @@ def decode(blob, channel_order: str = "bgr") -> np.ndarray:
     ``HipEngine.jpeg_decode``)."""
     coeffs, qtables, info = entropy_decode(blob)
     return reconstruct(coeffs, qtables, info, channel_order)
+
+
+# ---- EXIF orientation: the numpy form of jpeg_colour_oriented_kernel's store -------------------------------------------------
+# ``orientation="exif"`` on the JPEG entries applies tag 0x0112 as ``PIL.ImageOps.exif_transpose`` does (the fixture's reference) and,
+# as read in OpenCV's source but not run here, as the ExifTransform behind ``cv2.imdecode`` / ``cv2.imread`` with their default
+# flags does.  With the source ``(H, W)``, ``out[y, x]`` is
+#     1: src[y, x]         2: src[y, W-1-x]       3: src[H-1-y, W-1-x]     4: src[H-1-y, x]           -- out is H x W
+#     5: src[x, y]         6: src[H-1-x, y]       7: src[H-1-x, W-1-y]     8: src[x, W-1-y]           -- out is W x H
+# 6 is the quarter turn clockwise (a phone held upright), 8 counter-clockwise.  The default everywhere is "ignore".
+ORIENTATIONS = ("ignore", "exif")
+
+
+def check_orientation(orientation) -> bool:
+    """True for ``"exif"``, False for ``"ignore"``; any other value raises ``ValueError``."""
+    if not isinstance(orientation, str) or orientation not in ORIENTATIONS:
+        raise ValueError(f"orientation must be one of {ORIENTATIONS}, got {orientation!r}")
+    return orientation == "exif"
+
+
+def check_tag(tag) -> int:
+    """An integer orientation tag 0..8 (0: absent) as an int; anything else raises ``ValueError``."""
+    if isinstance(tag, bool) or not isinstance(tag, (int, np.integer)) or not 0 <= int(tag) <= 8:
+        raise ValueError(f"an orientation tag is an int 0..8, got {tag!r}")
+    return int(tag)
+
+
+def effective_tag(info: JpegInfo, orientation: str) -> int:
+    """The tag a launch applies to this stream: 0 under ``"ignore"`` and for tags 0 (absent) and 1, which change nothing; else 2..8."""
+    return info.orientation if check_orientation(orientation) and info.orientation >= 2 else 0
+
+
+def job_key(info: JpegInfo, orientation: str) -> tuple:
+    """What the streams of one launch share: ``(geometry, effective tag)``.  Under ``"ignore"`` the tag is 0 for every stream, so the
+    groups are the geometry's."""
+    return (info.geometry, effective_tag(info, orientation))
+
+
+def apply_orientation(array, tag):
+    """``array`` ``(h, w)`` or ``(h, w, c)`` as EXIF orientation ``tag`` turns it (the table above); tags 0 and 1 return it unchanged.
+    The definition the kernel is held to: a view, no copy."""
+    tag = check_tag(tag)
+    a = np.asarray(array)
+    if a.ndim not in (2, 3):
+        raise ValueError("apply_orientation expects an (h, w) or (h, w, c) array")
+    if tag >= 5:                                                           # out[y, x] = src[x, y], then the mirrors in OUTPUT axes
+        a = np.swapaxes(a, 0, 1)
+        rows, cols = tag in (7, 8), tag in (6, 7)                          # 8: src[x, W-1-y]; 6: src[H-1-x, y]; 7: both
+    else:
+        rows, cols = tag in (3, 4), tag in (2, 3)
+    if rows:
+        a = a[::-1]
+    if cols:
+        a = a[:, ::-1]
+    return a
+
+
+def oriented_shape(info: JpegInfo, tag) -> tuple[int, int]:
+    """``(height, width)`` of the stream's picture after ``apply_orientation(..., tag)``."""
+    return (info.width, info.height) if check_tag(tag) >= 5 else (info.height, info.width)
 
 
 # ---- JPEG encode: the numpy host form of csrc/jpeg_enc.hip -----------------------------------------------------------------

@@ -353,12 +353,14 @@ Status check_jpeg_info(const cvjpeg::Info& info) {
 }
 
 // The two fronts of the one-image pipeline: the caller's pixels (cv_process_image, cv_process_image_v2) or a JPEG stream
-// (cv_process_jpeg), which the entropy stage decodes into the page-locked block and the device reconstructs into the image's place.
+// (cv_process_jpeg, cv_process_jpeg_oriented), which the entropy stage decodes into the page-locked block and the device reconstructs
+// into the image's place.
 struct ImageFront {
     const uint8_t* image = nullptr;        // (h, w, 3) uint8, or
     const uint8_t* jpeg = nullptr;         // an encoded stream of jpeg_len bytes whose header is `info`
     size_t jpeg_len = 0;
     cvjpeg::Info info;
+    int orientation = 0;                   // the EXIF tag the reconstruction applies (0, 1: none); h and w are then the ORIENTED photo's
 };
 
 Status process_image(cv_engine_t* ue, cv_engine_t* ce, const ImageFront& front, int h, int w_, float threshold, int flip, int fallback_quad,
@@ -432,7 +434,7 @@ Status process_image(cv_engine_t* ue, cv_engine_t* ce, const ImageFront& front, 
             return fail(CV_ERR_INVALID, std::string("cv_process_jpeg: ") + why);
         e = hipMemcpyAsync(d_co, h_co, co_b, hipMemcpyHostToDevice, st);
         if (e == hipSuccess) e = hipMemcpyAsync(d_qt, h_qt, qt_b, hipMemcpyHostToDevice, st);
-        if (e == hipSuccess) e = jpeg_reconstruct_u8(d_co, d_qt, 1, front.info, kJpegBGR, d_pl, d_img, st);
+        if (e == hipSuccess) e = jpeg_reconstruct_oriented_u8(d_co, d_qt, 1, front.info, kJpegBGR, front.orientation, d_pl, d_img, st);
     } else {
         std::memcpy(h_img, image, img_b);
         e = hipMemcpyAsync(d_img, h_img, img_b, hipMemcpyHostToDevice, st);
@@ -527,6 +529,44 @@ Status process_image(cv_engine_t* ue, cv_engine_t* ce, const ImageFront& front, 
     if (out->labels) std::memcpy(out->labels, labels, sizeof(labels));
     out->found = 1;
     return Status();
+}
+
+// cv_jpeg_reconstruct_u8 and cv_jpeg_reconstruct_oriented_u8 (`entry` names the one in the messages)
+Status jpeg_reconstruct_entry(const char* entry, cv_engine_t* eng, const int16_t* coeffs, const uint16_t* qtables, int n, const cv_jpeg_info_t* info,
+                              int channel_order, int orientation, uint8_t* planes, size_t planes_bytes, uint8_t* dst, void* stream) {
+    const std::string name(entry);
+    CV_TRY(check_engine(eng));
+    if (!coeffs || !qtables || !info || !planes || !dst || n <= 0) return fail(CV_ERR_INVALID, name + ": bad argument");
+    const cvjpeg::Info& in = *reinterpret_cast<const cvjpeg::Info*>(info);
+    CV_TRY(check_jpeg_info(in));
+    if (channel_order != CV_JPEG_BGR && channel_order != CV_JPEG_RGB && channel_order != CV_JPEG_GRAY)
+        return fail(CV_ERR_INVALID, name + ": unknown channel order");
+    if (channel_order == CV_JPEG_GRAY && in.components != 1)
+        return fail(CV_ERR_INVALID, name + ": gray output is for 1-component streams only");
+    if (orientation < 0 || orientation > 8) return fail(CV_ERR_INVALID, name + ": orientation must be 0..8");
+    if (((uintptr_t)coeffs & 15u) || ((uintptr_t)qtables & 15u) || ((uintptr_t)planes & 7u))
+        return fail(CV_ERR_INVALID, name + ": coeffs and qtables must be 16-byte aligned, planes 8-byte aligned");
+    if ((size_t)n > ((size_t)1 << 31) / cvjpeg::layout_of(in).blocks) return fail(CV_ERR_INVALID, name + ": batch too large");
+    if (planes_bytes < jpeg_planes_bytes(in, n)) return fail(CV_ERR_INVALID, name + ": planes buffer too small");
+    DeviceGuard g(eng->impl.device);
+    const hipError_t e = jpeg_reconstruct_oriented_u8(coeffs, qtables, n, in, channel_order, orientation, planes, dst, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(e, "jpeg_reconstruct_u8");
+    return Status();
+}
+
+// cv_process_jpeg and cv_process_jpeg_oriented: the stream's header decides the geometry and, when asked, the orientation
+Status process_jpeg_entry(const char* entry, cv_engine_t* ue, cv_engine_t* ce, const uint8_t* bytes, size_t len, float threshold, int flip,
+                          int fallback_quad, int apply_orientation, cv_image_result_t* out, size_t out_size, void* stream) {
+    if (!bytes) return fail(CV_ERR_INVALID, std::string(entry) + ": null stream");
+    ImageFront front;
+    front.jpeg = bytes;
+    front.jpeg_len = len;
+    cvjpeg::parse_info(bytes, len, &front.info);
+    CV_TRY(check_jpeg_info(front.info));
+    front.orientation = apply_orientation ? front.info.orientation : 0;         // the parser reports 0..8 and nothing else
+    const bool transposed = front.orientation >= 5;
+    return process_image(ue, ce, front, transposed ? front.info.width : front.info.height, transposed ? front.info.height : front.info.width,
+                         threshold, flip, fallback_quad, out, out_size, stream);
 }
 
 }  // namespace
@@ -1401,36 +1441,31 @@ int cv_jpeg_entropy_decode(const uint8_t* bytes, size_t len, int16_t* coeffs, si
 int cv_jpeg_reconstruct_u8(cv_engine_t* eng, const int16_t* coeffs, const uint16_t* qtables, int n, const cv_jpeg_info_t* info,
                            int channel_order, uint8_t* planes, size_t planes_bytes, uint8_t* dst, void* stream) {
     return guarded("cv_jpeg_reconstruct_u8", [&]() -> Status {
-        CV_TRY(check_engine(eng));
-        if (!coeffs || !qtables || !info || !planes || !dst || n <= 0) return fail(CV_ERR_INVALID, "cv_jpeg_reconstruct_u8: bad argument");
-        const cvjpeg::Info& in = *reinterpret_cast<const cvjpeg::Info*>(info);
-        CV_TRY(check_jpeg_info(in));
-        if (channel_order != CV_JPEG_BGR && channel_order != CV_JPEG_RGB && channel_order != CV_JPEG_GRAY)
-            return fail(CV_ERR_INVALID, "cv_jpeg_reconstruct_u8: unknown channel order");
-        if (channel_order == CV_JPEG_GRAY && in.components != 1)
-            return fail(CV_ERR_INVALID, "cv_jpeg_reconstruct_u8: gray output is for 1-component streams only");
-        if (((uintptr_t)coeffs & 15u) || ((uintptr_t)qtables & 15u) || ((uintptr_t)planes & 7u))
-            return fail(CV_ERR_INVALID, "cv_jpeg_reconstruct_u8: coeffs and qtables must be 16-byte aligned, planes 8-byte aligned");
-        if ((size_t)n > ((size_t)1 << 31) / cvjpeg::layout_of(in).blocks) return fail(CV_ERR_INVALID, "cv_jpeg_reconstruct_u8: batch too large");
-        if (planes_bytes < jpeg_planes_bytes(in, n)) return fail(CV_ERR_INVALID, "cv_jpeg_reconstruct_u8: planes buffer too small");
-        DeviceGuard g(eng->impl.device);
-        const hipError_t e = jpeg_reconstruct_u8(coeffs, qtables, n, in, channel_order, planes, dst, (hipStream_t)stream);
-        if (e != hipSuccess) return hip_fail(e, "jpeg_reconstruct_u8");
-        return Status();
+        return jpeg_reconstruct_entry("cv_jpeg_reconstruct_u8", eng, coeffs, qtables, n, info, channel_order, 0, planes, planes_bytes, dst, stream);
+    });
+}
+
+int cv_jpeg_reconstruct_oriented_u8(cv_engine_t* eng, const int16_t* coeffs, const uint16_t* qtables, int n, const cv_jpeg_info_t* info,
+                                    int channel_order, int orientation, uint8_t* planes, size_t planes_bytes, uint8_t* dst, void* stream) {
+    return guarded("cv_jpeg_reconstruct_oriented_u8", [&]() -> Status {
+        return jpeg_reconstruct_entry("cv_jpeg_reconstruct_oriented_u8", eng, coeffs, qtables, n, info, channel_order, orientation, planes,
+                                      planes_bytes, dst, stream);
     });
 }
 
 int cv_process_jpeg(cv_engine_t* unet_engine, cv_engine_t* classifier_engine, const uint8_t* bytes, size_t len, float threshold, int flip,
                     int fallback_quad, cv_image_result_t* out, size_t out_size, void* stream) {
     return guarded("cv_process_jpeg", [&]() -> Status {
-        if (!bytes) return fail(CV_ERR_INVALID, "cv_process_jpeg: null stream");
-        ImageFront front;
-        front.jpeg = bytes;
-        front.jpeg_len = len;
-        cvjpeg::parse_info(bytes, len, &front.info);
-        CV_TRY(check_jpeg_info(front.info));
-        return process_image(unet_engine, classifier_engine, front, front.info.height, front.info.width, threshold, flip, fallback_quad, out,
-                             out_size, stream);
+        return process_jpeg_entry("cv_process_jpeg", unet_engine, classifier_engine, bytes, len, threshold, flip, fallback_quad, 0, out, out_size,
+                                  stream);
+    });
+}
+
+int cv_process_jpeg_oriented(cv_engine_t* unet_engine, cv_engine_t* classifier_engine, const uint8_t* bytes, size_t len, float threshold,
+                             int flip, int fallback_quad, int apply_orientation, cv_image_result_t* out, size_t out_size, void* stream) {
+    return guarded("cv_process_jpeg_oriented", [&]() -> Status {
+        return process_jpeg_entry("cv_process_jpeg_oriented", unet_engine, classifier_engine, bytes, len, threshold, flip, fallback_quad,
+                                  apply_orientation, out, out_size, stream);
     });
 }
 

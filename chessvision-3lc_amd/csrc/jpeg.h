@@ -14,7 +14,7 @@ struct Info {
     int32_t components;                    // 1 or 3
     int32_t luma_h, luma_v;                // luma sampling factors: 1x1, 2x1 or 2x2 (1x1 for a 1-component stream)
     int32_t restart_interval;              // MCUs between restart markers, 0 = none
-    int32_t orientation;                   // EXIF tag 0x0112 (1..8) as found, 0 = absent.  Reported, never applied.
+    int32_t orientation;                   // EXIF tag 0x0112 (1..8) as found, 0 = absent.  Reported; the oriented entries (cv_api.cpp) apply it.
     int32_t supported;                     // 0: `reason` says why not
     char reason[160];
 };

@@ -18,4 +18,10 @@ size_t jpeg_planes_bytes(const cvjpeg::Info& info, int n);
 hipError_t jpeg_reconstruct_u8(const int16_t* coeffs, const uint16_t* qtables, int n, const cvjpeg::Info& info, int order, uint8_t* planes,
                                uint8_t* dst, hipStream_t s);
 
+// The same with the EXIF orientation tag applied in the colour stage's store: orientation 0 (absent) and 1 are jpeg_reconstruct_u8
+// itself, 2..8 give dst = (n, h', w', 3 | 1) with (h', w') = (w, h) for the transposing tags 5..8; anything else is
+// hipErrorInvalidValue.  Still two launches over the same planes.
+hipError_t jpeg_reconstruct_oriented_u8(const int16_t* coeffs, const uint16_t* qtables, int n, const cvjpeg::Info& info, int order,
+                                        int orientation, uint8_t* planes, uint8_t* dst, hipStream_t s);
+
 }  // namespace cv

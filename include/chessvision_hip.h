@@ -626,7 +626,8 @@ int cv_process_image(cv_engine_t* unet_engine, cv_engine_t* classifier_engine, c
  * 1x1, 2x1 or 2x2 and chroma 1x1.  The decode is split where the hardware splits it: the serial Huffman stage on the host
  * (cv_jpeg_entropy_decode, one image per host thread), everything after it on the device (cv_jpeg_reconstruct_u8).  The pixels are
  * those of libjpeg with its defaults (JDCT_ISLOW, fancy up-sampling, fixed-point YCbCr tables), i.e. of cv2.imdecode without
- * EXIF rotation and of Pillow, byte for byte, on every stream an encoder writes.  Progressive, arithmetic, lossless, hierarchical and
+ * EXIF rotation and of Pillow, byte for byte, on every stream an encoder writes.  The EXIF orientation tag is applied by the entries
+ * that say so (cv_jpeg_reconstruct_oriented_u8, cv_process_jpeg_oriented) and by no other.  Progressive, arithmetic, lossless, hierarchical and
  * 12-bit streams, 4 components, Adobe RGB, other sampling factors, several scans and truncated or corrupt data are refused with
  * CV_ERR_INVALID and a message naming the reason and the byte offset; no partial image is ever returned. */
 typedef struct cv_jpeg_info {
@@ -634,7 +635,8 @@ typedef struct cv_jpeg_info {
     int32_t components;          /* 1 or 3 */
     int32_t luma_h, luma_v;      /* luma sampling factors; 1 x 1 for a 1-component stream */
     int32_t restart_interval;    /* MCUs between restart markers, 0: none */
-    int32_t orientation;         /* EXIF orientation tag (1..8), 0: absent.  Reported, never applied. */
+    int32_t orientation;         /* EXIF orientation tag (1..8), 0: absent.  Reported here; applied by
+                                    cv_jpeg_reconstruct_oriented_u8 and cv_process_jpeg_oriented alone. */
     int32_t supported;           /* 0: this library does not decode the stream; `reason` says why */
     char    reason[160];         /* empty when supported */
 } cv_jpeg_info_t;
@@ -662,13 +664,31 @@ int cv_jpeg_entropy_decode(const uint8_t* bytes, size_t len, int16_t* coeffs, si
  * CV_ERR_INVALID for a misaligned pointer, a short planes buffer or an info record that is not supported. */
 int cv_jpeg_reconstruct_u8(cv_engine_t* eng, const int16_t* coeffs, const uint16_t* qtables, int n, const cv_jpeg_info_t* info,
                            int channel_order, uint8_t* planes, size_t planes_bytes, uint8_t* dst, void* stream);
+/* cv_jpeg_reconstruct_u8 with the EXIF orientation applied in the colour stage's store (no second pass over the batch, no further
+ * buffer): `orientation` is the tag all n images share, 0..8 (what cv_jpeg_info reports; info->orientation itself is NOT read).  With
+ * (H, W) = (info->height, info->width), dst[y][x] is
+ *     0, 1: src[y][x]          2: src[y][W-1-x]      3: src[H-1-y][W-1-x]    4: src[H-1-y][x]         -- dst is (n, H, W, 3 | 1)
+ *     5: src[x][y]             6: src[H-1-x][y]      7: src[H-1-x][W-1-y]    8: src[x][W-1-y]         -- dst is (n, W, H, 3 | 1)
+ * where src is what cv_jpeg_reconstruct_u8 writes; 6 is the quarter turn clockwise, 8 counter-clockwise (the cases of
+ * PIL.ImageOps.exif_transpose, against which they are tested, and -- as read in OpenCV's source, not run -- of the ExifTransform
+ * behind cv2.imdecode).  0 and 1 launch exactly what cv_jpeg_reconstruct_u8 launches.  Every other argument, the two launches, and the
+ * stream contract are cv_jpeg_reconstruct_u8's: asynchronous on `stream`, no allocation, no synchronisation.  CV_ERR_INVALID also for
+ * an orientation outside 0..8. */
+int cv_jpeg_reconstruct_oriented_u8(cv_engine_t* eng, const int16_t* coeffs, const uint16_t* qtables, int n, const cv_jpeg_info_t* info,
+                                    int channel_order, int orientation, uint8_t* planes, size_t planes_bytes, uint8_t* dst, void* stream);
 /* cv_process_image_v2 with a different front: `bytes` is a JPEG stream instead of decoded pixels.  The entropy stage writes into the
  * extractor engine's page-locked block, the coefficients are uploaded and reconstructed (BGR) into the device image where
  * cv_process_image_v2 copies the caller's pixels; everything after that is the same code.  The quadrangle is in the stream's pixel
- * coordinates; EXIF orientation is not applied.  The engine's staging blocks grow by the coefficient pieces at the first call.
+ * coordinates; EXIF orientation is not applied (cv_process_jpeg_oriented applies it).  The engine's staging blocks grow by the coefficient pieces at the first call.
  * CV_ERR_INVALID with the parser's reason for a stream that is not supported. */
 int cv_process_jpeg(cv_engine_t* unet_engine, cv_engine_t* classifier_engine, const uint8_t* bytes, size_t len, float threshold,
                     int flip, int fallback_quad, cv_image_result_t* out, size_t out_size, void* stream);
+/* cv_process_jpeg with one more argument.  apply_orientation != 0: the stream's EXIF orientation tag (IFD0 of its first Exif APP1
+ * segment; absent or 1: nothing changes) is applied while the photo is reconstructed, as cv_jpeg_reconstruct_oriented_u8 does, so the
+ * device image, the resize, the quadrangle coordinates and the warp are all those of the upright photo: the result equals
+ * cv_process_image_v2 of the oriented pixels bit for bit.  apply_orientation == 0 is cv_process_jpeg.  The result struct is unchanged. */
+int cv_process_jpeg_oriented(cv_engine_t* unet_engine, cv_engine_t* classifier_engine, const uint8_t* bytes, size_t len, float threshold,
+                             int flip, int fallback_quad, int apply_orientation, cv_image_result_t* out, size_t out_size, void* stream);
 
 /* ---- JPEG encode (additions under ABI 6: look the symbols up with dlsym; the version stays 6) ------------------------------------ */
 /* Gray images to complete baseline JPEG files, byte for byte what libjpeg writes for a one-component image with its defaults
