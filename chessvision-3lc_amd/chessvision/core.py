@@ -593,6 +593,82 @@ class ChessVision:
                     out[i] = blob
         return out
 
+    _ENCODE_OUT_BYTES = 256 << 20                                # what one colour encode may allocate for its files' worst case
+
+    @classmethod
+    def _colour_slice(cls, h: int, w: int, subsampling: str) -> int:
+        """Images of one colour encode: its output allocation is n x ``jpeg_colour_max_bytes``, bounded here; at most 64."""
+        from .hip_backend import jpeg_colour_max_bytes
+        return max(1, min(64, cls._ENCODE_OUT_BYTES // jpeg_colour_max_bytes(h, w, subsampling)))
+
+    def encode_colour(self, images: Sequence[NDArray[np.uint8]], quality: int = 95, subsampling: str = "4:2:0",
+                      channel_order: str = "bgr") -> list[bytes]:
+        """Colour host arrays ``(h, w, 3)`` uint8 of any mix of sizes (1..4096 each way), BGR by default -> complete baseline JPEG
+        files in input order: byte for byte what ``PIL.Image.fromarray(rgb).save(f, "JPEG", quality=quality, subsampling=subsampling)``
+        writes, and with the default "4:2:0" what libjpeg's defaults give (``cv2.imwrite``, which has not been run here).
+        ``subsampling``: "4:2:0" | "4:2:2" | "4:4:4"; ``channel_order`` only says which byte of a pixel is R.  Images are grouped by
+        shape as in ``encode_gray``; each slice of a group is one ``HipEngine.jpeg_encode_colour``.  Bad arguments raise ``ValueError``
+        before an engine exists."""
+        from . import jpeg
+
+        jpeg.check_subsampling(subsampling)
+        jpeg.check_colour_order(channel_order)
+        arrays = [jpeg.check_colour_image(a, "encode_colour") for a in images]
+        groups: dict[tuple, list[int]] = {}
+        for i, a in enumerate(arrays):
+            groups.setdefault(a.shape[:2], []).append(i)
+        out: list = [None] * len(arrays)
+        if not arrays:
+            return out
+        eng = self._get_engine("unet")
+        for (h, w), ids in groups.items():
+            step = self._colour_slice(h, w, subsampling)
+            for k0 in range(0, len(ids), step):
+                part = ids[k0:k0 + step]
+                files = eng.jpeg_encode_colour(np.stack([arrays[i] for i in part]), quality, subsampling, channel_order)
+                for i, blob in zip(part, files):
+                    out[i] = blob
+        return out
+
+    def transcode_jpegs(self, blobs: Sequence[bytes], quality: int = 95, subsampling: str = "4:2:0",
+                        orientation: str = "ignore") -> list[bytes]:
+        """JPEG streams -> the files libjpeg writes for the photos they decode to, in input order: the reference endpoint's
+        ``cv2.imwrite(raw/<uuid>.jpg, cv2.imdecode(upload))`` in one call, equal to ``encode_colour(decode_jpegs(blobs, "bgr",
+        orientation), quality, subsampling)`` byte for byte -- but the pixels never leave the device.  Per (geometry, effective tag)
+        group and slice: the Huffman stage on host threads, the reconstruction (with the turn when ``orientation="exif"``) and the
+        colour encoder on the tensor where the decoder left it; only the files come back.  One-component streams are written as
+        three-component files, as ``IMREAD_COLOR`` followed by ``imwrite`` does.  Metadata (EXIF, ICC, comments) is dropped, as
+        ``imwrite`` drops it; under ``"ignore"`` a tagged photo is therefore written as stored, without its tag.  Streams the decoder
+        refuses raise ``jpeg.UnsupportedJpeg`` as in ``decode_jpegs``; a photo larger than 4096 either way raises ``ValueError``;
+        both before any GPU work.  Cost as it stands: each slice goes through ``HipEngine.jpeg_decode``, which waits for its stream
+        once (to release its page-locked buffer) before the slice's encode is queued, so the Huffman stage of the next slice does not
+        overlap the device work of this one; 256 photos of 512 x 512 take 0.05 s of wall clock (``profiles/jpeg_colour_encode.md``)."""
+        from . import jpeg
+
+        jpeg.check_orientation(orientation)
+        jpeg.check_subsampling(subsampling)
+        blobs = [bytes(b) for b in blobs]
+        infos = jpeg.parse_all(blobs)
+        large = [i for i, f in enumerate(infos) if max(f.width, f.height) > jpeg.ENCODE_MAX_SIDE]
+        if large:
+            raise ValueError(f"transcode_jpegs: streams {large} are larger than {jpeg.ENCODE_MAX_SIDE} pixels in width or height")
+        groups: dict[tuple, list[int]] = {}
+        for i, info in enumerate(infos):
+            groups.setdefault(jpeg.job_key(info, orientation), []).append(i)
+        out: list = [None] * len(blobs)
+        if not blobs:
+            return out
+        eng = self._get_engine("unet")
+        for (_, tag), ids in groups.items():
+            h, w = jpeg.oriented_shape(infos[ids[0]], tag)
+            step = self._colour_slice(h, w, subsampling)
+            for k0 in range(0, len(ids), step):
+                part = ids[k0:k0 + step]
+                photos = eng.jpeg_decode([blobs[i] for i in part], "bgr", orientation)
+                for i, blob in zip(part, eng.jpeg_encode_colour(photos, quality, subsampling, "bgr")):
+                    out[i] = blob
+        return out
+
     # ---- encoded input: JPEG streams in, the decode inside the library (chessvision/jpeg.py, csrc/jpeg.cpp, csrc/jpeg.hip) ----------
     def process_jpeg(self, blob, threshold: float = 0.5, flip: bool = False, orientation: str = "ignore") -> ChessVisionResult:
         """``process_image`` for a JPEG stream (``bytes``): one native call, ``cv_process_jpeg``, over the request slots.  The Huffman

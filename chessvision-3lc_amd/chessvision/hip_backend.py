@@ -151,6 +151,9 @@ SYMBOLS = [
     ("cv_jpeg_gray_header", _i, [_i, _i, _i, _vp, _vp]),
     ("cv_jpeg_gray_max_bytes", _i, [_i, _i, ctypes.POINTER(ctypes.c_size_t)]),
     ("cv_jpeg_encode_gray_u8", _i, [_vp, _vp, _i, _i, _i, _i, _vp, ctypes.c_size_t, _vp, _vp, _vp]),
+    ("cv_jpeg_colour_header", _i, [_i, _i, _i, _i, _vp, _vp]),
+    ("cv_jpeg_colour_max_bytes", _i, [_i, _i, _i, ctypes.POINTER(ctypes.c_size_t)]),
+    ("cv_jpeg_encode_colour_u8", _i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, ctypes.c_size_t, _vp, _vp, _vp]),
     ("cv_embedding_neighbours_scratch_bytes", ctypes.c_size_t, [_i, _i, _i, _i]),
     ("cv_embedding_neighbours", _i, [_vp, _vp, _i, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, ctypes.c_size_t, _vp]),
 ]
@@ -512,6 +515,31 @@ def jpeg_gray_header(h: int, w: int, quality: int = 95):
     quantisation table in natural order (``cv_jpeg_gray_header``; host only)."""
     header, qt = np.zeros(328, np.uint8), np.zeros(64, np.uint16)
     _check(load_library().cv_jpeg_gray_header(int(h), int(w), int(quality), header.ctypes.data, qt.ctypes.data))
+    return header.tobytes(), qt
+
+
+JPEG_SUBSAMPLINGS = {"4:4:4": 0, "4:2:2": 1, "4:2:0": 2}          # CV_JPEG_SUB_* (include/chessvision_hip.h)
+
+
+def _jpeg_subsampling(subsampling) -> int:
+    from .jpeg import check_subsampling
+    check_subsampling(subsampling)
+    return JPEG_SUBSAMPLINGS[subsampling]
+
+
+def jpeg_colour_max_bytes(h: int, w: int, subsampling: str = "4:2:0") -> int:
+    """The largest file ``HipEngine.jpeg_encode_colour`` can write for an h x w image (``cv_jpeg_colour_max_bytes``)."""
+    v = ctypes.c_size_t(0)
+    _check(load_library().cv_jpeg_colour_max_bytes(int(h), int(w), _jpeg_subsampling(subsampling), ctypes.byref(v)))
+    return int(v.value)
+
+
+def jpeg_colour_header(h: int, w: int, quality: int = 95, subsampling: str = "4:2:0"):
+    """``(header, qtables)``: the 623 bytes libjpeg writes in front of a colour image's entropy-coded segment and the (2, 64) uint16
+    quantisation tables, luma and chroma, in natural order (``cv_jpeg_colour_header``; host only)."""
+    header, qt = np.zeros(623, np.uint8), np.zeros((2, 64), np.uint16)
+    _check(load_library().cv_jpeg_colour_header(int(h), int(w), int(quality), _jpeg_subsampling(subsampling), header.ctypes.data,
+                                                qt.ctypes.data))
     return header.tobytes(), qt
 
 
@@ -1064,7 +1092,12 @@ class HipEngine:
             if a.ndim != 3:
                 raise HipBackendError("jpeg_encode_gray expects (n, h, w) uint8 images")
             images = torch.from_numpy(a).to(self.device)
-        out, offsets, lengths = self.jpeg_encode_gray_dev(images.contiguous(), quality)
+        return self._fetch_files(*self.jpeg_encode_gray_dev(images.contiguous(), quality))
+
+    @staticmethod
+    def _fetch_files(out: torch.Tensor, offsets: torch.Tensor, lengths: torch.Tensor) -> list:
+        """What an encoder's device form returned, as ``bytes`` per file: the offsets and lengths come back first, then exactly the
+        bytes the files occupy; both waits are on events of the current stream."""
         n = lengths.numel()
         table = torch.empty(2 * n + 1, dtype=torch.int64, pin_memory=True)
         table[:n + 1].copy_(offsets, non_blocking=True)
@@ -1079,6 +1112,40 @@ class HipEngine:
         landed.synchronize()
         h = host.numpy()
         return [h[int(t[i]):int(t[i]) + int(t[n + 1 + i])].tobytes() for i in range(n)]
+
+    def jpeg_encode_colour_dev(self, images: torch.Tensor, quality: int = 95, subsampling: str = "4:2:0", channel_order: str = "bgr"):
+        """Device form: ``images`` (n, h, w, 3) uint8 on the device in ``channel_order`` ("bgr" | "rgb": which byte of a pixel is R),
+        n >= 1, h and w 1..4096 -> ``(out, offsets, lengths)`` device tensors as ``jpeg_encode_gray_dev`` returns them: file i is
+        ``out[offsets[i] : offsets[i] + lengths[i]]``, a three-component baseline file with luma sampled as ``subsampling`` says
+        ("4:2:0" | "4:2:2" | "4:4:4").  ``out`` is sized for the worst case (``jpeg_colour_max_bytes`` per image).  Launches on the
+        current stream; nothing waits."""
+        from .jpeg import ORDERS, check_colour_order
+        check_colour_order(channel_order)
+        sub = _jpeg_subsampling(subsampling)
+        if not isinstance(images, torch.Tensor) or images.dtype != torch.uint8 or images.dim() != 4 or images.shape[3] != 3 \
+                or images.device != self.device or not images.is_contiguous():
+            raise HipBackendError("jpeg_encode_colour_dev expects a contiguous (n, h, w, 3) uint8 tensor on the engine's device")
+        n, h, w = (int(v) for v in images.shape[:3])
+        if n < 1 or not (1 <= h <= 4096 and 1 <= w <= 4096):
+            raise HipBackendError("jpeg_encode_colour_dev: n >= 1 images of 1..4096 x 1..4096 pixels")
+        each = jpeg_colour_max_bytes(h, w, subsampling)
+        out = torch.empty(n * each, dtype=torch.uint8, device=self.device)
+        offsets = torch.empty(n + 1, dtype=torch.int64, device=self.device)
+        lengths = torch.empty(n, dtype=torch.int32, device=self.device)
+        _check(self._lib.cv_jpeg_encode_colour_u8(self._h, _ptr(images), n, h, w, ORDERS[channel_order], sub, int(quality), _ptr(out),
+                                                  out.numel(), _ptr(offsets), _ptr(lengths), _stream_ptr(self.device)))
+        return out, offsets, lengths
+
+    def jpeg_encode_colour(self, images, quality: int = 95, subsampling: str = "4:2:0", channel_order: str = "bgr") -> list:
+        """Colour images of ONE size, (n, h, w, 3) uint8 as a device tensor or a numpy array -> n complete baseline JPEG files
+        (``bytes``): libjpeg's with its defaults, byte for byte (``jpeg.encode_colour`` is the numpy form).  Event waits only, and
+        exactly the files' bytes are downloaded, as in ``jpeg_encode_gray``."""
+        if isinstance(images, np.ndarray):
+            a = np.ascontiguousarray(images, dtype=np.uint8)
+            if a.ndim != 4 or a.shape[3] != 3:
+                raise HipBackendError("jpeg_encode_colour expects (n, h, w, 3) uint8 images")
+            images = torch.from_numpy(a).to(self.device)
+        return self._fetch_files(*self.jpeg_encode_colour_dev(images.contiguous(), quality, subsampling, channel_order))
 
     # -- introspection ----------------------------------------------------------------------------
     def activation(self, model: str, name: str) -> np.ndarray:

@@ -408,18 +408,22 @@ def encode_coefficients(image, quality: int = 95) -> np.ndarray:
     return np.where(nat < 0, -mag, mag)[:, ZIGZAG]
 
 
-def encode_gray(image, quality: int = 95) -> bytes:
-    """One gray image (h, w) uint8 -> the complete baseline JPEG file libjpeg writes for it at ``quality`` (clamped to 1..100), byte
-    for byte ``PIL.Image.fromarray(image, "L").save(f, "JPEG", quality=quality)``.  The numpy form of ``HipEngine.jpeg_encode_gray``
-    and its checker; it shares no code with the kernels."""
-    zz = encode_coefficients(image, quality)
-    h, w = np.asarray(image).shape
-    nb = zz.shape[0]
-    dc, ac = _huffman_codes(DC_BITS, DC_VALS), _huffman_codes(AC_BITS, AC_VALS)
+def _code_arrays(bits_vals_dc, bits_vals_ac):
+    """(dc_code, dc_len, ac_code, ac_len) arrays of one DC / AC table pair; absent AC symbols have length 0."""
+    dc, ac = _huffman_codes(*bits_vals_dc), _huffman_codes(*bits_vals_ac)
     dc_code, dc_len = np.array([dc[s][0] for s in range(12)], np.uint64), np.array([dc[s][1] for s in range(12)], np.int64)
     ac_code, ac_len = np.zeros(256, np.uint64), np.zeros(256, np.int64)
     for sym, (code, length) in ac.items():
         ac_code[sym], ac_len[sym] = code, length
+    return dc_code, dc_len, ac_code, ac_len
+
+
+def _entropy_segment(zz, diff, sel, tables) -> bytes:
+    """The entropy-coded segment of blocks ``zz`` (nb, 64) in coded order: block b has DC difference ``diff[b]`` and uses the table
+    set ``tables[sel[b]]`` (``_code_arrays``).  Bits most significant first, the last byte filled with 1-bits, FF followed by 00."""
+    nb = zz.shape[0]
+    dc_code, dc_len = np.stack([t[0] for t in tables]), np.stack([t[1] for t in tables])
+    ac_code, ac_len = np.stack([t[2] for t in tables]), np.stack([t[3] for t in tables])
 
     def size_and_extra(v):                                                  # category and the bits that follow its code
         mag = np.abs(v)
@@ -428,9 +432,8 @@ def encode_gray(image, quality: int = 95) -> bytes:
         return size, extra.astype(np.uint64)
 
     # one item per block for the DC difference, one per non-zero AC coefficient (its ZRLs in front), one per end-of-block
-    diff = zz[:, 0] - np.concatenate([[0], zz[:-1, 0]])
     s, e = size_and_extra(diff)
-    items = [(np.arange(nb) * 65, (dc_code[s] << s.astype(np.uint64)) | e, dc_len[s] + s)]
+    items = [(np.arange(nb) * 65, (dc_code[sel, s] << s.astype(np.uint64)) | e, dc_len[sel, s] + s)]
     pos = np.where(zz != 0, np.arange(64), -1)
     pos[:, 0] = 0
     prev = np.maximum.accumulate(pos, axis=1)
@@ -440,16 +443,19 @@ def encode_gray(image, quality: int = 95) -> bytes:
     s, e = size_and_extra(zz[b, k])
     sym = ((run & 15) << 4) | s
     zrl = run >> 4
-    val = (ac_code[sym] << s.astype(np.uint64)) | e
-    length = ac_len[sym] + s
-    zc, zl = int(ac_code[0xF0]), int(ac_len[0xF0])
+    t = sel[b]
+    val = (ac_code[t, sym] << s.astype(np.uint64)) | e
+    length = ac_len[t, sym] + s
+    zc, zl = ac_code[t, 0xF0], ac_len[t, 0xF0]
     for r in (1, 2, 3):
-        pre = np.uint64(sum(zc << (zl * i) for i in range(r)))
+        pre = np.zeros(b.size, np.uint64)
+        for _ in range(r):
+            pre = (pre << zl.astype(np.uint64)) | zc
         val = np.where(zrl == r, (pre << length.astype(np.uint64)) | val, val)
     length = length + zrl * zl
     items.append((b * 65 + k, val, length))
     eob = np.nonzero(zz[:, 63] == 0)[0]
-    items.append((eob * 65 + 64, np.full(eob.size, ac_code[0], np.uint64), np.full(eob.size, ac_len[0], np.int64)))
+    items.append((eob * 65 + 64, ac_code[sel[eob], 0], ac_len[sel[eob], 0]))
     key = np.concatenate([i[0] for i in items])
     order = np.argsort(key, kind="stable")
     val, length = np.concatenate([i[1] for i in items])[order], np.concatenate([i[2] for i in items])[order]
@@ -462,4 +468,166 @@ def encode_gray(image, quality: int = 95) -> bytes:
     payload = np.packbits(bits)
     ff = np.nonzero(payload == 0xFF)[0]
     payload = np.insert(payload, ff + 1, 0)                                 # FF is followed by a stuffed 00
-    return gray_header(w, h, quality) + payload.tobytes() + b"\xff\xd9"
+    return payload.tobytes()
+
+
+def encode_gray(image, quality: int = 95) -> bytes:
+    """One gray image (h, w) uint8 -> the complete baseline JPEG file libjpeg writes for it at ``quality`` (clamped to 1..100), byte
+    for byte ``PIL.Image.fromarray(image, "L").save(f, "JPEG", quality=quality)``.  The numpy form of ``HipEngine.jpeg_encode_gray``
+    and its checker; it shares no code with the kernels."""
+    zz = encode_coefficients(image, quality)
+    h, w = np.asarray(image).shape
+    diff = zz[:, 0] - np.concatenate([[0], zz[:-1, 0]])
+    tables = [_code_arrays((DC_BITS, DC_VALS), (AC_BITS, AC_VALS))]
+    return gray_header(w, h, quality) + _entropy_segment(zz, diff, np.zeros(zz.shape[0], np.int64), tables) + b"\xff\xd9"
+
+
+# ---- JPEG encode, colour: the numpy host form of the colour front end of csrc/jpeg_enc.hip -------------------------------------
+# What libjpeg writes for an RGB image with its defaults (``PIL.Image.fromarray(rgb).save(f, "JPEG", quality=q, subsampling=s)``):
+# three components, YCbCr by jccolor.c's 16-bit fixed point, chroma reduced by jcsample.c's plain box (no smoothing), one
+# interleaved scan, luma with table set 0 and chroma with set 1 (Annex K.2 quantiser, K.3.3.2 / K.3.3.4 codes), a 623-byte header.
+CHROMA_QUANT = np.array([17, 18, 24, 47, 99, 99, 99, 99, 18, 21, 26, 66, 99, 99, 99, 99, 24, 26, 56, 99, 99, 99, 99, 99, 47, 66, 99, 99,
+                         99, 99, 99, 99] + [99] * 32)
+DC1_BITS = (0, 3, 1, 1, 1, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0)
+DC1_VALS = tuple(range(12))
+AC1_BITS = (0, 2, 1, 2, 4, 4, 3, 4, 7, 5, 4, 4, 0, 1, 2, 0x77)
+AC1_VALS = (0x00, 0x01, 0x02, 0x03, 0x11, 0x04, 0x05, 0x21, 0x31, 0x06, 0x12, 0x41, 0x51, 0x07, 0x61, 0x71, 0x13, 0x22, 0x32, 0x81, 0x08,
+            0x14, 0x42, 0x91, 0xa1, 0xb1, 0xc1, 0x09, 0x23, 0x33, 0x52, 0xf0, 0x15, 0x62, 0x72, 0xd1, 0x0a, 0x16, 0x24, 0x34, 0xe1, 0x25,
+            0xf1, 0x17, 0x18, 0x19, 0x1a, 0x26, 0x27, 0x28, 0x29, 0x2a, 0x35, 0x36, 0x37, 0x38, 0x39, 0x3a, 0x43, 0x44, 0x45, 0x46, 0x47,
+            0x48, 0x49, 0x4a, 0x53, 0x54, 0x55, 0x56, 0x57, 0x58, 0x59, 0x5a, 0x63, 0x64, 0x65, 0x66, 0x67, 0x68, 0x69, 0x6a, 0x73, 0x74,
+            0x75, 0x76, 0x77, 0x78, 0x79, 0x7a, 0x82, 0x83, 0x84, 0x85, 0x86, 0x87, 0x88, 0x89, 0x8a, 0x92, 0x93, 0x94, 0x95, 0x96, 0x97,
+            0x98, 0x99, 0x9a, 0xa2, 0xa3, 0xa4, 0xa5, 0xa6, 0xa7, 0xa8, 0xa9, 0xaa, 0xb2, 0xb3, 0xb4, 0xb5, 0xb6, 0xb7, 0xb8, 0xb9, 0xba,
+            0xc2, 0xc3, 0xc4, 0xc5, 0xc6, 0xc7, 0xc8, 0xc9, 0xca, 0xd2, 0xd3, 0xd4, 0xd5, 0xd6, 0xd7, 0xd8, 0xd9, 0xda, 0xe2, 0xe3, 0xe4,
+            0xe5, 0xe6, 0xe7, 0xe8, 0xe9, 0xea, 0xf2, 0xf3, 0xf4, 0xf5, 0xf6, 0xf7, 0xf8, 0xf9, 0xfa)
+COLOUR_HEADER_BYTES = 623
+SUBSAMPLINGS = {"4:2:0": (2, 2), "4:2:2": (2, 1), "4:4:4": (1, 1)}          # luma sampling (horizontal, vertical); chroma is 1 x 1
+ENCODE_MAX_SIDE = 4096
+
+
+def check_subsampling(subsampling) -> tuple[int, int]:
+    """Luma's ``(horizontal, vertical)`` sampling factors of ``"4:2:0"`` / ``"4:2:2"`` / ``"4:4:4"``; anything else raises."""
+    if not isinstance(subsampling, str) or subsampling not in SUBSAMPLINGS:
+        raise ValueError(f"subsampling must be one of {sorted(SUBSAMPLINGS)}, got {subsampling!r}")
+    return SUBSAMPLINGS[subsampling]
+
+
+def check_colour_image(image, what: str = "encode_colour") -> np.ndarray:
+    """``image`` as an ``(h, w, 3)`` uint8 array, h and w 1..4096; anything else raises ``ValueError``."""
+    a = np.asarray(image)
+    if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3:
+        raise ValueError(f"{what} expects (h, w, 3) uint8 arrays, got {a.dtype} {a.shape}")
+    if not (1 <= a.shape[0] <= ENCODE_MAX_SIDE and 1 <= a.shape[1] <= ENCODE_MAX_SIDE):
+        raise ValueError(f"{what}: height and width must be 1..{ENCODE_MAX_SIDE}, got {a.shape[0]} x {a.shape[1]}")
+    return a
+
+
+def check_colour_order(channel_order) -> bool:
+    """True when byte 0 of a pixel is R (``"rgb"``), False for ``"bgr"``; anything else raises."""
+    if channel_order not in ("bgr", "rgb"):
+        raise ValueError(f"channel_order must be 'bgr' or 'rgb', got {channel_order!r}")
+    return channel_order == "rgb"
+
+
+def encode_chroma_quant_table(quality: int) -> np.ndarray:
+    """``encode_quant_table``'s scaling on the Annex K.2 chrominance table."""
+    q = min(100, max(1, int(quality)))
+    scale = 5000 // q if q < 50 else 200 - 2 * q
+    return np.clip((CHROMA_QUANT.astype(np.int64) * scale + 50) // 100, 1, 255)
+
+
+def colour_header(width: int, height: int, quality: int, subsampling: str = "4:2:0") -> bytes:
+    """The 623 bytes in front of the entropy-coded segment: SOI, APP0, DQT 0, DQT 1, SOF0 (three components), DHT DC0, AC0, DC1, AC1,
+    SOS."""
+    hs, vs = check_subsampling(subsampling)
+    out = bytearray(b"\xff\xd8\xff\xe0\x00\x10JFIF\x00\x01\x01\x00\x00\x01\x00\x01\x00\x00")
+    for k, qt in enumerate((encode_quant_table(quality), encode_chroma_quant_table(quality))):
+        out += b"\xff\xdb\x00\x43" + bytes([k]) + bytes(int(qt[z]) for z in ZIGZAG)
+    out += b"\xff\xc0\x00\x11\x08" + int(height).to_bytes(2, "big") + int(width).to_bytes(2, "big") + b"\x03"
+    out += bytes([1, (hs << 4) | vs, 0, 2, 0x11, 1, 3, 0x11, 1])
+    out += b"\xff\xc4\x00\x1f\x00" + bytes(DC_BITS) + bytes(DC_VALS)
+    out += b"\xff\xc4\x00\xb5\x10" + bytes(AC_BITS) + bytes(AC_VALS)
+    out += b"\xff\xc4\x00\x1f\x01" + bytes(DC1_BITS) + bytes(DC1_VALS)
+    out += b"\xff\xc4\x00\xb5\x11" + bytes(AC1_BITS) + bytes(AC1_VALS)
+    out += b"\xff\xda\x00\x0c\x03\x01\x00\x02\x11\x03\x11\x00\x3f\x00"
+    assert len(out) == COLOUR_HEADER_BYTES
+    return bytes(out)
+
+
+def colour_planes(image, subsampling: str = "4:2:0", channel_order: str = "bgr"):
+    """``(Y, Cb, Cr)`` int64 planes as the forward DCT sees them, before the level shift: Y padded to whole MCUs by replicating its
+    last column and row; chroma converted at full resolution, its last column replicated out to the MCU width, its last row only to
+    a whole row group, then reduced by the box filter, then its last REDUCED row replicated down to whole blocks."""
+    a = check_colour_image(image).astype(np.int64)
+    hs, vs = check_subsampling(subsampling)
+    r, g, b = (a[..., 0], a[..., 1], a[..., 2]) if check_colour_order(channel_order) else (a[..., 2], a[..., 1], a[..., 0])
+    h, w = r.shape
+    mh, mw = -(-h // (8 * vs)) * 8 * vs, -(-w // (8 * hs)) * 8 * hs
+    y = (19595 * r + 38470 * g + 7471 * b + 32768) >> 16
+    cb = (-11059 * r - 21709 * g + 32768 * b + (128 << 16) + 32767) >> 16
+    cr = (32768 * r - 27439 * g - 5329 * b + (128 << 16) + 32767) >> 16
+    planes = [np.pad(y, ((0, mh - h), (0, mw - w)), mode="edge")]
+    for c in (cb, cr):
+        c = np.pad(c, ((0, -(-h // vs) * vs - h), (0, mw - w)), mode="edge")
+        if hs == 2:
+            pairs = c[:, 0::2] + c[:, 1::2]
+            odd = np.arange(pairs.shape[1]) & 1
+            c = (pairs[0::2] + pairs[1::2] + 1 + odd) >> 2 if vs == 2 else (pairs + odd) >> 1
+        planes.append(np.pad(c, ((0, mh // vs - c.shape[0]), (0, 0)), mode="edge"))
+    return tuple(planes)
+
+
+def _plane_coefficients(plane, table) -> np.ndarray:
+    """A padded int64 plane -> (block_rows, block_cols, 64) quantised coefficients in zigzag order (``encode_coefficients``'s steps)."""
+    rows, cols = plane.shape[0] // 8, plane.shape[1] // 8
+    blk = (plane - 128).reshape(rows, 8, cols, 8).transpose(0, 2, 1, 3).reshape(rows * cols, 8, 8)
+    ws = _fdct_pass(np.moveaxis(blk, 2, 0), True)
+    out = _fdct_pass(np.moveaxis(ws, 2, 0), False)
+    nat = np.transpose(out, (2, 0, 1)).reshape(rows * cols, 64)
+    d = table << 3
+    mag = (np.abs(nat) + (d >> 1)) // d
+    return np.where(nat < 0, -mag, mag)[:, ZIGZAG].reshape(rows, cols, 64)
+
+
+def encode_colour_coefficients(image, quality: int = 95, subsampling: str = "4:2:0", channel_order: str = "bgr"):
+    """``(zz, comp, real)``: the quantised blocks of the scan in CODED order, ``(blocks, 64)`` int64 in zigzag order, MCU by MCU
+    (luma blocks row-major, then Cb, then Cr); ``comp`` (blocks,) is each block's component 0 / 1 / 2 and ``real`` (blocks,) is False
+    for the dummy luma blocks: those of an MCU that lie beyond the component's own ceil(h / 8) x ceil(w / 8) blocks.  A dummy holds the
+    DC of the block coded before it in its component and no AC."""
+    hs, vs = check_subsampling(subsampling)
+    yp, cbp, crp = colour_planes(image, subsampling, channel_order)
+    h, w = np.asarray(image).shape[:2]
+    my, mx = yp.shape[0] // (8 * vs), yp.shape[1] // (8 * hs)
+    yz = _plane_coefficients(yp, encode_quant_table(quality))
+    cq = encode_chroma_quant_table(quality)
+    cbz, crz = _plane_coefficients(cbp, cq), _plane_coefficients(crp, cq)
+    per = hs * vs + 2
+    zz = np.zeros((my, mx, per, 64), np.int64)
+    real = np.ones((my, mx, per), bool)
+    for v in range(vs):
+        for u in range(hs):
+            k = v * hs + u
+            zz[:, :, k] = yz[v::vs, u::hs]
+            by, bx = np.arange(my) * vs + v, np.arange(mx) * hs + u
+            real[:, :, k] = (by < -(-h // 8))[:, None] & (bx < -(-w // 8))[None, :]
+            if k:                                                           # block 0 of an MCU is always real
+                dummy = ~real[:, :, k]
+                zz[:, :, k][dummy] = 0
+                zz[:, :, k, 0][dummy] = zz[:, :, k - 1, 0][dummy]
+    zz[:, :, per - 2], zz[:, :, per - 1] = cbz, crz
+    comp = np.tile(np.array([0] * (hs * vs) + [1, 2]), my * mx)
+    return zz.reshape(-1, 64), comp, real.reshape(-1)
+
+
+def encode_colour(image, quality: int = 95, subsampling: str = "4:2:0", channel_order: str = "bgr") -> bytes:
+    """One colour image (h, w, 3) uint8, BGR by default -> the complete baseline JPEG file libjpeg writes for it at ``quality``
+    (clamped to 1..100): byte for byte ``PIL.Image.fromarray(rgb).save(f, "JPEG", quality=quality, subsampling=subsampling)``.
+    ``channel_order`` only says which byte of a pixel is R.  The numpy form of ``HipEngine.jpeg_encode_colour`` and its checker; it
+    shares no code with the kernels."""
+    zz, comp, _ = encode_colour_coefficients(image, quality, subsampling, channel_order)
+    h, w = np.asarray(image).shape[:2]
+    diff = np.zeros(zz.shape[0], np.int64)
+    for c in range(3):                                                      # DC prediction runs per component, from 0
+        dcs = zz[comp == c, 0]
+        diff[comp == c] = dcs - np.concatenate([[0], dcs[:-1]])
+    tables = [_code_arrays((DC_BITS, DC_VALS), (AC_BITS, AC_VALS)), _code_arrays((DC1_BITS, DC1_VALS), (AC1_BITS, AC1_VALS))]
+    return colour_header(w, h, quality, subsampling) + _entropy_segment(zz, diff, np.minimum(comp, 1), tables) + b"\xff\xd9"

@@ -1492,6 +1492,29 @@ int cv_jpeg_gray_header(int h, int w, int quality, uint8_t* header, uint16_t* qt
     });
 }
 
+// What the two encode entries share: the engine's scratch has one user at a time ON THE DEVICE, so an encode starts behind the previous
+// one, gray or colour, whatever stream that ran on.  `run(scratch, stream)` queues the launches.
+template <class Run>
+static Status jpeg_encode_on_engine(const char* name, cv_engine_t* eng, size_t need, void* stream, Run run) {
+    Engine& E = eng->impl;
+    hipStream_t st = (hipStream_t)stream;
+    DeviceGuard g(E.device);
+    std::lock_guard<std::mutex> lk(E.mu);
+    hipError_t e = hipSuccess;
+    if (!E.jpeg_enc_done) e = hipEventCreateWithFlags(&E.jpeg_enc_done, hipEventDisableTiming);
+    else e = hipStreamWaitEvent(st, E.jpeg_enc_done, 0);
+    if (e != hipSuccess) return hip_fail(e, name);
+    if (E.jpeg_enc_scratch.bytes < need) {                       // grown for a larger geometry only: the previous encode must have left it
+        e = hipEventSynchronize(E.jpeg_enc_done);
+        if (e != hipSuccess) return hip_fail(e, name);
+        CV_TRY(E.jpeg_enc_scratch.alloc(need, false));
+    }
+    e = run(E.jpeg_enc_scratch.ptr, st);
+    if (e == hipSuccess) e = hipEventRecord(E.jpeg_enc_done, st);
+    if (e != hipSuccess) return hip_fail(e, name);
+    return Status();
+}
+
 int cv_jpeg_encode_gray_u8(cv_engine_t* eng, const uint8_t* src, int n, int h, int w, int quality, uint8_t* out, size_t out_capacity,
                            int64_t* offsets, int32_t* lengths, void* stream) {
     return guarded("cv_jpeg_encode_gray_u8", [&]() -> Status {
@@ -1503,25 +1526,67 @@ int cv_jpeg_encode_gray_u8(cv_engine_t* eng, const uint8_t* src, int n, int h, i
         if (out_capacity / each < (size_t)n) return fail(CV_ERR_INVALID, "cv_jpeg_encode_gray_u8: out holds less than n x cv_jpeg_gray_max_bytes");
         cvjpeg::EncTables tables;
         if (cvjpeg::encoder_tables(w, h, quality, &tables) != cvjpeg::kOk) return fail(CV_ERR_INVALID, "cv_jpeg_encode_gray_u8: bad size");
-        Engine& E = eng->impl;
-        hipStream_t st = (hipStream_t)stream;
-        DeviceGuard g(E.device);
-        std::lock_guard<std::mutex> lk(E.mu);
-        hipError_t e = hipSuccess;
-        // the scratch has one user at a time ON THE DEVICE: this encode starts behind the previous one, whatever stream that ran on
-        if (!E.jpeg_enc_done) e = hipEventCreateWithFlags(&E.jpeg_enc_done, hipEventDisableTiming);
-        else e = hipStreamWaitEvent(st, E.jpeg_enc_done, 0);
-        if (e != hipSuccess) return hip_fail(e, "cv_jpeg_encode_gray_u8");
-        const size_t need = jpeg_encode_scratch_bytes(n, h, w);
-        if (E.jpeg_enc_scratch.bytes < need) {                   // grown for a larger geometry only: the previous encode must have left it
-            e = hipEventSynchronize(E.jpeg_enc_done);
-            if (e != hipSuccess) return hip_fail(e, "cv_jpeg_encode_gray_u8");
-            CV_TRY(E.jpeg_enc_scratch.alloc(need, false));
-        }
-        e = jpeg_encode_gray_u8(src, n, h, w, tables, E.jpeg_enc_scratch.ptr, out, offsets, lengths, st);
-        if (e == hipSuccess) e = hipEventRecord(E.jpeg_enc_done, st);
-        if (e != hipSuccess) return hip_fail(e, "jpeg_encode_gray_u8");
+        return jpeg_encode_on_engine("cv_jpeg_encode_gray_u8", eng, jpeg_encode_scratch_bytes(n, h, w), stream, [&](void* scratch, hipStream_t st) {
+            return jpeg_encode_gray_u8(src, n, h, w, tables, scratch, out, offsets, lengths, st);
+        });
+    });
+}
+
+// luma's sampling factors of a CV_JPEG_SUB_* value; false for any other
+static bool jpeg_subsampling(int subsampling, int* hs, int* vs) {
+    *hs = subsampling == CV_JPEG_SUB_444 ? 1 : 2;
+    *vs = subsampling == CV_JPEG_SUB_420 ? 2 : 1;
+    return subsampling == CV_JPEG_SUB_444 || subsampling == CV_JPEG_SUB_422 || subsampling == CV_JPEG_SUB_420;
+}
+
+int cv_jpeg_colour_max_bytes(int h, int w, int subsampling, size_t* bytes) {
+    return guarded("cv_jpeg_colour_max_bytes", [&]() -> Status {
+        int hs, vs;
+        if (!bytes || h < 1 || w < 1 || h > kJpegEncMaxSide || w > kJpegEncMaxSide)
+            return fail(CV_ERR_INVALID, "cv_jpeg_colour_max_bytes: height and width must be 1..4096");
+        if (!jpeg_subsampling(subsampling, &hs, &vs)) return fail(CV_ERR_INVALID, "cv_jpeg_colour_max_bytes: subsampling must be CV_JPEG_SUB_444 / 422 / 420");
+        *bytes = cvjpeg::colour_max_bytes(w, h, hs, vs);
         return Status();
+    });
+}
+
+int cv_jpeg_colour_header(int h, int w, int quality, int subsampling, uint8_t* header, uint16_t* qtables) {
+    return guarded("cv_jpeg_colour_header", [&]() -> Status {
+        int hs, vs;
+        cvjpeg::ScanTables t;
+        if (!jpeg_subsampling(subsampling, &hs, &vs)) return fail(CV_ERR_INVALID, "cv_jpeg_colour_header: subsampling must be CV_JPEG_SUB_444 / 422 / 420");
+        if (!header || cvjpeg::colour_encoder_tables(w, h, quality, hs, vs, &t) != cvjpeg::kOk)
+            return fail(CV_ERR_INVALID, "cv_jpeg_colour_header: null header or a size outside 1..65535");
+        std::memcpy(header, t.header, CV_JPEG_COLOUR_HEADER_BYTES);
+        if (qtables) {
+            cvjpeg::quant_table(quality, qtables);
+            cvjpeg::chroma_quant_table(quality, qtables + 64);
+        }
+        return Status();
+    });
+}
+
+int cv_jpeg_encode_colour_u8(cv_engine_t* eng, const uint8_t* src, int n, int h, int w, int channel_order, int subsampling, int quality,
+                             uint8_t* out, size_t out_capacity, int64_t* offsets, int32_t* lengths, void* stream) {
+    return guarded("cv_jpeg_encode_colour_u8", [&]() -> Status {
+        CV_TRY(check_engine(eng));
+        int hs, vs;
+        if (!src || !out || !offsets || !lengths || n < 1) return fail(CV_ERR_INVALID, "cv_jpeg_encode_colour_u8: bad argument");
+        if (h < 1 || w < 1 || h > kJpegEncMaxSide || w > kJpegEncMaxSide)
+            return fail(CV_ERR_INVALID, "cv_jpeg_encode_colour_u8: height and width must be 1..4096");
+        if (channel_order != CV_JPEG_BGR && channel_order != CV_JPEG_RGB)
+            return fail(CV_ERR_INVALID, "cv_jpeg_encode_colour_u8: channel_order must be CV_JPEG_BGR or CV_JPEG_RGB");
+        if (!jpeg_subsampling(subsampling, &hs, &vs))
+            return fail(CV_ERR_INVALID, "cv_jpeg_encode_colour_u8: subsampling must be CV_JPEG_SUB_444 / 422 / 420");
+        const size_t each = cvjpeg::colour_max_bytes(w, h, hs, vs);
+        if (out_capacity / each < (size_t)n) return fail(CV_ERR_INVALID, "cv_jpeg_encode_colour_u8: out holds less than n x cv_jpeg_colour_max_bytes");
+        cvjpeg::ScanTables tables;
+        if (cvjpeg::colour_encoder_tables(w, h, quality, hs, vs, &tables) != cvjpeg::kOk) return fail(CV_ERR_INVALID, "cv_jpeg_encode_colour_u8: bad size");
+        const int r_at = channel_order == CV_JPEG_RGB ? 0 : 2;
+        return jpeg_encode_on_engine("cv_jpeg_encode_colour_u8", eng, jpeg_encode_colour_scratch_bytes(n, h, w, hs, vs), stream,
+                                     [&](void* scratch, hipStream_t st) {
+                                         return jpeg_encode_colour_u8(src, n, h, w, r_at, hs, vs, tables, scratch, out, offsets, lengths, st);
+                                     });
     });
 }
 

@@ -493,4 +493,104 @@ int encoder_tables(int width, int height, int quality, EncTables* t) {
     return (p - t->header) == kGrayHeaderBytes ? kOk : kInvalid;
 }
 
+// ---- colour: the second table set and the three-component header ---------------------------------------------------------------
+namespace {
+
+const uint8_t kChromaQuant[64] = {17, 18, 24, 47, 99, 99, 99, 99, 18, 21, 26, 66, 99, 99, 99, 99, 24, 26, 56, 99, 99, 99, 99, 99, 47, 66, 99, 99, 99, 99, 99, 99,
+                                  99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99};
+const uint8_t kDc1Bits[16] = {0, 3, 1, 1, 1, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0};
+const uint8_t kAc1Bits[16] = {0, 2, 1, 2, 4, 4, 3, 4, 7, 5, 4, 4, 0, 1, 2, 0x77};
+const uint8_t kAc1Vals[162] = {
+    0x00, 0x01, 0x02, 0x03, 0x11, 0x04, 0x05, 0x21, 0x31, 0x06, 0x12, 0x41, 0x51, 0x07, 0x61, 0x71, 0x13, 0x22, 0x32, 0x81, 0x08, 0x14, 0x42,
+    0x91, 0xa1, 0xb1, 0xc1, 0x09, 0x23, 0x33, 0x52, 0xf0, 0x15, 0x62, 0x72, 0xd1, 0x0a, 0x16, 0x24, 0x34, 0xe1, 0x25, 0xf1, 0x17, 0x18, 0x19,
+    0x1a, 0x26, 0x27, 0x28, 0x29, 0x2a, 0x35, 0x36, 0x37, 0x38, 0x39, 0x3a, 0x43, 0x44, 0x45, 0x46, 0x47, 0x48, 0x49, 0x4a, 0x53, 0x54, 0x55,
+    0x56, 0x57, 0x58, 0x59, 0x5a, 0x63, 0x64, 0x65, 0x66, 0x67, 0x68, 0x69, 0x6a, 0x73, 0x74, 0x75, 0x76, 0x77, 0x78, 0x79, 0x7a, 0x82, 0x83,
+    0x84, 0x85, 0x86, 0x87, 0x88, 0x89, 0x8a, 0x92, 0x93, 0x94, 0x95, 0x96, 0x97, 0x98, 0x99, 0x9a, 0xa2, 0xa3, 0xa4, 0xa5, 0xa6, 0xa7, 0xa8,
+    0xa9, 0xaa, 0xb2, 0xb3, 0xb4, 0xb5, 0xb6, 0xb7, 0xb8, 0xb9, 0xba, 0xc2, 0xc3, 0xc4, 0xc5, 0xc6, 0xc7, 0xc8, 0xc9, 0xca, 0xd2, 0xd3, 0xd4,
+    0xd5, 0xd6, 0xd7, 0xd8, 0xd9, 0xda, 0xe2, 0xe3, 0xe4, 0xe5, 0xe6, 0xe7, 0xe8, 0xe9, 0xea, 0xf2, 0xf3, 0xf4, 0xf5, 0xf6, 0xf7, 0xf8, 0xf9,
+    0xfa};
+
+int quality_scale(int quality) {
+    const int q = clamp_quality(quality);
+    return q < 50 ? 5000 / q : 200 - 2 * q;
+}
+
+uint8_t* put(uint8_t* p, const uint8_t* bytes, size_t n) {
+    std::memcpy(p, bytes, n);
+    return p + n;
+}
+
+uint8_t* put_dht(uint8_t* p, uint8_t cls_id, const uint8_t bits[16], const uint8_t* vals, int nvals) {
+    const uint8_t head[5] = {0xff, 0xc4, 0, (uint8_t)(19 + nvals), cls_id};
+    return put(put(put(p, head, 5), bits, 16), vals, (size_t)nvals);
+}
+
+}  // namespace
+
+bool subsampling_ok(int hs, int vs) { return (hs == 2 && vs == 2) || (hs == 2 && vs == 1) || (hs == 1 && vs == 1); }
+
+void chroma_quant_table(int quality, uint16_t out[64]) {
+    const int scale = quality_scale(quality);
+    for (int i = 0; i < 64; ++i) {
+        const int v = (kChromaQuant[i] * scale + 50) / 100;
+        out[i] = (uint16_t)(v < 1 ? 1 : v > 255 ? 255 : v);
+    }
+}
+
+void scan_tables_of(const EncTables& gray, ScanTables* t) {
+    std::memset(t, 0, sizeof *t);
+    std::memcpy(t->divisor[0], gray.divisor, sizeof gray.divisor);
+    std::memcpy(t->dc[0], gray.dc, sizeof gray.dc);
+    std::memcpy(t->ac[0], gray.ac, sizeof gray.ac);
+    std::memcpy(t->header, gray.header, kGrayHeaderBytes);
+    t->header_bytes = kGrayHeaderBytes;
+}
+
+size_t colour_coded_blocks(int width, int height, int hs, int vs) {
+    const size_t mcus = (size_t)((width + 8 * hs - 1) / (8 * hs)) * (size_t)((height + 8 * vs - 1) / (8 * vs));
+    return mcus * (size_t)(hs * vs + 2);
+}
+
+size_t colour_max_bits(int width, int height, int hs, int vs) {
+    const size_t mcus = colour_coded_blocks(width, height, hs, vs) / (size_t)(hs * vs + 2);
+    return mcus * ((size_t)(hs * vs) * kEncMaxBlockBits + 2 * (size_t)kEncMaxChromaBlockBits);
+}
+
+size_t colour_max_bytes(int width, int height, int hs, int vs) {
+    const size_t payload = (colour_max_bits(width, height, hs, vs) + 7) / 8;
+    return (kColourHeaderBytes + 2 * payload + 2 + 15) & ~(size_t)15;
+}
+
+int colour_encoder_tables(int width, int height, int quality, int hs, int vs, ScanTables* t) {
+    if (!t || width < 1 || height < 1 || width > 65535 || height > 65535 || !subsampling_ok(hs, vs)) return kInvalid;
+    std::memset(t, 0, sizeof *t);
+    uint16_t qt[2][64];
+    quant_table(quality, qt[0]);
+    chroma_quant_table(quality, qt[1]);
+    for (int s = 0; s < 2; ++s)
+        for (int k = 0; k < 64; ++k) t->divisor[s][k] = (uint16_t)(qt[s][kNatural[k]] << 3);
+    derive_codes(kDcBits, kDcVals, 12, t->dc[0], 12);
+    derive_codes(kAcBits, kAcVals, 162, t->ac[0], 256);
+    derive_codes(kDc1Bits, kDcVals, 12, t->dc[1], 12);
+    derive_codes(kAc1Bits, kAc1Vals, 162, t->ac[1], 256);
+    const uint8_t app0[20] = {0xff, 0xd8, 0xff, 0xe0, 0, 16, 'J', 'F', 'I', 'F', 0, 1, 1, 0, 0, 1, 0, 1, 0, 0};
+    uint8_t* p = put(t->header, app0, 20);
+    for (int s = 0; s < 2; ++s) {
+        const uint8_t dqt[5] = {0xff, 0xdb, 0, 67, (uint8_t)s};
+        p = put(p, dqt, 5);
+        for (int k = 0; k < 64; ++k) *p++ = (uint8_t)qt[s][kNatural[k]];
+    }
+    const uint8_t sof[19] = {0xff, 0xc0, 0, 17, 8, (uint8_t)(height >> 8), (uint8_t)height, (uint8_t)(width >> 8), (uint8_t)width, 3,
+                             1, (uint8_t)((hs << 4) | vs), 0, 2, 0x11, 1, 3, 0x11, 1};
+    p = put(p, sof, 19);
+    p = put_dht(p, 0x00, kDcBits, kDcVals, 12);
+    p = put_dht(p, 0x10, kAcBits, kAcVals, 162);
+    p = put_dht(p, 0x01, kDc1Bits, kDcVals, 12);
+    p = put_dht(p, 0x11, kAc1Bits, kAc1Vals, 162);
+    const uint8_t sos[14] = {0xff, 0xda, 0, 12, 3, 1, 0x00, 2, 0x11, 3, 0x11, 0, 63, 0};
+    p = put(p, sos, 14);
+    t->header_bytes = kColourHeaderBytes;
+    return (p - t->header) == kColourHeaderBytes ? kOk : kInvalid;
+}
+
 }  // namespace cvjpeg

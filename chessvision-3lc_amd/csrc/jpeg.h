@@ -59,4 +59,34 @@ int encoder_tables(int width, int height, int quality, EncTables* t);
 // bytes a file of that size can reach at most: header, every block at kEncMaxBlockBits with every byte stuffed, EOI; a multiple of 16
 size_t gray_max_bytes(int width, int height);
 
+// ---- ... and of the COLOUR encoder ------------------------------------------------------------------------------------------------
+// What libjpeg writes for an RGB image with its defaults: three components (YCbCr), luma sampled hs x vs = 2x2 ("4:2:0"), 2x1
+// ("4:2:2") or 1x1 ("4:4:4") against chroma's 1x1, one interleaved scan; luma with table set 0 (the gray encoder's), chroma with set 1:
+// the Annex K.2 chrominance quantiser scaled like the luminance one, the Annex K.3.3.2 / K.3.3.4 DC1 / AC1 Huffman tables.
+// A chroma DC code is up to 11 bits long (luma: 9), so a chroma block reaches 22 + 63 * 26 bits.
+enum { kColourHeaderBytes = 623, kEncMaxChromaBlockBits = 22 + 63 * 26 };
+
+// What the kernels of a scan read besides the pixels, gray or colour: two table sets (a gray scan uses set 0 alone) and the header
+// with its length.  About 3 KB: handed to the set-up kernel by value, under the 4 KB a kernel's arguments may take.
+struct ScanTables {
+    uint16_t divisor[2][64];               // quantiser steps << 3 in ZIGZAG order, luma / chroma
+    uint32_t dc[2][12];                    // (code << 8) | length of each DC category
+    uint32_t ac[2][256];                   // (code << 8) | length of each (run << 4 | size) symbol, 0 where Annex K has none
+    uint8_t header[kColourHeaderBytes + 1];// gray: EncTables::header; colour: SOI, APP0, DQT 0, DQT 1, SOF0, DHT DC0, AC0, DC1, AC1, SOS
+    uint32_t header_bytes;                 // kGrayHeaderBytes or kColourHeaderBytes
+};
+
+bool subsampling_ok(int hs, int vs);                       // 2x2, 2x1 or 1x1
+void chroma_quant_table(int quality, uint16_t out[64]);    // natural order, every entry 1..255
+void scan_tables_of(const EncTables& gray, ScanTables* t); // a gray scan: set 0 and the 328-byte header, everything else 0
+// width, height 1..65535, (hs, vs) as above.  Fills every byte of *t; returns kInvalid for a null pointer or an argument outside that.
+int colour_encoder_tables(int width, int height, int quality, int hs, int vs, ScanTables* t);
+// blocks of one image in coded order, the dummy luma blocks of partial MCUs included: MCUs x (hs * vs + 2)
+size_t colour_coded_blocks(int width, int height, int hs, int vs);
+// bits the scan of one image can reach at most: every luma block (dummies too) at kEncMaxBlockBits, every chroma block at
+// kEncMaxChromaBlockBits
+size_t colour_max_bits(int width, int height, int hs, int vs);
+// bytes a file can reach at most: header, colour_max_bits with every byte stuffed, EOI; a multiple of 16
+size_t colour_max_bytes(int width, int height, int hs, int vs);
+
 }  // namespace cvjpeg

@@ -25,4 +25,12 @@ size_t jpeg_encode_scratch_bytes(int n, int h, int w);
 hipError_t jpeg_encode_gray_u8(const uint8_t* src, int n, int h, int w, const cvjpeg::EncTables& tables, void* scratch, uint8_t* out,
                                int64_t* offsets, int32_t* lengths, hipStream_t s);
 
+// The colour encoder: n images (n, h, w, 3) uint8, R at byte `r_at` of a pixel (0: RGB, 2: BGR), luma sampled hs x vs (2x2, 2x1, 1x1) ->
+// n three-component files, libjpeg's byte for byte.  The same contract with cvjpeg::colour_max_bytes(w, h, hs, vs) per image in `out`
+// and jpeg_encode_colour_scratch_bytes of scratch; `tables` from cvjpeg::colour_encoder_tables.  A pass takes
+// min(n, kJpegEncChunkImages, max(1, kJpegEncChunkBlocks / coded blocks per image)) images, the dummy blocks of partial MCUs counted.
+size_t jpeg_encode_colour_scratch_bytes(int n, int h, int w, int hs, int vs);
+hipError_t jpeg_encode_colour_u8(const uint8_t* src, int n, int h, int w, int r_at, int hs, int vs, const cvjpeg::ScanTables& tables,
+                                 void* scratch, uint8_t* out, int64_t* offsets, int32_t* lengths, hipStream_t s);
+
 }  // namespace cv

@@ -711,6 +711,29 @@ int cv_jpeg_gray_max_bytes(int h, int w, size_t* bytes);
 int cv_jpeg_encode_gray_u8(cv_engine_t* eng, const uint8_t* src, int n, int h, int w, int quality, uint8_t* out, size_t out_capacity,
                            int64_t* offsets, int32_t* lengths, void* stream);
 
+/* ---- JPEG encode, colour: what libjpeg writes for an RGB image with its defaults, byte for byte --------------------------------
+ * (PIL.Image.fromarray(rgb).save(f, "JPEG", quality=q, subsampling=s); 4:2:0 is libjpeg's default and so cv2.imwrite's, which has not
+ * been run here): three components, jccolor.c's YCbCr, jcsample.c's plain box for chroma with libjpeg's edge padding, one interleaved
+ * scan, luma with the gray encoder's tables and chroma with the Annex K.2 quantiser and the K.3.3.2 / K.3.3.4 Huffman tables, a
+ * 623-byte header (SOI, APP0, DQT 0, DQT 1, SOF0, DHT DC0, AC0, DC1, AC1, SOS).  Smoothing, other sampling factors, optimised tables,
+ * progressive, restart markers, EXIF and ICC are not written. */
+#define CV_JPEG_COLOUR_HEADER_BYTES 623
+enum { CV_JPEG_SUB_444 = 0, CV_JPEG_SUB_422 = 1, CV_JPEG_SUB_420 = 2 };     /* luma sampled 1x1, 2x1, 2x2 against chroma's 1x1 */
+/* header: CV_JPEG_COLOUR_HEADER_BYTES bytes; qtables: 2 x 64 uint16 in natural order (luma, chroma), or NULL.  Host only, no engine.
+ * h, w: 1..65535. */
+int cv_jpeg_colour_header(int h, int w, int quality, int subsampling, uint8_t* header, uint16_t* qtables);
+/* The largest file an h x w image (1..4096 each) can give: header + every coded block -- the dummy luma blocks of partial MCUs
+ * included -- at 20 + 63 * 26 bits (luma) or 22 + 63 * 26 bits (chroma) with every byte stuffed + EOI, a multiple of 16. */
+int cv_jpeg_colour_max_bytes(int h, int w, int subsampling, size_t* bytes);
+/* src: DEVICE, (n, h, w, 3) uint8 in channel_order CV_JPEG_BGR / CV_JPEG_RGB (which only says which byte of a pixel is R), n >= 1, h
+ * and w 1..4096.  out: DEVICE, out_capacity >= n * cv_jpeg_colour_max_bytes(h, w, subsampling) bytes; offsets: DEVICE, n + 1 int64;
+ * lengths: DEVICE, n int32.  File i is the lengths[i] bytes at out + offsets[i]; offsets are multiples of 16 in input order and
+ * offsets[n] is the end of the last file rounded up.  Launches only, on `stream`; images are worked through in fixed chunks over the
+ * scratch the gray encoder uses (grown once per larger geometry), so n is unbounded, and gray and colour encodes of one engine are
+ * ordered on the device, whatever their streams.  The output is a pure function of pixels, order, subsampling and quality. */
+int cv_jpeg_encode_colour_u8(cv_engine_t* eng, const uint8_t* src, int n, int h, int w, int channel_order, int subsampling, int quality,
+                             uint8_t* out, size_t out_capacity, int64_t* offsets, int32_t* lengths, void* stream);
+
 /* MFMA lane-map self test: computes D = A(16xK) * B(Kx16) with the kernels' fragment loaders for both
  * precisions and returns the max abs error against a host reference (used by tests; 0 expected). */
 int cv_selftest_mfma(cv_engine_t* eng, float* max_err_f16, float* max_err_f32);
