@@ -930,6 +930,27 @@ class ChessVision:
         with torch.cuda.device(self.device):
             return model.engine.embedding_neighbours(queries, corpus, k, exclude_self)
 
+    def reduce_embeddings(self, table, method: str = "pacmap", n_neighbors=None, seed: int = 0, init="pca"):
+        """An embedding table reduced to 2-D for browsing -- what the reference asks 3LC for right after collecting the table
+        (``run.reduce_embeddings_by_foreign_table_url(..., method="pacmap")``).  ``table``: (N, C) host array or tensor, e.g.
+        ``embeddings.stack(results)[0]``; ``init``: "pca" or an (N, 2) array of starting coordinates.  Returns a ``Reduction``
+        (``coordinates`` (N, 2) float32, the pairs, the neighbour search's record).  ``chessvision/embeddings.py``: ``pacmap`` is the
+        definition, a reading of the paper and of the package's defaults.  With a HIP model plugged in the pairs and the optimiser
+        run on its engine, on the caller's current stream, and equal the numpy form bit for bit; otherwise the numpy form itself runs.
+        Only ``method="pacmap"`` exists."""
+        from . import embeddings as emb
+
+        if method != "pacmap":
+            raise ValueError(f"method must be 'pacmap', got {method!r}")
+        model = next((m for m in (self._classifier, self._board_extractor) if m is not None and self._native(m)), None)
+        if model is None:
+            return emb.pacmap(table, n_neighbors=n_neighbors, seed=seed, init=init)
+        pre, start = emb.pacmap_inputs(table, init)
+        with torch.cuda.device(self.device):
+            pairs = model.engine.pacmap_pairs(pre, n_neighbors, seed=seed)
+            coords = model.engine.pacmap_optimise(start, pairs)
+        return emb.Reduction(coords, pairs, int(pairs.neighbours.shape[1]), pairs.stats)
+
     def _pipeline_streams(self):
         """(host->device, device->host, compute) streams of ``process_images``, created once per instance."""
         if self._streams is None:

@@ -19,14 +19,17 @@ model objects that are not HIP models, and the host form of the neighbour search
 take forward hooks.
 
 What the table is collected for: the reference reduces it with ``run.reduce_embeddings_by_foreign_table_url(..., method="pacmap")``
-(``process_pipeline.py:351``, ``train_classifier.py:312``).  The PaCMAP reduction itself stays out of scope; the exact k-nearest-
-neighbour graph it (and UMAP) starts from is served: ``neighbours`` here is the definition and the checker in numpy,
-``HipEngine.embedding_neighbours`` / ``ChessVision.embedding_neighbours`` the device form, equal to it bit for bit.  ``stack`` turns
-``process_images(..., embeddings=True)`` results into the table, ``duplicate_groups`` answers "which uploads are near-duplicates".
+(``process_pipeline.py:351``, ``train_classifier.py:312``).  The exact k-nearest-neighbour graph it (and UMAP) starts from is served:
+``neighbours`` here is the definition and the checker in numpy, ``HipEngine.embedding_neighbours`` / ``ChessVision.embedding_neighbours``
+the device form, equal to it bit for bit.  ``stack`` turns ``process_images(..., embeddings=True)`` results into the table,
+``duplicate_groups`` answers "which uploads are near-duplicates".  The reduction itself is the last part of this file: ``pacmap`` is the
+definition in numpy (a reading of the paper and of the package's defaults, see there), ``HipEngine.pacmap_pairs`` /
+``HipEngine.pacmap_optimise`` / ``ChessVision.reduce_embeddings`` the device form, equal to it bit for bit.
 """
 from __future__ import annotations
 
 import dataclasses
+import math
 
 import numpy as np
 
@@ -282,3 +285,363 @@ def stack(results, which: str = "board_extractor"):
     if not rows:
         return np.zeros((0, 0), np.float32), np.zeros((0, 2), np.int32)
     return np.concatenate(rows, axis=0), np.asarray([k for ks in keys for k in ks], dtype=np.int32).reshape(-1, 2)
+
+
+# ---- PaCMAP: the definition (include/chessvision_hip.h: cv_pacmap_pairs, cv_pacmap_optimise) -----------------------------------------
+# A READING of Wang, Huang, Rudin, Shaposhnik, "Understanding How Dimension Reduction Tools Work" (JMLR 2021) and of the defaults of
+# the authors' ``pacmap`` package; no copy of the package is part of this project.  Where the reading departs from the package it says
+# so: the neighbour candidates are exact (no annoy) and at most MAX_NEIGHBOURS of them, the random draws come from a counter-based
+# generator (other numbers, the same distribution), the gradient is a gather in a fixed order (equal to the package's scatter up to the
+# order of float32 sums), and the Adam bias powers are running products.  DESIGN.md section 4 "Embedding reduction".
+PACMAP_MAX_NEIGHBOURS, PACMAP_MAX_MID_NEAR, PACMAP_MAX_FURTHER = 32, 16, 64      # csrc/pacmap.h
+PACMAP_PCA_DIMS = 100
+PACMAP_MID_NEAR_DRAWS = 6
+PACMAP_MAX_DRAWS = 1 << 16               # draws of one point in one stream; never reached with the argument rules below
+PACMAP_MAX_ROWS = 1 << 22                # kNeighbourMaxRows
+PACMAP_ITERATIONS = 450
+PACMAP_KIND_SHIFT = 28                   # an incidence entry: other point | kind << 28 (0 neighbour, 1 mid-near, 2 further)
+_U64 = np.uint64
+
+
+@dataclasses.dataclass
+class PacmapPairs:
+    """``neighbours`` (N, n_neighbors), ``mid_near`` (N, n_MN), ``further`` (N, n_FP): int32 partners of every point; ``stats``: the
+    neighbour search's record plus ``mid_near_draws`` and ``further_draws`` (rejected draws included) and ``candidates`` (kc)."""
+    neighbours: np.ndarray
+    mid_near: np.ndarray
+    further: np.ndarray
+    stats: dict
+
+
+@dataclasses.dataclass
+class Reduction:
+    """``coordinates`` (N, 2) float32; ``pairs``: the ``PacmapPairs`` they were optimised over; ``n_neighbors``; ``stats`` = pairs.stats."""
+    coordinates: np.ndarray
+    pairs: PacmapPairs
+    n_neighbors: int
+    stats: dict
+
+
+def pacmap_mix(x) -> np.ndarray:
+    """The splitmix64 finaliser on uint64 arrays (wrapping arithmetic)."""
+    x = np.atleast_1d(np.asarray(x, dtype=np.uint64))
+    with np.errstate(over="ignore"):
+        x = x + _U64(0x9E3779B97F4A7C15)
+        x = (x ^ (x >> _U64(30))) * _U64(0xBF58476D1CE4E5B9)
+        x = (x ^ (x >> _U64(27))) * _U64(0x94D049BB133111EB)
+        return x ^ (x >> _U64(31))
+
+
+def pacmap_key(seed: int, stream: int, i) -> np.ndarray:
+    """``mix(seed ^ mix((stream << 40) | i))`` for an array of points i."""
+    i = np.atleast_1d(np.asarray(i)).astype(np.uint64)
+    return pacmap_mix(_U64(int(seed) & 0xFFFFFFFFFFFFFFFF) ^ pacmap_mix(_U64(int(stream) << 40) | i))
+
+
+def pacmap_draw(key, t, n: int) -> np.ndarray:
+    """Draw number t of the points whose keys are given: ``((mix(key + t) >> 32) * n) >> 32``, an index in [0, n)."""
+    with np.errstate(over="ignore"):
+        x = pacmap_mix(np.asarray(key, np.uint64) + np.asarray(t, np.uint64))
+        return (((x >> _U64(32)) * _U64(int(n))) >> _U64(32)).astype(np.int64)
+
+
+def pacmap_default_neighbours(n: int) -> int:
+    return 10 if n < 10000 else int(round(10 + 15 * (math.log10(n) - 4)))
+
+
+def check_pacmap_arguments(n: int, n_neighbors=None, n_MN=None, n_FP=None) -> tuple[int, int, int, int]:
+    """The argument rules both forms share -> ``(n_neighbors, n_MN, n_FP, kc)`` with the defaults filled in; kc is the number of
+    exact candidates the scaled-distance choice looks at."""
+    n = int(n)
+    nn = pacmap_default_neighbours(n) if n_neighbors is None else int(n_neighbors)
+    if not 1 <= nn <= PACMAP_MAX_NEIGHBOURS:
+        raise ValueError(f"n_neighbors must be in [1, {PACMAP_MAX_NEIGHBOURS}], got {nn}" +
+                         (f" (the default for {n} rows)" if n_neighbors is None else ""))
+    nmn = int(round(0.5 * nn)) if n_MN is None else int(n_MN)
+    nfp = int(round(2 * nn)) if n_FP is None else int(n_FP)
+    if not 0 <= nmn <= PACMAP_MAX_MID_NEAR:
+        raise ValueError(f"n_MN must be in [0, {PACMAP_MAX_MID_NEAR}], got {nmn}")
+    if not 0 <= nfp <= PACMAP_MAX_FURTHER:
+        raise ValueError(f"n_FP must be in [0, {PACMAP_MAX_FURTHER}], got {nfp}")
+    least = max(7, PACMAP_MID_NEAR_DRAWS + nmn, nn + nfp + 1)
+    if n < least:
+        raise ValueError(f"n_neighbors={nn}, n_MN={nmn}, n_FP={nfp} need at least {least} rows, the table has {n}")
+    if n > PACMAP_MAX_ROWS:
+        raise ValueError(f"the table has {n} rows, the neighbour search takes at most {PACMAP_MAX_ROWS}")
+    if 2 * n * (nn + nmn + nfp) >= 1 << 31:
+        raise ValueError(f"{n} rows with {nn + nmn + nfp} pairs each: the incidence lists' int32 offsets overflow")
+    return nn, nmn, nfp, min(nn + 50, MAX_NEIGHBOURS, n - 1)
+
+
+def _finite_table(a, name: str) -> np.ndarray:
+    a = _table(a, name)
+    if not np.isfinite(a).all():
+        raise ValueError(f"{name} holds a NaN or an infinity")
+    return a
+
+
+def _principal_axes(centred: np.ndarray, dims: int) -> np.ndarray:
+    """(C, dims) float64: eigenvectors of the covariance by descending eigenvalue, each flipped so that its largest-magnitude
+    component is positive."""
+    cov = centred.T @ centred / max(1, centred.shape[0] - 1)
+    w, v = np.linalg.eigh(cov)
+    axes = v[:, np.argsort(-w, kind="stable")[:dims]]
+    top = np.abs(axes).argmax(axis=0)
+    return axes * np.where(axes[top, np.arange(axes.shape[1])] < 0, -1.0, 1.0)
+
+
+def pacmap_preprocess(table) -> np.ndarray:
+    """(N, C) -> float32 (N, C'): more than 100 channels are centred and projected onto the 100 leading principal axes; otherwise
+    the table is shifted by its global minimum, divided by its global maximum (where that is not zero) and centred.  float64 on the
+    host; the result is an INPUT of both forms, so nothing downstream depends on LAPACK's rounding."""
+    x = _finite_table(table, "table").astype(np.float64)
+    if x.shape[1] > PACMAP_PCA_DIMS:
+        x = x - x.mean(axis=0)
+        x = x @ _principal_axes(x, PACMAP_PCA_DIMS)
+    else:
+        x = x - x.min()
+        top = x.max()
+        if top > 0:
+            x = x / top
+        x = x - x.mean(axis=0)
+    return np.ascontiguousarray(x, dtype=np.float32)
+
+
+def pacmap_init(pre, projected: bool = False) -> np.ndarray:
+    """float32 (N, 2): 0.01 x the first two columns of ``pre`` when ``pacmap_preprocess`` projected (``projected=True``: the table had
+    more than 100 channels), otherwise 0.01 x the two leading principal axes of ``pre`` by the same rule.  A one-channel table gets
+    a zero second coordinate."""
+    x = _finite_table(pre, "pre").astype(np.float64)
+    if not projected:
+        x = x - x.mean(axis=0)
+        x = x @ _principal_axes(x, 2)
+    y = np.zeros((x.shape[0], 2), np.float64)
+    y[:, :min(2, x.shape[1])] = 0.01 * x[:, :2]
+    return y.astype(np.float32)
+
+
+def _pacmap_scaled_choice(idx: np.ndarray, d: np.ndarray, nn: int) -> np.ndarray:
+    """Row i keeps the nn candidates with the smallest ``(D_ij / (sigma_i * sigma_j), j)``; sigma = max(mean of sqrt(D) at candidate
+    ranks 3, 4, 5, 1e-10), summed in rank order in float64."""
+    kc = idx.shape[1]
+    root = np.sqrt(d)
+    if kc > 3:
+        hi = min(kc, 6)
+        s = root[:, 3].copy()
+        for r in range(4, hi):
+            s = s + root[:, r]
+        sigma = s / float(hi - 3)
+    else:
+        sigma = root[:, kc - 1].copy()
+    sigma = np.maximum(sigma, 1e-10)
+    scaled = d / (sigma[:, None] * sigma[idx])
+    order = np.lexsort((idx, scaled), axis=1)[:, :nn]
+    return np.take_along_axis(idx, order, axis=1).astype(np.int32)
+
+
+def _pacmap_draw_until(key, t, n: int, want: int, forbidden: np.ndarray, what: str) -> np.ndarray:
+    """Every point draws until it holds ``want`` distinct indices that are not itself and not in its row of ``forbidden`` (N, F);
+    ``t`` (N,) uint64, the points' draw counters, moves on.  -> held (N, want) int64, in the order drawn."""
+    rows = key.shape[0]
+    held = np.full((rows, want), -1, np.int64)
+    count = np.zeros(rows, np.int64)
+    while True:
+        a = np.flatnonzero(count < want)
+        if a.size == 0:
+            return held
+        if (t[a] >= _U64(PACMAP_MAX_DRAWS)).any():
+            raise RuntimeError(f"pacmap: a point drew {PACMAP_MAX_DRAWS} {what} candidates without filling its list")
+        j = pacmap_draw(key[a], t[a], n)
+        t[a] += _U64(1)
+        ok = (j != a) & ~(held[a] == j[:, None]).any(axis=1) & ~(forbidden[a] == j[:, None]).any(axis=1)
+        sel = a[ok]
+        held[sel, count[sel]] = j[ok]
+        count[sel] += 1
+
+
+def pacmap_pairs(pre, n_neighbors=None, n_MN=None, n_FP=None, seed: int = 0) -> PacmapPairs:
+    """The three pair sets of a preprocessed table, in numpy -- the definition the device form is held to exactly.
+
+    Neighbours: the exact graph of ``pre`` (``neighbours``, kc = min(n_neighbors + 50, 64, N - 1) candidates) re-ranked by the
+    scaled distance.  Mid-near (stream 1), slot by slot: draw until six distinct indices are held that are neither i nor an earlier
+    mid-near partner of i; the partner is the SECOND smallest by ``(D(i, .), j)``.  Further (stream 2): draw until n_FP distinct
+    indices are held that are neither i nor in i's neighbour row.  Draw t of point i in a stream is ``pacmap_draw(pacmap_key(seed,
+    stream, i), t, N)``; t counts every draw, rejected ones included."""
+    x = _finite_table(pre, "pre")
+    n = x.shape[0]
+    nn, nmn, nfp, kc = check_pacmap_arguments(n, n_neighbors, n_MN, n_FP)
+    graph = neighbours(x, k=kc)
+    nbr = _pacmap_scaled_choice(graph.indices.astype(np.int64), graph.sq_distances, nn)
+
+    x64 = x.astype(np.float64)
+    rows = np.arange(n)
+    key = pacmap_key(seed, 1, rows)
+    t = np.zeros(n, np.uint64)
+    mid = np.full((n, nmn), -1, np.int64)
+    for slot in range(nmn):
+        held = _pacmap_draw_until(key, t, n, PACMAP_MID_NEAR_DRAWS, mid[:, :slot], "mid-near")
+        d = np.zeros(held.shape, np.float64)
+        for ch in range(x.shape[1]):                          # D of neighbours(): ascending channel, product and sum each rounded
+            diff = x64[:, ch, None] - x64[held, ch]
+            d += diff * diff
+        mid[:, slot] = held[rows, np.lexsort((held, d), axis=1)[:, 1]]
+    mid_draws = int(t.sum())
+
+    t = np.zeros(n, np.uint64)
+    far = _pacmap_draw_until(pacmap_key(seed, 2, rows), t, n, nfp, nbr, "further")
+    stats = dict(graph.stats, candidates=kc, mid_near_draws=mid_draws, further_draws=int(t.sum()))
+    return PacmapPairs(nbr, mid.astype(np.int32), far.astype(np.int32), stats)
+
+
+def pacmap_incidence(pairs: PacmapPairs, mid_near: bool = True) -> tuple[np.ndarray, np.ndarray]:
+    """The incident entries of every point as a CSR structure -> ``(offsets (N + 1,) int32, entries int32)``, an entry being
+    ``other | kind << 28``.  Point p's list: its own neighbour pairs by slot, its own mid-near pairs, its own further pairs, then the
+    entries where p is another point's partner, ordered by (kind, source point, slot).  ``mid_near=False`` leaves the mid-near
+    entries out and keeps the order of the rest (the lists of iterations 200 and later)."""
+    kinds = [np.asarray(pairs.neighbours), np.asarray(pairs.mid_near), np.asarray(pairs.further)]
+    if not mid_near:
+        kinds[1] = kinds[1][:, :0]
+    n = kinds[0].shape[0]
+    own = np.concatenate([a.astype(np.int64) | (k << PACMAP_KIND_SHIFT) for k, a in enumerate(kinds)], axis=1)
+    per = own.shape[1]
+    dst = np.concatenate([a.astype(np.int64).ravel() for a in kinds])                  # (kind, source, slot) order already
+    src = np.concatenate([np.repeat(np.arange(n, dtype=np.int64), a.shape[1]) | (k << PACMAP_KIND_SHIFT) for k, a in enumerate(kinds)])
+    if dst.size and (dst.min() < 0 or dst.max() >= n):
+        raise ValueError("pacmap_incidence: a partner index lies outside the table")
+    order = np.argsort(dst, kind="stable")
+    incoming = np.bincount(dst, minlength=n)
+    offsets = np.concatenate([[0], np.cumsum(per + incoming)])
+    if offsets[-1] >= 1 << 31:
+        raise ValueError("pacmap_incidence: the int32 offsets overflow")
+    entries = np.empty(int(offsets[-1]), np.int32)
+    entries[(offsets[:-1, None] + np.arange(per)).ravel()] = own.ravel()
+    first = np.cumsum(incoming) - incoming
+    at = dst[order]
+    entries[offsets[:-1][at] + per + np.arange(dst.size) - first[at]] = src[order]
+    return offsets.astype(np.int32), entries
+
+
+def pacmap_schedule(iterations: int = PACMAP_ITERATIONS) -> np.ndarray:
+    """(iterations, 4) float32 rows ``(lr_t, w_n, w_MN, w_FP)``: float64 on the host, rounded once.  ``lr_t = sqrt(1 - b2) / (1 - b1)``
+    with b1 = 0.9^(it+1) and b2 = 0.999^(it+1) as running products (``b *= beta`` per iteration: the same bits in every language)."""
+    out = np.empty((int(iterations), 4), np.float64)
+    b1 = b2 = 1.0
+    for it in range(int(iterations)):
+        b1 *= 0.9
+        b2 *= 0.999
+        if it < 100:
+            w = (2.0, (1.0 - it / 100.0) * 1000.0 + (it / 100.0) * 3.0, 1.0)
+        elif it < 200:
+            w = (3.0, 3.0, 1.0)
+        else:
+            w = (1.0, 0.0, 1.0)
+        out[it] = (math.sqrt(1.0 - b2) / (1.0 - b1),) + w
+    return out.astype(np.float32)
+
+
+class _PacmapWalk:
+    """The incidence lists laid out for numpy: points sorted by descending list length, so that the points that still have an entry
+    at position ``pos`` are a prefix, and per position the other point, the kind and the kind's constants of every such point."""
+
+    def __init__(self, offsets: np.ndarray, entries: np.ndarray):
+        f32 = np.float32
+        lens = np.diff(offsets.astype(np.int64))
+        self.perm = np.argsort(-lens, kind="stable")
+        sorted_lens = lens[self.perm]
+        start = offsets.astype(np.int64)[self.perm]
+        add = np.array([10.0, 10000.0, 1.0], f32)
+        num = np.array([20.0, 20000.0, 2.0], f32)
+        sign = np.array([1.0, 1.0, -1.0], f32)
+        self.steps = []
+        for pos in range(int(sorted_lens.max()) if lens.size else 0):
+            r = int(np.searchsorted(-sorted_lens, -pos, side="left"))     # points with more than pos entries
+            e = entries[start[:r] + pos]
+            kind = e >> PACMAP_KIND_SHIFT
+            self.steps.append((r, e & ((1 << PACMAP_KIND_SHIFT) - 1), kind, add[kind], num[kind], sign[kind]))
+
+    def gradient(self, y: np.ndarray, weights) -> np.ndarray:
+        """(N, 2) float32 gradient of every point at coordinates y, every operation rounded once to float32, entries in list order."""
+        f32 = np.float32
+        wk = np.asarray(weights, f32)
+        ys = y[self.perm]
+        y0, y1, s0, s1 = y[:, 0], y[:, 1], ys[:, 0].copy(), ys[:, 1].copy()
+        g0, g1 = np.zeros(y.shape[0], f32), np.zeros(y.shape[0], f32)
+        for r, other, kind, add, num, sign in self.steps:
+            e0 = s0[:r] - y0[other]
+            e1 = s1[:r] - y1[other]
+            d = f32(1.0) + e0 * e0
+            d = d + e1 * e1
+            t = add + d
+            w = wk[kind] * (num / (t * t))
+            g0[:r] = g0[:r] + sign * (w * e0)                 # g - x and g + (-x) are the same float32
+            g1[:r] = g1[:r] + sign * (w * e1)
+        g = np.empty_like(y)
+        g[self.perm, 0], g[self.perm, 1] = g0, g1
+        return g
+
+
+def pacmap_trajectory(init, pairs: PacmapPairs, keep=(PACMAP_ITERATIONS,)) -> dict:
+    """``{iterations: coordinates}`` for every count in ``keep``, from ONE run of max(keep) iterations: the state after k iterations
+    does not depend on how many follow.  ``pacmap_optimise`` is the last of them."""
+    y = np.ascontiguousarray(np.asarray(init, np.float32)).copy()
+    n = np.asarray(pairs.neighbours).shape[0]
+    if y.shape != (n, 2) or not np.isfinite(y).all():
+        raise ValueError(f"init must be a finite ({n}, 2) array, got shape {y.shape}")
+    keep = sorted(int(k) for k in keep)
+    if not keep or keep[0] < 0:
+        raise ValueError("iteration counts must be non-negative")
+    f32 = np.float32
+    schedule = pacmap_schedule(keep[-1])
+    c1, c2, eps = f32(1.0 - 0.9), f32(1.0 - 0.999), f32(1e-7)
+    m, v = np.zeros_like(y), np.zeros_like(y)
+    walks = {}
+    out = {0: y.copy()} if keep[0] == 0 else {}
+    with np.errstate(all="ignore"):
+        for it in range(keep[-1]):
+            lr, w_n, w_mn, w_fp = schedule[it]
+            with_mid = it < 200
+            if with_mid not in walks:
+                walks[with_mid] = _PacmapWalk(*pacmap_incidence(pairs, with_mid))
+            g = walks[with_mid].gradient(y, (w_n, w_mn, w_fp))
+            m = m + c1 * (g - m)
+            v = v + c2 * (g * g - v)
+            y = y - (lr * m) / (np.sqrt(v) + eps)
+            if it + 1 in keep:
+                out[it + 1] = y.copy()
+    return out
+
+
+def pacmap_optimise(init, pairs: PacmapPairs, iterations: int = PACMAP_ITERATIONS) -> np.ndarray:
+    """(N, 2) float32 coordinates after ``iterations`` Adam steps from ``init`` -- the definition the device form is held to bit for
+    bit.  Per iteration every point gathers over its incidence list (``pacmap_incidence``) at the PREVIOUS iteration's coordinates:
+
+        e = Y[p] - Y[q];  d = 1;  d = d + e0*e0;  d = d + e1*e1
+        neighbour:  t = 10 + d;     w = w_n  * (20    / (t*t));  g = g + w*e
+        mid-near:   t = 10000 + d;  w = w_MN * (20000 / (t*t));  g = g + w*e        (left out from iteration 200 on, w_MN = 0)
+        further:    t = 1 + d;      w = w_FP * (2     / (t*t));  g = g - w*e
+        m = m + c1*(g - m);  v = v + c2*(g*g - v);  Y = Y - (lr_t*m) / (sqrt(v) + 1e-7)
+
+    in float32, one rounding per operation; ``pacmap_schedule`` holds lr_t and the weights."""
+    return pacmap_trajectory(init, pairs, (int(iterations),))[int(iterations)]
+
+
+def pacmap(table, n_neighbors=None, n_MN=None, n_FP=None, seed: int = 0, init="pca", iterations: int = PACMAP_ITERATIONS) -> Reduction:
+    """The whole reduction in numpy: preprocess, pairs, initialise (``init="pca"`` or an (N, 2) array), optimise."""
+    pre, start = pacmap_inputs(table, init)
+    pairs = pacmap_pairs(pre, n_neighbors, n_MN, n_FP, seed)
+    coords = pacmap_optimise(start, pairs, iterations)
+    return Reduction(coords, pairs, int(pairs.neighbours.shape[1]), pairs.stats)
+
+
+def pacmap_inputs(table, init="pca") -> tuple[np.ndarray, np.ndarray]:
+    """``(pre, start)``: the two host arrays both forms start from."""
+    x = _finite_table(table, "table")
+    pre = pacmap_preprocess(x)
+    if isinstance(init, str):
+        if init != "pca":
+            raise ValueError(f"init must be 'pca' or an (N, 2) array, got {init!r}")
+        return pre, pacmap_init(pre, projected=x.shape[1] > PACMAP_PCA_DIMS)
+    start = np.ascontiguousarray(np.asarray(init.detach().cpu() if hasattr(init, "detach") else init), dtype=np.float32)
+    if start.shape != (x.shape[0], 2) or not np.isfinite(start).all():
+        raise ValueError(f"init must be 'pca' or a finite ({x.shape[0]}, 2) array, got shape {start.shape}")
+    return pre, start

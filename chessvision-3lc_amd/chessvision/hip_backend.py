@@ -156,10 +156,22 @@ SYMBOLS = [
     ("cv_jpeg_encode_colour_u8", _i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, ctypes.c_size_t, _vp, _vp, _vp]),
     ("cv_embedding_neighbours_scratch_bytes", ctypes.c_size_t, [_i, _i, _i, _i]),
     ("cv_embedding_neighbours", _i, [_vp, _vp, _i, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, ctypes.c_size_t, _vp]),
+    ("cv_pacmap_plan", _i, [_i, _i, _i, _i, _i, _vp]),
+    ("cv_pacmap_pairs", _i, [_vp, _vp, _i, _i, _i, _i, _i, ctypes.c_uint64, _vp, _vp, _vp, _vp, _vp, ctypes.c_size_t, _vp]),
+    ("cv_pacmap_optimise", _i, [_vp, _vp, _i, _vp, _vp, ctypes.c_int64, _i, _vp, _vp, ctypes.c_size_t, _vp]),
 ]
 NEIGHBOURS_EXCLUDE_SELF, NEIGHBOURS_EXACT_ONLY = 1, 2
 # cv_neighbour_stats_t (include/chessvision_hip.h): eight int32
 NEIGHBOUR_STATS = ("query_rows", "certified_rows", "exact_rows", "nonfinite_query_rows", "nonfinite_corpus_rows")
+# cv_pacmap_stats_t: the neighbour record, then two int64 and two int32
+PACMAP_STATS = np.dtype({"names": ["neighbours", "mid_near_draws", "further_draws", "draw_overflow", "candidates"],
+                         "formats": [("<i4", (8,)), "<i8", "<i8", "<i4", "<i4"], "offsets": [0, 32, 40, 48, 52], "itemsize": 64})
+
+
+class PacmapPlan(ctypes.Structure):
+    """cv_pacmap_plan_t"""
+    _fields_ = [(name, ctypes.c_int32) for name in ("n", "c", "n_neighbors", "n_mn", "n_fp", "candidates")] + \
+               [("pairs_scratch_bytes", ctypes.c_uint64), ("optimise_scratch_bytes", ctypes.c_uint64)]
 
 # cv_score_record_t (include/chessvision_hip.h): one 64-byte record per image
 SCORE_RECORD = np.dtype({"names": ["hist", "above_half", "n_nan", "top_sum", "top_count", "reserved"],
@@ -848,6 +860,88 @@ class HipEngine:
         indices, dist, stats = self.embedding_neighbours_dev(a, b, int(k), exclude_self, exact_only)
         record = stats.cpu().numpy()
         return Neighbours(indices.cpu().numpy(), dist.cpu().numpy(), {name: int(record[i]) for i, name in enumerate(NEIGHBOUR_STATS)})
+
+    def pacmap_plan(self, n: int, c: int, n_neighbors: int, n_mn: int, n_fp: int) -> PacmapPlan:
+        """``cv_pacmap_plan``: the limits checked, kc and the two scratch sizes."""
+        plan = PacmapPlan()
+        _check(self._lib.cv_pacmap_plan(int(n), int(c), int(n_neighbors), int(n_mn), int(n_fp), ctypes.byref(plan)))
+        return plan
+
+    def pacmap_pairs_dev(self, pre: torch.Tensor, n_neighbors: int, n_mn: int, n_fp: int, seed: int = 0):
+        """The device half of ``pacmap_pairs`` (``cv_pacmap_pairs``): ``pre`` (N, C), a dense finite float32 tensor on this device, ->
+        ``(neighbours (N, n_neighbors), mid_near (N, n_mn), further (N, n_fp), stats (64,) uint8)`` device tensors, the pair sets
+        int32.  Launched on the current stream; the scratch comes from the caching allocator on that stream.  Nothing is
+        synchronised or copied."""
+        if not isinstance(pre, torch.Tensor) or pre.dtype != torch.float32 or pre.device != self.device or pre.dim() != 2 \
+                or not pre.is_contiguous():
+            raise HipBackendError("pacmap_pairs expects pre as a dense (rows, channels) float32 tensor on the engine's device")
+        n, c = (int(v) for v in pre.shape)
+        plan = self.pacmap_plan(n, c, n_neighbors, n_mn, n_fp)
+        need = int(plan.pairs_scratch_bytes)
+        with torch.cuda.device(self.device):
+            scratch = torch.empty(max(need, 16), dtype=torch.uint8, device=self.device)
+            nbr, mid, far = (torch.empty((n, int(k)), dtype=torch.int32, device=self.device) for k in (n_neighbors, n_mn, n_fp))
+            stats = torch.empty(64, dtype=torch.uint8, device=self.device)
+            _check(self._lib.cv_pacmap_pairs(self._h, _ptr(pre), n, c, int(n_neighbors), int(n_mn), int(n_fp),
+                                             int(seed) & 0xFFFFFFFFFFFFFFFF, _ptr(nbr), _ptr(mid) if n_mn else None,
+                                             _ptr(far) if n_fp else None, _ptr(stats), _ptr(scratch), need, _stream_ptr(self.device)))
+        return nbr, mid, far, stats
+
+    def pacmap_pairs(self, pre, n_neighbors=None, n_MN=None, n_FP=None, seed: int = 0):
+        """``chessvision.embeddings.pacmap_pairs`` on the device, index for index: a host array or tensor in (moved to the device if
+        need be), a ``PacmapPairs`` of numpy arrays out.  Synchronises the current stream."""
+        from .embeddings import PacmapPairs, _finite_table, check_pacmap_arguments
+
+        if isinstance(pre, torch.Tensor):
+            pre = pre.to(self.device, torch.float32).contiguous()
+            if pre.dim() != 2 or pre.shape[0] < 1 or pre.shape[1] < 1:
+                raise ValueError(f"pre must be a (rows, channels) table, got shape {tuple(pre.shape)}")
+            if not bool(torch.isfinite(pre).all()):
+                raise ValueError("pre holds a NaN or an infinity")
+        else:
+            pre = torch.tensor(_finite_table(pre, "pre")).to(self.device)          # a copy: the caller's array may be read-only
+        nn, nmn, nfp, kc = check_pacmap_arguments(pre.shape[0], n_neighbors, n_MN, n_FP)
+        nbr, mid, far, stats = self.pacmap_pairs_dev(pre, nn, nmn, nfp, seed)
+        record = stats.cpu().numpy().view(PACMAP_STATS)[0]
+        if int(record["draw_overflow"]):
+            raise RuntimeError("pacmap: a point gave up drawing candidates without filling its list")
+        out = {name: int(record["neighbours"][i]) for i, name in enumerate(NEIGHBOUR_STATS)}
+        out.update(candidates=int(record["candidates"]), mid_near_draws=int(record["mid_near_draws"]),
+                   further_draws=int(record["further_draws"]))
+        return PacmapPairs(nbr.cpu().numpy(), mid.cpu().numpy(), far.cpu().numpy(), out)
+
+    def pacmap_optimise_dev(self, init: torch.Tensor, offsets: torch.Tensor, entries: torch.Tensor, iterations: int = 450) -> torch.Tensor:
+        """The device half of ``pacmap_optimise`` (``cv_pacmap_optimise``): ``init`` (N, 2) float32, ``offsets`` (N + 1,) and
+        ``entries`` int32 (``embeddings.pacmap_incidence``), dense tensors on this device, -> the (N, 2) float32 coordinates after
+        ``iterations`` steps, one launch each on the current stream.  Nothing is synchronised or copied."""
+        n = int(init.shape[0]) if isinstance(init, torch.Tensor) and init.dim() == 2 else 0
+        for name, t, dtype, shape in (("init", init, torch.float32, (n, 2)), ("offsets", offsets, torch.int32, (n + 1,)),
+                                      ("entries", entries, torch.int32, None)):
+            if not isinstance(t, torch.Tensor) or t.dtype != dtype or t.device != self.device or not t.is_contiguous() \
+                    or (shape is not None and tuple(t.shape) != shape) or t.dim() != (1 if shape is None else len(shape)) or n < 1:
+                raise HipBackendError(f"pacmap_optimise expects {name} as a dense {dtype} tensor on the engine's device, init (N, 2), "
+                                      "offsets (N + 1,), entries (E,)")
+        need = int(self.pacmap_plan(n, 1, 1, 0, 0).optimise_scratch_bytes)    # depends on n alone
+        with torch.cuda.device(self.device):
+            scratch = torch.empty(max(need, 16), dtype=torch.uint8, device=self.device)
+            out = torch.empty((n, 2), dtype=torch.float32, device=self.device)
+            _check(self._lib.cv_pacmap_optimise(self._h, _ptr(init), n, _ptr(offsets), _ptr(entries), int(entries.numel()), int(iterations),
+                                                _ptr(out), _ptr(scratch), need, _stream_ptr(self.device)))
+        return out
+
+    def pacmap_optimise(self, init, pairs, iterations: int = 450) -> np.ndarray:
+        """``chessvision.embeddings.pacmap_optimise`` on the device, bit for bit: the incidence lists are built on the host with the
+        definition's own stable sort (``embeddings.pacmap_incidence``), uploaded, and walked by one launch per iteration.
+        Synchronises the current stream."""
+        from .embeddings import pacmap_incidence
+
+        start = np.ascontiguousarray(np.asarray(init.detach().cpu() if isinstance(init, torch.Tensor) else init), dtype=np.float32)
+        n = int(np.asarray(pairs.neighbours).shape[0])
+        if start.shape != (n, 2) or not np.isfinite(start).all():
+            raise ValueError(f"init must be a finite ({n}, 2) array, got shape {start.shape}")
+        offsets, entries = pacmap_incidence(pairs)
+        dev = [torch.tensor(a).to(self.device) for a in (start, offsets, entries)]
+        return self.pacmap_optimise_dev(*dev, iterations=int(iterations)).cpu().numpy()
 
     def extraction_scores_dev(self, values: torch.Tensor, transform: str = "none", want_mask: bool = False):
         """The device half of ``extraction_scores``: launches the score kernel on the current stream behind whatever produced

@@ -17,6 +17,7 @@
 #include "jpeg_enc_device.h"
 #include "models.h"
 #include "neighbours.h"
+#include "pacmap.h"
 #include "pipeline.h"
 #include "pointwise.h"
 
@@ -39,6 +40,10 @@ static_assert(sizeof(cv_neighbour_stats_t) == sizeof(cv::NeighbourStats) && size
               offsetof(cv_neighbour_stats_t, nonfinite_corpus_rows) == offsetof(cv::NeighbourStats, nonfinite_corpus_rows) &&
               (int)CV_NEIGHBOURS_EXCLUDE_SELF == (int)cv::kNeighbourExcludeSelf && (int)CV_NEIGHBOURS_EXACT_ONLY == (int)cv::kNeighbourExactOnly,
               "cv_neighbour_stats_t is the kernels' record");
+static_assert(sizeof(cv_pacmap_stats_t) == sizeof(cv::PacmapStats) && sizeof(cv_pacmap_stats_t) == 64 &&
+              offsetof(cv_pacmap_stats_t, mid_near_draws) == offsetof(cv::PacmapStats, mid_near_draws) &&
+              offsetof(cv_pacmap_stats_t, candidates) == offsetof(cv::PacmapStats, candidates),
+              "cv_pacmap_stats_t is the kernels' record");
 static_assert(sizeof(cv_square_score_t) == 24 && sizeof(cv_board_score_t) == 64, "layouts the Python binding mirrors");
 
 using namespace cv;
@@ -1628,6 +1633,77 @@ int cv_embedding_neighbours(cv_engine_t* eng, const float* queries, int q, const
     });
 }
 
+// ---- embedding reduction: PaCMAP (pacmap.hip) ---------------------------------------------------------------------------------------
+static Status pacmap_limits(const std::string& me, int n, int c, int n_neighbors, int n_mn, int n_fp) {
+    if (n_neighbors < 1 || n_neighbors > kPacmapMaxNeighbours)
+        return fail(CV_ERR_INVALID, me + "n_neighbors must be in [1, 32], got " + std::to_string(n_neighbors));
+    if (n_mn < 0 || n_mn > kPacmapMaxMidNear) return fail(CV_ERR_INVALID, me + "n_mn must be in [0, 16], got " + std::to_string(n_mn));
+    if (n_fp < 0 || n_fp > kPacmapMaxFurther) return fail(CV_ERR_INVALID, me + "n_fp must be in [0, 64], got " + std::to_string(n_fp));
+    if (c < 1 || c > kNeighbourMaxC) return fail(CV_ERR_INVALID, me + "c must be in [1, 4096], got " + std::to_string(c));
+    if (!pacmap_in_limits(n, c, n_neighbors, n_mn, n_fp))
+        return fail(CV_ERR_INVALID, me + "n must be at least max(7, 6 + n_mn, n_neighbors + n_fp + 1) and at most 2^22, with 2 n (n_neighbors + "
+                                         "n_mn + n_fp) below 2^31, got " + std::to_string(n));
+    return Status();
+}
+
+int cv_pacmap_plan(int n, int c, int n_neighbors, int n_mn, int n_fp, cv_pacmap_plan_t* plan) {
+    return guarded("cv_pacmap_plan", [&]() -> Status {
+        if (!plan) return fail(CV_ERR_INVALID, "cv_pacmap_plan: plan is null");
+        CV_TRY(pacmap_limits("cv_pacmap_plan: ", n, c, n_neighbors, n_mn, n_fp));
+        const PacmapPlan p = pacmap_plan(n, c, n_neighbors, n_mn, n_fp);
+        *plan = cv_pacmap_plan_t{n, c, n_neighbors, n_mn, n_fp, p.kc, (uint64_t)p.pairs_bytes, (uint64_t)p.optimise_bytes};
+        return Status();
+    });
+}
+
+int cv_pacmap_pairs(cv_engine_t* eng, const float* pre, int n, int c, int n_neighbors, int n_mn, int n_fp, uint64_t seed,
+                    int32_t* neighbours, int32_t* mid_near, int32_t* further, cv_pacmap_stats_t* stats, void* scratch,
+                    size_t scratch_bytes, void* stream) {
+    return guarded("cv_pacmap_pairs", [&]() -> Status {
+        CV_TRY(check_engine(eng));
+        const std::string me = "cv_pacmap_pairs: ";
+        CV_TRY(pacmap_limits(me, n, c, n_neighbors, n_mn, n_fp));
+        if (!pre || ((uintptr_t)pre & 3u)) return fail(CV_ERR_INVALID, me + "pre must be a 4-byte aligned device pointer");
+        if (!neighbours || ((uintptr_t)neighbours & 3u)) return fail(CV_ERR_INVALID, me + "neighbours must be a 4-byte aligned device pointer");
+        if ((n_mn && !mid_near) || ((uintptr_t)mid_near & 3u)) return fail(CV_ERR_INVALID, me + "mid_near must be a 4-byte aligned device pointer");
+        if ((n_fp && !further) || ((uintptr_t)further & 3u)) return fail(CV_ERR_INVALID, me + "further must be a 4-byte aligned device pointer");
+        if ((uintptr_t)stats & 7u) return fail(CV_ERR_INVALID, me + "stats must be 8-byte aligned");
+        const size_t need = pacmap_plan(n, c, n_neighbors, n_mn, n_fp).pairs_bytes;
+        if (!scratch || ((uintptr_t)scratch & 15u)) return fail(CV_ERR_INVALID, me + "scratch must be a 16-byte aligned device pointer");
+        if (scratch_bytes < need)
+            return fail(CV_ERR_INVALID, me + "scratch_bytes is " + std::to_string(scratch_bytes) + ", " + std::to_string(need) + " needed");
+        DeviceGuard g(eng->impl.device);
+        hipError_t e = pacmap_pairs(pre, n, c, n_neighbors, n_mn, n_fp, seed, neighbours, mid_near, further,
+                                    reinterpret_cast<PacmapStats*>(stats), scratch, (hipStream_t)stream);
+        if (e != hipSuccess) return hip_fail(e, "pacmap_pairs");
+        return Status();
+    });
+}
+
+int cv_pacmap_optimise(cv_engine_t* eng, const float* init, int n, const int32_t* offsets, const int32_t* entries, int64_t n_entries,
+                       int iterations, float* out, void* scratch, size_t scratch_bytes, void* stream) {
+    return guarded("cv_pacmap_optimise", [&]() -> Status {
+        CV_TRY(check_engine(eng));
+        const std::string me = "cv_pacmap_optimise: ";
+        if (n < 7 || n > kNeighbourMaxRows) return fail(CV_ERR_INVALID, me + "n must be in [7, 2^22], got " + std::to_string(n));
+        if (iterations < 0) return fail(CV_ERR_INVALID, me + "iterations must not be negative, got " + std::to_string(iterations));
+        if (n_entries < 1 || n_entries >= (int64_t(1) << 31))
+            return fail(CV_ERR_INVALID, me + "n_entries must be in [1, 2^31), got " + std::to_string(n_entries));
+        if (!init || ((uintptr_t)init & 7u)) return fail(CV_ERR_INVALID, me + "init must be an 8-byte aligned device pointer");
+        if (!out || ((uintptr_t)out & 7u) || out == init) return fail(CV_ERR_INVALID, me + "out must be an 8-byte aligned device pointer other than init");
+        if (!offsets || ((uintptr_t)offsets & 3u)) return fail(CV_ERR_INVALID, me + "offsets must be a 4-byte aligned device pointer");
+        if (!entries || ((uintptr_t)entries & 3u)) return fail(CV_ERR_INVALID, me + "entries must be a 4-byte aligned device pointer");
+        const size_t need = pacmap_plan(n, 1, 1, 0, 0).optimise_bytes;
+        if (!scratch || ((uintptr_t)scratch & 15u)) return fail(CV_ERR_INVALID, me + "scratch must be a 16-byte aligned device pointer");
+        if (scratch_bytes < need)
+            return fail(CV_ERR_INVALID, me + "scratch_bytes is " + std::to_string(scratch_bytes) + ", " + std::to_string(need) + " needed");
+        DeviceGuard g(eng->impl.device);
+        hipError_t e = pacmap_optimise(init, n, offsets, entries, iterations, out, scratch, (hipStream_t)stream);
+        if (e != hipSuccess) return hip_fail(e, "pacmap_optimise");
+        return Status();
+    });
+}
+
 // ---- the JPEG decoder's two halves are part of this translation unit -------------------------------------------------------
 // The library's list of units is fixed (every build of it, the host-only sanitizer builds included, compiles and links exactly
 // that list).  jpeg.cpp stays a plain C++17 file that g++ compiles on its own; jpeg.hip holds the two kernels and their launch wrapper.
@@ -1635,3 +1711,4 @@ int cv_embedding_neighbours(cv_engine_t* eng, const float* queries, int q, const
 #include "jpeg.hip"
 #include "jpeg_enc.hip"
 #include "neighbours.hip"
+#include "pacmap.hip"

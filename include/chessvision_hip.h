@@ -543,8 +543,8 @@ int cv_square_records_finish(const cv_square_record_t* records, int n, int batch
 /* The one thing the embeddings are collected for: the reference reduces the table with run.reduce_embeddings_by_foreign_table_url(...,
  * method="pacmap") (scripts/process_new_raw/process_pipeline.py:351, scripts/train/train_classifier.py:312) so that uploads and squares
  * can be browsed by similarity.  PaCMAP and UMAP both start from the k-nearest-neighbour graph of the table; this is that graph, exact.
- * The reduction itself, PaCMAP's scaled-distance neighbour choice, other metrics (normalise the rows for cosine), approximate indices
- * and corpora that do not fit the device are out of scope.
+ * The PaCMAP reduction built on it is the next section.  Other metrics (normalise the rows for cosine), approximate indices and
+ * corpora that do not fit the device are out of scope.
  *
  * Definition, for float32 rows a (query) and b (corpus) of length c:
  *     D(a, b):  s = 0.0 (double);  for ch = 0 .. c-1 ascending:  t = (double)a[ch] - (double)b[ch];  p = t * t;  s = s + p;  return s
@@ -579,6 +579,71 @@ size_t cv_embedding_neighbours_scratch_bytes(int q, int n, int c, int k);
 int cv_embedding_neighbours(cv_engine_t* eng, const float* queries, int q, const float* corpus, int n, int c, int k, int flags,
                             int32_t* indices, double* sq_distances, cv_neighbour_stats_t* stats, void* scratch, size_t scratch_bytes,
                             void* stream);
+
+/* ---- embedding reduction: PaCMAP (additions under ABI 6; detect with dlsym(handle, "cv_pacmap_pairs")) -------------------------- */
+/* The call the table is collected for, run.reduce_embeddings_by_foreign_table_url(..., method="pacmap"), as two device entries.  No
+ * copy of the pacmap package is here: this is a READING of Wang, Huang, Rudin, Shaposhnik, "Understanding How Dimension Reduction Tools
+ * Work" (JMLR 2021) and of the package's defaults, defined in numpy by chessvision/embeddings.py (pacmap_pairs, pacmap_incidence,
+ * pacmap_schedule, pacmap_optimise) and derived in DESIGN.md section 4 "Embedding reduction".  Both entries equal that definition
+ * exactly: the pairs index for index, the coordinates bit for bit, the same run to run.
+ *
+ * The host prepares two arrays (embeddings.pacmap_preprocess / pacmap_init, float64 LAPACK work that is an INPUT of the definition):
+ *   pre  (n, c) float32, every value finite: the table projected onto its 100 leading principal axes (more than 100 channels) or
+ *        scaled to [0, 1] and centred;     init (n, 2) float32: the starting coordinates.
+ *
+ * cv_pacmap_pairs -> three int32 arrays of partners per point:
+ *   neighbours (n, n_neighbors)  the kc = min(n_neighbors + 50, 64, n - 1) exact nearest rows (cv_embedding_neighbours of pre against
+ *       itself, exclude-self) re-ranked: sigma_i = max(mean of sqrt(D) at candidate ranks 3, 4, 5 (zero-based), 1e-10) in double, summed
+ *       in rank order; row i keeps the n_neighbors candidates with the smallest (D_ij / (sigma_i * sigma_j), j), ascending.
+ *   mid_near (n, n_mn)  slot by slot: draw until six distinct indices are held that are neither i nor an earlier mid-near partner of
+ *       i; the partner is the SECOND smallest of the six by (D(i, .), j), D as cv_embedding_neighbours defines it.
+ *   further (n, n_fp)  draw until n_fp distinct indices are held that are neither i nor in i's neighbour row, in the order drawn.
+ *   Draws (all uint64, wrapping):  mix(x): x += 0x9E3779B97F4A7C15; x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9;
+ *       x = (x ^ (x >> 27)) * 0x94D049BB133111EB; return x ^ (x >> 31).   key = mix(seed ^ mix((stream << 40) | i)), stream 1 for
+ *       mid-near and 2 for further;  draw t of point i = ((mix(key + t) >> 32) * n) >> 32, t counting every draw of the point in the
+ *       stream from 0, rejected ones included.  A point that reaches 65536 draws in a stream gives up: draw_overflow is set and its
+ *       remaining partners are -1 (not reachable by chance inside the limits below).
+ * Limits: 1 <= n_neighbors <= 32, 0 <= n_mn <= 16, 0 <= n_fp <= 64, 1 <= c <= 4096, max(7, 6 + n_mn, n_neighbors + n_fp + 1) <= n <=
+ *   1 << 22, and 2 n (n_neighbors + n_mn + n_fp) < 2^31.  cv_pacmap_plan checks them and sizes both scratch blocks.
+ *
+ * cv_pacmap_optimise: `iterations` Adam steps (the package runs 450) over the incidence lists of the pairs, a CSR structure the caller
+ *   builds from the three arrays (embeddings.pacmap_incidence; a counting sort): offsets (n + 1) int32, entries (offsets[n]) int32, an
+ *   entry being other | kind << 28 (0 neighbour, 1 mid-near, 2 further).  Point p's list, in this order: its own neighbour pairs by
+ *   slot, its own mid-near pairs, its own further pairs, then the entries where p is another point's partner, ordered by (kind, source
+ *   point, slot).  The ORDER is part of the definition: float32 sums are taken in it.  Per iteration it = 0 .. iterations - 1, all
+ *   points reading the previous iteration's Y, float32, every operation rounded once:
+ *       g = (0, 0);  for each entry with other point q:   e = Y[p] - Y[q];  d = 1;  d = d + e0*e0;  d = d + e1*e1
+ *           neighbour:  t = 10 + d;     w = w_n  * (20    / (t*t));  g = g + w*e
+ *           mid-near:   t = 10000 + d;  w = w_MN * (20000 / (t*t));  g = g + w*e      (skipped from iteration 200 on, where w_MN = 0)
+ *           further:    t = 1 + d;      w = w_FP * (2     / (t*t));  g = g - w*e
+ *       m = m + c1*(g - m);  v = v + c2*(g*g - v);  Y = Y - (lr_t*m) / (sqrt(v) + 1e-7f),   c1 = (float)(1 - 0.9), c2 = (float)(1 - 0.999)
+ *   Host scalars, double rounded to float: lr_t = sqrt(1 - b2) / (1 - b1), b1 = 0.9^(it+1) and b2 = 0.999^(it+1) as running products;
+ *   it < 100: w_MN = (1 - it/100) * 1000 + (it/100) * 3, w_n = 2; it < 200: w_MN = 3, w_n = 3; then w_MN = 0, w_n = 1; w_FP = 1.
+ *   An entry whose point lies outside [0, n) is skipped.  One plain launch per iteration on `stream`.
+ *
+ * pre, the pair arrays, init, out, offsets, entries, stats, scratch: DEVICE.  init and out 8-byte aligned, out != init; stats nullable,
+ * 8-byte aligned; scratch 16-byte aligned, at least plan.pairs_scratch_bytes / plan.optimise_scratch_bytes (the latter depends on n
+ * alone); a pair array of zero columns may be NULL.  The caller owns the scratch and may reuse it once `stream` has passed the call.
+ * Asynchronous on `stream`; allocate nothing and synchronise nothing.  CV_ERR_INVALID names the offending argument. */
+typedef struct cv_pacmap_stats {      /* 64 bytes */
+    cv_neighbour_stats_t neighbours;  /* the candidate search's record */
+    int64_t mid_near_draws;           /* draws of all points, rejected ones included */
+    int64_t further_draws;
+    int32_t draw_overflow;            /* 1: a point gave up drawing, the pairs are not usable */
+    int32_t candidates;               /* kc */
+    int32_t reserved[2];              /* 0 */
+} cv_pacmap_stats_t;
+typedef struct cv_pacmap_plan {
+    int32_t n, c, n_neighbors, n_mn, n_fp;
+    int32_t candidates;               /* kc */
+    uint64_t pairs_scratch_bytes, optimise_scratch_bytes;
+} cv_pacmap_plan_t;
+int cv_pacmap_plan(int n, int c, int n_neighbors, int n_mn, int n_fp, cv_pacmap_plan_t* plan);
+int cv_pacmap_pairs(cv_engine_t* eng, const float* pre, int n, int c, int n_neighbors, int n_mn, int n_fp, uint64_t seed,
+                    int32_t* neighbours, int32_t* mid_near, int32_t* further, cv_pacmap_stats_t* stats, void* scratch,
+                    size_t scratch_bytes, void* stream);
+int cv_pacmap_optimise(cv_engine_t* eng, const float* init, int n, const int32_t* offsets, const int32_t* entries, int64_t n_entries,
+                       int iterations, float* out, void* scratch, size_t scratch_bytes, void* stream);
 
 /* ---- one image, host to host: the native form of ChessVision.process_image (core.py:152-195) ---------------------------------- */
 /* Everything a cgo / JNI / C++ host needs for the reference's per-image entry point in ONE call: INTER_AREA resize to 256x256
