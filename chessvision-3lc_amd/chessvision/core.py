@@ -951,6 +951,47 @@ class ChessVision:
             coords = model.engine.pacmap_optimise(start, pairs)
         return emb.Reduction(coords, pairs, int(pairs.neighbours.shape[1]), pairs.stats)
 
+    def fit_embedding_map(self, table, method: str = "pacmap", n_neighbors=None, seed: int = 0, init="pca"):
+        """``reduce_embeddings`` that keeps what placing other tables into the same map needs -- the first half of the reference's
+        ``run.reduce_embeddings_by_foreign_table_url``, which fits the reducer on one table (the training set's embeddings) and
+        applies it to every other table of the run.  Returns an ``embeddings.EmbeddingMap``; its ``reduction`` is what
+        ``reduce_embeddings`` returns for the same arguments.  ``embeddings.pacmap_fit`` is the definition; with a HIP model plugged
+        in the pairs, the optimiser and the basis rows' scale run on its engine and equal it bit for bit.  ``embeddings.save_map``
+        / ``load_map`` keep a map across restarts."""
+        from . import embeddings as emb
+
+        if method != "pacmap":
+            raise ValueError(f"method must be 'pacmap', got {method!r}")
+        model = next((m for m in (self._classifier, self._board_extractor) if m is not None and self._native(m)), None)
+        if model is None:
+            return emb.pacmap_fit(table, n_neighbors=n_neighbors, seed=seed, init=init)
+        pre, start, parameters = emb.pacmap_fit_inputs(table, init)
+        with torch.cuda.device(self.device):
+            pairs = model.engine.pacmap_pairs(pre, n_neighbors, seed=seed)
+            coords = model.engine.pacmap_optimise(start, pairs)
+            nn = int(pairs.neighbours.shape[1])
+            sigma = model.engine.pacmap_basis_scale_dev(torch.tensor(pre).to(self.device), nn).cpu().numpy()
+        return emb.map_from_fit(emb.Reduction(coords, pairs, nn, pairs.stats), pre, sigma, parameters)
+
+    def place_embeddings(self, map, table, init="pca"):
+        """Other rows -- the validation set, an earlier epoch, tonight's uploads -- placed into a fitted map (``fit_embedding_map``),
+        whose points stay where they are: the second half of ``run.reduce_embeddings_by_foreign_table_url``.  ``table``: (Q, C) host
+        array or tensor with the channels the map was fitted on; ``init``: "pca" (the fit's start evaluated at the new rows) or a
+        (Q, 2) array.  Returns an ``embeddings.Placement`` (``coordinates`` (Q, 2) float32, the basis rows each new row was pulled
+        towards, the neighbour search's record).  ``embeddings.pacmap_transform`` is the definition, a reading of the package's
+        ``transform``; with a HIP model plugged in the pairs and all 450 steps (one launch) run on its engine, on the caller's
+        current stream, and equal it bit for bit; otherwise the numpy form itself runs."""
+        from . import embeddings as emb
+
+        model = next((m for m in (self._classifier, self._board_extractor) if m is not None and self._native(m)), None)
+        if model is None:
+            return emb.pacmap_transform(map, table, init=init)
+        pre_new, start = emb.pacmap_transform_inputs(map, table, init)
+        with torch.cuda.device(self.device):
+            nbr, stats = model.engine.pacmap_place_pairs(map, pre_new)
+            coords = model.engine.pacmap_place(start, map.reduction.coordinates, nbr)
+        return emb.Placement(coords, nbr, stats)
+
     def _pipeline_streams(self):
         """(host->device, device->host, compute) streams of ``process_images``, created once per instance."""
         if self._streams is None:

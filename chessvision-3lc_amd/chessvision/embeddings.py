@@ -24,7 +24,10 @@ What the table is collected for: the reference reduces it with ``run.reduce_embe
 the device form, equal to it bit for bit.  ``stack`` turns ``process_images(..., embeddings=True)`` results into the table,
 ``duplicate_groups`` answers "which uploads are near-duplicates".  The reduction itself is the last part of this file: ``pacmap`` is the
 definition in numpy (a reading of the paper and of the package's defaults, see there), ``HipEngine.pacmap_pairs`` /
-``HipEngine.pacmap_optimise`` / ``ChessVision.reduce_embeddings`` the device form, equal to it bit for bit.
+``HipEngine.pacmap_optimise`` / ``ChessVision.reduce_embeddings`` the device form, equal to it bit for bit.  After it, the other half of
+that call: ``pacmap_fit`` keeps what placing further tables into the same map needs (``EmbeddingMap``), ``pacmap_transform`` places
+them (a reading of the package's ``transform``); ``HipEngine.pacmap_place_pairs`` / ``HipEngine.pacmap_place`` /
+``ChessVision.fit_embedding_map`` / ``ChessVision.place_embeddings`` are the device form, again bit for bit.
 """
 from __future__ import annotations
 
@@ -390,40 +393,62 @@ def _principal_axes(centred: np.ndarray, dims: int) -> np.ndarray:
     return axes * np.where(axes[top, np.arange(axes.shape[1])] < 0, -1.0, 1.0)
 
 
+def _pacmap_preprocess_fit(table) -> tuple[np.ndarray, dict]:
+    """``pacmap_preprocess`` and the float64 parameters it used (``EmbeddingMap``'s ``projected``, ``channel_mean``, ``axes``,
+    ``minimum``, ``maximum``), so that ``pacmap_preprocess_new`` can apply the same operations to other rows."""
+    x = _finite_table(table, "table").astype(np.float64)
+    par = {"projected": x.shape[1] > PACMAP_PCA_DIMS, "channels": x.shape[1], "axes": np.zeros((x.shape[1], 0), np.float64),
+           "minimum": 0.0, "maximum": 0.0}
+    if par["projected"]:
+        par["channel_mean"] = x.mean(axis=0)
+        x = x - par["channel_mean"]
+        par["axes"] = _principal_axes(x, PACMAP_PCA_DIMS)
+        x = x @ par["axes"]
+    else:
+        par["minimum"] = float(x.min())
+        x = x - x.min()
+        top = x.max()
+        par["maximum"] = float(top)
+        if top > 0:
+            x = x / top
+        par["channel_mean"] = x.mean(axis=0)
+        x = x - par["channel_mean"]
+    return np.ascontiguousarray(x, dtype=np.float32), par
+
+
 def pacmap_preprocess(table) -> np.ndarray:
     """(N, C) -> float32 (N, C'): more than 100 channels are centred and projected onto the 100 leading principal axes; otherwise
     the table is shifted by its global minimum, divided by its global maximum (where that is not zero) and centred.  float64 on the
     host; the result is an INPUT of both forms, so nothing downstream depends on LAPACK's rounding."""
-    x = _finite_table(table, "table").astype(np.float64)
-    if x.shape[1] > PACMAP_PCA_DIMS:
-        x = x - x.mean(axis=0)
-        x = x @ _principal_axes(x, PACMAP_PCA_DIMS)
-    else:
-        x = x - x.min()
-        top = x.max()
-        if top > 0:
-            x = x / top
-        x = x - x.mean(axis=0)
-    return np.ascontiguousarray(x, dtype=np.float32)
+    return _pacmap_preprocess_fit(table)[0]
+
+
+def _pacmap_init_fit(pre, projected: bool = False) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """``pacmap_init`` and what it used when not projected: the (C',) float64 mean of ``pre`` and the (C', 2) (one column for a
+    one-channel table) float64 axes; both empty when projected."""
+    x = _finite_table(pre, "pre").astype(np.float64)
+    mean, axes = np.zeros(0, np.float64), np.zeros((x.shape[1], 0), np.float64)
+    if not projected:
+        mean = x.mean(axis=0)
+        x = x - mean
+        axes = _principal_axes(x, 2)
+        x = x @ axes
+    y = np.zeros((x.shape[0], 2), np.float64)
+    y[:, :min(2, x.shape[1])] = 0.01 * x[:, :2]
+    return y.astype(np.float32), mean, axes
 
 
 def pacmap_init(pre, projected: bool = False) -> np.ndarray:
     """float32 (N, 2): 0.01 x the first two columns of ``pre`` when ``pacmap_preprocess`` projected (``projected=True``: the table had
     more than 100 channels), otherwise 0.01 x the two leading principal axes of ``pre`` by the same rule.  A one-channel table gets
     a zero second coordinate."""
-    x = _finite_table(pre, "pre").astype(np.float64)
-    if not projected:
-        x = x - x.mean(axis=0)
-        x = x @ _principal_axes(x, 2)
-    y = np.zeros((x.shape[0], 2), np.float64)
-    y[:, :min(2, x.shape[1])] = 0.01 * x[:, :2]
-    return y.astype(np.float32)
+    return _pacmap_init_fit(pre, projected)[0]
 
 
-def _pacmap_scaled_choice(idx: np.ndarray, d: np.ndarray, nn: int) -> np.ndarray:
-    """Row i keeps the nn candidates with the smallest ``(D_ij / (sigma_i * sigma_j), j)``; sigma = max(mean of sqrt(D) at candidate
-    ranks 3, 4, 5, 1e-10), summed in rank order in float64."""
-    kc = idx.shape[1]
+def _pacmap_sigma(d: np.ndarray) -> np.ndarray:
+    """(rows,) float64 scale of every row of ascending candidate distances ``d`` (rows, kc): max(mean of sqrt(D) at candidate ranks
+    3, 4, 5, 1e-10), summed in rank order; with three candidates or fewer the last one's sqrt(D)."""
+    kc = d.shape[1]
     root = np.sqrt(d)
     if kc > 3:
         hi = min(kc, 6)
@@ -433,8 +458,15 @@ def _pacmap_scaled_choice(idx: np.ndarray, d: np.ndarray, nn: int) -> np.ndarray
         sigma = s / float(hi - 3)
     else:
         sigma = root[:, kc - 1].copy()
-    sigma = np.maximum(sigma, 1e-10)
-    scaled = d / (sigma[:, None] * sigma[idx])
+    return np.maximum(sigma, 1e-10)
+
+
+def _pacmap_scaled_choice(idx: np.ndarray, d: np.ndarray, nn: int, sigma: np.ndarray | None = None) -> np.ndarray:
+    """Row i keeps the nn candidates with the smallest ``(D_ij / (sigma_i * sigma_j), j)``; sigma_i = ``_pacmap_sigma`` of the row's
+    own candidates, sigma_j the same (a table against itself) or, where ``sigma`` is given, that array's entry j (new rows against
+    a fitted basis)."""
+    own = _pacmap_sigma(d)
+    scaled = d / (own[:, None] * (own if sigma is None else sigma)[idx])
     order = np.lexsort((idx, scaled), axis=1)[:, :nn]
     return np.take_along_axis(idx, order, axis=1).astype(np.int32)
 
@@ -467,6 +499,11 @@ def pacmap_pairs(pre, n_neighbors=None, n_MN=None, n_FP=None, seed: int = 0) -> 
     mid-near partner of i; the partner is the SECOND smallest by ``(D(i, .), j)``.  Further (stream 2): draw until n_FP distinct
     indices are held that are neither i nor in i's neighbour row.  Draw t of point i in a stream is ``pacmap_draw(pacmap_key(seed,
     stream, i), t, N)``; t counts every draw, rejected ones included."""
+    return _pacmap_pairs_sigma(pre, n_neighbors, n_MN, n_FP, seed)[0]
+
+
+def _pacmap_pairs_sigma(pre, n_neighbors=None, n_MN=None, n_FP=None, seed: int = 0) -> tuple[PacmapPairs, np.ndarray]:
+    """``pacmap_pairs`` and the (N,) float64 scale of every row that its neighbour choice used (``EmbeddingMap.sigma``)."""
     x = _finite_table(pre, "pre")
     n = x.shape[0]
     nn, nmn, nfp, kc = check_pacmap_arguments(n, n_neighbors, n_MN, n_FP)
@@ -490,7 +527,7 @@ def pacmap_pairs(pre, n_neighbors=None, n_MN=None, n_FP=None, seed: int = 0) -> 
     t = np.zeros(n, np.uint64)
     far = _pacmap_draw_until(pacmap_key(seed, 2, rows), t, n, nfp, nbr, "further")
     stats = dict(graph.stats, candidates=kc, mid_near_draws=mid_draws, further_draws=int(t.sum()))
-    return PacmapPairs(nbr, mid.astype(np.int32), far.astype(np.int32), stats)
+    return PacmapPairs(nbr, mid.astype(np.int32), far.astype(np.int32), stats), _pacmap_sigma(graph.sq_distances)
 
 
 def pacmap_incidence(pairs: PacmapPairs, mid_near: bool = True) -> tuple[np.ndarray, np.ndarray]:
@@ -627,21 +664,255 @@ def pacmap_optimise(init, pairs: PacmapPairs, iterations: int = PACMAP_ITERATION
 
 def pacmap(table, n_neighbors=None, n_MN=None, n_FP=None, seed: int = 0, init="pca", iterations: int = PACMAP_ITERATIONS) -> Reduction:
     """The whole reduction in numpy: preprocess, pairs, initialise (``init="pca"`` or an (N, 2) array), optimise."""
-    pre, start = pacmap_inputs(table, init)
-    pairs = pacmap_pairs(pre, n_neighbors, n_MN, n_FP, seed)
-    coords = pacmap_optimise(start, pairs, iterations)
-    return Reduction(coords, pairs, int(pairs.neighbours.shape[1]), pairs.stats)
+    return pacmap_fit(table, n_neighbors, n_MN, n_FP, seed, init, iterations).reduction
+
+
+def pacmap_fit_inputs(table, init="pca") -> tuple[np.ndarray, np.ndarray, dict]:
+    """``(pre, start, parameters)``: the two host arrays both forms start from, and the float64 parameters of the preprocessing and
+    of the "pca" start that ``map_from_fit`` stores."""
+    x = _finite_table(table, "table")
+    pre, par = _pacmap_preprocess_fit(x)
+    pca, par["start_mean"], par["start_axes"] = _pacmap_init_fit(pre, projected=par["projected"])
+    if isinstance(init, str):
+        if init != "pca":
+            raise ValueError(f"init must be 'pca' or an (N, 2) array, got {init!r}")
+        return pre, pca, par
+    start = np.ascontiguousarray(np.asarray(init.detach().cpu() if hasattr(init, "detach") else init), dtype=np.float32)
+    if start.shape != (x.shape[0], 2) or not np.isfinite(start).all():
+        raise ValueError(f"init must be 'pca' or a finite ({x.shape[0]}, 2) array, got shape {start.shape}")
+    return pre, start, par
 
 
 def pacmap_inputs(table, init="pca") -> tuple[np.ndarray, np.ndarray]:
     """``(pre, start)``: the two host arrays both forms start from."""
-    x = _finite_table(table, "table")
-    pre = pacmap_preprocess(x)
+    return pacmap_fit_inputs(table, init)[:2]
+
+
+# ---- placing new rows into a fitted map (include/chessvision_hip.h: cv_pacmap_basis_scale, cv_pacmap_place_pairs, cv_pacmap_place) ----
+# Again a READING, of the ``pacmap`` package's ``transform``: pairs from every new point to its nearest basis points by the scaled
+# distance, the attraction term alone, the basis held still, the same 450-step schedule.  Where it departs from the package: the
+# neighbour candidates are exact and at most MAX_NEIGHBOURS of them, and the Adam bias powers are running products.  DESIGN.md section 4
+# "Placing new points".
+@dataclasses.dataclass
+class EmbeddingMap:
+    """A fitted map, everything ``pacmap_transform`` needs to place other rows into it.  ``reduction``: the ``Reduction`` of the
+    basis; ``pre`` (N, C') float32: the preprocessed basis, exactly the array the fit used; ``sigma`` (N,) float64: the basis rows'
+    scale in the neighbour choice.  The preprocessing, float64: ``projected``, ``channels`` (C of the fitted table),
+    ``channel_mean`` (C,) -- of the table when projected, of the shifted and scaled table otherwise --, ``axes`` (C, 100) when
+    projected ((C, 0) otherwise), ``minimum`` and ``maximum``: the table's global minimum and its global maximum after the shift
+    (0.0 when projected).  The "pca" start when not projected: ``start_mean`` (C',), the mean of ``pre``, and ``start_axes`` (C', 2)
+    ((C', 1) for a one-channel table); both empty when projected."""
+    reduction: Reduction
+    pre: np.ndarray
+    sigma: np.ndarray
+    projected: bool
+    channels: int
+    channel_mean: np.ndarray
+    axes: np.ndarray
+    minimum: float
+    maximum: float
+    start_mean: np.ndarray
+    start_axes: np.ndarray
+
+
+@dataclasses.dataclass
+class Placement:
+    """``coordinates`` (Q, 2) float32 of the new rows in the map; ``neighbours`` (Q, n_neighbors) int32: the basis rows each was
+    pulled towards; ``stats``: the neighbour search's record plus ``candidates`` (kc)."""
+    coordinates: np.ndarray
+    neighbours: np.ndarray
+    stats: dict
+
+
+def map_from_fit(reduction: Reduction, pre: np.ndarray, sigma: np.ndarray, parameters: dict) -> EmbeddingMap:
+    """The ``EmbeddingMap`` of a fit from its parts (``parameters``: the dict of ``pacmap_fit_inputs``)."""
+    return EmbeddingMap(reduction, pre, np.ascontiguousarray(sigma, dtype=np.float64), **parameters)
+
+
+def pacmap_fit(table, n_neighbors=None, n_MN=None, n_FP=None, seed: int = 0, init="pca",
+               iterations: int = PACMAP_ITERATIONS) -> EmbeddingMap:
+    """``pacmap`` that keeps what placing needs: ``pacmap_fit(t).reduction`` IS ``pacmap(t)``."""
+    pre, start, par = pacmap_fit_inputs(table, init)
+    pairs, sigma = _pacmap_pairs_sigma(pre, n_neighbors, n_MN, n_FP, seed)
+    coords = pacmap_optimise(start, pairs, iterations)
+    return map_from_fit(Reduction(coords, pairs, int(pairs.neighbours.shape[1]), pairs.stats), pre, sigma, par)
+
+
+def pacmap_preprocess_new(map: EmbeddingMap, table) -> np.ndarray:
+    """(Q, C) rows of the kind the map was fitted on -> float32 (Q, C'): the float64 operations of ``pacmap_preprocess`` with the
+    map's stored parameters (a global maximum of zero is not divided by, as in the fit).  Like ``map.pre`` an INPUT of both forms."""
+    x = _finite_table(table, "table").astype(np.float64)
+    if x.shape[1] != map.channels:
+        raise ValueError(f"table has {x.shape[1]} channels, the map was fitted on {map.channels}")
+    if map.projected:
+        x = x - map.channel_mean
+        x = x @ map.axes
+    else:
+        x = x - map.minimum
+        if map.maximum > 0:
+            x = x / map.maximum
+        x = x - map.channel_mean
+    return np.ascontiguousarray(x, dtype=np.float32)
+
+
+def check_pacmap_place_arguments(q: int, n: int, c_new: int, c: int, n_neighbors: int) -> int:
+    """The argument rules both forms of the placement share -> kc, the number of exact candidates of a new row."""
+    if c_new != c:
+        raise ValueError(f"the new rows have {c_new} channels, the map's basis {c}")
+    if not 1 <= q <= PACMAP_MAX_ROWS:
+        raise ValueError(f"between 1 and {PACMAP_MAX_ROWS} new rows can be placed at once, got {q}")
+    if not 1 <= n_neighbors <= PACMAP_MAX_NEIGHBOURS or n < max(7, n_neighbors + 1) or n > PACMAP_MAX_ROWS:
+        raise ValueError(f"a map of {n} rows with n_neighbors={n_neighbors} is outside what pacmap fits")
+    return min(n_neighbors + 50, MAX_NEIGHBOURS, n)
+
+
+def _place_tables(map: EmbeddingMap, pre_new) -> tuple[np.ndarray, int, int]:
+    x = _finite_table(pre_new, "pre_new")
+    nn = int(map.reduction.n_neighbors)
+    return x, nn, check_pacmap_place_arguments(x.shape[0], map.pre.shape[0], x.shape[1], map.pre.shape[1], nn)
+
+
+def _pacmap_place_pairs(map: EmbeddingMap, pre_new) -> tuple[np.ndarray, dict]:
+    x, nn, kc = _place_tables(map, pre_new)
+    graph = neighbours(x, corpus=map.pre, k=kc, exclude_self=False)
+    nbr = _pacmap_scaled_choice(graph.indices.astype(np.int64), graph.sq_distances, nn, sigma=np.asarray(map.sigma, np.float64))
+    return nbr, dict(graph.stats, candidates=kc)
+
+
+def pacmap_place_pairs(map: EmbeddingMap, pre_new) -> np.ndarray:
+    """(Q, n_neighbors) int32, the basis rows every new row is pulled towards -- the definition the device form is held to index for
+    index.  Candidates: the kc = min(n_neighbors + 50, 64, N) exact nearest basis rows (``neighbours(pre_new, corpus=map.pre)``, no
+    row excluded).  sigma_q of a new row: the fit's rule on its own candidates (max(mean of sqrt(D) at ranks 3, 4, 5, 1e-10)); the
+    row keeps the n_neighbors candidates with the smallest ``(D_qj / (sigma_q * map.sigma[j]), j)``, ascending."""
+    return _pacmap_place_pairs(map, pre_new)[0]
+
+
+def pacmap_place_init(map: EmbeddingMap, pre_new) -> np.ndarray:
+    """float32 (Q, 2): the fit's "pca" start evaluated at the new rows -- 0.01 x the first two columns when the map projected,
+    otherwise 0.01 x ``(pre_new - map.start_mean) @ map.start_axes``."""
+    x = _place_tables(map, pre_new)[0].astype(np.float64)
+    if not map.projected:
+        x = x - map.start_mean
+        x = x @ map.start_axes
+    y = np.zeros((x.shape[0], 2), np.float64)
+    y[:, :min(2, x.shape[1])] = 0.01 * x[:, :2]
+    return y.astype(np.float32)
+
+
+def check_pacmap_place_inputs(init, basis_coordinates, pairs) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """``(init (Q, 2) float32, basis (N, 2) float32, pairs (Q, nn) int32)`` of a placement as dense host arrays, shapes checked."""
+    host = lambda a: np.asarray(a.detach().cpu() if hasattr(a, "detach") else a)
+    y = np.ascontiguousarray(host(init), dtype=np.float32)
+    yb = np.ascontiguousarray(host(basis_coordinates), dtype=np.float32)
+    p = np.ascontiguousarray(host(pairs), dtype=np.int32)
+    if p.ndim != 2 or not 1 <= p.shape[1] <= PACMAP_MAX_NEIGHBOURS or not 1 <= p.shape[0] <= PACMAP_MAX_ROWS:
+        raise ValueError(f"pairs must be a (Q, n_neighbors) table with Q >= 1 and 1 <= n_neighbors <= {PACMAP_MAX_NEIGHBOURS}, "
+                         f"got shape {p.shape}")
+    if y.shape != (p.shape[0], 2) or not np.isfinite(y).all():
+        raise ValueError(f"init must be a finite ({p.shape[0]}, 2) array, got shape {y.shape}")
+    if yb.ndim != 2 or yb.shape[1] != 2 or not 1 <= yb.shape[0] <= PACMAP_MAX_ROWS or not np.isfinite(yb).all():
+        raise ValueError(f"basis_coordinates must be a finite (N, 2) array, got shape {yb.shape}")
+    return y, yb, p
+
+
+def pacmap_place_trajectory(init, basis_coordinates, pairs, keep=(PACMAP_ITERATIONS,)) -> dict:
+    """``{iterations: coordinates}`` for every count in ``keep``, from ONE run of max(keep) iterations of ``pacmap_place``."""
+    y, yb, p = check_pacmap_place_inputs(init, basis_coordinates, pairs)
+    y = y.copy()
+    keep = sorted(int(k) for k in keep)
+    if not keep or keep[0] < 0:
+        raise ValueError("iteration counts must be non-negative")
+    f32 = np.float32
+    live = (p >= 0) & (p < yb.shape[0])
+    at = np.where(live, p, 0)
+    b0, b1 = yb[at, 0], yb[at, 1]                             # (Q, nn): the partners' coordinates never move
+    schedule = pacmap_schedule(keep[-1])
+    c1, c2, eps, one, ten, twenty = f32(1.0 - 0.9), f32(1.0 - 0.999), f32(1e-7), f32(1.0), f32(10.0), f32(20.0)
+    m, v = np.zeros_like(y), np.zeros_like(y)
+    out = {0: y.copy()} if keep[0] == 0 else {}
+    with np.errstate(all="ignore"):
+        for it in range(keep[-1]):
+            lr, w_n = schedule[it, 0], schedule[it, 1]
+            g = np.zeros_like(y)
+            for u in range(p.shape[1]):                       # slots in order, every operation rounded once to float32
+                e0 = y[:, 0] - b0[:, u]
+                e1 = y[:, 1] - b1[:, u]
+                d = one + e0 * e0
+                d = d + e1 * e1
+                t = ten + d
+                w = w_n * (twenty / (t * t))
+                g[:, 0] = np.where(live[:, u], g[:, 0] + w * e0, g[:, 0])
+                g[:, 1] = np.where(live[:, u], g[:, 1] + w * e1, g[:, 1])
+            m = m + c1 * (g - m)
+            v = v + c2 * (g * g - v)
+            y = y - (lr * m) / (np.sqrt(v) + eps)
+            if it + 1 in keep:
+                out[it + 1] = y.copy()
+    return out
+
+
+def pacmap_place(init, basis_coordinates, pairs, iterations: int = PACMAP_ITERATIONS) -> np.ndarray:
+    """(Q, 2) float32 coordinates of the new points after ``iterations`` Adam steps from ``init`` -- the definition the device form
+    is held to bit for bit.  ``basis_coordinates`` (N, 2): the fitted map, held still; ``pairs`` (Q, nn) int32: every new point's
+    partners in it (``pacmap_place_pairs``).  Per iteration and new point p, with Yb the basis coordinates:
+
+        g = 0;  for slot u in order (a partner outside [0, N) is skipped):
+            e = Y[p] - Yb[b_u];  d = 1;  d = d + e0*e0;  d = d + e1*e1;  t = 10 + d;  w = w_n * (20 / (t*t));  g = g + w*e
+        m = m + c1*(g - m);  v = v + c2*(g*g - v);  Y[p] = Y[p] - (lr_t*m) / (sqrt(v) + 1e-7)
+
+    in float32, one rounding per operation; lr_t and w_n are columns 0 and 1 of ``pacmap_schedule`` (2, then 3, then 1).  No
+    mid-near and no further term: a new point is only pulled.  No new point reads another, so a batch equals its rows placed one
+    at a time, bit for bit."""
+    return pacmap_place_trajectory(init, basis_coordinates, pairs, (int(iterations),))[int(iterations)]
+
+
+def pacmap_transform_inputs(map: EmbeddingMap, table, init="pca") -> tuple[np.ndarray, np.ndarray]:
+    """``(pre_new, start)``: the two host arrays both forms of the placement start from."""
+    pre_new = pacmap_preprocess_new(map, table)
+    _place_tables(map, pre_new)
     if isinstance(init, str):
         if init != "pca":
-            raise ValueError(f"init must be 'pca' or an (N, 2) array, got {init!r}")
-        return pre, pacmap_init(pre, projected=x.shape[1] > PACMAP_PCA_DIMS)
+            raise ValueError(f"init must be 'pca' or a (Q, 2) array, got {init!r}")
+        return pre_new, pacmap_place_init(map, pre_new)
     start = np.ascontiguousarray(np.asarray(init.detach().cpu() if hasattr(init, "detach") else init), dtype=np.float32)
-    if start.shape != (x.shape[0], 2) or not np.isfinite(start).all():
-        raise ValueError(f"init must be 'pca' or a finite ({x.shape[0]}, 2) array, got shape {start.shape}")
-    return pre, start
+    if start.shape != (pre_new.shape[0], 2) or not np.isfinite(start).all():
+        raise ValueError(f"init must be 'pca' or a finite ({pre_new.shape[0]}, 2) array, got shape {start.shape}")
+    return pre_new, start
+
+
+def pacmap_transform(map: EmbeddingMap, table, init="pca", iterations: int = PACMAP_ITERATIONS) -> Placement:
+    """The whole placement in numpy: preprocess with the map's parameters, pairs into the basis, initialise, place."""
+    pre_new, start = pacmap_transform_inputs(map, table, init)
+    nbr, stats = _pacmap_place_pairs(map, pre_new)
+    return Placement(pacmap_place(start, map.reduction.coordinates, nbr, iterations), nbr, stats)
+
+
+_MAP_ARRAYS = ("pre", "sigma", "channel_mean", "axes", "start_mean", "start_axes")
+_PAIR_ARRAYS = ("neighbours", "mid_near", "further")
+
+
+def save_map(path, map: EmbeddingMap) -> None:
+    """One ``.npz`` of arrays and scalars (no pickle), written to exactly ``path``; ``load_map`` reproduces every array bit for bit."""
+    keys = sorted(map.reduction.stats)
+    content = {name: np.asarray(getattr(map, name)) for name in _MAP_ARRAYS}
+    content.update({name: np.asarray(getattr(map.reduction.pairs, name)) for name in _PAIR_ARRAYS})
+    content.update(coordinates=np.asarray(map.reduction.coordinates), n_neighbors=np.int64(map.reduction.n_neighbors),
+                   projected=np.bool_(map.projected), channels=np.int64(map.channels), minimum=np.float64(map.minimum),
+                   maximum=np.float64(map.maximum), stats_keys=np.asarray(keys, dtype=np.str_),
+                   stats_values=np.asarray([int(map.reduction.stats[k]) for k in keys], dtype=np.int64), format=np.int64(1))
+    with open(path, "wb") as f:
+        np.savez(f, **content)
+
+
+def load_map(path) -> EmbeddingMap:
+    """The ``EmbeddingMap`` that ``save_map`` wrote."""
+    with np.load(path, allow_pickle=False) as z:
+        if "format" not in z.files or int(z["format"]) != 1:
+            raise ValueError(f"{path} is not an embedding map of this version")
+        stats = {str(k): int(v) for k, v in zip(z["stats_keys"], z["stats_values"])}
+        pairs = PacmapPairs(*(z[name] for name in _PAIR_ARRAYS), stats)
+        reduction = Reduction(z["coordinates"], pairs, int(z["n_neighbors"]), stats)
+        return EmbeddingMap(reduction, z["pre"], z["sigma"], bool(z["projected"]), int(z["channels"]), z["channel_mean"], z["axes"],
+                            float(z["minimum"]), float(z["maximum"]), z["start_mean"], z["start_axes"])
+
+

@@ -159,6 +159,10 @@ SYMBOLS = [
     ("cv_pacmap_plan", _i, [_i, _i, _i, _i, _i, _vp]),
     ("cv_pacmap_pairs", _i, [_vp, _vp, _i, _i, _i, _i, _i, ctypes.c_uint64, _vp, _vp, _vp, _vp, _vp, ctypes.c_size_t, _vp]),
     ("cv_pacmap_optimise", _i, [_vp, _vp, _i, _vp, _vp, ctypes.c_int64, _i, _vp, _vp, ctypes.c_size_t, _vp]),
+    ("cv_pacmap_place_plan", _i, [_i, _i, _i, _i, _vp]),
+    ("cv_pacmap_basis_scale", _i, [_vp, _vp, _i, _i, _i, _vp, _vp, ctypes.c_size_t, _vp]),
+    ("cv_pacmap_place_pairs", _i, [_vp, _vp, _i, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, ctypes.c_size_t, _vp]),
+    ("cv_pacmap_place", _i, [_vp, _vp, _i, _vp, _i, _vp, _i, _i, _vp, _vp]),
 ]
 NEIGHBOURS_EXCLUDE_SELF, NEIGHBOURS_EXACT_ONLY = 1, 2
 # cv_neighbour_stats_t (include/chessvision_hip.h): eight int32
@@ -172,6 +176,12 @@ class PacmapPlan(ctypes.Structure):
     """cv_pacmap_plan_t"""
     _fields_ = [(name, ctypes.c_int32) for name in ("n", "c", "n_neighbors", "n_mn", "n_fp", "candidates")] + \
                [("pairs_scratch_bytes", ctypes.c_uint64), ("optimise_scratch_bytes", ctypes.c_uint64)]
+
+
+class PacmapPlacePlan(ctypes.Structure):
+    """cv_pacmap_place_plan_t"""
+    _fields_ = [(name, ctypes.c_int32) for name in ("q", "n", "c", "n_neighbors", "candidates", "reserved")] + \
+               [("scale_scratch_bytes", ctypes.c_uint64), ("pairs_scratch_bytes", ctypes.c_uint64)]
 
 # cv_score_record_t (include/chessvision_hip.h): one 64-byte record per image
 SCORE_RECORD = np.dtype({"names": ["hist", "above_half", "n_nan", "top_sum", "top_count", "reserved"],
@@ -942,6 +952,84 @@ class HipEngine:
         offsets, entries = pacmap_incidence(pairs)
         dev = [torch.tensor(a).to(self.device) for a in (start, offsets, entries)]
         return self.pacmap_optimise_dev(*dev, iterations=int(iterations)).cpu().numpy()
+
+    def pacmap_place_plan(self, q: int, n: int, c: int, n_neighbors: int) -> PacmapPlacePlan:
+        """``cv_pacmap_place_plan``: the limits checked, kc and the two scratch sizes."""
+        plan = PacmapPlacePlan()
+        _check(self._lib.cv_pacmap_place_plan(int(q), int(n), int(c), int(n_neighbors), ctypes.byref(plan)))
+        return plan
+
+    def _dense(self, what: str, name: str, t, dtype, shape) -> None:
+        """``t`` is a dense tensor of ``dtype`` on this device; ``shape``: its shape with None for any extent of at least 1."""
+        if not isinstance(t, torch.Tensor) or t.dtype != dtype or t.device != self.device or not t.is_contiguous() \
+                or t.dim() != len(shape) or any(int(have) < 1 or (want is not None and int(have) != want) for have, want in zip(t.shape, shape)):
+            raise HipBackendError(f"{what} expects {name} as a dense {dtype} tensor of shape {shape} on the engine's device")
+
+    def pacmap_basis_scale_dev(self, pre: torch.Tensor, n_neighbors: int) -> torch.Tensor:
+        """``cv_pacmap_basis_scale``: ``pre`` (N, C), a dense finite float32 tensor on this device, -> the (N,) float64 device tensor
+        of the rows' scale in ``pacmap_pairs``' neighbour choice (``EmbeddingMap.sigma``).  Launched on the current stream; nothing
+        is synchronised or copied."""
+        self._dense("pacmap_basis_scale", "pre", pre, torch.float32, (None, None))
+        n, c = (int(v) for v in pre.shape)
+        need = int(self.pacmap_place_plan(1, n, c, n_neighbors).scale_scratch_bytes)
+        with torch.cuda.device(self.device):
+            scratch = torch.empty(max(need, 16), dtype=torch.uint8, device=self.device)
+            sigma = torch.empty(n, dtype=torch.float64, device=self.device)
+            _check(self._lib.cv_pacmap_basis_scale(self._h, _ptr(pre), n, c, int(n_neighbors), _ptr(sigma), _ptr(scratch), need,
+                                                   _stream_ptr(self.device)))
+        return sigma
+
+    def pacmap_place_pairs_dev(self, pre_new: torch.Tensor, pre: torch.Tensor, sigma: torch.Tensor, n_neighbors: int):
+        """The device half of ``pacmap_place_pairs`` (``cv_pacmap_place_pairs``): ``pre_new`` (Q, C) and ``pre`` (N, C) dense finite
+        float32, ``sigma`` (N,) float64, tensors on this device, -> ``(neighbours (Q, n_neighbors) int32, stats (8,) int32)`` device
+        tensors.  Launched on the current stream; the scratch comes from the caching allocator on that stream.  Nothing is
+        synchronised or copied."""
+        self._dense("pacmap_place_pairs", "pre_new", pre_new, torch.float32, (None, None))
+        q, c = (int(v) for v in pre_new.shape)
+        self._dense("pacmap_place_pairs", "pre", pre, torch.float32, (None, c))
+        n = int(pre.shape[0])
+        self._dense("pacmap_place_pairs", "sigma", sigma, torch.float64, (n,))
+        need = int(self.pacmap_place_plan(q, n, c, n_neighbors).pairs_scratch_bytes)
+        with torch.cuda.device(self.device):
+            scratch = torch.empty(max(need, 16), dtype=torch.uint8, device=self.device)
+            nbr = torch.empty((q, int(n_neighbors)), dtype=torch.int32, device=self.device)
+            stats = torch.empty(8, dtype=torch.int32, device=self.device)
+            _check(self._lib.cv_pacmap_place_pairs(self._h, _ptr(pre_new), q, _ptr(pre), n, c, int(n_neighbors), _ptr(sigma), _ptr(nbr),
+                                                   _ptr(stats), _ptr(scratch), need, _stream_ptr(self.device)))
+        return nbr, stats
+
+    def pacmap_place_pairs(self, map, pre_new):
+        """``chessvision.embeddings.pacmap_place_pairs`` on the device, index for index: the map's basis and scale and the new rows
+        are uploaded, -> ``(neighbours (Q, n_neighbors) int32 numpy array, stats dict)``.  Synchronises the current stream."""
+        from .embeddings import _place_tables
+
+        x, nn, kc = _place_tables(map, pre_new)
+        dev = [torch.tensor(a).to(self.device) for a in (x, np.ascontiguousarray(map.pre, dtype=np.float32),
+                                                         np.ascontiguousarray(map.sigma, dtype=np.float64))]
+        nbr, stats = self.pacmap_place_pairs_dev(*dev, nn)
+        record = stats.cpu().numpy()
+        return nbr.cpu().numpy(), dict({name: int(record[i]) for i, name in enumerate(NEIGHBOUR_STATS)}, candidates=kc)
+
+    def pacmap_place_dev(self, init: torch.Tensor, basis: torch.Tensor, pairs: torch.Tensor, iterations: int = 450) -> torch.Tensor:
+        """The device half of ``pacmap_place`` (``cv_pacmap_place``): ``init`` (Q, 2) and ``basis`` (N, 2) float32, ``pairs``
+        (Q, n_neighbors) int32, dense tensors on this device, -> the (Q, 2) float32 coordinates after ``iterations`` steps: one
+        launch on the current stream.  Nothing is synchronised or copied."""
+        self._dense("pacmap_place", "init", init, torch.float32, (None, 2))
+        q = int(init.shape[0])
+        self._dense("pacmap_place", "basis", basis, torch.float32, (None, 2))
+        self._dense("pacmap_place", "pairs", pairs, torch.int32, (q, None))
+        with torch.cuda.device(self.device):
+            out = torch.empty((q, 2), dtype=torch.float32, device=self.device)
+            _check(self._lib.cv_pacmap_place(self._h, _ptr(init), q, _ptr(basis), int(basis.shape[0]), _ptr(pairs), int(pairs.shape[1]),
+                                             int(iterations), _ptr(out), _stream_ptr(self.device)))
+        return out
+
+    def pacmap_place(self, init, basis_coordinates, pairs, iterations: int = 450) -> np.ndarray:
+        """``chessvision.embeddings.pacmap_place`` on the device, bit for bit.  Synchronises the current stream."""
+        from .embeddings import check_pacmap_place_inputs
+
+        dev = [torch.tensor(a).to(self.device) for a in check_pacmap_place_inputs(init, basis_coordinates, pairs)]
+        return self.pacmap_place_dev(*dev, iterations=int(iterations)).cpu().numpy()
 
     def extraction_scores_dev(self, values: torch.Tensor, transform: str = "none", want_mask: bool = False):
         """The device half of ``extraction_scores``: launches the score kernel on the current stream behind whatever produced

@@ -44,6 +44,8 @@ static_assert(sizeof(cv_pacmap_stats_t) == sizeof(cv::PacmapStats) && sizeof(cv_
               offsetof(cv_pacmap_stats_t, mid_near_draws) == offsetof(cv::PacmapStats, mid_near_draws) &&
               offsetof(cv_pacmap_stats_t, candidates) == offsetof(cv::PacmapStats, candidates),
               "cv_pacmap_stats_t is the kernels' record");
+static_assert(sizeof(cv_pacmap_place_plan_t) == 40 && offsetof(cv_pacmap_place_plan_t, scale_scratch_bytes) == 24,
+              "cv_pacmap_place_plan_t is the layout the Python binding mirrors");
 static_assert(sizeof(cv_square_score_t) == 24 && sizeof(cv_board_score_t) == 64, "layouts the Python binding mirrors");
 
 using namespace cv;
@@ -1700,6 +1702,92 @@ int cv_pacmap_optimise(cv_engine_t* eng, const float* init, int n, const int32_t
         DeviceGuard g(eng->impl.device);
         hipError_t e = pacmap_optimise(init, n, offsets, entries, iterations, out, scratch, (hipStream_t)stream);
         if (e != hipSuccess) return hip_fail(e, "pacmap_optimise");
+        return Status();
+    });
+}
+
+// ---- placing new rows into a fitted map (pacmap.hip) --------------------------------------------------------------------------------
+static Status pacmap_place_limits(const std::string& me, int q, int n, int c, int n_neighbors) {
+    if (q < 1 || q > kNeighbourMaxRows) return fail(CV_ERR_INVALID, me + "q must be in [1, 2^22], got " + std::to_string(q));
+    if (n_neighbors < 1 || n_neighbors > kPacmapMaxNeighbours)
+        return fail(CV_ERR_INVALID, me + "n_neighbors must be in [1, 32], got " + std::to_string(n_neighbors));
+    if (c < 1 || c > kNeighbourMaxC) return fail(CV_ERR_INVALID, me + "c must be in [1, 4096], got " + std::to_string(c));
+    if (!pacmap_place_in_limits(q, n, c, n_neighbors))
+        return fail(CV_ERR_INVALID, me + "n must be at least max(7, n_neighbors + 1) and at most 2^22, got " + std::to_string(n));
+    return Status();
+}
+
+static Status pacmap_scratch(const std::string& me, const void* scratch, size_t scratch_bytes, size_t need) {
+    if (!scratch || ((uintptr_t)scratch & 15u)) return fail(CV_ERR_INVALID, me + "scratch must be a 16-byte aligned device pointer");
+    if (scratch_bytes < need)
+        return fail(CV_ERR_INVALID, me + "scratch_bytes is " + std::to_string(scratch_bytes) + ", " + std::to_string(need) + " needed");
+    return Status();
+}
+
+int cv_pacmap_place_plan(int q, int n, int c, int n_neighbors, cv_pacmap_place_plan_t* plan) {
+    return guarded("cv_pacmap_place_plan", [&]() -> Status {
+        if (!plan) return fail(CV_ERR_INVALID, "cv_pacmap_place_plan: plan is null");
+        CV_TRY(pacmap_place_limits("cv_pacmap_place_plan: ", q, n, c, n_neighbors));
+        const PacmapPlacePlan p = pacmap_place_plan(q, n, c, n_neighbors);
+        *plan = cv_pacmap_place_plan_t{q, n, c, n_neighbors, p.kc, 0, (uint64_t)p.scale_bytes, (uint64_t)p.pairs_bytes};
+        return Status();
+    });
+}
+
+int cv_pacmap_basis_scale(cv_engine_t* eng, const float* pre, int n, int c, int n_neighbors, double* sigma, void* scratch,
+                          size_t scratch_bytes, void* stream) {
+    return guarded("cv_pacmap_basis_scale", [&]() -> Status {
+        CV_TRY(check_engine(eng));
+        const std::string me = "cv_pacmap_basis_scale: ";
+        CV_TRY(pacmap_place_limits(me, 1, n, c, n_neighbors));
+        if (!pre || ((uintptr_t)pre & 3u)) return fail(CV_ERR_INVALID, me + "pre must be a 4-byte aligned device pointer");
+        if (!sigma || ((uintptr_t)sigma & 7u)) return fail(CV_ERR_INVALID, me + "sigma must be an 8-byte aligned device pointer");
+        CV_TRY(pacmap_scratch(me, scratch, scratch_bytes, pacmap_place_plan(1, n, c, n_neighbors).scale_bytes));
+        DeviceGuard g(eng->impl.device);
+        hipError_t e = pacmap_basis_scale(pre, n, c, n_neighbors, sigma, scratch, (hipStream_t)stream);
+        if (e != hipSuccess) return hip_fail(e, "pacmap_basis_scale");
+        return Status();
+    });
+}
+
+int cv_pacmap_place_pairs(cv_engine_t* eng, const float* pre_new, int q, const float* pre, int n, int c, int n_neighbors,
+                          const double* sigma, int32_t* neighbours, cv_neighbour_stats_t* stats, void* scratch, size_t scratch_bytes,
+                          void* stream) {
+    return guarded("cv_pacmap_place_pairs", [&]() -> Status {
+        CV_TRY(check_engine(eng));
+        const std::string me = "cv_pacmap_place_pairs: ";
+        CV_TRY(pacmap_place_limits(me, q, n, c, n_neighbors));
+        if (!pre_new || ((uintptr_t)pre_new & 3u)) return fail(CV_ERR_INVALID, me + "pre_new must be a 4-byte aligned device pointer");
+        if (!pre || ((uintptr_t)pre & 3u)) return fail(CV_ERR_INVALID, me + "pre must be a 4-byte aligned device pointer");
+        if (!sigma || ((uintptr_t)sigma & 7u)) return fail(CV_ERR_INVALID, me + "sigma must be an 8-byte aligned device pointer");
+        if (!neighbours || ((uintptr_t)neighbours & 3u)) return fail(CV_ERR_INVALID, me + "neighbours must be a 4-byte aligned device pointer");
+        if ((uintptr_t)stats & 3u) return fail(CV_ERR_INVALID, me + "stats must be 4-byte aligned");
+        CV_TRY(pacmap_scratch(me, scratch, scratch_bytes, pacmap_place_plan(q, n, c, n_neighbors).pairs_bytes));
+        DeviceGuard g(eng->impl.device);
+        hipError_t e = pacmap_place_pairs(pre_new, q, pre, n, c, n_neighbors, sigma, neighbours, reinterpret_cast<NeighbourStats*>(stats),
+                                          scratch, (hipStream_t)stream);
+        if (e != hipSuccess) return hip_fail(e, "pacmap_place_pairs");
+        return Status();
+    });
+}
+
+int cv_pacmap_place(cv_engine_t* eng, const float* init, int q, const float* basis, int n, const int32_t* neighbours, int n_neighbors,
+                    int iterations, float* out, void* stream) {
+    return guarded("cv_pacmap_place", [&]() -> Status {
+        CV_TRY(check_engine(eng));
+        const std::string me = "cv_pacmap_place: ";
+        if (q < 1 || q > kNeighbourMaxRows) return fail(CV_ERR_INVALID, me + "q must be in [1, 2^22], got " + std::to_string(q));
+        if (n < 1 || n > kNeighbourMaxRows) return fail(CV_ERR_INVALID, me + "n must be in [1, 2^22], got " + std::to_string(n));
+        if (n_neighbors < 1 || n_neighbors > kPacmapMaxNeighbours)
+            return fail(CV_ERR_INVALID, me + "n_neighbors must be in [1, 32], got " + std::to_string(n_neighbors));
+        if (iterations < 0) return fail(CV_ERR_INVALID, me + "iterations must not be negative, got " + std::to_string(iterations));
+        if (!init || ((uintptr_t)init & 7u)) return fail(CV_ERR_INVALID, me + "init must be an 8-byte aligned device pointer");
+        if (!basis || ((uintptr_t)basis & 7u)) return fail(CV_ERR_INVALID, me + "basis must be an 8-byte aligned device pointer");
+        if (!out || ((uintptr_t)out & 7u) || out == init) return fail(CV_ERR_INVALID, me + "out must be an 8-byte aligned device pointer other than init");
+        if (!neighbours || ((uintptr_t)neighbours & 3u)) return fail(CV_ERR_INVALID, me + "neighbours must be a 4-byte aligned device pointer");
+        DeviceGuard g(eng->impl.device);
+        hipError_t e = pacmap_place(init, q, basis, n, neighbours, n_neighbors, iterations, out, (hipStream_t)stream);
+        if (e != hipSuccess) return hip_fail(e, "pacmap_place");
         return Status();
     });
 }

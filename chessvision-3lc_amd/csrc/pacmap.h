@@ -1,4 +1,5 @@
-// pacmap.h -- host interface of the PaCMAP reduction of embedding tables (pacmap.hip): the three pair sets and the optimiser.
+// pacmap.h -- host interface of the PaCMAP reduction of embedding tables (pacmap.hip): the three pair sets and the optimiser, and
+// (last part) the placement of new rows into a fitted map.
 //
 // The definition is chessvision/embeddings.py (pacmap_pairs, pacmap_incidence, pacmap_schedule, pacmap_optimise), a reading of Wang,
 // Huang, Rudin, Shaposhnik (JMLR 2021) and of the pacmap package's defaults; DESIGN.md section 4 "Embedding reduction".  Both device
@@ -63,7 +64,35 @@ hipError_t pacmap_pairs(const float* pre, int n, int c, int n_neighbors, int n_m
 hipError_t pacmap_optimise(const float* init, int n, const int32_t* offsets, const int32_t* entries, int iterations, float* out,
                            void* scratch, hipStream_t s);
 
-// Row `it` of embeddings.pacmap_schedule: lr_t, w_n, w_MN, w_FP.
-void pacmap_schedule_row(int it, double& b1, double& b2, float out[4]);
+// Row `it` of embeddings.pacmap_schedule: lr_t, w_n, w_MN, w_FP.  Double multiply, square root and divide round correctly on both
+// sides, so the host's optimiser loop and the placement kernel get the same bits from it.
+__host__ __device__ void pacmap_schedule_row(int it, double& b1, double& b2, float out[4]);
+
+// ---- placing new rows into a fitted map (embeddings.pacmap_place_pairs, pacmap_place; a reading of the package's transform) -----------
+//   basis scale  the fit's candidate search and sigma kernel again, sigma written to the caller's (n,) array: what the map keeps;
+//   place pairs  embedding_neighbours of the q new rows against the basis (kc = min(n_neighbors + 50, 64, n), no row excluded), the
+//                sigma kernel over the q candidate rows, the choose kernel with sigma_q from those and sigma_j from the basis array;
+//   place        ONE launch: one lane per new point, its partners' coordinates staged in LDS, every Adam step in registers.
+struct PacmapPlacePlan {
+    int q, n, c, n_neighbors, kc;
+    size_t off_stats, off_cand_i, off_cand_d, off_sigma, off_search, pairs_bytes;   // the place-pairs scratch, offsets multiples of 256
+    size_t scale_bytes;                                                             // the basis-scale scratch: pacmap_plan's pairs block
+};
+
+// q in [1, kNeighbourMaxRows]; n, c and n_neighbors as pacmap_in_limits(n, c, n_neighbors, 0, 0) has them.
+bool pacmap_place_in_limits(int q, int n, int c, int n_neighbors);
+PacmapPlacePlan pacmap_place_plan(int q, int n, int c, int n_neighbors);
+
+// All pointers DEVICE; launches and hipMemsetAsync only on s, nothing is allocated, nothing synchronises.
+// sigma (n,) double <- the scale of every row of pre (n, c) in pacmap_pairs' neighbour choice; scratch 16-byte aligned, scale_bytes.
+hipError_t pacmap_basis_scale(const float* pre, int n, int c, int n_neighbors, double* sigma, void* scratch, hipStream_t s);
+// neighbours (q, n_neighbors) int32 <- the partners in the basis pre (n, c) of the new rows pre_new (q, c), all values finite; sigma
+// (n,) double as pacmap_basis_scale wrote it; stats nullable; scratch 16-byte aligned, pairs_bytes.
+hipError_t pacmap_place_pairs(const float* pre_new, int q, const float* pre, int n, int c, int n_neighbors, const double* sigma,
+                              int32_t* neighbours, NeighbourStats* stats, void* scratch, hipStream_t s);
+// out (q, 2) <- init (q, 2) after `iterations` steps towards basis (n, 2) over neighbours (q, n_neighbors) (a partner outside [0, n)
+// is skipped); float32, 8-byte aligned, out != init.  No scratch.  iterations == 0 copies init.
+hipError_t pacmap_place(const float* init, int q, const float* basis, int n, const int32_t* neighbours, int n_neighbors, int iterations,
+                        float* out, hipStream_t s);
 
 }  // namespace cv

@@ -1,6 +1,7 @@
-// pacmap.hip -- PaCMAP on the device: scaled-distance neighbour choice, mid-near and further draws, the Adam optimiser.
-// The contract is in pacmap.h and include/chessvision_hip.h (cv_pacmap_pairs, cv_pacmap_optimise); the definition both are held to
-// is chessvision/embeddings.py.  Every float operation that the definition rounds is rounded here: contraction is off in each
+// pacmap.hip -- PaCMAP on the device: scaled-distance neighbour choice, mid-near and further draws, the Adam optimiser; and the
+// placement of new rows into a fitted map: their pairs into the basis and all Adam steps of every new point in one launch.
+// The contract is in pacmap.h and include/chessvision_hip.h (cv_pacmap_pairs, cv_pacmap_optimise, cv_pacmap_basis_scale,
+// cv_pacmap_place_pairs, cv_pacmap_place); the definition all are held to is chessvision/embeddings.py.  Every float operation that the definition rounds is rounded here: contraction is off in each
 // function that computes, division and square root are the correctly rounded defaults (no fast-math in the Makefile).  This file is
 // part of cv_api.cpp's translation unit.
 #include <math.h>
@@ -59,18 +60,20 @@ __global__ __launch_bounds__(kPmBlock) void pm_sigma_kernel(const double* __rest
 }
 
 // One wave per row, lane t holds candidate t (kc <= 64): its rank among the row's candidates by (scaled, j) is its output slot.
+// sigma_row has `rows` entries, sigma_col n: the same array for a table against itself, the new rows' and the basis' for a placement.
 __global__ __launch_bounds__(256) void pm_choose_kernel(const int32_t* __restrict__ cand_i, const double* __restrict__ cand_d,
-                                                        const double* __restrict__ sigma, int n, int kc, int nn, int32_t* __restrict__ out) {
+                                                        const double* __restrict__ sigma_row, const double* __restrict__ sigma_col, int rows,
+                                                        int n, int kc, int nn, int32_t* __restrict__ out) {
 #pragma clang fp contract(off)
     const int lane = threadIdx.x & 63, row = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= n) return;
+    if (row >= rows) return;
     int j = 0x7fffffff;
     double sc = (double)__builtin_huge_valf();
     if (lane < kc) {
         const int cj = cand_i[(size_t)row * kc + lane];
-        if (cj >= 0 && cj < n) {                             // a finite table has n - 1 >= kc eligible rows: always
+        if (cj >= 0 && cj < n) {                             // finite tables have at least kc eligible rows: always
             j = cj;
-            const double scale = sigma[row] * sigma[cj];
+            const double scale = sigma_row[row] * sigma_col[cj];
             sc = cand_d[(size_t)row * kc + lane] / scale;
         }
     }
@@ -209,6 +212,57 @@ __global__ __launch_bounds__(kPmBlock) void pm_step_kernel(const float2* __restr
     yout[p] = y;
 }
 
+// ---- placement: every Adam step of a new point in one launch ---------------------------------------------------------------------------
+// One lane per new point.  Its partners' coordinates never move: they are read once into LDS as [slot][lane] float2 (8-byte reads of
+// consecutive lanes: conflict-free; a private array indexed by the slot would live in scratch memory) and walked `iterations` times
+// with m and v in registers.  The schedule is pacmap_schedule_row, evaluated by every lane in double.
+__global__ __launch_bounds__(kPmBlock) void pm_place_kernel(const float2* __restrict__ init, int q, const float2* __restrict__ basis, int n,
+                                                            const int32_t* __restrict__ pairs, int nn, int iterations,
+                                                            float2* __restrict__ out) {
+#pragma clang fp contract(off)
+    __shared__ float2 partner[kPacmapMaxNeighbours][kPmBlock];
+    const int lane = threadIdx.x, p = blockIdx.x * kPmBlock + lane;
+    if (p >= q) return;                                       // no barrier below: a lane reads only the LDS column it wrote
+    uint32_t live = 0;
+    for (int u = 0; u < nn; ++u) {
+        const int b = pairs[(size_t)p * nn + u];
+        const bool ok = b >= 0 && b < n;
+        if (ok) live |= 1u << u;
+        partner[u][lane] = ok ? basis[b] : make_float2(0.f, 0.f);
+    }
+    float2 y = init[p];
+    float m0 = 0.f, m1 = 0.f, v0 = 0.f, v1 = 0.f;
+    const float c1 = (float)(1.0 - 0.9), c2 = (float)(1.0 - 0.999), eps = 1e-7f;
+    double b1 = 1.0, b2 = 1.0;
+    for (int it = 0; it < iterations; ++it) {
+        float row[4];
+        pacmap_schedule_row(it, b1, b2, row);
+        const float lr = row[0], w_n = row[1];
+        float g0 = 0.f, g1 = 0.f;
+        for (int u = 0; u < nn; ++u) {
+            const float2 yb = partner[u][lane];
+            const float e0 = y.x - yb.x, e1 = y.y - yb.y;
+            float d = 1.f;
+            d = d + e0 * e0;
+            d = d + e1 * e1;
+            const float t = 10.f + d;
+            const float w = w_n * (20.f / (t * t));
+            const float s0 = w * e0, s1 = w * e1;
+            if ((live >> u) & 1u) {
+                g0 = g0 + s0;
+                g1 = g1 + s1;
+            }
+        }
+        m0 = m0 + c1 * (g0 - m0);
+        m1 = m1 + c1 * (g1 - m1);
+        v0 = v0 + c2 * (g0 * g0 - v0);
+        v1 = v1 + c2 * (g1 * g1 - v1);
+        y.x = y.x - (lr * m0) / (sqrtf(v0) + eps);
+        y.y = y.y - (lr * m1) / (sqrtf(v1) + eps);
+    }
+    out[p] = y;
+}
+
 inline size_t pm_up(size_t v) { return (v + 255) & ~(size_t)255; }
 
 }  // namespace
@@ -260,13 +314,78 @@ hipError_t pacmap_pairs(const float* pre, int n, int c, int n_neighbors, int n_m
         return e;
     const dim3 lanes((n + kPmBlock - 1) / kPmBlock), block(kPmBlock);
     hipLaunchKernelGGL(pm_sigma_kernel, lanes, block, 0, s, cand_d, n, p.kc, sigma, st);
-    hipLaunchKernelGGL(pm_choose_kernel, dim3((n + 3) / 4), dim3(256), 0, s, cand_i, cand_d, sigma, n, p.kc, n_neighbors, neighbours);
+    hipLaunchKernelGGL(pm_choose_kernel, dim3((n + 3) / 4), dim3(256), 0, s, cand_i, cand_d, sigma, sigma, n, n, p.kc, n_neighbors, neighbours);
     if (n_mn) hipLaunchKernelGGL(pm_mid_near_kernel, lanes, block, 0, s, pre, n, c, n_mn, seed, mid_near, st);
     if (n_fp) hipLaunchKernelGGL(pm_further_kernel, lanes, block, 0, s, neighbours, n, n_neighbors, n_fp, seed, further, st);
     return hipGetLastError();
 }
 
-void pacmap_schedule_row(int it, double& b1, double& b2, float out[4]) {
+hipError_t pacmap_basis_scale(const float* pre, int n, int c, int n_neighbors, double* sigma, void* scratch, hipStream_t s) {
+    if (!pre || !sigma || !scratch || ((uintptr_t)scratch & 15u) || !pacmap_in_limits(n, c, n_neighbors, 0, 0)) return hipErrorInvalidValue;
+    const PacmapPlan p = pacmap_plan(n, c, n_neighbors, 0, 0);
+    char* base = static_cast<char*>(scratch);
+    PacmapStats* st = reinterpret_cast<PacmapStats*>(base + p.off_stats);
+    int32_t* cand_i = reinterpret_cast<int32_t*>(base + p.off_cand_i);
+    double* cand_d = reinterpret_cast<double*>(base + p.off_cand_d);
+    hipError_t e;
+    if ((e = embedding_neighbours(pre, n, pre, n, c, p.kc, kNeighbourExcludeSelf, cand_i, cand_d, &st->neighbours, base + p.off_search, s)) !=
+        hipSuccess)
+        return e;
+    hipLaunchKernelGGL(pm_sigma_kernel, dim3((n + kPmBlock - 1) / kPmBlock), dim3(kPmBlock), 0, s, cand_d, n, p.kc, sigma, st);
+    return hipGetLastError();
+}
+
+bool pacmap_place_in_limits(int q, int n, int c, int n_neighbors) {
+    return q >= 1 && q <= kNeighbourMaxRows && pacmap_in_limits(n, c, n_neighbors, 0, 0);
+}
+
+PacmapPlacePlan pacmap_place_plan(int q, int n, int c, int n_neighbors) {
+    PacmapPlacePlan p{};
+    p.q = q; p.n = n; p.c = c; p.n_neighbors = n_neighbors;
+    p.kc = std::min(std::min(n_neighbors + kPacmapExtraCandidates, kNeighbourMaxK), n);
+    size_t o = 0;
+    auto take = [&](size_t bytes) { const size_t at = o; o += pm_up(bytes); return at; };
+    p.off_stats = take(sizeof(PacmapStats));
+    p.off_cand_i = take((size_t)q * p.kc * sizeof(int32_t));
+    p.off_cand_d = take((size_t)q * p.kc * sizeof(double));
+    p.off_sigma = take((size_t)q * sizeof(double));
+    p.off_search = take(neighbour_plan(q, n, c, p.kc).bytes);
+    p.pairs_bytes = o;
+    p.scale_bytes = pacmap_plan(n, c, n_neighbors, 0, 0).pairs_bytes;
+    return p;
+}
+
+hipError_t pacmap_place_pairs(const float* pre_new, int q, const float* pre, int n, int c, int n_neighbors, const double* sigma,
+                              int32_t* neighbours, NeighbourStats* stats, void* scratch, hipStream_t s) {
+    if (!pre_new || !pre || !sigma || !neighbours || !scratch || ((uintptr_t)scratch & 15u) || !pacmap_place_in_limits(q, n, c, n_neighbors))
+        return hipErrorInvalidValue;
+    const PacmapPlacePlan p = pacmap_place_plan(q, n, c, n_neighbors);
+    char* base = static_cast<char*>(scratch);
+    PacmapStats* st = reinterpret_cast<PacmapStats*>(base + p.off_stats);
+    int32_t* cand_i = reinterpret_cast<int32_t*>(base + p.off_cand_i);
+    double* cand_d = reinterpret_cast<double*>(base + p.off_cand_d);
+    double* sigma_q = reinterpret_cast<double*>(base + p.off_sigma);
+    hipError_t e;
+    if ((e = embedding_neighbours(pre_new, q, pre, n, c, p.kc, 0, cand_i, cand_d, stats ? stats : &st->neighbours, base + p.off_search, s)) !=
+        hipSuccess)
+        return e;
+    hipLaunchKernelGGL(pm_sigma_kernel, dim3((q + kPmBlock - 1) / kPmBlock), dim3(kPmBlock), 0, s, cand_d, q, p.kc, sigma_q, st);
+    hipLaunchKernelGGL(pm_choose_kernel, dim3((q + 3) / 4), dim3(256), 0, s, cand_i, cand_d, sigma_q, sigma, q, n, p.kc, n_neighbors, neighbours);
+    return hipGetLastError();
+}
+
+hipError_t pacmap_place(const float* init, int q, const float* basis, int n, const int32_t* neighbours, int n_neighbors, int iterations,
+                        float* out, hipStream_t s) {
+    if (!init || !basis || !neighbours || !out || out == init || ((uintptr_t)init & 7u) || ((uintptr_t)basis & 7u) || ((uintptr_t)out & 7u) ||
+        q < 1 || q > kNeighbourMaxRows || n < 1 || n > kNeighbourMaxRows || n_neighbors < 1 || n_neighbors > kPacmapMaxNeighbours ||
+        iterations < 0)
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL(pm_place_kernel, dim3((q + kPmBlock - 1) / kPmBlock), dim3(kPmBlock), 0, s, reinterpret_cast<const float2*>(init), q,
+                       reinterpret_cast<const float2*>(basis), n, neighbours, n_neighbors, iterations, reinterpret_cast<float2*>(out));
+    return hipGetLastError();
+}
+
+__host__ __device__ void pacmap_schedule_row(int it, double& b1, double& b2, float out[4]) {
 #pragma clang fp contract(off)
     b1 = b1 * 0.9;
     b2 = b2 * 0.999;

@@ -645,6 +645,51 @@ int cv_pacmap_pairs(cv_engine_t* eng, const float* pre, int n, int c, int n_neig
 int cv_pacmap_optimise(cv_engine_t* eng, const float* init, int n, const int32_t* offsets, const int32_t* entries, int64_t n_entries,
                        int iterations, float* out, void* scratch, size_t scratch_bytes, void* stream);
 
+/* ---- placing new rows into a fitted map (additions under ABI 6; detect with dlsym(handle, "cv_pacmap_place")) ------------------- */
+/* The other half of run.reduce_embeddings_by_foreign_table_url: the reducer is fitted on one table (the entries above) and every other
+ * table of the run is placed into the SAME map, the basis held still.  Again a READING, of the pacmap package's transform: pairs from
+ * each new point to its nearest basis points by the scaled distance, the attraction term alone, the same 450-step schedule; defined
+ * in numpy by chessvision/embeddings.py (pacmap_place_pairs, pacmap_place), derived in DESIGN.md section 4 "Placing new points".  The
+ * entries equal that definition exactly: pairs index for index, coordinates bit for bit.  Deviations from the package: exact
+ * neighbour candidates, at most 64 of them, the Adam bias powers as running products.
+ *
+ * What the caller keeps of a fit (embeddings.EmbeddingMap): pre (n, c) float32, the preprocessed basis; its coordinates (n, 2); and
+ *   sigma (n) double, the rows' scale in cv_pacmap_pairs' neighbour choice, which cv_pacmap_basis_scale recomputes: the candidate
+ *   search of cv_pacmap_pairs (kc = min(n_neighbors + 50, 64, n - 1), exclude-self) and max(mean of sqrt(D) at ranks 3, 4, 5, 1e-10).
+ * New rows are preprocessed on the host with the fit's stored parameters (embeddings.pacmap_preprocess_new) -> pre_new (q, c).
+ *
+ * cv_pacmap_place_pairs -> neighbours (q, n_neighbors) int32: the kc = min(n_neighbors + 50, 64, n) exact nearest basis rows of
+ *   every new row (cv_embedding_neighbours, flags 0: no row excluded); sigma_q by the rule above on the row's own candidates; the
+ *   row keeps the n_neighbors candidates with the smallest (D_qj / (sigma_q * sigma[j]), j), ascending.  stats: the search's record.
+ * cv_pacmap_place: ONE launch for all iterations, one lane per new point (no new point reads another: a batch equals its rows placed
+ *   one at a time, bit for bit).  Per iteration it = 0 .. iterations - 1 and new point p, Yb = basis, float32, every operation
+ *   rounded once:
+ *       g = (0, 0);  for slot u in order (a partner outside [0, n) is skipped):
+ *           e = Y[p] - Yb[b_u];  d = 1;  d = d + e0*e0;  d = d + e1*e1;  t = 10 + d;  w = w_n * (20 / (t*t));  g = g + w*e
+ *       m = m + c1*(g - m);  v = v + c2*(g*g - v);  Y[p] = Y[p] - (lr_t*m) / (sqrt(v) + 1e-7f)
+ *   with lr_t, w_n, c1, c2 as cv_pacmap_optimise has them (computed in the kernel, in double).  iterations == 0: out = init.
+ * Limits: 1 <= q <= 1 << 22, 1 <= n_neighbors <= 32, 1 <= c <= 4096, max(7, n_neighbors + 1) <= n <= 1 << 22.  cv_pacmap_place_plan
+ *   checks them and sizes the two scratch blocks; cv_pacmap_place needs none and takes any 1 <= n <= 1 << 22.
+ *
+ * All array arguments: DEVICE.  init, basis and out 8-byte aligned, out != init; sigma 8-byte aligned; stats nullable; scratch
+ * 16-byte aligned, the caller's, reusable once `stream` has passed the call.  Asynchronous on `stream`; allocate nothing and
+ * synchronise nothing.  CV_ERR_INVALID names the offending argument. */
+typedef struct cv_pacmap_place_plan {
+    int32_t q, n, c, n_neighbors;
+    int32_t candidates;               /* kc of cv_pacmap_place_pairs */
+    int32_t reserved;                 /* 0 */
+    uint64_t scale_scratch_bytes;     /* cv_pacmap_basis_scale (depends on n, c, n_neighbors) */
+    uint64_t pairs_scratch_bytes;     /* cv_pacmap_place_pairs */
+} cv_pacmap_place_plan_t;
+int cv_pacmap_place_plan(int q, int n, int c, int n_neighbors, cv_pacmap_place_plan_t* plan);
+int cv_pacmap_basis_scale(cv_engine_t* eng, const float* pre, int n, int c, int n_neighbors, double* sigma, void* scratch,
+                          size_t scratch_bytes, void* stream);
+int cv_pacmap_place_pairs(cv_engine_t* eng, const float* pre_new, int q, const float* pre, int n, int c, int n_neighbors,
+                          const double* sigma, int32_t* neighbours, cv_neighbour_stats_t* stats, void* scratch, size_t scratch_bytes,
+                          void* stream);
+int cv_pacmap_place(cv_engine_t* eng, const float* init, int q, const float* basis, int n, const int32_t* neighbours, int n_neighbors,
+                    int iterations, float* out, void* stream);
+
 /* ---- one image, host to host: the native form of ChessVision.process_image (core.py:152-195) ---------------------------------- */
 /* Everything a cgo / JNI / C++ host needs for the reference's per-image entry point in ONE call: INTER_AREA resize to 256x256
  * (core.py:212), UNet forward, sigmoid / threshold mask (core.py:273, utils.py:101-112), contours -> quadrangle (core.py:357-411),
