@@ -1411,6 +1411,16 @@ class HipEngine:
                                                  bias.ctypes.data_as(_fp), _ptr(y), _stream_ptr(self.device)))
         return y
 
+    def op_kernels(self) -> list[str]:
+        """Kernel form strings of the launches the last op_conv2d / op_conv_transpose2x2 call (or profile()) recorded, in launch
+        order: what the launch planner chose for that shape, e.g. ``conv3x3_halo_kernel<half_t,64,8x16,splitK4>``."""
+        out = []
+        kern = ctypes.create_string_buffer(160)
+        while self._lib.cv_profile_entry(self._h, len(out), None, 0, None, None, None) == 0:
+            _check(self._lib.cv_profile_entry_kernel(self._h, len(out), kern, 160))
+            out.append(kern.value.decode())
+        return out
+
     def op_outc_1x1(self, x, w, bias, threshold: float = 0.5):
         """(n,c,h,w) -> (logits (n,1,h,w) f32, mask (n,h,w) u8) through the stand-alone OutConv kernel."""
         x = x.to(self.device, torch.float32).contiguous()

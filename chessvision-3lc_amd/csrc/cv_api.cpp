@@ -933,6 +933,21 @@ int cv_engine_import_calibration(cv_engine_t* eng, const char* model, const int3
     });
 }
 
+// The single-layer convolution entry points run their one launch with the launch recorder on (Engine::profiling: run_conv then
+// describes the launch it plans -- name, kernel form string, MACs, bytes -- exactly as it does for cv_profile_convs), so that a test can
+// ask which kernel form a shape took: cv_profile_entry / cv_profile_entry_kernel describe that launch until the next recorded call.
+// The recorder changes no planner choice: it only keeps run_conv from deferring a launch for pairing, which needs a `defer` slot
+// that these entry points never set.
+static Status run_conv_recorded(Engine& e, ConvLayer& L, const TensorRef& x, const TensorRef& y, const TensorRef* res, bool relu, hipStream_t st) {
+    e.prof_clear();
+    e.profiling = true;
+    Status s = e.run_conv(L, x, y, res, relu, st);
+    e.profiling = false;
+    if (s.ok()) s = e.prof_collect();
+    if (!s.ok()) e.prof_clear();
+    return s;
+}
+
 int cv_op_conv2d(cv_engine_t* eng, const float* x, int n, int cin, int h, int w_, const float* w_host, int cout,
                  int k, int stride, const float* scale_host, const float* shift_host, const float* residual,
                  int relu, float* y, void* stream) {
@@ -961,7 +976,7 @@ int cv_op_conv2d(cv_engine_t* eng, const float* x, int n, int cin, int h, int w_
                 s = ar.create(n, ho, wo, cout, e.dt);
                 if (s.ok()) { err = pack_nchw_f32(e.dt, residual, cout, ar.ref(n), e.guard_ptr(), st); rr = ar.ref(n); }
             }
-            if (s.ok() && err == hipSuccess) s = e.run_conv(L, ax.ref(n), ay.ref(n), residual ? &rr : nullptr, relu != 0, st);
+            if (s.ok() && err == hipSuccess) s = run_conv_recorded(e, L, ax.ref(n), ay.ref(n), residual ? &rr : nullptr, relu != 0, st);
             if (s.ok() && err == hipSuccess) err = unpack_nchw_f32(e.dt, ay.ref(n), y, st);
             if (s.ok() && err == hipSuccess) err = hipStreamSynchronize(st);
             if (s.ok() && err != hipSuccess) s = hip_fail(err, "cv_op_conv2d");
@@ -986,7 +1001,7 @@ int cv_op_conv_transpose2x2(cv_engine_t* eng, const float* x, int n, int cin, in
         Status s;
         if ((s = ax.create(n, h, w_, cin, e.dt)).ok() && (s = ay.create(n, 2 * h, 2 * w_, cout, e.dt)).ok()) {
             hipError_t err = pack_nchw_f32(e.dt, x, cin, ax.ref(n), e.guard_ptr(), st);
-            if (err == hipSuccess) s = e.run_conv(L, ax.ref(n), ay.ref(n), nullptr, false, st);
+            if (err == hipSuccess) s = run_conv_recorded(e, L, ax.ref(n), ay.ref(n), nullptr, false, st);
             if (s.ok() && err == hipSuccess) err = unpack_nchw_f32(e.dt, ay.ref(n), y, st);
             if (s.ok() && err == hipSuccess) err = hipStreamSynchronize(st);
             if (s.ok() && err != hipSuccess) s = hip_fail(err, "cv_op_conv_transpose2x2");

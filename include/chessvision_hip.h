@@ -250,7 +250,9 @@ int cv_profile_convs(cv_engine_t* eng, const char* model, const void* x, int bat
                      void* stream, float* conv_ms_total, int* conv_launches, float* all_ms_total);
 
 /* Iterate the per-launch records of the last cv_profile_convs call (index 0 .. until CV_ERR_INVALID):
- * name = producing module, ms = event-timed duration, macs = algorithmic multiply-accumulates. */
+ * name = producing module, ms = event-timed duration, macs = algorithmic multiply-accumulates.
+ * cv_op_conv2d and cv_op_conv_transpose2x2 record their own launch the same way: after either call the records describe
+ * that one launch (and nothing else) until the next recorded call replaces them. */
 int cv_profile_entry(cv_engine_t* eng, int index, char* name, int name_cap, float* ms, double* macs,
                      int* is_conv);
 
@@ -265,7 +267,10 @@ int cv_profile_entry_kernel(cv_engine_t* eng, int index, char* kernel, int kerne
 /* Stand-alone single-layer entry points used by the parity tests (float32 NCHW device tensors in,
  * float32 NCHW out; packing to the internal layout happens inside, on `stream`).
  *   conv:  y = act( scale[c] * conv2d(x, w, stride, pad=(k-1)/2) + shift[c] (+ residual) )
- *          w: HOST (cout,cin,k,k) float32; scale/shift: HOST (cout); residual nullable (device). */
+ *          w: HOST (cout,cin,k,k) float32; scale/shift: HOST (cout); residual nullable (device).
+ * The two convolution entry points run with the launch recorder on: cv_profile_entry / cv_profile_entry_kernel then name the
+ * kernel form the launch planner chose for this shape ("conv_igemm_kernel<half_t,128x128,ring3,POS>", ...), so a test can
+ * check that a shape still reaches the form it was written for.  Recording does not change the planner's choice. */
 int cv_op_conv2d(cv_engine_t* eng, const float* x, int n, int cin, int h, int w_, const float* w_host,
                  int cout, int k, int stride, const float* scale_host, const float* shift_host,
                  const float* residual, int relu, float* y, void* stream);
