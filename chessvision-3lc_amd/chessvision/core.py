@@ -17,8 +17,11 @@ Deliberate deviations, all on the permissive side:
   * ``board_extractor_weights=None`` resolves to ``constants.BEST_EXTRACTOR_WEIGHTS`` at load time (the reference
     crashes on ``Path(None)``); the attribute itself keeps the value passed in.
   * model ids ``""`` / ``"unet"`` / ``"hip"`` select the UNet, ``""`` / ``"resnet18"`` the ResNet-18, ``"resnet34"`` the ResNet-34
-    (``evaluate.py:212,214`` passes ``""``); ``"yolo"`` raises ImportError -- that model family is out of scope.  As in the reference,
-    the classifier's architecture comes from the id, never from the checkpoint.
+    (``evaluate.py:212,214`` passes ``""``), ``"yolov8n-cls"`` .. ``"yolov8x-cls"`` an ultralytics YOLOv8-cls classifier (the names the
+    reference's ``train_yolo_classifier.py`` passes to ``--model``, minus ``.pt``; it is fed as the reference feeds it: the (64,1,64,64)
+    squares in [0,1], no resize or crop, index k = ``constants.LABEL_NAMES[k]``).  ``"yolo"`` still raises ImportError and ``None`` still
+    means ResNet-18: the YOLO segmentation extractor is out of scope.  As in the reference, the classifier's architecture comes from
+    the id, never from the checkpoint.
   * lazy initialisation is guarded by a lock (Flask request threads share one instance, ``cv_endpoint.py:131-133``).
   * extras: ``precision=`` kwarg (env ``CHESSVISION_HIP_PRECISION``: "f16x3" (default) | "f32" | "f16" | "f16r", or
     "<extractor>+<classifier>", e.g. "f16x3+f16r" = f32-grade UNet with the classifier in its fp16 mode -- one engine per model),
@@ -165,7 +168,8 @@ class ChessVision:
         logger.info("Initializing piece classifier model...")
         model_id = self._classifier_model_id
         if model_id == "yolo":
-            raise ImportError("YOLO classifiers are outside the MI355X hot path (ResNet-18 / ResNet-34 only)")
+            raise ImportError("YOLO classifiers are outside the MI355X hot path (ResNet-18 / ResNet-34 only) under the id 'yolo': "
+                              "name the architecture -- classifier_model_id='yolov8m-cls' (or n / s / l / x) runs a YOLOv8-cls checkpoint")
         if model_id is None:
             # the reference tries YOLO first and falls back to ResNet-18 on ImportError (core.py:113-130)
             logger.info("YOLO not available, falling back to ResNet18")
@@ -335,12 +339,9 @@ class ChessVision:
             unet_eng, cls_eng = engines[parts[0]], engines[parts[-1]]
             state, _ = utils.read_checkpoint(self._board_extractor_weights or constants.BEST_EXTRACTOR_WEIGHTS)
             unet_eng.load_unet(state)
-            state, _ = utils.read_checkpoint(self._classifier_weights or constants.BEST_CLASSIFIER_WEIGHTS)
             arch = getattr(self._classifier, "model_name", "") or "resnet18"  # the architecture of the primary classifier
-            if arch == "resnet18":
-                cls_eng.load_resnet18(state)
-            else:
-                cls_eng.load_resnet(state, arch)
+            state, _ = utils.read_classifier_checkpoint(self._classifier_weights or constants.BEST_CLASSIFIER_WEIGHTS, arch)
+            utils.load_classifier_state(cls_eng, arch, state)
             slot = _RequestSlot(unet_eng, cls_eng, torch.cuda.Stream(self.device))
             self._warm_slot(slot)
         except Exception as exc:                                            # no replica: the instance keeps serving with what it has

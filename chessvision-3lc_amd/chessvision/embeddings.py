@@ -58,6 +58,10 @@ def module_names(model: str, bilinear: bool = False) -> list[str]:
             p = f"up{i}"
             names += [p, p + ".up"] + _double_conv(p + ".conv")
         return names + ["outc", "outc.conv"]
+    if model.startswith("yolov8"):
+        raise ValueError(f"{model}: the reference's integer layer indices are positions in named_modules() of its UNet and its timm ResNets; "
+                         "a YOLOv8-cls classifier has no such table here -- name the tap by its state-dict prefix instead ('model.4.m.1', "
+                         "'model.9.conv'; 'global_pool' is the pooled model.9.conv output, the embedding)")
     if model not in _RESNET_DEPTHS:
         raise ValueError(f"model must be 'unet', 'resnet18' or 'resnet34', got {model!r}")
     names = ["", "conv1", "bn1", "act1", "maxpool"]

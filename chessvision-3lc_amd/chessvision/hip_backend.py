@@ -24,6 +24,9 @@ _LIB_NAME = "libchessvision_hip.so"
 PREC_F32, PREC_F16, PREC_F16X3, PREC_F16R = 0, 1, 2, 3
 ABI_VERSION = 6
 RESNET_ARCHS = ("resnet18", "resnet34")     # piece classifiers with a HIP implementation (cv_load_resnet)
+# ultralytics YOLOv8-cls, all five scales (cv_load_yolo_cls): the names the reference's training script passes to --model, minus ".pt"
+YOLO_CLS_ARCHS = ("yolov8n-cls", "yolov8s-cls", "yolov8m-cls", "yolov8l-cls", "yolov8x-cls")
+CLASSIFIER_ARCHS = RESNET_ARCHS + YOLO_CLS_ARCHS
 _PRECISIONS = {"f32": PREC_F32, "fp32": PREC_F32, "float32": PREC_F32, "f16": PREC_F16, "fp16": PREC_F16,
                "float16": PREC_F16, "f16x3": PREC_F16X3, "split": PREC_F16X3, "f16r": PREC_F16R}
 _PREC_NAMES = {PREC_F32: "f32", PREC_F16: "f16", PREC_F16X3: "f16x3", PREC_F16R: "f16r"}
@@ -81,6 +84,7 @@ SYMBOLS = [
     ("cv_load_unet", _i, [_vp, ctypes.POINTER(_Param), _i]),
     ("cv_load_resnet18", _i, [_vp, ctypes.POINTER(_Param), _i]),
     ("cv_load_resnet", _i, [_vp, ctypes.c_char_p, ctypes.POINTER(_Param), _i]),
+    ("cv_load_yolo_cls", _i, [_vp, ctypes.c_char_p, ctypes.POINTER(_Param), _i]),
     ("cv_engine_set_chunk", _i, [_vp, _i, _i]),
     ("cv_unet_forward", _i, [_vp, _vp, _i, _vp, _vp]),
     ("cv_resnet18_forward", _i, [_vp, _vp, _i, _vp, _vp]),
@@ -101,6 +105,10 @@ SYMBOLS = [
     ("cv_profile_entry", _i, [_vp, _i, ctypes.c_char_p, _i, ctypes.POINTER(_f), ctypes.POINTER(ctypes.c_double),
                               ctypes.POINTER(_i)]),
     ("cv_op_conv2d", _i, [_vp, _vp, _i, _i, _i, _i, _fp, _i, _i, _i, _fp, _fp, _vp, _i, _vp, _vp]),
+    ("cv_op_conv2d_act", _i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _fp, _i, _i, _i, _fp, _fp, _i, _i, _vp, _i, _i, _i, _i, _i, _vp]),
+    ("cv_op_conv_epilogue_ok", _i, [_i, _i, _i, _i, _i, _i, _i, ctypes.POINTER(_i)]),
+    ("cv_op_stem3x3s2", _i, [_vp, _vp, _i, _i, _i, _fp, _fp, _fp, _f, _f, _i, _vp, _vp]),
+    ("cv_op_head_pool_fc", _i, [_vp, _vp, _i, _i, _i, _i, _fp, _fp, _i, _i, _vp, _vp, _vp]),
     ("cv_op_conv_transpose2x2", _i, [_vp, _vp, _i, _i, _i, _i, _fp, _i, _fp, _vp, _vp]),
     ("cv_op_outc_1x1", _i, [_vp, _vp, _i, _i, _i, _i, _fp, _fp, _f, _vp, _vp, _vp]),
     ("cv_op_maxpool2x2", _i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp]),
@@ -620,7 +628,7 @@ class HipEngine:
             self.resnet_chunk //= 2                      # ... which the f32 engine halves for its stem output (resnet.cpp: resnet_load)
         self.has_unet = False
         self.has_resnet = False
-        self.classifier_arch: str | None = None      # "resnet18" | "resnet34" once a ResNet is loaded
+        self.classifier_arch: str | None = None      # "resnet18" | "resnet34" | "yolov8m-cls" | ... once a classifier is loaded
 
     # -- lifecycle ------------------------------------------------------------------------------
     def close(self) -> None:
@@ -655,6 +663,19 @@ class HipEngine:
 
     def load_resnet18(self, state_dict: Mapping[str, object]) -> None:
         self.load_resnet(state_dict, "resnet18")
+
+    def load_yolo_cls(self, state_dict: Mapping[str, object], arch: str) -> None:
+        """Pack an ultralytics YOLOv8-cls piece classifier (13 classes): ``arch`` is one of ``YOLO_CLS_ARCHS`` and decides which keys
+        the state dict must hold -- those of ``YOLO(path).model.state_dict()``, as trained or as ``model.fuse()`` leaves them.  It takes
+        the engine's classifier slot: the ``resnet18_forward*`` entries then run it (embedding: (N,1280), the pooled ``model.9.conv``
+        output).  Precisions f32, f16x3 and f16; f16r is refused."""
+        if arch not in YOLO_CLS_ARCHS:
+            raise HipBackendError(f"YOLOv8-cls architecture must be one of {YOLO_CLS_ARCHS}, got {arch!r}")
+        table, n, keep = _as_param_table(state_dict)
+        _check(self._lib.cv_load_yolo_cls(self._h, arch.encode(), table, n))
+        del keep
+        self.has_resnet = True                           # "the classifier slot is filled": what the pipeline entry points ask
+        self.classifier_arch = arch
 
     # -- forward ----------------------------------------------------------------------------------
     def _dev_f32(self, x: torch.Tensor, shape_tail) -> torch.Tensor:
@@ -1401,6 +1422,49 @@ class HipEngine:
                                       _stream_ptr(self.device)))
         return y
 
+    ACTS = {"none": 0, "relu": 1, "silu": 2}
+
+    def op_conv2d_act(self, x, w, y_init, x_coff=0, y_coff=0, stride=1, scale=None, shift=None, act="silu", act_first=False,
+                      res_coff=-1, in_exp=0, out_exp=0) -> torch.Tensor:
+        """One convolution as the YOLOv8-cls plan launches it (``cv_op_conv2d_act``): reads channels [x_coff, x_coff + Cin) of ``x``
+        (N, Cx, H, W), writes channels [y_coff, y_coff + Cout) of a tensor that starts as ``y_init`` (N, Cy, Ho, Wo) and returns the
+        whole tensor; ``res_coff`` >= 0 adds channels [res_coff, res_coff + Cout) of ``y_init`` as the residual."""
+        x = x.to(self.device, torch.float32).contiguous()
+        y = y_init.to(self.device, torch.float32).contiguous().clone()
+        w = _np_f32(w)
+        cout, cin, k, _ = w.shape
+        sc = _np_f32(scale) if scale is not None else None
+        sh = _np_f32(shift) if shift is not None else None
+        _check(self._lib.cv_op_conv2d_act(self._h, _ptr(x), x.shape[0], x.shape[1], x_coff, cin, x.shape[2], x.shape[3], w.ctypes.data_as(_fp),
+                                          cout, k, stride, sc.ctypes.data_as(_fp) if sc is not None else None,
+                                          sh.ctypes.data_as(_fp) if sh is not None else None, self.ACTS[act], int(bool(act_first)), _ptr(y),
+                                          y.shape[1], y_coff, res_coff, in_exp, out_exp, _stream_ptr(self.device)))
+        return y
+
+    def op_stem3x3s2(self, x, w, scale, shift, normalize=None, out_exp=0) -> torch.Tensor:
+        """The YOLOv8-cls stem alone: ``x`` (N,64,64) float32 in [0,1] or uint8 (``normalize`` = (mean, std): uint8 only) ->
+        (N, C0, 32, 32) float32; ``w`` (C0, 9) is the one-channel filter bank."""
+        u8 = x.dtype == torch.uint8
+        x = x.to(self.device).contiguous() if u8 else x.to(self.device, torch.float32).contiguous()
+        w, sc, sh = _np_f32(w), _np_f32(scale), _np_f32(shift)
+        c0 = w.shape[0]
+        y = torch.empty((x.shape[0], c0, 32, 32), dtype=torch.float32, device=self.device)
+        mean, std = (float(v) for v in normalize) if normalize is not None else (0.0, 0.0)
+        _check(self._lib.cv_op_stem3x3s2(self._h, _ptr(x), int(u8), x.shape[0], c0, w.ctypes.data_as(_fp), sc.ctypes.data_as(_fp),
+                                         sh.ctypes.data_as(_fp), mean, std, out_exp, _ptr(y), _stream_ptr(self.device)))
+        return y
+
+    def op_head_pool_fc(self, x, w, bias, softmax=False, in_exp=0):
+        """The YOLOv8-cls head alone: ``x`` (N, C, H, W) -> (logits or probabilities (N,13), pooled features (N, C))."""
+        x = x.to(self.device, torch.float32).contiguous()
+        w, bias = _np_f32(w), _np_f32(bias)
+        n, c, h, wd = x.shape
+        out = torch.empty((n, 13), dtype=torch.float32, device=self.device)
+        pooled = torch.empty((n, c), dtype=torch.float32, device=self.device)
+        _check(self._lib.cv_op_head_pool_fc(self._h, _ptr(x), n, c, h, wd, w.ctypes.data_as(_fp), bias.ctypes.data_as(_fp), int(bool(softmax)),
+                                            in_exp, _ptr(out), _ptr(pooled), _stream_ptr(self.device)))
+        return out, pooled
+
     def op_conv_transpose2x2(self, x, w, bias) -> torch.Tensor:
         x = x.to(self.device, torch.float32).contiguous()
         w, bias = _np_f32(w), _np_f32(bias)
@@ -1491,14 +1555,14 @@ class HipBoardExtractor(_HipModel):
 
 
 class HipPieceClassifier(_HipModel):
-    """timm ResNet-18 or ResNet-34 (1ch, 13 classes) forward on MI355X; drop-in for ``ChessVision.classifier`` (core.py:74-82,241).
+    """timm ResNet-18 / ResNet-34 (1ch, 13 classes) or ultralytics YOLOv8-cls forward on MI355X; drop-in for ``ChessVision.classifier`` (core.py:74-82,241).
     ``model_name`` is the architecture, which decides how a checkpoint is loaded (``utils.load_model_checkpoint``)."""
 
     model_name = "resnet18"
 
     def __init__(self, engine: HipEngine, metadata: dict | None = None, arch: str = "resnet18"):
-        if arch not in RESNET_ARCHS:
-            raise HipBackendError(f"classifier architecture {arch!r} has no HIP implementation (supported: {', '.join(RESNET_ARCHS)})")
+        if arch not in CLASSIFIER_ARCHS:
+            raise HipBackendError(f"classifier architecture {arch!r} has no HIP implementation (supported: {', '.join(CLASSIFIER_ARCHS)})")
         super().__init__(engine, metadata)
         self.model_name = arch
 

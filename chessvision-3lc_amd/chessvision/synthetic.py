@@ -220,14 +220,66 @@ def resnet34_state_dict(seed: int = 2):
     return _fill(resnet34_spec(), seed, residual_gamma=RESNET34_RESIDUAL_GAMMA)
 
 
+# ultralytics YOLOv8-cls (yolov8-cls.yaml): stem and stage widths, Bottlenecks per C2f
+YOLOV8_CLS = {"n": ((16, 32, 64, 128, 256), (1, 2, 2, 1)), "s": ((32, 64, 128, 256, 512), (1, 2, 2, 1)),
+              "m": ((48, 96, 192, 384, 768), (2, 4, 4, 2)), "l": ((64, 128, 256, 512, 1024), (3, 6, 6, 3)),
+              "x": ((80, 160, 320, 640, 1280), (3, 6, 6, 3))}
+YOLOV8_CLS_RESIDUAL_GAMMA = 0.5
+YOLOV8_CLS_LOGIT_GAIN = 2.0
+YOLOV8_CLS_VAR_SCALE = {"n": 0.8, "s": 0.85, "m": 0.9, "l": 0.94, "x": 0.94}
+
+
+def _yolo_scale(scale: str) -> str:
+    return scale[6] if scale.startswith("yolov8") else scale
+
+
+def yolov8_cls_spec(scale: str = "m", num_classes: int = 13, in_chans: int = 3):
+    """[(key, shape, kind)] of ``YOLO("yolov8{scale}-cls").model.state_dict()`` without ``num_batches_tracked``: Conv = conv + bn,
+    C2f = cv1, cv2, then its Bottlenecks ``m.i`` (cv1, cv2), Classify = conv + linear.  ``scale``: "m" or "yolov8m-cls"."""
+    w, d = YOLOV8_CLS[_yolo_scale(scale)]
+
+    def conv(p, cin, cout, k):
+        return [(f"{p}.conv.weight", (cout, cin, k, k), "conv")] + _bn(f"{p}.bn", cout)
+
+    spec = conv("model.0", in_chans, w[0], 3)
+    for i in range(4):
+        c = w[i + 1] // 2
+        spec += conv(f"model.{2 * i + 1}", w[i], w[i + 1], 3)
+        p = f"model.{2 * i + 2}"
+        spec += conv(f"{p}.cv1", w[i + 1], 2 * c, 1) + conv(f"{p}.cv2", (2 + d[i]) * c, w[i + 1], 1)
+        for j in range(d[i]):
+            spec += conv(f"{p}.m.{j}.cv1", c, c, 3) + conv(f"{p}.m.{j}.cv2", c, c, 3)
+    spec += conv("model.9.conv", w[4], 1280, 1)
+    spec += [("model.9.linear.weight", (num_classes, 1280), "linear"), ("model.9.linear.bias", (num_classes,), "beta")]
+    return spec
+
+
+def yolov8_cls_state_dict(seed: int = 2, scale: str = "m"):
+    """Trained-looking YOLOv8-cls state dict for ``scale`` ("m" or "yolov8m-cls"), keys and shapes of ``yolov8_cls_spec`` with the
+    3-channel stem the reference's training script leaves: He-normal convolutions, BatchNorm statistics that keep activations O(1)
+    through the SiLU layers (running variances x ``YOLOV8_CLS_VAR_SCALE``, the second BatchNorm of every Bottleneck x
+    ``YOLOV8_CLS_RESIDUAL_GAMMA``) and a linear layer x ``YOLOV8_CLS_LOGIT_GAIN`` so that most squares have a clear arg-max.  How the
+    three constants were chosen: profiles/yolov8_cls.md."""
+    sd = _fill(yolov8_cls_spec(scale), seed)
+    for key in sd:
+        if key.endswith(".running_var"):
+            sd[key] = np.ascontiguousarray(sd[key] * np.float32(YOLOV8_CLS_VAR_SCALE[_yolo_scale(scale)]))
+        if ".m." in key and key.endswith(".cv2.bn.weight"):
+            sd[key] = np.ascontiguousarray(sd[key] * np.float32(YOLOV8_CLS_RESIDUAL_GAMMA))
+    sd["model.9.linear.weight"] = np.ascontiguousarray(sd["model.9.linear.weight"] * np.float32(YOLOV8_CLS_LOGIT_GAIN))
+    return sd
+
+
 def resnet_state_dict(arch: str = "resnet18", seed: int = 2):
+    if arch.startswith("yolov8"):
+        return yolov8_cls_state_dict(seed, arch)
     return {"resnet18": resnet18_state_dict, "resnet34": resnet34_state_dict}[arch](seed)
 
 
 def save_checkpoints(directory, seed_unet: int = 1, seed_resnet: int = 2, bilinear: bool = False, segmenting: bool = False,
                      classifier_arch: str = "resnet18"):
     """Write random-init checkpoints in the reference's formats (train_unet.py:31-40, train_classifier.py:114-125);
-    ``classifier_arch`` = "resnet18" | "resnet34" picks the piece classifier's architecture."""
+    ``classifier_arch`` = "resnet18" | "resnet34" | "yolov8{n,s,m,l,x}-cls" picks the piece classifier's architecture."""
     import torch
     from pathlib import Path
 

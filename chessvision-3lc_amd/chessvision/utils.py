@@ -54,26 +54,71 @@ def read_checkpoint(checkpoint_path: str | os.PathLike) -> tuple[Mapping[str, An
     return blob, metadata
 
 
+YOLO_CONVERSION = "YOLO(path).model.float().state_dict()"
+
+
+def read_yolo_cls_checkpoint(checkpoint_path: str | os.PathLike) -> tuple[Mapping[str, Any], dict]:
+    """(state_dict, metadata) of a YOLOv8-cls checkpoint: any layout ``read_checkpoint`` understands that holds the keys of
+    ``YOLO(path).model.state_dict()``.  An ultralytics ``.pt`` pickles the model object; ``YOLO(path)`` unpickles it fully, which runs
+    code from the file, so that route is taken only where ultralytics is importable AND ``CHESSVISION_ALLOW_PICKLE=1`` says the file
+    is trusted -- the switch ``read_checkpoint`` asks for.  Otherwise the error prints the one-line conversion."""
+    try:
+        state, metadata = read_checkpoint(checkpoint_path)
+        if isinstance(state, Mapping) and any(str(k).startswith("model.0.") for k in state):
+            return state, metadata
+        problem = "it holds no 'model.0.*' keys (an ultralytics .pt pickles the model object, not a state dict)"
+    except (RuntimeError, ImportError, AttributeError) as exc:    # weights_only refused it, or full unpickling needs ultralytics' classes
+        problem = f"{type(exc).__name__}: {exc}"
+    convert = (f"convert it where ultralytics is installed: torch.save({YOLO_CONVERSION}, 'classifier_state.pt') and pass that file "
+               "as classifier_weights")
+    try:
+        from ultralytics import YOLO
+    except ImportError:
+        raise RuntimeError(f"{checkpoint_path} is not a plain state-dict checkpoint ({problem}) and ultralytics is not importable "
+                           f"here; {convert}") from None
+    if os.environ.get("CHESSVISION_ALLOW_PICKLE") != "1":
+        raise RuntimeError(f"{checkpoint_path} is not a plain state-dict checkpoint ({problem}); reading it through ultralytics "
+                           f"unpickles it fully: set CHESSVISION_ALLOW_PICKLE=1 if you trust the file, or {convert}")
+    return YOLO(str(checkpoint_path)).model.float().state_dict(), {}
+
+
+def load_classifier_state(engine, arch: str, state: Mapping[str, Any]) -> None:
+    """Pack ``state`` as the piece classifier ``arch`` into ``engine`` (the one place that knows which loader an id means)."""
+    from .hip_backend import YOLO_CLS_ARCHS
+
+    if arch in YOLO_CLS_ARCHS:
+        engine.load_yolo_cls(state, arch)
+    elif arch == "resnet18":
+        engine.load_resnet18(state)
+    else:
+        engine.load_resnet(state, arch)
+
+
+def read_classifier_checkpoint(checkpoint_path, arch: str):
+    from .hip_backend import YOLO_CLS_ARCHS
+
+    return read_yolo_cls_checkpoint(checkpoint_path) if arch in YOLO_CLS_ARCHS else read_checkpoint(checkpoint_path)
+
+
 def load_model_checkpoint(model, checkpoint_path: str, device: torch.device | None = None):
     """Reference-compatible entry point (utils.py:42-86): ``model`` is a HIP model object; its engine receives the
     packed weights, ``model.metadata`` is set when the checkpoint carries one."""
-    state, metadata = read_checkpoint(checkpoint_path)
     if model.model_name == "unet":
+        state, metadata = read_checkpoint(checkpoint_path)
         model.engine.load_unet(state)
     else:
         # the architecture comes from the model id, never from the checkpoint (reference core.py:139-146); a mismatch fails on the
         # first key the other architecture lacks, and the message says which id the checkpoint needs
         from .hip_backend import HipBackendError
 
+        state, metadata = read_classifier_checkpoint(checkpoint_path, model.model_name)
         try:
-            if model.model_name == "resnet18":
-                model.engine.load_resnet18(state)
-            else:
-                model.engine.load_resnet(state, model.model_name)
+            load_classifier_state(model.engine, model.model_name, state)
         except HipBackendError as exc:
-            found = _resnet_arch_of(state)
+            found = _resnet_arch_of(state) or yolo_cls_arch(state)
             if found and found != model.model_name:
-                raise HipBackendError(f"{exc} -- {checkpoint_path} holds a {found} state dict: load it with "
+                kind = found if found.startswith("yolov8") else found + " state dict"
+                raise HipBackendError(f"{exc} -- {checkpoint_path}: this is a {kind} checkpoint: pass "
                                       f"classifier_model_id={found!r}") from exc
             raise
     if metadata:
@@ -90,14 +135,34 @@ def _resnet_arch_of(state: Mapping[str, Any]) -> str | None:
     return {(2, 2, 2, 2): "resnet18", (3, 4, 6, 3): "resnet34"}.get(tuple(depth))
 
 
+_YOLO_CLS_STEM_WIDTH = {16: "yolov8n-cls", 32: "yolov8s-cls", 48: "yolov8m-cls", 64: "yolov8l-cls", 80: "yolov8x-cls"}
+
+
+def yolo_cls_arch(state: Mapping[str, Any]) -> str | None:
+    """Which YOLOv8-cls scale a state dict looks like, from its shapes: the stem's output channels tell the five scales apart (16 / 32 /
+    48 / 64 / 80) and the number of Bottlenecks in ``model.2`` must agree (n, s: 1; m: 2; l, x: 3).  None: not a YOLOv8-cls dict.  Used for
+    error messages; the architecture that is LOADED always comes from the model id."""
+    stem = state.get("model.0.conv.weight") if hasattr(state, "get") else None
+    shape = tuple(getattr(stem, "shape", ()))
+    if len(shape) != 4:
+        return None
+    arch = _YOLO_CLS_STEM_WIDTH.get(int(shape[0]))
+    blocks = {k.split(".")[3] for k in state if k.startswith("model.2.m.") and k.split(".")[3].isdigit()}
+    want = {"n": 1, "s": 1, "m": 2, "l": 3, "x": 3}
+    if arch is None or len(blocks) != want[arch[6]] or "model.9.linear.weight" not in state:
+        return None
+    return arch
+
+
 def get_classifier_model(model_id: str = "resnet18", engine=None):
     """The piece classifier architecture (reference utils.py:32-39: timm ``model_id``, 13 classes, 1 input channel).
-    ``resnet18`` and ``resnet34`` have a HIP implementation; ``""`` / None mean ``resnet18``."""
-    from .hip_backend import RESNET_ARCHS, HipBackendError, HipPieceClassifier
+    ``resnet18`` and ``resnet34`` have a HIP implementation, and so have ultralytics' ``yolov8{n,s,m,l,x}-cls`` (the names the
+    reference's ``train_yolo_classifier.py`` passes to ``--model``, minus ``.pt``); ``""`` / None mean ``resnet18``."""
+    from .hip_backend import CLASSIFIER_ARCHS, HipBackendError, HipPieceClassifier
 
     arch = model_id or "resnet18"
-    if arch not in RESNET_ARCHS:
-        raise HipBackendError(f"classifier architecture {model_id!r} has no HIP implementation (supported: {', '.join(RESNET_ARCHS)})")
+    if arch not in CLASSIFIER_ARCHS:
+        raise HipBackendError(f"classifier architecture {model_id!r} has no HIP implementation (supported: {', '.join(CLASSIFIER_ARCHS)})")
     return HipPieceClassifier(engine, arch=arch)
 
 

@@ -207,6 +207,18 @@ __device__ __forceinline__ void trunk32_store(float* dst, const float* v) {
     *reinterpret_cast<f4*>(dst + 4) = f4{v[4], v[5], v[6], v[7]};
 }
 
+// Activation of the implicit-GEMM epilogues on N values of one store unit (ConvParams::relu / act_in / act_out; wave-uniform choice).
+// SiLU runs on the true value: stored v * act_in (= 2^out_exp) in, result * act_out (= 2^-out_exp) out -- both products exact.
+template <int N> __device__ __forceinline__ void epi_activate(const ConvParams& p, float* w) {
+    if (p.relu == kActSilu) {
+#pragma unroll
+        for (int j = 0; j < N; ++j) w[j] = silu_f32(w[j] * p.act_in) * p.act_out;
+    } else if (p.relu) {
+#pragma unroll
+        for (int j = 0; j < N; ++j) w[j] = w[j] > 0.f ? w[j] : 0.f;
+    }
+}
+
 // A lane whose `bad` accumulator went NaN stored a non-finite value: record the launch's layer id (lowest id wins, so
 // the host names the FIRST layer that left the representable range).
 __device__ __forceinline__ void report_bad(const ConvParams& p, float bad) {

@@ -1018,6 +1018,7 @@ bool conv_halo_supported(int Ho, int Wo) {
 }
 
 hipError_t conv_halo_chain_launch(const ConvParams& p, int n_images, hipStream_t stream) {
+    if (!conv_epilogue_ok(kConvFormHaloChain, p)) return hipErrorInvalidValue;      // the chained epilogues are ReLU, residual first
     if (!p.chain || (p.nStages != 36 && p.nStages != 54) || p.Ho != 16 || p.Wo != 16 || p.yCs != 64 || p.xCs != 64 || p.ksplit > 1 || n_images < 1)
         return hipErrorInvalidValue;
     // CHAIN 1: one workgroup per CU (its 512 registers per lane see to that)
@@ -1028,6 +1029,9 @@ hipError_t conv_halo_chain_launch(const ConvParams& p, int n_images, hipStream_t
 }
 
 hipError_t conv_halo_launch(int dt, const ConvParams& p, int n_images, hipStream_t stream, int th) {
+    // this family's epilogues know ReLU after the residual, or nothing: SiLU and the activation-first order belong to conv_igemm.hip,
+    // and a launch that asks for them here is refused instead of run as ReLU
+    if (!conv_epilogue_ok(kConvFormHalo, p)) return hipErrorInvalidValue;
     const int img = (p.Ho == 8 && p.Wo == 8) ? 8 : 0;
     if (img || th != 8) th = 16;
 #define X(T, TH, IMG) \

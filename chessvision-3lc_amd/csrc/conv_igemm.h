@@ -19,6 +19,13 @@ enum ConvCfg {            // <channel tile> x <pixel tile> of one 256-thread wor
     kNumConvCfg = 6
 };
 
+// What each launch form's epilogue can do, as pure predicates of the launch parameters (ConvParams::relu / act_first and what rides
+// on the epilogue); every launcher asks its own before anything else and returns hipErrorInvalidValue on false -- a form never runs an
+// activation it was not asked for.  kConvFormIgemm: plain / position-major / split-K second pass (none | ReLU | SiLU, either order;
+// SiLU or the activation-first order not with the fused 1x1 head or the fused pool, which are written for post-ReLU values).
+// kConvFormPair: none | ReLU after the residual.  kConvFormHalo: the same.  kConvFormHaloChain: ReLU after the residual only.
+enum ConvForm { kConvFormIgemm = 0, kConvFormPair = 1, kConvFormHalo = 2, kConvFormHaloChain = 3 };
+bool conv_epilogue_ok(int form, const ConvParams& p);
 hipError_t conv_igemm_prepare();                                   // raise dynamic-LDS limits (once per device)
 hipError_t conv_igemm_launch(int cfg, int ns, int dt, const ConvParams& p, hipStream_t stream);   // ns = LDS ring depth 2|3
 // position-major launch (ConvParams::ptab / pcount / posN / nPtPer set; table-free offsets; unsplit): rows = [output position][image]

@@ -34,7 +34,10 @@ namespace cv {
 // LDS is spent on the offset table (lets two 80 KB workgroups share a CU).
 // POS: GEMM rows ordered [output position][image]; the K loop walks only the stages whose tap reads a real pixel at the tile's
 // position (ConvParams::ptab; the 3x3 layers on ResNet-18's 2x2 / 4x4 / 8x8 maps at throughput batch sizes).
-template <typename T, int CT, int PT, int WGC, int NS, int NW, bool SEP, bool POS = false>
+// EXT: the epilogue with the activation selector and the order flag (ConvParams::act_*: the YOLOv8-cls layers).  A compile-time
+// parameter: measured as a run-time option of the one epilogue it cost the headline 0.3 % (profiles/yolov8_cls.md), so the launches
+// that ask for ReLU-after-residual or nothing run the instantiation they always ran.
+template <typename T, int CT, int PT, int WGC, int NS, int NW, bool SEP, bool POS = false, bool EXT = false>
 __global__ __launch_bounds__(64 * NW) void conv_igemm_kernel(const ConvParams p) {
     const unsigned nwg = gridDim.x, bid = blockIdx.x;
 #include "conv_igemm_body.h"
@@ -51,7 +54,7 @@ __global__ __launch_bounds__(64 * NW) void conv_igemm_pair_kernel(const ConvPara
     // two copies of the body, each on its own kernel argument (choosing `p` at run time -- a reference to pa or pb -- makes the compiler
     // park a copy of the 448-byte parameter block in scratch) and each in its own arithmetic: TA != TB is the fp16 classifier, whose
     // shortcut convolutions run on the f32-input MFMA (resnet.cpp)
-    constexpr bool POS = false;
+    constexpr bool POS = false, EXT = false;
     if (blockIdx.x < a_pad) {
         if (blockIdx.x >= a_n) return;
         typedef TA T;
@@ -71,7 +74,7 @@ __global__ __launch_bounds__(64 * NW) void conv_igemm_pair_kernel(const ConvPara
 // split index, whatever order the first pass's workgroups finished in.  POOL: one lane = the same 8 channels of a 2 x 2 pixel
 // block, which also yields the block's max_pool2d(2) value (UNet encoder: the pooled copy next to the skip tensor, as the halo
 // kernel's fused epilogue writes it) -- a split launch then needs no stand-alone pooling kernel behind it.
-template <typename T, bool POOL>
+template <typename T, bool POOL, bool EXT = false>
 __global__ __launch_bounds__(64) void conv_splitk_reduce_kernel(const ConvParams p) {
     constexpr int UN = 8;
     constexpr int NPX = POOL ? 4 : 1;
@@ -139,6 +142,9 @@ __global__ __launch_bounds__(64) void conv_splitk_reduce_kernel(const ConvParams
             co = row - grp * p.Cout;
             ob += (unsigned)((grp >> 1) * p.yWp + (grp & 1));
         }
+        if constexpr (EXT) {
+            if (p.act_first) epi_activate<UN>(p, w);
+        }
         if (rbase) {
             bool done = false;
             if constexpr (__is_same(T, half_t)) {
@@ -151,7 +157,9 @@ __global__ __launch_bounds__(64) void conv_splitk_reduce_kernel(const ConvParams
             }
             if (!done) OutVec<T, UN>::add(rbase + (size_t)ob * p.rCs + p.rCoff + co, p.rCoff + co, w, p.res_mul);
         }
-        if (p.relu) {
+        if constexpr (EXT) {
+            if (!p.act_first) epi_activate<UN>(p, w);
+        } else if (p.relu) {
 #pragma unroll
             for (int j = 0; j < UN; ++j) w[j] = w[j] > 0.f ? w[j] : 0.f;
         }
@@ -172,15 +180,28 @@ __global__ __launch_bounds__(64) void conv_splitk_reduce_kernel(const ConvParams
 }
 
 // ---- host-side launch -------------------------------------------------------------------------------
+static bool epi_ext(const ConvParams& p) { return p.relu == kActSilu || p.act_first != 0; }     // needs the EXT instantiation
+bool conv_epilogue_ok(int form, const ConvParams& p) {
+    if (p.relu < kActNone || p.relu > kActSilu || (p.act_first != 0 && p.act_first != 1)) return false;
+    switch (form) {
+    case kConvFormIgemm: return !(epi_ext(p) && (p.head_w || p.pool_y));
+    case kConvFormPair:
+    case kConvFormHalo: return !epi_ext(p);
+    case kConvFormHaloChain: return p.relu == kActRelu && !p.act_first;
+    default: return false;
+    }
+}
+static bool epi_unsupported(const ConvParams& p) { return !conv_epilogue_ok(kConvFormIgemm, p); }
 template <typename T, int CT, int PT, int WGC, int NS, int NW, bool SEP>
 static hipError_t launch_one(const ConvParams& p, hipStream_t stream) {
     const int stages = p.ksplit > 1 ? p.kper : p.nStages;    // the offset table in LDS covers one split only
     const size_t lds = (size_t)NS * (CT + PT) * 128 + (SEP ? 0 : (((size_t)stages * 8 * 4 + 15) & ~(size_t)15));
-    if (lds > 160 * 1024) return hipErrorInvalidValue;
+    if (lds > 160 * 1024 || epi_unsupported(p)) return hipErrorInvalidValue;
     const int nPt = (p.M + PT - 1) / PT;
     const int splits = p.ksplit > 1 ? p.ksplit : 1;
-    auto kern = conv_igemm_kernel<T, CT, PT, WGC, NS, NW, SEP>;
-    hipLaunchKernelGGL(kern, dim3((unsigned)(nPt * p.nCt * splits)), dim3(64 * NW), lds, stream, p);
+    const dim3 grid((unsigned)(nPt * p.nCt * splits)), block(64 * NW);
+    if (epi_ext(p)) hipLaunchKernelGGL((conv_igemm_kernel<T, CT, PT, WGC, NS, NW, SEP, false, true>), grid, block, lds, stream, p);
+    else hipLaunchKernelGGL((conv_igemm_kernel<T, CT, PT, WGC, NS, NW, SEP>), grid, block, lds, stream, p);
     return hipGetLastError();
 }
 
@@ -188,11 +209,13 @@ static hipError_t launch_one(const ConvParams& p, hipStream_t stream) {
 template <typename T, int CT, int PT, int WGC, int NS, int NW>
 static hipError_t launch_pos(const ConvParams& p, hipStream_t stream) {
     const size_t lds = (size_t)NS * (CT + PT) * 128;
+    if (epi_unsupported(p)) return hipErrorInvalidValue;
     if (lds > 160 * 1024 || !p.kbase || !p.ptab || !p.pcount || !p.porder || p.ksplit > 1 || p.head_w || p.posN <= 0) return hipErrorInvalidValue;
     if (p.nPtPer != (p.posN + PT - 1) / PT || p.M != p.posN * p.Ho * p.Wo) return hipErrorInvalidValue;
-    auto kern = conv_igemm_kernel<T, CT, PT, WGC, NS, NW, true, true>;
     const unsigned col_groups = ((unsigned)(p.nPtPer * p.nCt) + 7u) >> 3;          // columns (image tile, channel tile) per XCD
-    hipLaunchKernelGGL(kern, dim3(8u * col_groups * (unsigned)(p.Ho * p.Wo)), dim3(64 * NW), lds, stream, p);
+    const dim3 grid(8u * col_groups * (unsigned)(p.Ho * p.Wo)), block(64 * NW);
+    if (epi_ext(p)) hipLaunchKernelGGL((conv_igemm_kernel<T, CT, PT, WGC, NS, NW, true, true, true>), grid, block, lds, stream, p);
+    else hipLaunchKernelGGL((conv_igemm_kernel<T, CT, PT, WGC, NS, NW, true, true>), grid, block, lds, stream, p);
     return hipGetLastError();
 }
 
@@ -200,7 +223,7 @@ static hipError_t launch_pos(const ConvParams& p, hipStream_t stream) {
 template <typename TA, typename TB, int CT, int PT, int WGC, int NS, int NW>
 static hipError_t launch_pair(const ConvParams& a, const ConvParams& b, hipStream_t stream) {
     const size_t lds = (size_t)NS * (CT + PT) * 128;
-    if (lds > 160 * 1024) return hipErrorInvalidValue;
+    if (lds > 160 * 1024 || !conv_epilogue_ok(kConvFormPair, a) || !conv_epilogue_ok(kConvFormPair, b)) return hipErrorInvalidValue;   // the pair kernel has the plain epilogue
     auto blocks = [](const ConvParams& p) { return (unsigned)(((p.M + PT - 1) / PT) * p.nCt * (p.ksplit > 1 ? p.ksplit : 1)); };
     const unsigned a_n = blocks(a), b_n = blocks(b), a_pad = (a_n + 7u) & ~7u;
     auto kern = conv_igemm_pair_kernel<TA, TB, CT, PT, WGC, NS, NW, true>;
@@ -211,12 +234,14 @@ static hipError_t launch_pair(const ConvParams& a, const ConvParams& b, hipStrea
 // second pass of a split-K launch (either conv kernel): sums p.partial over the splits and runs the layer's epilogue
 hipError_t conv_splitk_reduce_launch(int dt, const ConvParams& p, hipStream_t stream) {
     if (p.ksplit <= 1 || !p.partial) return hipErrorInvalidValue;
+    if (epi_unsupported(p)) return hipErrorInvalidValue;
     const bool pool = p.pool_y != nullptr;                 // fused 2x2 max-pool: even output extent, no pixel shuffle (checked by the engine)
     if (pool && (p.shuffle || (p.Ho & 1) || (p.Wo & 1))) return hipErrorInvalidValue;
     const long long units = (long long)(pool ? p.M / 4 : p.M) * (p.rows / 8);
     const dim3 grid((unsigned)((units + 63) / 64)), block(64);
 #define CV_REDUCE(T) \
-    do { if (pool) hipLaunchKernelGGL((conv_splitk_reduce_kernel<T, true>), grid, block, 0, stream, p); \
+    do { if (epi_ext(p)) hipLaunchKernelGGL((conv_splitk_reduce_kernel<T, false, true>), grid, block, 0, stream, p); /* never with a pool */ \
+         else if (pool) hipLaunchKernelGGL((conv_splitk_reduce_kernel<T, true>), grid, block, 0, stream, p); \
          else hipLaunchKernelGGL((conv_splitk_reduce_kernel<T, false>), grid, block, 0, stream, p); } while (0)
     if (dt == kF16) CV_REDUCE(half_t); else if (dt == kSplit) CV_REDUCE(split_t); else CV_REDUCE(float);
 #undef CV_REDUCE
@@ -231,6 +256,12 @@ static hipError_t prepare_one() {
     e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv_igemm_kernel<T, CT, PT, WGC, NS, NW, true>),
                             hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     if (e != hipSuccess) return e;
+    e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv_igemm_kernel<T, CT, PT, WGC, NS, NW, false, false, true>),
+                            hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    if (e != hipSuccess) return e;
+    e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv_igemm_kernel<T, CT, PT, WGC, NS, NW, true, false, true>),
+                            hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    if (e != hipSuccess) return e;
     e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv_igemm_pair_kernel<T, T, CT, PT, WGC, NS, NW, true>),
                             hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     if (e != hipSuccess || !__is_same(T, half_t)) return e;
@@ -240,6 +271,9 @@ static hipError_t prepare_one() {
 
 template <typename T, int CT, int PT, int WGC, int NS, int NW>
 static hipError_t prepare_pos() {
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv_igemm_kernel<T, CT, PT, WGC, NS, NW, true, true, true>),
+                                             hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    if (e != hipSuccess) return e;
     return hipFuncSetAttribute(reinterpret_cast<const void*>(conv_igemm_kernel<T, CT, PT, WGC, NS, NW, true, true>),
                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
 }

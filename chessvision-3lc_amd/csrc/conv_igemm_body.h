@@ -1,5 +1,6 @@
 // conv_igemm_body.h -- the body of conv_igemm_kernel / conv_igemm_pair_kernel (conv_igemm.hip), included TEXTUALLY inside both.
-// Expects in scope: the template parameters T, CT, PT, WGC, NS, NW, SEP and the constant POS (position-major rows, ConvParams::ptab);
+// Expects in scope: the template parameters T, CT, PT, WGC, NS, NW, SEP, the constant POS (position-major rows, ConvParams::ptab) and the
+// constant EXT (the epilogue knows SiLU and the activation-first order, ConvParams::act_*; false: ReLU after the residual or nothing);
 // `p` (the layer's ConvParams); `nwg` / `bid` (unsigned: the number of workgroups that run this layer and this workgroup's index
 // among them).  A function taking ConvParams by reference or by
 // value instead changes the register allocation of the production kernels (152 -> 156, 228 -> 232, 254 -> 255 VGPRs, measured on the
@@ -282,7 +283,7 @@
         }
     }
 
-    // ---- epilogue: BN affine (+ residual) (+ ReLU), convert, 16-B NHWC stores -------------------------
+    // ---- epilogue: BN affine (+ residual) (+ ReLU / SiLU, before or after the residual), convert, 16-B NHWC stores -------------------------
     constexpr int NV = 4 * FC;                          // consecutive channels held by this lane
     const int row0 = ctTile * CT + wci * WCT + q * NV;  // first GEMM row (== channel, by host permutation)
     if (!POS && p.ksplit > 1) {                         // (position-major launches are never split, nor do they feed the fused head)
@@ -408,6 +409,9 @@
                 ob += (unsigned)((grp >> 1) * p.yWp + (grp & 1));
             }
             if (lv && row < p.rows) {
+                if constexpr (EXT) {
+                    if (p.act_first) epi_activate<UN>(p, w);
+                }
                 if (rbase) {
                     bool done = false;
                     if constexpr (__is_same(T, half_t)) {
@@ -420,7 +424,9 @@
                     }
                     if (!done) OutVec<T, UN>::add(rbase + (size_t)ob * p.rCs + p.rCoff + co, p.rCoff + co, w, p.res_mul);
                 }
-                if (p.relu) {
+                if constexpr (EXT) {
+                    if (!p.act_first) epi_activate<UN>(p, w);
+                } else if (p.relu) {
 #pragma unroll
                     for (int j = 0; j < UN; ++j) w[j] = w[j] > 0.f ? w[j] : 0.f;
                 }

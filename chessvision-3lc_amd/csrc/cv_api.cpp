@@ -129,15 +129,30 @@ Status load_resnet(cv_engine_t* eng, const char* arch, const cv_param_t* params,
     return resnet_load(eng->impl, pm, arch);
 }
 
-// by-name entry points: "unet" | the loaded ResNet's architecture name.  Sets *is_resnet; a known name of a model that is not the loaded
-// one fails with CV_ERR_STATE naming what is loaded, an unknown name with CV_ERR_INVALID.
+Status load_yolo_cls(cv_engine_t* eng, const char* arch, const cv_param_t* params, int n_params) {
+    CV_TRY(check_engine(eng));
+    if (!arch || !yolo_cls_arch(arch))
+        return fail(CV_ERR_INVALID, "cv_load_yolo_cls: arch must be 'yolov8n-cls', 'yolov8s-cls', 'yolov8m-cls', 'yolov8l-cls' or 'yolov8x-cls', got " +
+                                        (arch ? "'" + std::string(arch) + "'" : std::string("NULL")));
+    std::lock_guard<std::mutex> load_lk(load_mutex());
+    std::lock_guard<std::mutex> lk(eng->impl.mu);
+    DeviceGuard g(eng->impl.device);
+    ParamMap pm;
+    CV_TRY(to_map(params, n_params, pm));
+    return yolo_cls_load(eng->impl, pm, arch);
+}
+
+// by-name entry points: "unet" | the loaded classifier's architecture name (a ResNet or a YOLOv8-cls).  Sets *is_resnet -- "the
+// classifier slot" -- ; a known name of a model that is not the loaded one fails with CV_ERR_STATE naming what is loaded, an unknown
+// name with CV_ERR_INVALID.
 Status model_by_name(const Engine& e, const char* model, bool* is_resnet) {
     *is_resnet = false;
     if (std::strcmp(model, "unet") == 0) return Status();
-    if (!resnet_arch(model)) return fail(CV_ERR_INVALID, "model must be 'unet', 'resnet18' or 'resnet34'");
+    if (!resnet_arch(model) && !yolo_cls_arch(model)) return fail(CV_ERR_INVALID, "model must be 'unet', 'resnet18', 'resnet34' or 'yolov8{n,s,m,l,x}-cls'");
     *is_resnet = true;
-    if (e.resnet && std::strcmp(e.resnet->arch->name, model) != 0)
-        return fail(CV_ERR_STATE, "model '" + std::string(model) + "' is not loaded: this engine holds " + e.resnet->arch->name);
+    const char* held = classifier_name(e);
+    if (held && std::strcmp(held, model) != 0)
+        return fail(CV_ERR_STATE, "model '" + std::string(model) + "' is not loaded: this engine holds " + held);
     return Status();
 }
 
@@ -145,7 +160,7 @@ Status model_by_name(const Engine& e, const char* model, bool* is_resnet) {
 Status activation_by_name(Engine& e, const char* model, const char* name, TensorRef* t) {
     bool is_resnet = false;
     CV_TRY(model_by_name(e, model, &is_resnet));
-    return is_resnet ? resnet_activation(e, name, t) : unet_activation(e, name, t);
+    return is_resnet ? classifier_activation(e, name, t) : unet_activation(e, name, t);
 }
 
 Status check_embedding(const float* embedding) {
@@ -174,7 +189,7 @@ Status resnet_entry(cv_engine_t* eng, const void* x, bool x_u8, int n, float* ou
         return fail(CV_ERR_INVALID, "cv_resnet_forward_u8_norm: mean must be finite, std finite and > 0");
     std::lock_guard<std::mutex> lk(eng->impl.mu);
     DeviceGuard g(eng->impl.device);
-    return resnet_forward(eng->impl, x, x_u8, n, out, softmax, (hipStream_t)stream, embedding, norm);
+    return classifier_forward(eng->impl, x, x_u8, n, out, softmax, (hipStream_t)stream, embedding, norm);
 }
 
 // ---- single-layer entry points (parity tests) -------------------------------------------------------
@@ -303,10 +318,10 @@ Status engine_calibration(cv_engine_t* eng, const char* model, int32_t* exps, in
     std::vector<Activation*>* acts = nullptr;
     bool is_resnet = false;
     const Status s = model_by_name(e, model, &is_resnet);
-    if (!s.ok()) return s.code == CV_ERR_INVALID ? fail(CV_ERR_STATE, "model must be a loaded 'unet', 'resnet18' or 'resnet34'") : s;
+    if (!s.ok()) return s.code == CV_ERR_INVALID ? fail(CV_ERR_STATE, "model must be a loaded 'unet', 'resnet18', 'resnet34' or 'yolov8{n,s,m,l,x}-cls'") : s;
     if (!is_resnet && e.unet) acts = &e.unet->acts;
-    else if (is_resnet && e.resnet) acts = &e.resnet->acts;
-    else return fail(CV_ERR_STATE, "model must be a loaded 'unet', 'resnet18' or 'resnet34'");
+    else if (is_resnet && classifier_model(e)) acts = &classifier_model(e)->acts;
+    else return fail(CV_ERR_STATE, "model must be a loaded 'unet', 'resnet18', 'resnet34' or 'yolov8{n,s,m,l,x}-cls'");
     const int n = 2 * (int)acts->size();
     if (!import) {
         *count = n;
@@ -493,7 +508,7 @@ Status process_image(cv_engine_t* ue, cv_engine_t* ce, const ImageFront& front, 
             std::lock_guard<std::mutex> lk(C.mu);
             // the 64 x 13 probabilities are written by the head kernel straight into the page-locked block (device-visible under
             // its host address): 3.3 KB over PCIe inside the kernel instead of one more copy operation at the end of the stream
-            s = resnet_forward(C, d_sq, true, 64, h_pr, true, st);
+            s = classifier_forward(C, d_sq, true, 64, h_pr, true, st);
         }
         if (!s.ok()) return s;
         // the side stream joins `st` on the DEVICE (the download finished long before the classifier): one host synchronisation per call
@@ -652,6 +667,7 @@ int cv_engine_destroy(cv_engine_t* eng) {
         ReleaseAlreadySynced quiescent;                 // nothing can be queued on a dying engine's buffers from here on
         eng->impl.unet.reset();
         eng->impl.resnet.reset();
+        eng->impl.yolo.reset();
         delete eng;
         return Status();
     });
@@ -661,7 +677,7 @@ int cv_engine_set_chunk(cv_engine_t* eng, int unet_images, int resnet_squares) {
     return guarded("cv_engine_set_chunk", [&]() -> Status {
         CV_TRY(check_engine(eng));
         std::lock_guard<std::mutex> lk(eng->impl.mu);
-        if (eng->impl.unet || eng->impl.resnet) return fail(CV_ERR_STATE, "cv_engine_set_chunk must precede cv_load_*");
+        if (eng->impl.unet || eng->impl.resnet || eng->impl.yolo) return fail(CV_ERR_STATE, "cv_engine_set_chunk must precede cv_load_*");
         if (unet_images < 0 || resnet_squares < 0) return fail(CV_ERR_INVALID, "negative chunk");
         if (unet_images) eng->impl.unet_chunk = unet_images;
         if (resnet_squares) eng->impl.resnet_chunk = resnet_squares;
@@ -683,6 +699,10 @@ int cv_load_unet(cv_engine_t* eng, const cv_param_t* params, int n_params) {
 
 int cv_load_resnet(cv_engine_t* eng, const char* arch, const cv_param_t* params, int n_params) {
     return guarded("cv_load_resnet", [&]() -> Status { return load_resnet(eng, arch, params, n_params); });
+}
+
+int cv_load_yolo_cls(cv_engine_t* eng, const char* arch, const cv_param_t* params, int n_params) {
+    return guarded("cv_load_yolo_cls", [&]() -> Status { return load_yolo_cls(eng, arch, params, n_params); });
 }
 
 int cv_load_resnet18(cv_engine_t* eng, const cv_param_t* params, int n_params) {
@@ -743,7 +763,7 @@ int cv_embedding_dim(cv_engine_t* eng, const char* model, int* channels) {
         std::lock_guard<std::mutex> lk(eng->impl.mu);
         bool is_resnet = false;
         CV_TRY(model_by_name(eng->impl, model, &is_resnet));
-        *channels = is_resnet ? (eng->impl.resnet ? 512 : 0) : unet_embedding_dim(eng->impl);
+        *channels = is_resnet ? classifier_embedding_dim(eng->impl) : unet_embedding_dim(eng->impl);
         if (*channels == 0) return fail(CV_ERR_STATE, "cv_embedding_dim: model '" + std::string(model) + "' is not loaded");
         return Status();
     });
@@ -760,7 +780,7 @@ int cv_activation_channel_means(cv_engine_t* eng, const char* model, const char*
         // "global_pool" (the classifier's hook, named_modules()[90]) is the mean of layer4's output: pooled here, it needs no tensor of
         // its own.  The UNet has no tensor of that name.
         const bool pooled_layer4 = std::strcmp(name, "global_pool") == 0 && std::strcmp(model, "unet") != 0;
-        CV_TRY(activation_by_name(eng->impl, model, pooled_layer4 ? "layer4" : name, &t));
+        CV_TRY(activation_by_name(eng->impl, model, pooled_layer4 ? classifier_pool_tap(eng->impl) : name, &t));
         dims[0] = t.N; dims[1] = t.C;
         if (!out_dev) return Status();                        // shape query
         const std::string tap = "cv_activation_channel_means('" + std::string(name) + "')";
@@ -828,7 +848,7 @@ int cv_model_macs(cv_engine_t* eng, const char* model, int64_t* macs) {
         if (!model || !macs) return fail(CV_ERR_INVALID, "null argument");
         bool is_resnet = false;
         CV_TRY(model_by_name(eng->impl, model, &is_resnet));
-        *macs = is_resnet ? resnet_macs(eng->impl) : unet_macs(eng->impl);
+        *macs = is_resnet ? classifier_macs(eng->impl) : unet_macs(eng->impl);
         if (*macs == 0) return fail(CV_ERR_STATE, "model not loaded");
         return Status();
     });
@@ -848,7 +868,7 @@ int cv_profile_convs(cv_engine_t* eng, const char* model, const void* x, int bat
         e.profiling = true;
         Status s;
         for (int i = 0; i < iters && s.ok(); ++i) {
-            if (is_resnet) s = resnet_forward(e, x, false, batch, (float*)out, false, (hipStream_t)stream);
+            if (is_resnet) s = classifier_forward(e, x, false, batch, (float*)out, false, (hipStream_t)stream);
             else s = unet_forward(e, x, false, batch, (float*)out, nullptr, 0.5f, (hipStream_t)stream);
         }
         e.profiling = false;
@@ -938,10 +958,11 @@ int cv_engine_import_calibration(cv_engine_t* eng, const char* model, const int3
 // ask which kernel form a shape took: cv_profile_entry / cv_profile_entry_kernel describe that launch until the next recorded call.
 // The recorder changes no planner choice: it only keeps run_conv from deferring a launch for pairing, which needs a `defer` slot
 // that these entry points never set.
-static Status run_conv_recorded(Engine& e, ConvLayer& L, const TensorRef& x, const TensorRef& y, const TensorRef* res, bool relu, hipStream_t st) {
+static Status run_conv_recorded(Engine& e, ConvLayer& L, const TensorRef& x, const TensorRef& y, const TensorRef* res, int act, hipStream_t st,
+                                bool act_first = false) {
     e.prof_clear();
     e.profiling = true;
-    Status s = e.run_conv(L, x, y, res, relu, st);
+    Status s = e.run_conv(L, x, y, res, act, st, nullptr, nullptr, nullptr, act_first);
     e.profiling = false;
     if (s.ok()) s = e.prof_collect();
     if (!s.ok()) e.prof_clear();
@@ -982,6 +1003,113 @@ int cv_op_conv2d(cv_engine_t* eng, const float* x, int n, int cin, int h, int w_
             if (s.ok() && err != hipSuccess) s = hip_fail(err, "cv_op_conv2d");
         }
         return s;
+    });
+}
+
+int cv_op_conv2d_act(cv_engine_t* eng, const float* x, int n, int x_channels, int x_coff, int cin, int h, int w_, const float* w_host, int cout,
+                     int k, int stride, const float* scale_host, const float* shift_host, int act, int act_first, float* y, int y_channels,
+                     int y_coff, int res_coff, int in_exp, int out_exp, void* stream) {
+    return guarded("cv_op_conv2d_act", [&]() -> Status {
+        CV_TRY(check_engine(eng));
+        if (!x || !w_host || !y || n <= 0 || cin <= 0 || cout <= 0 || h <= 0 || w_ <= 0 || stride <= 0 || x_coff < 0 || y_coff < 0 ||
+            x_coff + cin > x_channels || y_coff + cout > y_channels || x_channels % 8 || y_channels % 8 || cin % 8 ||
+            (res_coff >= 0 && res_coff + cout > y_channels) || in_exp < -60 || in_exp > 60 || out_exp < -60 || out_exp > 60)
+            return fail(CV_ERR_INVALID, "cv_op_conv2d_act: bad argument");
+        std::lock_guard<std::mutex> lk(eng->impl.mu);
+        DeviceGuard g(eng->impl.device);
+        Engine& e = eng->impl;
+        if (e.dt == kF32 && (in_exp || out_exp)) return fail(CV_ERR_INVALID, "cv_op_conv2d_act: the f32 engine stores true values (exponents must be 0)");
+        hipStream_t st = (hipStream_t)stream;
+        const int pad = (k - 1) / 2;
+        const int ho = (h + 2 * pad - k) / stride + 1, wo = (w_ + 2 * pad - k) / stride + 1;
+        std::vector<float> ones(cout, 1.f), zeros(cout, 0.f);
+        ConvLayer L;
+        e.ws_slot = 0;
+        CV_TRY(L.build_conv("op_conv2d_act", e.dt, w_host, cout, cin, k, stride, scale_host ? scale_host : ones.data(),
+                            shift_host ? shift_host : zeros.data(), cin, (int64_t)n * ho * wo, (ho == wo) ? ho : 0));
+        Activation ax, ay;
+        ax.exp = in_exp; ay.exp = out_exp;
+        CV_TRY(ax.create(n, h, w_, x_channels, e.dt));
+        CV_TRY(ay.create(n, ho, wo, y_channels, e.dt));
+        hipError_t err = pack_nchw_f32(e.dt, x, x_channels, ax.ref(n), e.guard_ptr(), st);
+        if (err == hipSuccess) err = pack_nchw_f32(e.dt, y, y_channels, ay.ref(n), e.guard_ptr(), st);      // what the launch must leave alone
+        if (err != hipSuccess) return hip_fail(err, "cv_op_conv2d_act");
+        const TensorRef rr = ay.ref(n, res_coff < 0 ? 0 : res_coff, cout);
+        CV_TRY(run_conv_recorded(e, L, ax.ref(n, x_coff, cin), ay.ref(n, y_coff, cout), res_coff >= 0 ? &rr : nullptr, act, st, act_first != 0));
+        err = unpack_nchw_f32(e.dt, ay.ref(n), y, st);
+        if (err == hipSuccess) err = hipStreamSynchronize(st);
+        return err != hipSuccess ? hip_fail(err, "cv_op_conv2d_act") : Status();
+    });
+}
+
+int cv_op_conv_epilogue_ok(int form, int act, int act_first, int with_head, int with_pool, int with_fuse0, int shuffle, int* ok) {
+    return guarded("cv_op_conv_epilogue_ok", [&]() -> Status {
+        if (!ok || form < 0 || form > 4) return fail(CV_ERR_INVALID, "cv_op_conv_epilogue_ok: bad argument");
+        if (form == 4) {                                     // the planner's own check (Engine::run_conv)
+            *ok = Engine::epilogue_plan_ok(act, act_first != 0, with_head != 0, with_pool != 0, with_fuse0 != 0, shuffle != 0) ? 1 : 0;
+            return Status();
+        }
+        // the predicate every launcher of that form asks first (conv_igemm.h: conv_epilogue_ok); it reads the options and whether a
+        // fused head / pool rides on the epilogue, never through a pointer
+        static float dummy;
+        ConvParams p;
+        std::memset(&p, 0, sizeof(p));
+        p.relu = act; p.act_first = act_first; p.act_in = p.act_out = 1.f;
+        if (with_head) p.head_w = &dummy;
+        if (with_pool) p.pool_y = reinterpret_cast<char*>(&dummy);
+        *ok = conv_epilogue_ok(form, p) ? 1 : 0;
+        return Status();
+    });
+}
+
+int cv_op_stem3x3s2(cv_engine_t* eng, const void* x, int x_u8, int n, int c0, const float* w_host, const float* scale_host,
+                    const float* shift_host, float mean, float std, int out_exp, float* y, void* stream) {
+    return guarded("cv_op_stem3x3s2", [&]() -> Status {
+        CV_TRY(check_engine(eng));
+        if (!x || !w_host || !scale_host || !shift_host || !y || n <= 0 || c0 < 8 || c0 % 8 || out_exp < -60 || out_exp > 60)
+            return fail(CV_ERR_INVALID, "cv_op_stem3x3s2: bad argument");
+        std::lock_guard<std::mutex> lk(eng->impl.mu);
+        DeviceGuard g(eng->impl.device);
+        Engine& e = eng->impl;
+        hipStream_t st = (hipStream_t)stream;
+        DeviceBuffer w, sc, sh;
+        CV_TRY(w.upload(w_host, (size_t)c0 * 9 * sizeof(float)));
+        CV_TRY(sc.upload(scale_host, (size_t)c0 * sizeof(float)));
+        CV_TRY(sh.upload(shift_host, (size_t)c0 * sizeof(float)));
+        Activation ay;
+        ay.exp = e.dt == kF32 ? 0 : out_exp;
+        CV_TRY(ay.create(n, 32, 32, c0, e.dt));
+        const InputNorm nm{mean, std};
+        hipError_t err = stem3x3s2(e.dt, x, x_u8 != 0, n, (const float*)w.ptr, (const float*)sc.ptr, (const float*)sh.ptr, ay.ref(n),
+                                   e.guard_ptr(), 0xfffffffeu, st, (x_u8 && std > 0.f) ? &nm : nullptr);
+        if (err == hipSuccess) err = unpack_nchw_f32(e.dt, ay.ref(n), y, st);
+        if (err == hipSuccess) err = hipStreamSynchronize(st);
+        return err != hipSuccess ? hip_fail(err, "cv_op_stem3x3s2") : Status();
+    });
+}
+
+int cv_op_head_pool_fc(cv_engine_t* eng, const float* x, int n, int c, int h, int w_, const float* w_host, const float* bias_host,
+                       int softmax, int in_exp, float* out, float* pooled, void* stream) {
+    return guarded("cv_op_head_pool_fc", [&]() -> Status {
+        CV_TRY(check_engine(eng));
+        if (!x || !w_host || !bias_host || !out || n <= 0 || c < 8 || c % 8 || h <= 0 || w_ <= 0 || in_exp < -60 || in_exp > 60)
+            return fail(CV_ERR_INVALID, "cv_op_head_pool_fc: bad argument");
+        CV_TRY(check_embedding(pooled));
+        std::lock_guard<std::mutex> lk(eng->impl.mu);
+        DeviceGuard g(eng->impl.device);
+        Engine& e = eng->impl;
+        hipStream_t st = (hipStream_t)stream;
+        DeviceBuffer w, b;
+        CV_TRY(w.upload(w_host, (size_t)13 * c * sizeof(float)));
+        CV_TRY(b.upload(bias_host, 13 * sizeof(float)));
+        Activation ax;
+        ax.exp = e.dt == kF32 ? 0 : in_exp;
+        CV_TRY(ax.create(n, h, w_, c, e.dt));
+        hipError_t err = pack_nchw_f32(e.dt, x, c, ax.ref(n), e.guard_ptr(), st);
+        if (err == hipSuccess)
+            err = head_pool_fc(e.dt, ax.ref(n), (const float*)w.ptr, (const float*)b.ptr, out, pooled, softmax, e.guard_ptr(), 0xfffffffeu, st);
+        if (err == hipSuccess) err = hipStreamSynchronize(st);
+        return err != hipSuccess ? hip_fail(err, "cv_op_head_pool_fc") : Status();
     });
 }
 

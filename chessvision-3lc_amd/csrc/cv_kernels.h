@@ -55,6 +55,10 @@ __device__ __forceinline__ void split_pair(float v0, float v1, unsigned& hp, uns
 #endif
 }
 
+// SiLU (x * sigmoid(x)) in float32 on a TRUE value (not a range-scaled one): the accurate library exponential (<= 1 ulp) and an IEEE
+// division, so the result is within ~3 ulp of the exact one; t -> -inf gives -0, as the limit does (exp overflows to +inf).
+__device__ __forceinline__ float silu_f32(float t) { return t / (1.f + expf(-t)); }
+
 // Hand-over of wave-private LDS staging between the lanes of ONE wave (epilogue transposes, pooled-row stores): the writes of every
 // lane are ordered before the reads of every lane at the language level -- release / acquire fences at wavefront scope around a wave
 // barrier -- instead of relying on a compiler-only barrier plus the fact that a wave's DS operations issue in order.
@@ -113,7 +117,7 @@ struct ConvParams {
     int rows;                 // real GEMM rows (multiple of 16); rows beyond are padding
     int nStages;              // K stages of 128 bytes
     int nCt;                  // channel tiles
-    int relu;
+    int relu;                 // activation of the epilogue, an EpiAct: 0 none | 1 ReLU | 2 SiLU (implicit-GEMM family only, see act_*)
     int shuffle;              // 1: rows = (dy,dx,co) of a k2 s2 transposed conv -> pixel-shuffle store
     // optional fused 1x1 head (UNet OutConv, Cout == 64 == one channel tile): logit = sum_c relu(bn(conv))[c] * head_w[c]
     // + head_b is written to head_logits[pixel] (f32, (N,1,H,W)) INSTEAD of the activation tensor; head_mask (nullable)
@@ -172,6 +176,14 @@ struct ConvParams {
     const int* porder;        // [Ho*Wo] positions by falling stage count: the walk starts the long K loops first (see conv_igemm_body.h)
     int posN;                 // images in the launch = rows per position
     int nPtPer;               // pixel tiles per position = ceil(posN / PT)
+    // Epilogue order and the SiLU range factors (conv_igemm.hip and its split-K second pass; every other launch form refuses them).
+    // act_first = 1: affine -> activation -> + residual, nothing after the add (YOLOv8 Bottleneck: x + Conv(Conv(x)));
+    // 0: affine -> + residual -> activation (ResNet BasicBlock).  SiLU does not commute with the power-of-two range scaling of the
+    // f16-based engines as ReLU does, so it runs on the TRUE value: stored = silu(v * act_in) * act_out with act_in = 2^out_exp,
+    // act_out = 2^-out_exp (both products exact; 1 and 1 in the f32 engine), silu(t) = t / (1 + exp(-t)) in float32.
+    int act_first;
+    float act_in, act_out;
 };
+enum EpiAct : int { kActNone = 0, kActRelu = 1, kActSilu = 2 };
 
 }  // namespace cv

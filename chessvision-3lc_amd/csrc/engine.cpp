@@ -836,7 +836,7 @@ Status Engine::measure_tap_sums(ConvLayer& L, const TensorRef& x, int Ho, int Wo
 
 size_t Engine::workspace_bytes() const {
     size_t total = 0;
-    for (const ModelBase* M : {(const ModelBase*)unet.get(), (const ModelBase*)resnet.get()})
+    for (const ModelBase* M : {(const ModelBase*)unet.get(), (const ModelBase*)resnet.get(), (const ModelBase*)yolo.get()})
         if (M) for (const Activation* a : M->acts) total += a->buf.bytes + a->buf32.bytes;
     return total;
 }
@@ -855,7 +855,7 @@ Status need(const ParamMap& pm, const std::string& key, std::vector<int64_t> sha
     return Status();
 }
 
-Status bn_fold(const ParamMap& pm, const std::string& prefix, int c, std::vector<float>& scale, std::vector<float>& shift) {
+Status bn_fold(const ParamMap& pm, const std::string& prefix, int c, std::vector<float>& scale, std::vector<float>& shift, float eps) {
     const float *g, *b, *m, *v;
     CV_TRY(need(pm, prefix + ".weight", {c}, &g));
     CV_TRY(need(pm, prefix + ".bias", {c}, &b));
@@ -863,7 +863,7 @@ Status bn_fold(const ParamMap& pm, const std::string& prefix, int c, std::vector
     CV_TRY(need(pm, prefix + ".running_var", {c}, &v));
     scale.resize(c); shift.resize(c);
     for (int i = 0; i < c; ++i) {
-        const float s = g[i] / std::sqrt(v[i] + 1e-5f);
+        const float s = g[i] / std::sqrt(v[i] + eps);
         scale[i] = s;
         shift[i] = b[i] - m[i] * s;
     }
@@ -871,11 +871,11 @@ Status bn_fold(const ParamMap& pm, const std::string& prefix, int c, std::vector
 }
 
 Status build_conv_bn(Engine& e, ConvLayer& L, const ParamMap& pm, const std::string& conv_key, const std::string& bn_key, int cout,
-                     int cin, int k, int stride, int cinPad, int64_t pixels, int out_hw, int layer_dt) {
+                     int cin, int k, int stride, int cinPad, int64_t pixels, int out_hw, int layer_dt, float bn_eps) {
     const float* w;
     CV_TRY(need(pm, conv_key + ".weight", {cout, cin, k, k}, &w));
     std::vector<float> sc, sh;
-    CV_TRY(bn_fold(pm, bn_key, cout, sc, sh));
+    CV_TRY(bn_fold(pm, bn_key, cout, sc, sh, bn_eps));
     CV_TRY(L.build_conv(conv_key, layer_dt < 0 ? e.dt : layer_dt, w, cout, cin, k, stride, sc.data(), sh.data(), cinPad, pixels, out_hw));
     L.layer_id = e.register_layer(conv_key);
     return Status();
@@ -921,8 +921,19 @@ static bool halo_th8_for(const ConvLayer& L, const ConvParams& p, int ct, int Ho
     return !fused && Ho != 8 && knobs().halo_th8 && wgs < knobs().halo_th8_max_tiles;
 }
 
-Status Engine::run_conv(ConvLayer& L, const TensorRef& x, const TensorRef& y, const TensorRef* res, bool relu,
-                        hipStream_t s, const Head* head, const TensorRef* pool_out, const Fuse0* fuse0) {
+bool Engine::epilogue_plan_ok(int act, bool act_first, bool head, bool pool, bool fuse0, bool shuffle) {
+    if (act != kActNone && act != kActRelu && act != kActSilu) return false;
+    return !((act == kActSilu || act_first) && (head || pool || fuse0 || shuffle));
+}
+
+Status Engine::run_conv(ConvLayer& L, const TensorRef& x, const TensorRef& y, const TensorRef* res, int act,
+                        hipStream_t s, const Head* head, const TensorRef* pool_out, const Fuse0* fuse0, bool act_first) {
+    if (act != kActNone && act != kActRelu && act != kActSilu) return fail(1, L.name + ": unknown epilogue activation " + std::to_string(act));
+    // SiLU and the activation-first order exist in the generic implicit-GEMM family only (plain, position-major, split-K; not the pair): the
+    // planner below never picks the halo kernel for them, and what is written for post-ReLU values is refused outright
+    const bool generic_only = act == kActSilu || act_first;
+    if (!epilogue_plan_ok(act, act_first, head != nullptr, pool_out != nullptr, fuse0 != nullptr, L.shuffle))
+        return fail(1, L.name + ": the fused head, the fused pool, the fused first layer and the pixel shuffle take ReLU-after-residual epilogues only");
     if (x.C != L.cinPad) return fail(1, L.name + ": input slice has " + std::to_string(x.C) + " channels, layer packs " + std::to_string(L.cinPad));
     // a layer normally runs in the engine's arithmetic; the f16r engine runs the ResNet shortcut convolutions in f32 on the
     // trunk's f32 twins (L.dt == kF32, x / y = Activation::ref32)
@@ -974,7 +985,10 @@ Status Engine::run_conv(ConvLayer& L, const TensorRef& x, const TensorRef& y, co
     p.M = x.N * Ho * Wo; p.Ho = Ho; p.Wo = Wo;
     p.xHp = x.H + 2; p.xWp = x.W + 2; p.stride = L.stride; p.xCs = x.Cs; p.xCoffBytes = x.Coff * esz;
     p.yHp = y.H + 2; p.yWp = y.W + 2; p.yCs = y.Cs; p.yCoff = y.Coff;
-    p.Cout = L.cout; p.rows = L.rows; p.nStages = L.nStages; p.nCt = L.nCt; p.relu = relu ? 1 : 0; p.shuffle = L.shuffle ? 1 : 0;
+    p.Cout = L.cout; p.rows = L.rows; p.nStages = L.nStages; p.nCt = L.nCt; p.relu = act; p.shuffle = L.shuffle ? 1 : 0;
+    p.act_first = act_first ? 1 : 0;
+    p.act_in = p.act_out = 1.f;
+    if (act == kActSilu) { p.act_in = std::ldexp(1.f, out_exp); p.act_out = std::ldexp(1.f, -out_exp); }
     if (head) {
         if (L.rows != 64 || L.shuffle) return fail(1, L.name + ": the fused 1x1 head needs a 64-channel layer");
         p.head_w = head->w; p.head_b = head->b; p.head_logits = head->logits; p.head_mask = head->mask; p.head_thr = head->thr;
@@ -989,7 +1003,7 @@ Status Engine::run_conv(ConvLayer& L, const TensorRef& x, const TensorRef& y, co
     p.nCt = (L.rows + conv_cfg_ct(cfg) - 1) / conv_cfg_ct(cfg);
     // 3x3 / stride-1 layers whose patch grid divides the image keep the input patch in LDS across the nine taps
     const bool halo_capable = L.k == 3 && L.stride == 1 && !L.shuffle && kbase != nullptr && L.nStages % 9 == 0 &&
-                              knobs().halo && ct == 64 && conv_halo_supported(Ho, Wo);
+                              knobs().halo && ct == 64 && conv_halo_supported(Ho, Wo) && !generic_only;
     // few patches: the generic kernel's smaller tiles give more workgroups (with the 8 x 16 patch variant the halo kernel doubles its own)
     bool halo = halo_capable && blocks_for(L.rows, p.M, ct, 256) >= ((knobs().halo_th8 && Ho != 8) ? 64 : 128);
     // Split-K: a launch with fewer output tiles than CUs leaves most of the chip idle while every workgroup walks a long K loop
@@ -1133,7 +1147,7 @@ Status Engine::run_conv(ConvLayer& L, const TensorRef& x, const TensorRef& y, co
                                  std::to_string(conv_cfg_pt(cfg)) + ",ring" + std::to_string(ns) + (L.shuffle ? ",shuffle" : "") +
                                  (p.ksplit > 1 ? ",splitK" + std::to_string(p.ksplit) : std::string()) + (pos_major ? ",POS" : "") + ">";
     }
-    if (defer && knobs().pair && !halo && !pos_major && !profiling && !calibrating && !stamp_dev && !head && !fuse0 && p.kbase && !(pool_out && !fuse_pool) &&
+    if (defer && knobs().pair && !generic_only && !halo && !pos_major && !profiling && !calibrating && !stamp_dev && !head && !fuse0 && p.kbase && !(pool_out && !fuse_pool) &&
         !(defer_first && p.ksplit > 1) &&
         blocks_for(L.rows, p.M, conv_cfg_ct(cfg), conv_cfg_pt(cfg)) * (p.ksplit > 1 ? p.ksplit : 1) <= knobs().pair_max_blocks) {
         defer->held = true; defer->cfg = cfg; defer->ns = ns; defer->dt = dt; defer->p = p; defer->name = L.name;

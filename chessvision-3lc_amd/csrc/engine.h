@@ -273,8 +273,10 @@ class Engine {
 
     struct UNet;
     struct ResNet;
+    struct YoloCls;
     std::unique_ptr<UNet> unet;
-    std::unique_ptr<ResNet> resnet;
+    std::unique_ptr<ResNet> resnet;                 // the classifier slot holds one of the two: loading either drops the other
+    std::unique_ptr<YoloCls> yolo;
 
     DeviceBuffer scratch;                               // small per-call parameter blocks (homographies)
     // f32 partial sums of split-K conv launches (grown on demand).  One buffer per model: the UNet pass and the ResNet-18 pass of one
@@ -371,8 +373,14 @@ class Engine {
     static constexpr int kNotFused = 100;           // run_conv's status code when `fuse0` was requested but the launch cannot take it
     // pool_out: also produce max_pool2d(y, 2) -- fused into the conv epilogue when the halo kernel runs the layer,
     // otherwise by the stand-alone pooling kernel right after it
-    Status run_conv(ConvLayer& L, const TensorRef& x, const TensorRef& y, const TensorRef* res, bool relu,
-                    hipStream_t s, const Head* head = nullptr, const TensorRef* pool_out = nullptr, const Fuse0* fuse0 = nullptr);
+    // act: an EpiAct (a bool still reads as none / ReLU).  act_first: affine -> activation -> + residual, nothing after the add (the
+    // YOLOv8 Bottleneck); default affine -> + residual -> activation.  SiLU and act_first run on the generic implicit-GEMM family only.
+    // what run_conv accepts of those options, as a pure predicate: a known activation, and SiLU / act_first never together with the
+    // fused head, the fused pool, the fused first layer or the pixel shuffle (all written for ReLU-after-residual values)
+    static bool epilogue_plan_ok(int act, bool act_first, bool head, bool pool, bool fuse0, bool shuffle);
+    Status run_conv(ConvLayer& L, const TensorRef& x, const TensorRef& y, const TensorRef* res, int act,
+                    hipStream_t s, const Head* head = nullptr, const TensorRef* pool_out = nullptr, const Fuse0* fuse0 = nullptr,
+                    bool act_first = false);
     // Two INDEPENDENT layers in one launch (conv_igemm_pair_kernel; round 5, single boards).  A caller that is about to run two
     // layers with no dependency between them points `defer` at a PendingConv before each run_conv: a launch that qualifies (generic
     // kernel, table-free offsets, no profiling / calibration / stand-alone pool behind it; the FIRST of the two also

@@ -11,9 +11,10 @@ namespace cv {
 // ---- state dict -> layers (engine.cpp) -----------------------------------------------------------------------------------------
 Status need(const ParamMap& pm, const std::string& key, std::vector<int64_t> shape, const float** out);
 // BatchNorm2d(eval): y = (x - mean) / sqrt(var + eps) * gamma + beta  ->  scale, shift
-Status bn_fold(const ParamMap& pm, const std::string& prefix, int c, std::vector<float>& scale, std::vector<float>& shift);
+// (eps: torch's default 1e-5; ultralytics sets 1e-3 and a state dict does not carry it)
+Status bn_fold(const ParamMap& pm, const std::string& prefix, int c, std::vector<float>& scale, std::vector<float>& shift, float eps = 1e-5f);
 Status build_conv_bn(Engine& e, ConvLayer& L, const ParamMap& pm, const std::string& conv_key, const std::string& bn_key, int cout,
-                     int cin, int k, int stride, int cinPad, int64_t pixels, int out_hw = 0, int layer_dt = -1);
+                     int cin, int k, int stride, int cinPad, int64_t pixels, int out_hw = 0, int layer_dt = -1, float bn_eps = 1e-5f);
 void bn_keys(std::vector<std::string>& out, const std::string& p);       // appends the four keys of BatchNorm2d `p`
 // `known` = every key the architecture defines, so that a checkpoint of a DIFFERENT architecture (extra / renamed keys: the
 // reference's UNet is an un-vendored submodule on an `experimental` branch) is rejected instead of half-loaded
@@ -38,7 +39,7 @@ inline int frag_row_channel(int nfrag, int f, int i) { return 4 * nfrag * (i / 4
 // `model_reserve` (re)allocates every tensor for min(n, engine chunk) items the first time a batch of that size arrives --
 // a single-image server (the reference's Flask endpoint) stays under 1 GB, a throughput job grows once to its chunk.
 struct ModelBase {
-    int slot = 0;                                   // 0 = UNet, 1 = ResNet: Engine::order_forward / ws_slot, GraphKey::model
+    int slot = 0;                                   // 0 = UNet, 1 = the classifier (ResNet | YOLOv8-cls): Engine::order_forward / ws_slot, GraphKey::model
     int cap = 0;                                    // items (images / squares) the workspace currently holds
     int max_cap = 0;                                // engine chunk: items per pass
     int last_n = 0;                                 // items in the most recent chunk
@@ -111,8 +112,58 @@ struct Engine::ResNet : ModelBase {
     void build_taps(const Engine& e, int S) override;
 };
 
+// ultralytics YOLOv8-cls (yolov8-cls.yaml; Conv, C2f, Bottleneck, Classify of ultralytics.nn.modules), one input channel, 13 classes:
+//   model.0 Conv(1, w0, 3, 2)  model.1 Conv(w0, w1, 3, 2)  model.2 C2f(w1, n0)  model.3 Conv(w1, w2, 3, 2)  model.4 C2f(w2, n1)
+//   model.5 Conv(w2, w3, 3, 2)  model.6 C2f(w3, n2)  model.7 Conv(w3, w4, 3, 2)  model.8 C2f(w4, n3)
+//   model.9 Classify: Conv(w4, 1280, 1) -> average pool -> Linear(1280, 13)
+// Conv = Conv2d(bias=False) + BatchNorm2d(eps=1e-3) + SiLU.  C2f(w, n), c = w / 2: cv1 = Conv(w, 2c, 1) fills channels [0, 2c) of ONE
+// (2 + n) c-channel tensor; Bottleneck i reads [(1+i)c, (2+i)c), writes [(2+i)c, (3+i)c) = input + Conv(c,c,3)(Conv(c,c,3)(input)) -- the add
+// AFTER the SiLU, nothing after the add; cv2 = Conv((2+n)c, w, 1) reads the whole tensor.  The five scales differ in widths and depths.
+struct YoloClsArch {
+    const char* name;                               // "yolov8n-cls" ... "yolov8x-cls"
+    int width[5];                                   // w0 .. w4
+    int depth[4];                                   // Bottlenecks of the four C2f
+};
+const YoloClsArch* yolo_cls_arch(const std::string& name);    // null: not one of the five
+constexpr int kYoloHeadC = 1280;
+
+struct Engine::YoloCls : ModelBase {
+    YoloCls() { slot = 1; }
+    const YoloClsArch* arch = nullptr;
+    DeviceBuffer stem_w, stem_scale, stem_shift, fc_w, fc_b;      // model.0 (float32 kernel, true BN constants), model.9.linear
+    unsigned stem_id = 0, head_id = 0;
+    struct Bottleneck { ConvLayer cv1, cv2; Activation mid; };
+    struct Stage {                                  // model.(2s+1) and model.(2s+2)
+        ConvLayer down, cv1, cv2;
+        std::unique_ptr<Bottleneck[]> m;
+        int n = 0, c = 0, hw = 0;
+        Activation down_out, cat, out;              // model.(2s+1); the (2+n)c-channel concat tensor (one exponent); model.(2s+2)
+    };
+    Stage stage[4];
+    ConvLayer head_conv;                            // model.9.conv
+    Activation stem_out, head_out;
+    void build_taps(const Engine& e, int S) override;
+};
+
 // x in [0,1] is held as x * 2^7 inside the f16-based engines (both models' inputs)
 constexpr int kInputExp = -7;
+
+// The classifier slot holds a ResNet or a YOLOv8-cls; what the C ABI's classifier entries need of whichever is loaded.
+// classifier_calibration_squares: the loaders' calibration batch, n_range + n_bias squares of 64 x 64 floats in [0, 1] -- noise, flat grey
+// levels, ramps and checkers for the ranges, then noise and smooth bilinear fields for the rounding-bias pass (resnet.cpp).
+void classifier_calibration_squares(std::vector<float>& host, int n_range, int n_total);
+const char* classifier_name(const Engine& e);                 // architecture name of the loaded classifier, or null
+ModelBase* classifier_model(Engine& e);
+int classifier_embedding_dim(const Engine& e);                // 512 | 1280 | 0: none loaded
+const char* classifier_pool_tap(const Engine& e);             // the tensor whose channel means are the embedding: "layer4" | "model.9.conv"
+Status classifier_forward(Engine& e, const void* x, bool x_u8, int n, float* out, bool softmax, hipStream_t s, float* embedding = nullptr,
+                          const InputNorm* norm = nullptr);
+Status classifier_activation(Engine& e, const std::string& name, TensorRef* out);
+int64_t classifier_macs(Engine& e);
+Status yolo_cls_load(Engine& e, const ParamMap& pm, const std::string& arch);
+Status yolo_cls_forward(Engine& e, const void* x, bool x_u8, int n, float* out, bool softmax, hipStream_t s, float* embedding = nullptr,
+                        const InputNorm* norm = nullptr);
+Status yolo_cls_activation(Engine& e, const std::string& name, TensorRef* out);
 
 // ---- chunks, load-time calibration, the forward driver -----------------------------------------------------------------------------
 // chunk(offset, count) over n items, at most the workspace's capacity at a time

@@ -60,6 +60,16 @@ hipError_t head_avgpool_fc(int dt, const TensorRef& src, const float* w, const f
                            int softmax, unsigned* flag, unsigned layer_id, hipStream_t s);
 hipError_t softmax13(const float* logits, int n, float* probs, hipStream_t s);
 
+// YOLOv8-cls stem: conv 3x3 s2 p1 (1 -> dst.C, no bias) + BN affine + SiLU, float32 arithmetic in every engine.  x as stem7x7's
+// (float, u8 scaled by /255, u8 normalised); w: [dst.C][9] f32 (the checkpoint's three input channels summed), scale / shift: [dst.C]
+// TRUE constants (no range factors: 2^-dst.exp is applied after the SiLU).  dst: the whole 32 x 32 tensor, dst.C a multiple of 8.
+hipError_t stem3x3s2(int dt, const void* x, bool x_is_u8, int n, const float* w, const float* scale, const float* shift,
+                     const TensorRef& dst, unsigned* flag, unsigned layer_id, hipStream_t s, const InputNorm* norm = nullptr);
+// head_avgpool_fc for any channel count that is a multiple of 8 (YOLOv8-cls: 1280): global average pool + Linear(C -> 13)
+// (+ optional softmax); pooled (nullable, (n, C) float32, 16-byte aligned) receives the pooled features.  w: [13][C] f32, b: [13]
+hipError_t head_pool_fc(int dt, const TensorRef& src, const float* w, const float* b, float* out, float* pooled, int softmax,
+                        unsigned* flag, unsigned layer_id, hipStream_t s);
+
 // Board-extraction quality scores (the per-image reductions behind the reference's `confidence` and `distribution` columns,
 // scripts/process_new_raw/process_pipeline.py:357-377, 460-467).  values: n images of `count` contiguous float32 (4 <= count <= 2^24);
 // transform 0 scores them as given, 1 scores v = 1 / (1 + __expf(-x)) (outc_1x1's mask expression).  One record per image:

@@ -1011,6 +1011,158 @@ __global__ __launch_bounds__(256) void head_kernel(TensorRef src, const float* _
     report_bad(flag, layer_id, bad);
 }
 
+// ---- YOLOv8-cls stem: conv 3x3 s2 p1, 1 -> C0 (16 .. 80), + BN affine + SiLU ----------------------------------
+// stem7x7_kernel's scheme on a 3x3 filter: one workgroup per 64x64 square, the zero-bordered plane in LDS, each lane one output pixel
+// at a time with its 9-pixel patch in registers, the C0 x 9 filter bank wave-uniform through the scalar cache; float32 throughout, in
+// every engine (the stem holds under 1 % of the smallest scale's MACs).  The three input channels of the checkpoint see the same plane
+// (the reference repeats it), so the loader has summed their filters: one channel here.  `mul` = 2^-exp of the stored output, applied
+// AFTER the SiLU (cv_kernels.h: silu_f32).  NORM as in stem7x7_kernel.
+template <typename T, typename XT, bool NORM = false>
+__global__ __launch_bounds__(256) void stem3x3s2_kernel(const XT* __restrict__ x, const float* __restrict__ w,
+                                                        const float* __restrict__ scale, const float* __restrict__ shift,
+                                                        TensorRef dst, float mul, InputNorm norm, unsigned* flag, unsigned layer_id) {
+    constexpr int IN = 64, LD = IN + 2, OUT = 32;
+    constexpr int GN = Grp<T>::N;
+    __shared__ float plane[LD * LD];
+    const int n = blockIdx.x;
+    const int tid = threadIdx.x;
+    for (int i = tid; i < LD * LD; i += 256) plane[i] = 0.f;
+    __syncthreads();
+    const XT* xs = x + (size_t)n * IN * IN;
+    for (int i = tid; i < IN * IN; i += 256) {
+        float v = (float)xs[i];
+        if (sizeof(XT) == 1) v = v / 255.f;
+        if (NORM) v = (v - norm.mean) / norm.std;
+        plane[(i / IN + 1) * LD + (i % IN) + 1] = v;
+    }
+    __syncthreads();
+    float bad = 0.f;
+    for (int it = 0; it < OUT * OUT / 256; ++it) {
+        const int pid = it * 256 + tid;
+        const int oy = pid / OUT, ox = pid % OUT;
+        float patch[9];
+#pragma unroll
+        for (int ky = 0; ky < 3; ++ky)
+#pragma unroll
+            for (int kx = 0; kx < 3; ++kx) patch[ky * 3 + kx] = plane[(2 * oy + ky) * LD + 2 * ox + kx];
+        const size_t opix = pix_index(dst, n, oy, ox);
+#pragma unroll 1
+        for (int cb = 0; cb < dst.C; cb += 8) {          // dst.C is a multiple of 8 (checked by the wrapper)
+            const float* wc = w + cb * 9;
+            float v[8];
+#pragma unroll
+            for (int c = 0; c < 8; ++c) {
+                float a = 0.f;
+#pragma unroll
+                for (int k = 0; k < 9; ++k) a = __builtin_fmaf(patch[k], wc[c * 9 + k], a);
+                a = a * scale[cb + c] + shift[cb + c];
+                v[c] = silu_f32(a) * mul;
+            }
+#pragma unroll
+            for (int i = 0; i < 8; i += GN) {
+                int par;
+                char* d = grp_ptr<T>(dst, opix, (cb + i) / GN, &par);
+                Grp<T>::store(d, par, v + i, bad);
+            }
+        }
+    }
+    report_bad(flag, layer_id, bad);
+}
+
+// ---- YOLOv8-cls head: adaptive_avg_pool2d(1) + Linear(C -> 13) (+ softmax) (+ the pooled features) ------------------------------
+// head_kernel generalised to any C that is a multiple of 8 (C = 1280: 20 channels per lane, whose 13 x 20 weights do not fit in
+// registers as the 13 x 8 of the 512-channel form do).  One wave walks kHeadQ squares at a time: for each of its channel groups
+// (group = lane, lane + 64, ...) it loads the 13 x GN weights once and uses them for the kHeadQ squares, so the weights cross L2 ->
+// CU once per kHeadQ squares.  Per square and channel: the H x W values summed in raster order, mean = sum * mul / (H W), 13 FMAs in
+// channel order; the 64 lanes' partial sums meet in a xor butterfly (every lane ends with every logit).  A square's arithmetic does not
+// depend on its place in the batch.  pooled (nullable): the means, (n, C) float32 -- the input of the linear layer.
+constexpr int kHeadQ = 4;
+template <typename T>
+__global__ __launch_bounds__(256) void head_pool_fc_kernel(TensorRef src, const float* __restrict__ w, const float* __restrict__ b,
+                                                           float mul, float* __restrict__ out, float* __restrict__ pooled, int softmax,
+                                                           unsigned* flag, unsigned layer_id) {
+    constexpr int NC = 13;
+    constexpr int GN = Grp<T>::N;
+    const int lane = threadIdx.x & 63;
+    const int wave0 = blockIdx.x * 4 + (threadIdx.x >> 6), nwaves = gridDim.x * 4;
+    const int groups = src.C / GN;
+    const float inv = mul / (float)(src.H * src.W);
+    float bad = 0.f;
+    for (int n0 = wave0 * kHeadQ; n0 < src.N; n0 += nwaves * kHeadQ) {
+        float acc[kHeadQ][NC];
+#pragma unroll
+        for (int q = 0; q < kHeadQ; ++q)
+#pragma unroll
+            for (int k = 0; k < NC; ++k) acc[q][k] = 0.f;
+        for (int g = lane; g < groups; g += 64) {
+            float wr[NC][GN];
+#pragma unroll
+            for (int k = 0; k < NC; ++k)
+#pragma unroll
+                for (int j = 0; j < GN; j += 4) {
+                    const f4 t = *reinterpret_cast<const f4*>(w + (size_t)k * src.C + g * GN + j);
+                    wr[k][j] = t[0]; wr[k][j + 1] = t[1]; wr[k][j + 2] = t[2]; wr[k][j + 3] = t[3];
+                }
+#pragma unroll
+            for (int q = 0; q < kHeadQ; ++q) {
+                const int n = n0 + q;
+                if (n >= src.N) break;                       // wave-uniform
+                float sum[GN];
+#pragma unroll
+                for (int j = 0; j < GN; ++j) sum[j] = 0.f;
+                for (int y = 0; y < src.H; ++y)
+                    for (int xx = 0; xx < src.W; ++xx) {
+                        int par;
+                        float v[GN];
+                        Grp<T>::load(grp_ptr<T>(src, pix_index(src, n, y, xx), g, &par), par, v);
+#pragma unroll
+                        for (int j = 0; j < GN; ++j) sum[j] += v[j];
+                    }
+#pragma unroll
+                for (int j = 0; j < GN; ++j) sum[j] *= inv;
+                if (pooled) {
+#pragma unroll
+                    for (int j = 0; j < GN; j += 4)
+                        *reinterpret_cast<f4*>(pooled + (size_t)n * src.C + g * GN + j) = f4{sum[j], sum[j + 1], sum[j + 2], sum[j + 3]};
+                }
+#pragma unroll
+                for (int k = 0; k < NC; ++k)
+#pragma unroll
+                    for (int j = 0; j < GN; ++j) acc[q][k] = __builtin_fmaf(sum[j], wr[k][j], acc[q][k]);
+            }
+        }
+#pragma unroll
+        for (int q = 0; q < kHeadQ; ++q) {
+            const int n = n0 + q;
+            if (n >= src.N) break;
+            float mine = 0.f, mx = -INFINITY;
+#pragma unroll
+            for (int k = 0; k < NC; ++k) {
+                float v = acc[q][k];
+#pragma unroll
+                for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);
+                v += b[k];
+                acc[q][k] = v;
+                mx = fmaxf(mx, v);
+                if (lane == k) mine = v;
+            }
+            if (lane < NC) bad = __builtin_fmaf(mine, 0.f, bad);
+            if (softmax) {
+                float sum = 0.f, e_mine = 0.f;
+#pragma unroll
+                for (int k = 0; k < NC; ++k) {
+                    const float e = __expf(acc[q][k] - mx);
+                    sum += e;
+                    if (lane == k) e_mine = e;
+                }
+                mine = e_mine / sum;
+            }
+            if (lane < NC) out[(size_t)n * NC + lane] = mine;
+        }
+    }
+    report_bad(flag, layer_id, bad);
+}
+
 __global__ void softmax13_kernel(const float* __restrict__ logits, int n, float* __restrict__ probs) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
@@ -1587,6 +1739,30 @@ hipError_t head_avgpool_fc(int dt, const TensorRef& src, const float* w, const f
     const int blocks = (src.N + 3) / 4;
     const dim3 g((unsigned)(blocks < 1 ? 1 : blocks > 2048 ? 2048 : blocks)), blk(256);
     with_dtype(dt, [&](auto t) { hipLaunchKernelGGL(head_kernel<tag_t<decltype(t)>>, g, blk, 0, s, src, w, b, pow2f(src.exp), out, softmax, flag, layer_id); });
+    return hipGetLastError();
+}
+hipError_t stem3x3s2(int dt, const void* x, bool x_is_u8, int n, const float* w, const float* scale, const float* shift,
+                     const TensorRef& dst, unsigned* flag, unsigned layer_id, hipStream_t s, const InputNorm* norm) {
+    if (n < 1 || dst.N < n || dst.C % 8 || dst.C < 8 || dst.C != dst.Cs || dst.Coff != 0 || dst.H != 32 || dst.W != 32 || (norm && !x_is_u8))
+        return hipErrorInvalidValue;
+    const dim3 g((unsigned)n), b(256);
+    const InputNorm nm = norm ? *norm : InputNorm{0.f, 1.f};
+    with_dtype(dt, [&](auto t) {
+        with_input(x, x_is_u8, norm != nullptr, [&](auto* px, auto NORM) {
+            hipLaunchKernelGGL((stem3x3s2_kernel<tag_t<decltype(t)>, pointee_t<decltype(px)>, decltype(NORM)::value>), g, b, 0, s, px, w, scale, shift,
+                               dst, pow2f(-dst.exp), nm, flag, layer_id);
+        });
+    });
+    return hipGetLastError();
+}
+hipError_t head_pool_fc(int dt, const TensorRef& src, const float* w, const float* b, float* out, float* pooled, int softmax,
+                        unsigned* flag, unsigned layer_id, hipStream_t s) {
+    if (src.N < 1 || src.C % 8 || src.C < 8 || src.Coff != 0 || src.Cs != src.C || src.split || ((uintptr_t)pooled & 15u)) return hipErrorInvalidValue;
+    const int blocks = (src.N + 4 * kHeadQ - 1) / (4 * kHeadQ);
+    const dim3 g((unsigned)(blocks > 2048 ? 2048 : blocks)), blk(256);
+    with_dtype(dt, [&](auto t) {
+        hipLaunchKernelGGL(head_pool_fc_kernel<tag_t<decltype(t)>>, g, blk, 0, s, src, w, b, pow2f(src.exp), out, pooled, softmax, flag, layer_id);
+    });
     return hipGetLastError();
 }
 hipError_t extraction_scores(const float* values, int n, int count, int transform, ScoreRecord* records, uint8_t* half_mask,

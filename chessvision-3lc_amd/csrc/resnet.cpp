@@ -50,6 +50,38 @@ static Status stem_set_exp(Engine::ResNet& R, int dt, int out_exp, hipStream_t s
     return Status();
 }
 
+void classifier_calibration_squares(std::vector<float>& host, int kCal, int kBias) {
+    host.assign((size_t)kBias * 4096, 0.f);
+    uint32_t rs = 0x2545F491u;
+    auto rnd = [&]() { rs = rs * 1664525u + 1013904223u; return (rs >> 24) & 0xffu; };
+    for (int q = 0; q < kCal; ++q)
+        for (int y = 0; y < 64; ++y)
+            for (int x = 0; x < 64; ++x) {
+                float v;
+                if (q < 48) v = (float)rnd();
+                else if (q < 80) v = (float)((q - 48) * 8 + 3);                                   // flat levels 3..251
+                else if (q < 104) v = (float)(((x * (q - 79)) + y * 3) & 255);                      // ramps
+                else v = (((x >> (q & 3)) + (y >> ((q >> 2) & 3))) & 1) ? 235.f : (float)(20 + (q - 104) * 6);   // checkers
+                host[((size_t)q * 64 + y) * 64 + x] = v / 255.f;
+            }
+    for (int q = kCal; q < kBias; ++q) {
+        float grid[5][5];
+        for (auto& row : grid) for (float& g : row) g = (float)rnd();
+        for (int y = 0; y < 64; ++y)
+            for (int x = 0; x < 64; ++x) {
+                float v;
+                if (q < kCal + 64) v = (float)rnd();
+                else {                                                                               // bilinear, cell = 16 pixels
+                    const int gy = y >> 4, gx = x >> 4;
+                    const float fy = (float)(y & 15) / 16.f, fx = (float)(x & 15) / 16.f;
+                    const float top = grid[gy][gx] * (1.f - fx) + grid[gy][gx + 1] * fx, bot = grid[gy + 1][gx] * (1.f - fx) + grid[gy + 1][gx + 1] * fx;
+                    v = std::floor(top * (1.f - fy) + bot * fy + 0.5f);
+                }
+                host[((size_t)q * 64 + y) * 64 + x] = v / 255.f;
+            }
+    }
+}
+
 Status resnet_load(Engine& e, const ParamMap& pm, const std::string& arch) {
     const ResNetArch* A = resnet_arch(arch);
     if (!A) return fail(1, "unknown ResNet architecture '" + arch + "' (supported: 'resnet18', 'resnet34')");
@@ -206,35 +238,8 @@ Status resnet_load(Engine& e, const ParamMap& pm, const std::string& arch) {
     Status st = model_reserve(e, R, 128);
     if (st.ok() && dt != kF32 && calibration_enabled()) {
         constexpr int kCal = 128, kBias = 256;
-        std::vector<float> host((size_t)kBias * 4096);
-        uint32_t rs = 0x2545F491u;
-        auto rnd = [&]() { rs = rs * 1664525u + 1013904223u; return (rs >> 24) & 0xffu; };
-        for (int q = 0; q < kCal; ++q)
-            for (int y = 0; y < 64; ++y)
-                for (int x = 0; x < 64; ++x) {
-                    float v;
-                    if (q < 48) v = (float)rnd();
-                    else if (q < 80) v = (float)((q - 48) * 8 + 3);                                   // flat levels 3..251
-                    else if (q < 104) v = (float)(((x * (q - 79)) + y * 3) & 255);                      // ramps
-                    else v = (((x >> (q & 3)) + (y >> ((q >> 2) & 3))) & 1) ? 235.f : (float)(20 + (q - 104) * 6);   // checkers
-                    host[((size_t)q * 64 + y) * 64 + x] = v / 255.f;
-                }
-        for (int q = kCal; q < kBias; ++q) {
-            float grid[5][5];
-            for (auto& row : grid) for (float& g : row) g = (float)rnd();
-            for (int y = 0; y < 64; ++y)
-                for (int x = 0; x < 64; ++x) {
-                    float v;
-                    if (q < kCal + 64) v = (float)rnd();
-                    else {                                                                               // bilinear, cell = 16 pixels
-                        const int gy = y >> 4, gx = x >> 4;
-                        const float fy = (float)(y & 15) / 16.f, fx = (float)(x & 15) / 16.f;
-                        const float top = grid[gy][gx] * (1.f - fx) + grid[gy][gx + 1] * fx, bot = grid[gy + 1][gx] * (1.f - fx) + grid[gy + 1][gx + 1] * fx;
-                        v = std::floor(top * (1.f - fy) + bot * fy + 0.5f);
-                    }
-                    host[((size_t)q * 64 + y) * 64 + x] = v / 255.f;
-                }
-        }
+        std::vector<float> host;
+        classifier_calibration_squares(host, kCal, kBias);
         DeviceBuffer xin;
         st = xin.upload(host.data(), host.size() * sizeof(float));
         std::vector<ConvLayer*> layers;                                         // the f16 layers of the rounding-bias pass
@@ -248,6 +253,7 @@ Status resnet_load(Engine& e, const ParamMap& pm, const std::string& arch) {
                                  [&](const float* x, int n, float* out) { return resnet_chunk(e, x, false, n, out, false, nullptr); });
     }
     if (!st.ok()) e.resnet.reset();
+    else e.yolo.reset();                                 // the classifier slot holds one model
     return st;
 }
 
@@ -452,3 +458,6 @@ Status resnet_forward(Engine& e, const void* x, bool x_u8, int n, float* out, bo
 }
 
 }  // namespace cv
+
+// the classifier slot's other model rides in this translation unit (Makefile: YOLO; why: the head of yolo_cls.cpp)
+#include "yolo_cls.cpp"

@@ -132,6 +132,18 @@ int cv_load_unet(cv_engine_t* eng, const cv_param_t* params, int n_params);
  * CV_ERR_STATE naming what is loaded. */
 int cv_load_resnet(cv_engine_t* eng, const char* arch, const cv_param_t* params, int n_params);
 int cv_load_resnet18(cv_engine_t* eng, const cv_param_t* params, int n_params);
+/* The piece classifier as ultralytics' YOLOv8-cls: arch = "yolov8n-cls" | "yolov8s-cls" | "yolov8m-cls" | "yolov8l-cls" | "yolov8x-cls"
+ * (any other fails with CV_ERR_INVALID and the message lists the five), 13 classes.  Keys are those of YOLO(path).model.state_dict():
+ * model.0.conv.weight, model.0.bn.{weight,bias,running_mean,running_var}, model.2.cv1.conv.weight, model.2.m.0.cv1.conv.weight, ...,
+ * model.9.conv.conv.weight, model.9.linear.{weight,bias}; BatchNorm eps is 1e-3.  The stem weight may have three input channels (summed
+ * into one at load: the reference feeds the grey square three times) or one.  The form model.fuse() leaves (X.conv.weight + X.conv.bias,
+ * no X.bn.*) is accepted too, a dict that mixes the two is refused; validation is as strict as cv_load_resnet's.
+ * The classifier slot of an engine holds ONE model, a ResNet or a YOLOv8-cls: a successful load replaces whichever was there.  Every
+ * classifier entry (cv_resnet18_forward*, cv_resnet_forward_u8_norm, cv_process_image*, cv_process_jpeg*) runs what the slot holds and
+ * the by-name entries take the loaded architecture's name.  Input as the reference passes it: (n, 1, 64, 64) in [0, 1], no resize, no
+ * crop; the float entries return logits, the u8 entries the softmax.  The embedding (cv_embedding_dim: 1280) is the pooled
+ * model.9.conv output, the linear layer's input.  Precisions: f32, f16x3, f16; CV_PREC_F16R is refused (its f32 trunk is ResNet's). */
+int cv_load_yolo_cls(cv_engine_t* eng, const char* arch, const cv_param_t* params, int n_params);
 
 /* Largest number of images (UNet) / squares (ResNet) processed per internal pass; larger batches are
  * looped inside the forward call.  0 = keep default (64 images / 16384 squares).  Must be called before cv_load_*.
@@ -275,6 +287,30 @@ int cv_op_conv2d(cv_engine_t* eng, const float* x, int n, int cin, int h, int w_
                  int cout, int k, int stride, const float* scale_host, const float* shift_host,
                  const float* residual, int relu, float* y, void* stream);
 /*   conv-transpose k2 s2:  y(n,cout,2h,2w) = convT(x, w) + bias;  w: HOST (cin,cout,2,2) */
+/* cv_op_conv2d with the epilogue options and channel slices of the YOLOv8-cls plan.  x: (n, x_channels, h, w) device float32, the layer
+ * reads channels [x_coff, x_coff + cin); y: (n, y_channels, ho, wo) device float32, IN and OUT: it is stored as given, the layer writes
+ * channels [y_coff, y_coff + cout) and the whole tensor comes back -- channels outside the slice must return unchanged.  act: 0 none |
+ * 1 ReLU | 2 SiLU; act_first: activation, then the residual, nothing after (default: residual, then activation).  res_coff >= 0: the
+ * residual is channels [res_coff, res_coff + cout) of y as given (stride 1 only); < 0: none.  in_exp / out_exp: the tensors are stored
+ * as value * 2^-exp in the f16-based engines (0 in the f32 engine).  Channel counts and offsets are multiples of 8.  The launch is
+ * recorded as cv_op_conv2d's is. */
+int cv_op_conv2d_act(cv_engine_t* eng, const float* x, int n, int x_channels, int x_coff, int cin, int h, int w_, const float* w_host, int cout,
+                     int k, int stride, const float* scale_host, const float* shift_host, int act, int act_first, float* y, int y_channels,
+                     int y_coff, int res_coff, int in_exp, int out_exp, void* stream);
+/* Which epilogue options a launch form accepts -- the pure predicate its launcher asks before anything else (a refused launch returns
+ * an error; no form ever runs an activation it was not asked for).  form 0: implicit-GEMM (plain / position-major / split-K second
+ * pass), 1: the pair launch, 2: the halo kernel, 3: its chained launch, 4: the planner (Engine::run_conv).  act: 0 none | 1 ReLU |
+ * 2 SiLU; act_first as in cv_op_conv2d_act; with_head / with_pool: a fused 1x1 head / fused pool rides on the epilogue; with_fuse0 /
+ * shuffle (form 4 only): the fused first layer / the pixel-shuffle store.  *ok = 1 accepted, 0 refused.  Launches nothing. */
+int cv_op_conv_epilogue_ok(int form, int act, int act_first, int with_head, int with_pool, int with_fuse0, int shuffle, int* ok);
+/* The YOLOv8-cls stem alone: conv 3x3 s2 p1 (1 -> c0) + affine + SiLU.  x: (n, 64, 64) device float32 or uint8 (x_u8; std > 0: the bytes
+ * are normalised ((u8 / 255) - mean) / std); w_host [c0][9], scale_host / shift_host [c0]; y: (n, c0, 32, 32) device float32. */
+int cv_op_stem3x3s2(cv_engine_t* eng, const void* x, int x_u8, int n, int c0, const float* w_host, const float* scale_host,
+                    const float* shift_host, float mean, float std, int out_exp, float* y, void* stream);
+/* The YOLOv8-cls head alone: average pool over h x w + Linear(c -> 13) (+ softmax).  x: (n, c, h, w) device float32; w_host [13][c],
+ * bias_host [13]; out: (n, 13) device float32; pooled: (n, c) device float32, 16-byte aligned, or NULL. */
+int cv_op_head_pool_fc(cv_engine_t* eng, const float* x, int n, int c, int h, int w_, const float* w_host, const float* bias_host,
+                       int softmax, int in_exp, float* out, float* pooled, void* stream);
 int cv_op_conv_transpose2x2(cv_engine_t* eng, const float* x, int n, int cin, int h, int w_,
                             const float* w_host, int cout, const float* bias_host, float* y, void* stream);
 /*   conv 1x1 c -> 1 + bias: logits (n,1,h,w) float32; mask (nullable, n x h x w uint8) = sigmoid(logit) > threshold ? 255 : 0
