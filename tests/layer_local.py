@@ -1,4 +1,4 @@
-"""Layer-local parity: every tapped layer of the UNet and of the ResNet classifiers against float64, one layer at a time.
+"""Layer-local parity: every tapped layer of the UNet, the ResNet and the YOLOv8-cls classifiers against float64, one layer at a time.
 
 TEST INFRASTRUCTURE -- a plain module (no conftest), imports nothing from ``chessvision.hip_backend``, so the CPU tests drive it with
 forward hooks of the torch oracle and the GPU tests with ``HipEngine.activation``.
@@ -10,7 +10,8 @@ bar.  Nothing upstream of the input tap and nothing downstream of the output tap
 
 Three parts:
   * float64 reference ops on ``torch.nn.functional`` over ``double`` tensors, straight from a reference-format state dict (they share no
-    code with oracle/unet_ref.py / oracle/resnet_ref.py beyond torch itself; BatchNorm eps = 1e-5, folded in float64);
+    code with oracle/unet_ref.py / oracle/resnet_ref.py / tests/yolov8_cls_ref.py beyond torch itself; BatchNorm eps = 1e-5 -- 1e-3 for
+    YOLOv8-cls -- folded in float64);
   * the edge tables: one ``Op`` per module output, (output tap, input taps, reference function, kind).  Where an engine fuses a tensor
     away (the stated ``expected_absent`` set) the edge spans the ops from the nearest upstream tap; any OTHER missing tap fails the run;
   * ``check_edges``: evaluates the edges for the chosen images, returns the figures and raises ONE AssertionError naming every failing edge.
@@ -28,6 +29,7 @@ import torch
 import torch.nn.functional as F
 
 BN_EPS = 1e-5
+YOLO_BN_EPS = 1e-3                 # ultralytics sets it in initialize_weights; a state dict does not carry it
 INPUT = "@x"                       # the caller's input tensor (float32 as the engine receives it, or u8 / 255 done in float32)
 
 # ---- bars ---------------------------------------------------------------------------------------------------------------------
@@ -62,6 +64,29 @@ def conv_bn(sd, conv, bn, x, stride=1, residual=None, relu=True):
     if residual is not None:
         y = y + residual
     return F.relu(y) if relu else y
+
+
+def conv_act(sd, p, x, stride=1, act="silu", shortcut=None, eps=YOLO_BN_EPS):
+    """ultralytics ``Conv`` ``p``: conv k x k / stride / pad k // 2, then the eval-mode BatchNorm (``p.bn.*``, folded in float64) or -- a
+    checkpoint as ``model.fuse()`` leaves it -- the bias ``p.conv.bias`` with scale 1, then the activation, then (+ shortcut): the add
+    comes AFTER the activation.  A filter with more input channels than ``x`` has is summed over them (the grey square repeated)."""
+    w = _p(sd, p + ".conv.weight")
+    if w.shape[1] != x.shape[1]:
+        assert x.shape[1] == 1, (p, tuple(w.shape), tuple(x.shape))
+        w = w.sum(1, keepdim=True)
+    if p + ".conv.bias" in sd:
+        shift = _p(sd, p + ".conv.bias")
+    else:
+        scale = _p(sd, p + ".bn.weight") / torch.sqrt(_p(sd, p + ".bn.running_var") + eps)
+        shift = _p(sd, p + ".bn.bias") - _p(sd, p + ".bn.running_mean") * scale
+        w = w * scale.view(-1, 1, 1, 1)
+    y = F.conv2d(x, w, shift, stride=stride, padding=w.shape[-1] // 2)
+    y = {"silu": lambda t: t * torch.sigmoid(t), "relu": F.relu, "none": lambda t: t}[act](y)
+    return y if shortcut is None else y + shortcut
+
+
+def yolo_head(sd, x):
+    return F.linear(x.mean((2, 3)), _p(sd, "model.9.linear.weight"), _p(sd, "model.9.linear.bias"))
 
 
 def maxpool2(x):
@@ -159,8 +184,61 @@ def resnet_ops(sd, entry: str = "float") -> list:
     return ops
 
 
+YOLO_STEM_WIDTHS = {16: "n", 32: "s", 48: "m", 64: "l", 80: "x"}
+
+
+def is_yolo_cls(sd) -> bool:
+    return "model.0.conv.weight" in sd
+
+
+def yolo_cls_scale(sd) -> str:
+    """"n" | "s" | "m" | "l" | "x" by the widths in the dict: the stem's and, as a cross-check, model.9.conv's input (16 x the stem's)."""
+    w0, w4 = int(sd["model.0.conv.weight"].shape[0]), int(sd["model.9.conv.conv.weight"].shape[1])
+    assert w0 in YOLO_STEM_WIDTHS and w4 == 16 * w0, f"not a YOLOv8-cls state dict: stem width {w0}, model.9.conv input {w4}"
+    return YOLO_STEM_WIDTHS[w0]
+
+
+def yolo_cls_depths(sd) -> tuple:
+    return tuple(len({k.split(".")[3] for k in sd if k.startswith(f"model.{P}.m.")}) for P in (2, 4, 6, 8))
+
+
+def yolo_cls_ops(sd, arch=None, entry: str = "float") -> list:
+    """Every module output of the ultralytics YOLOv8-cls in ``sd`` (as trained, or as ``model.fuse()`` leaves it) by its tap name
+    (yolo_cls.cpp: Engine::YoloCls::build_taps) + "logits"; ``entry="u8"`` adds "probs".  ``arch`` ("yolov8x-cls" or "x"), when given,
+    must be the scale the widths of ``sd`` say.  A C2f's chunk / cat move nothing: its Bottlenecks read and write channel slices of
+    tensors that are themselves taps, so every edge goes from stored inputs to one stored output."""
+    scale = yolo_cls_scale(sd)
+    if arch is not None:
+        assert (arch[6] if arch.startswith("yolov8") else arch) == scale, f"{arch!r} asked for, the state dict is yolov8{scale}-cls"
+    ops = [Op("model.0", [INPUT], lambda sd, x: conv_act(sd, "model.0", x, stride=2), "conv")]
+    cur = "model.0"
+    for s, n in enumerate(yolo_cls_depths(sd)):
+        down, P = f"model.{2 * s + 1}", f"model.{2 * s + 2}"
+        c = int(sd[P + ".cv1.conv.weight"].shape[0]) // 2
+        ops.append(Op(down, [cur], lambda sd, x, p=down: conv_act(sd, p, x, stride=2), "conv"))
+        ops.append(Op(P + ".cv1", [down], lambda sd, x, p=P + ".cv1": conv_act(sd, p, x), "conv"))
+        for i in range(n):
+            b = f"{P}.m.{i}"
+            if i == 0:                               # the second half of cv1's output: torch.chunk(2, 1)[1]
+                src, cut = P + ".cv1", (lambda t, c=c: t[:, c:2 * c])
+            else:
+                src, cut = f"{P}.m.{i - 1}", (lambda t: t)
+            ops.append(Op(b + ".cv1", [src], lambda sd, x, p=b + ".cv1", cut=cut: conv_act(sd, p, cut(x)), "conv"))
+            ops.append(Op(b, [b + ".cv1", src], lambda sd, y, r, p=b + ".cv2", cut=cut: conv_act(sd, p, y, shortcut=cut(r)), "conv"))
+        ops.append(Op(P, [P + ".cv1"] + [f"{P}.m.{i}" for i in range(n)],
+                      lambda sd, *xs, p=P + ".cv2": conv_act(sd, p, torch.cat(xs, 1)), "conv"))
+        cur = P
+    ops.append(Op("model.9.conv", [cur], lambda sd, x: conv_act(sd, "model.9.conv", x), "conv"))
+    ops.append(Op("logits", ["model.9.conv"], lambda sd, x: yolo_head(sd, x), "head"))
+    if entry == "u8":
+        ops.append(Op("probs", ["logits"], lambda sd, x: softmax(x), "softmax"))
+    return ops
+
+
 def ops_for(sd, entry: str = "float") -> list:
-    return unet_ops(sd) if is_unet(sd) else resnet_ops(sd, entry)
+    if is_unet(sd):
+        return unet_ops(sd)
+    return yolo_cls_ops(sd, entry=entry) if is_yolo_cls(sd) else resnet_ops(sd, entry)
 
 
 def expected_absent(sd, precision: str, entry: str = "float", fused_head: bool = True, chain_form: int = 2) -> frozenset:
@@ -175,6 +253,8 @@ def expected_absent(sd, precision: str, entry: str = "float", fused_head: bool =
         if fused_head:
             absent |= {"up4.conv.double_conv.5", "up4"}
         return frozenset(absent)
+    if is_yolo_cls(sd):                             # every layer is one launch and every output is stored, in every precision
+        return frozenset({"logits"} if entry == "u8" else ())
     if precision != "f32":
         absent.add("act1")                          # stem + max-pool in one kernel
     if precision == "f16r":                         # layer1 (up to three blocks) as one chained launch
